@@ -38,6 +38,12 @@ Besides the contract fields the JSON line carries
   cpu_baseline    - the reference's CPU comparator, PyTorch SDPA on the host cores of this box
                     (rank 0, N = 1 only), on the largest batch x heads sample of config 2 that fits ~12 s; the numpy fp64
                     oracle port is timed next to it (`oracle_port_tflops`).
+
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the LAST timed step returned to its caller - the attention
+                    output and the gradients of q, k and v - as DIR/{out,dq,dk,dv}.npy (float32, flattened).  Each array holds
+                    the same fixed, seeded sample of about 2 M of its 67 M elements (sorted flat indices, dump_outputs()),
+                    about 33 MB in all.  The inputs are seeded too, so two builds run with the same arguments can be compared
+                    output for output.
 """
 import argparse
 import json
@@ -105,6 +111,24 @@ def settle(fn, ms=60.0):
 def event_time_ms(fn, iters, warm=1):
     """Median duration of `fn` over `iters` individually-evented calls."""
     return med_min(event_times_ms(fn, iters, warm))[0]
+
+
+DUMP_SAMPLE = 1 << 21          # flat indices drawn per dumped array (unique ones are kept: ~2.06 M of config 2's 67 M elements)
+
+
+def dump_outputs(path, arrays, seed=421):
+    """--dump-outputs: write every tensor of `arrays` as path/<name>.npy in float32, flattened.  An array of more than DUMP_SAMPLE
+    elements is cut to a fixed sample of them: DUMP_SAMPLE flat indices drawn from a CPU generator seeded with `seed`,
+    deduplicated and sorted - the same for every run and every build, so that dumps compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(seed)
+            idx = torch.unique(torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g))
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
 
 
 # ------------------------------------------------------------------------------------------------ power / clock
@@ -507,13 +531,19 @@ def dry_run(args, rank, world, dist, backend):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (ms_per_step is their mean)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: exercise the launch / rendezvous / barrier / MAX-over-ranks / JSON path only (CPU test of N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (out, dq, dk, dv; a fixed sample, float32) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU steps; --dry-run computes nothing")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -536,10 +566,13 @@ def main():
     mk = lambda h: torch.randn(B, S, h, D, generator=g).to(torch.bfloat16).to(dev)
     q, k, v, do = mk(H), mk(Hk), mk(Hk), mk(H)
     q.requires_grad_(True); k.requires_grad_(True); v.requires_grad_(True)
+    last = {}                      # --dump-outputs: what the latest step handed its caller
 
     def step():
         o = flash_attn.flash_attn_func(q, k, v, causal=c["causal"])
         o.backward(do)
+        if args.dump_outputs:
+            last.update(out=o.detach(), dq=q.grad, dk=k.grad, dv=v.grad)
         q.grad = k.grad = v.grad = None
 
     def barrier():
@@ -603,6 +636,9 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = timed_region()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    last.clear()
     ms_per_step = elapsed / args.steps * 1e3
     value = world * step_flops / (elapsed / args.steps) / 1e12
     cold_ms = cold_elapsed / args.steps * 1e3

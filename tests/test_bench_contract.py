@@ -34,11 +34,43 @@ def test_flop_convention_matches_baseline_md():
     assert abs(m.fwd_flops(m.CFG) / 1e9 - 549.76) < 0.01
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: float32 .npy per array, the same seeded sample of flat indices on every call, small arrays whole,
+    config 2's four outputs within 64 MB."""
+    import numpy as np
+    import torch
+    m = _bench_module()
+    x = torch.randn(8, 4096, 16, 128, generator=torch.Generator().manual_seed(5)).to(torch.bfloat16)
+    m.dump_outputs(str(tmp_path / "a"), {"out": x, "small": x[0, :2]})
+    m.dump_outputs(str(tmp_path / "b"), {"out": x})
+    a, b = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "b" / "out.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert 0.9 * m.DUMP_SAMPLE < a.size <= m.DUMP_SAMPLE and 4 * a.nbytes <= 64 << 20
+    idx = torch.unique(torch.randint(x.numel(), (m.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(421)))
+    assert np.array_equal(a, x.reshape(-1)[idx].float().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), x[0, :2].reshape(-1).float().numpy())
+
+
+def test_bench_rejects_a_run_without_timed_steps():
+    for extra in (["--steps", "0"], ["--dry-run", "--dump-outputs", "unused"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True,
+                             cwd=ROOT, timeout=120)
+        assert out.returncode == 2 and "error" in out.stderr, (extra, out.stderr[-500:])
+
+
 @pytest.mark.gpu
-def test_bench_json_line_contract():
+def test_bench_json_line_contract(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=600)
+                          "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, cwd=ROOT,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
+    # the last timed step's outputs: the op's output and the three gradients, finite, float32, within 64 MB
+    import numpy as np
+    dumped = {f: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert set(dumped) == {"out.npy", "dq.npy", "dk.npy", "dv.npy"}, set(dumped)
+    assert sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    for f, a in dumped.items():
+        assert a.dtype == np.float32 and a.size > 1_000_000 and np.isfinite(a).all() and np.abs(a).max() > 0, f
     d = json.loads(out.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo/flash-attention-v100_amd"); sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "flash-attention-v100_amd")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import flash_attn
 def run(B,S,H,Hk,D=128,causal=True,dt=torch.bfloat16,Sk=None,window=(-1,-1)):
     Sk = Sk or S

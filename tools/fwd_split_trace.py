@@ -1,5 +1,5 @@
 import os, sys, warnings, torch
-sys.path.insert(0, "/root/repo/flash-attention-v100_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "flash-attention-v100_amd"))
 import flash_attn
 from flash_attn_mi355 import flash_attn_interface as fi
 warnings.simplefilter("ignore")

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo/flash-attention-v100_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "flash-attention-v100_amd"))
 import torch, flash_attn
 def t(fn, n=10):
     for _ in range(3): fn()
