@@ -15,6 +15,7 @@
 
 namespace fa {
 int launch_fwd(const KArgs& a, hipStream_t stream);
+int launch_fwd_fp8(const KArgs& a, hipStream_t stream);  // fa_fwd_fp8.hip: fp8-e4m3 q, k, v
 size_t fwd_split_workspace_bytes(const KArgs& a);        // fa_fwd_asm.hip: forward key split of one-wave causal launches
 int launch_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t n_idx, int64_t row_bytes,
                        int64_t src_stride, int64_t n_src_rows, hipStream_t stream);
@@ -60,12 +61,15 @@ static bool varlen_grid_env() {
 
 static bool supported_head_dim(int d) { return d == 64 || d == 128 || d == 256; }
 
-// Checks shared by every op (reference: fused_mha_forward.cu:324-340).
-static int check_common(const fa_params& p, bool need_out) {
+// Checks shared by every op (reference: fused_mha_forward.cu:324-340).  fp8_q: the op takes fp8-e4m3 q (fa_fwd, fa_varlen_fwd).
+static int check_common(const fa_params& p, bool need_out, bool fp8_q = false) {
     const bool no_keys = (p.seqlen_k == 0 && !p.cu_seqlens_k);
     FA_CHECK(p.q && (no_keys || (p.k && p.v)), "q, k, v must not be NULL");
     FA_CHECK(!need_out || (p.o && p.lse), "o and lse must not be NULL");
-    FA_CHECK(p.dtype == FA_FP16 || p.dtype == FA_BF16, "q must be fp16 or bf16");
+    if (fp8_q)
+        FA_CHECK(p.dtype == FA_FP16 || p.dtype == FA_BF16 || p.dtype == FA_FP8_E4M3, "q must be fp16 or bf16 (or fp8-e4m3 with fp8-e4m3 k/v)");
+    else
+        FA_CHECK(p.dtype == FA_FP16 || p.dtype == FA_BF16, "q must be fp16 or bf16");
     FA_CHECK((p.flags & ~(FA_FLAG_KEEP_WINDOW | FA_FLAG_NO_DKV_SPLIT | FA_FLAG_DS_HANDOFF | FA_FLAG_FWD_KEY_SPLIT)) == 0, "fa_params::flags has unknown bits set (zero-initialise the struct)");
     FA_CHECK(p.batch > 0, "batch size must be positive");
     FA_CHECK(p.head_dim <= 256, "head dimension must be <= 256");
@@ -74,7 +78,8 @@ static int check_common(const fa_params& p, bool need_out) {
     FA_CHECK(p.p_dropout >= 0.f && p.p_dropout < 1.f, "p_dropout must be in [0, 1)");
     if (p.softcap > 0.f) FA_CHECK(p.p_dropout == 0.f, "Softcapping does not support dropout for now");
     const int kv_al = p.kv_dtype == FA_FP8_E4M3 ? 16 : 8;
-    FA_CHECK((p.q_row_stride % 8) == 0 && (p.q_head_stride % 8) == 0 && (p.k_row_stride % kv_al) == 0 &&
+    const int q_al = p.dtype == FA_FP8_E4M3 ? 16 : 8;
+    FA_CHECK((p.q_row_stride % q_al) == 0 && (p.q_head_stride % q_al) == 0 && (p.k_row_stride % kv_al) == 0 &&
              (p.k_head_stride % kv_al) == 0 && (p.v_row_stride % kv_al) == 0 && (p.v_head_stride % kv_al) == 0,
              "q/k/v strides must be multiples of 16 bytes");
     FA_CHECK((reinterpret_cast<uintptr_t>(p.q) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.k) & 15) == 0 &&
@@ -115,6 +120,24 @@ static void normalize(fa_params& p, bool kvcache) {
     if (p.window_right >= p.seqlen_k && (!keep || p.window_right >= p.seqlen_q - 1)) p.window_right = -1;
 }
 
+// fp8-e4m3 q, k, v (fa_fwd / fa_varlen_fwd, fa_fwd_fp8.hip): what the kernel covers, and descales of 0 turned into 1.0
+static int check_fp8_q(fa_params& p) {
+    FA_CHECK(p.kv_dtype == FA_FP8_E4M3, "fp8-e4m3 q needs fp8-e4m3 k and v");
+    FA_CHECK(p.o_dtype == FA_FP16 || p.o_dtype == FA_BF16, "fp8-e4m3 q: o_dtype must be FA_FP16 or FA_BF16");
+    float* ds[3] = {&p.q_descale, &p.k_descale, &p.v_descale};
+    for (float* d : ds) {
+        FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "fp8-e4m3 q: q/k/v descales must be finite and >= 0 (0 = 1.0)");
+        if (*d == 0.f) *d = 1.f;
+    }
+    if (p.alibi_slopes) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: ALiBi is not supported");
+    if (p.softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: softcap is not supported");
+    if (p.p_dropout > 0.f || p.dmask) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: dropout is not supported");
+    if (p.block_table) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: paged K/V is not supported");
+    if (p.head_dim > 128) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: head dimension %d is not supported (64, 128)", p.head_dim);
+    FA_CHECK(p.head_dim_v % 16 == 0, "fp8-e4m3 q: head_dim_v must be a multiple of 16");
+    return FA_OK;
+}
+
 static fa::KArgs make_args(const fa_params& p, int block_m) {
     fa::KArgs a;
     memset(&a, 0, sizeof(a));
@@ -141,7 +164,8 @@ int fa_abi_version(void) { return FA_ABI_VERSION; }
 size_t fa_params_size(void) { return sizeof(fa_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
-    return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}; head_dim {64,128,256}; "
+    return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
+           "head_dim {64,128,256}; "
            "ops fwd/bwd/varlen_fwd/varlen_bwd/fwd_kvcache";
 }
 
@@ -205,6 +229,7 @@ static bool varlen_mixed_route(const fa_params& p, fa_params& d) {
 size_t fa_fwd_workspace_bytes(const fa_params* p) {
     fa_params d;
     if (!p) return 0;
+    if (p->dtype == FA_FP8_E4M3) return 0;               // fp8 q: one kernel, no split, no decode route
     if (varlen_decode_route(*p, d)) return fa::decode_workspace_bytes(d);
     if (varlen_mixed_route(*p, d)) return fa::decode_workspace_bytes(d);
     if (!p->cu_seqlens_q && !p->cu_seqlens_k && !p->block_table && p->seqlen_q > 0 && p->seqlen_k > 0 && p->kv_dtype == p->dtype) {
@@ -235,14 +260,19 @@ int fa_fwd(const fa_params* pp, void* stream) {
     fa_params p = *pp;
     p.cu_seqlens_q = p.cu_seqlens_k = p.seqused_k = nullptr;
     p.block_table = nullptr;
-    int rc = check_common(p, true);
+    int rc = check_common(p, true, true);
     if (rc) return rc;
+    const bool q8 = p.dtype == FA_FP8_E4M3;
+    if (q8) {
+        rc = check_fp8_q(p);
+        if (rc) return rc;
+    }
     FA_CHECK(p.kv_dtype == p.dtype, "k/v must have the same dtype as q");
     FA_CHECK(p.seqlen_q >= 0 && p.seqlen_k >= 0, "sequence lengths must be non-negative");
     if (p.seqlen_q == 0) return FA_OK;
     normalize(p, false);
     fa::KArgs a = make_args(p, 128);
-    rc = fa::launch_fwd(a, static_cast<hipStream_t>(stream));
+    rc = q8 ? fa::launch_fwd_fp8(a, static_cast<hipStream_t>(stream)) : fa::launch_fwd(a, static_cast<hipStream_t>(stream));
     if (rc) return fail(FA_ERR_UNSUPPORTED, "no forward kernel for this configuration");
     return check_hip("fa_fwd launch");
 }
@@ -250,8 +280,26 @@ int fa_fwd(const fa_params* pp, void* stream) {
 int fa_varlen_fwd(const fa_params* pp, void* stream) {
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
-    int rc = check_common(p, true);
+    int rc = check_common(p, true, true);
     if (rc) return rc;
+    if (p.dtype == FA_FP8_E4M3) {
+        // fp8-e4m3 q, k, v (fa_fwd_fp8.hip): non-paged, flat work list
+        rc = check_fp8_q(p);
+        if (rc) return rc;
+        FA_CHECK(p.cu_seqlens_q && p.cu_seqlens_k, "cu_seqlens_q and cu_seqlens_k are required");
+        if (p.total_q == 0 || p.seqlen_q == 0) return FA_OK;
+        normalize(p, false);
+        fa::KArgs a = make_args(p, 128);
+        a.seqlens_k = p.seqused_k;
+        if (p.total_q > 0) {
+            a.flat_blocks = p.total_q / 128 + p.batch;
+            a.pair_qblocks = 0;
+            a.n_qblocks = a.n_qblocks_total;
+        }
+        rc = fa::launch_fwd_fp8(a, static_cast<hipStream_t>(stream));
+        if (rc) return fail(FA_ERR_UNSUPPORTED, "no fp8 varlen forward kernel for this configuration");
+        return check_hip("fa_varlen_fwd (fp8) launch");
+    }
     // fp8-e4m3 K / V (this build's extension, as in fa_fwd_kvcache): paged caches, forward only, head dim 64 / 128
     if (p.kv_dtype == FA_FP8_E4M3) {
         FA_CHECK(p.block_table, "fp8 K/V through the varlen op: paged K/V (block_table) only");

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FA_MI355_LIB") or os.path.join(_HERE, "libfa_mi355.so")   # env: A/B experiment builds
 
 FA_FP16, FA_BF16, FA_FP8_E4M3 = 0, 1, 2
-FA_ABI_VERSION = 3
+FA_ABI_VERSION = 4
 FA_FLAG_KEEP_WINDOW = 1
 FA_FLAG_NO_DKV_SPLIT = 2
 FA_FLAG_DS_HANDOFF = 4
@@ -54,6 +54,7 @@ class FaParams(ctypes.Structure):
         ("k_descale", _f32), ("v_descale", _f32),
         ("num_splits", _i32), ("flags", _i32),
         ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("q_descale", _f32), ("o_dtype", _i32),                      # ABI 4: fp8-e4m3 q, k, v
     ]
 
 

@@ -10,7 +10,9 @@ deliberate (DESIGN.md "divergences"):
   * fp16 AND bf16; any head_dim <= 256 (zero-padded to 64/128/256 on the host);
   * `return_attn_probs=True` works with dropout_p == 0 (returns an empty dmask) instead of
     raising (kernel/fused_mha_forward.cu:371);
-  * `flash_attn_with_kvcache` accepts fp8-e4m3 caches with `k_descale` / `v_descale`.
+  * `flash_attn_with_kvcache` accepts fp8-e4m3 caches with `k_descale` / `v_descale`;
+  * `flash_attn_func` / `flash_attn_varlen_func` accept float8_e4m3fn q, k AND v (forward only, bf16 out; the varlen
+    function takes `q_descale` / `k_descale` / `v_descale`).
 There is no CPU fallback: tensors must live on an AMD GPU and the HIP library must load.
 """
 import collections
@@ -70,6 +72,46 @@ def _check_shape(t, shape, name):
     the C ABI only sees pointers and strides, so a mismatched tensor must be rejected here."""
     if tuple(t.shape) != tuple(shape):
         raise RuntimeError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+_FP8 = torch.float8_e4m3fn
+
+
+def _is_fp8_qkv(q, k, v):
+    """all three float8_e4m3fn: the fp8 forward (fa_fwd_fp8.hip); a mix of fp8 and 16-bit inputs raises"""
+    n = sum(t.dtype == _FP8 for t in (q, k, v))
+    if 0 < n < 3:
+        raise RuntimeError("q, k and v must all be float8_e4m3fn (the fp8 forward) or all fp16 / bf16")
+    return n == 3
+
+
+def _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes, paged=False):
+    """what the fp8 forward does not cover: raised here, before anything is allocated or launched"""
+    if head_size_og > 128:
+        raise RuntimeError(f"fp8 forward: head dimension {head_size_og} is not supported (at most 128)")
+    if dropout_p > 0.0:
+        raise RuntimeError("fp8 forward: dropout is not supported")
+    if softcap > 0.0:
+        raise RuntimeError("fp8 forward: softcap is not supported")
+    if alibi_slopes is not None:
+        raise RuntimeError("fp8 forward: ALiBi is not supported")
+    if paged:
+        raise RuntimeError("fp8 forward: paged k / v (block_table) is not supported with fp8 q")
+
+
+def _check_fp8_no_grad(*tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("the fp8 (float8_e4m3fn) forward is forward-only: no backward")
+
+
+def _prep8(x: torch.Tensor, d16: int) -> torch.Tensor:
+    """_prep for fp8 tensors: the head dim zero-padded to a multiple of 16 (`d16`; the kernels read whole 16-byte chunks),
+    16-byte aligned rows"""
+    d = x.shape[-1]
+    if d != d16:
+        x = torch.nn.functional.pad(x.view(torch.uint8), [0, d16 - d]).view(_FP8)      # (code 0x00 = +0.0)
+    ok = x.stride(-1) == 1 and x.data_ptr() % 16 == 0 and all(s % 16 == 0 for s in x.stride()[:-1])
+    return x if ok else x.contiguous()
 
 
 def _check_qkv(q, k, v):
@@ -208,12 +250,51 @@ def _base_params(q, dtype, scale, causal, window_size, softcap):
 FWD_SPLIT = os.environ.get("FA_FWD_SPLIT", "0") == "1"
 
 
+def _dense_forward_fp8(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax):
+    """fa_fwd on float8_e4m3fn [B, S, H, D] q, k, v (descales 1): bf16 out, fp32 LSE; the return tuple of _dense_forward."""
+    if q.dim() != 4:
+        raise RuntimeError("q, k, v must be (batch, seqlen, nheads, headdim)")
+    B, M, H_Q, head_size_og = q.shape
+    N, H_K = k.shape[1], k.shape[2]
+    _check_shape(k, (B, N, H_K, head_size_og), "k")
+    _check_shape(v, (B, N, H_K, head_size_og), "v")
+    _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes)
+    d16 = (head_size_og + 15) // 16 * 16
+    q_, k_, v_ = _prep8(q, d16), _prep8(k, d16), _prep8(v, d16)
+    if softmax_scale is None:
+        softmax_scale = head_size_og ** -0.5
+    out_ = torch.empty((B, M, H_Q, d16), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((B, H_Q, M), dtype=torch.float32, device=q.device)
+    p = _base_params(q_, torch.bfloat16, softmax_scale, causal, window_size, softcap)
+    p.dtype = p.kv_dtype = _lib.FA_FP8_E4M3
+    p.o_dtype = _lib.FA_BF16
+    p.q_descale = 1.0
+    p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
+    _set3(p, "q", q_, "bshd"); _set3(p, "k", k_, "bshd"); _set3(p, "v", v_, "bshd")
+    _set3(p, "o", out_, "bshd")
+    p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
+    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
+    p.seqlen_q, p.seqlen_k = M, N
+    _set_head_dim(p, d16)
+    if q_.numel() > 0:
+        with _on_device(q.device):
+            _lib.call("fa_fwd", p, _stream(q.device))
+    res = out_ if d16 == head_size_og else out_[..., :head_size_og].contiguous()
+    dmask = torch.empty((0,), dtype=torch.bfloat16, device=q.device)
+    return res, lse, dmask, (q_, k_, v_, out_), (0, 0), softmax_scale
+
+
 def _dense_forward(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                    return_softmax, out=None, keep_window=False):
     """One fa_fwd call on [B, S, H, D] views (any strides with a contiguous last dim).  keep_window (sharding.py only):
     FA_FLAG_KEEP_WINDOW - a right window of >= seqlen_k keys stays a window where it still hides keys (seqlen_q >
     seqlen_k); the public functions keep the reference's normalisation, which drops it."""
     _check_device(q, k, v)
+    if _is_fp8_qkv(q, k, v):
+        if out is not None or keep_window:
+            raise RuntimeError("fp8 forward: no caller-allocated out / sharding window")
+        return _dense_forward_fp8(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
+                                  return_softmax)
     _check_qkv(q, k, v)
     if q.dim() != 4:
         raise RuntimeError("q, k, v must be (batch, seqlen, nheads, headdim)")
@@ -435,9 +516,19 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: float = None
                     causal: bool = False, window_size: Tuple[int, int] = (-1, -1),
                     softcap: float = 0.0, alibi_slopes: Optional[torch.Tensor] = None,
                     deterministic: bool = False, return_attn_probs: bool = False):
-    """Dense Flash Attention (B, M, H, D)"""
+    """Dense Flash Attention (B, M, H, D)
+
+    fp8: with q, k and v all torch.float8_e4m3fn the forward runs on the fp8 matrix pipe (head dim <= 128, no dropout,
+    softcap or ALiBi; forward only) and returns a bfloat16 `out` and the fp32 LSE.  The inputs are taken as they are
+    (descales 1): for tensors that dequantise as code * descale pass softmax_scale * q_descale * k_descale and multiply
+    `out` by v_descale (flash_attn_varlen_func also takes the three descales as keywords)."""
     deterministic = _warn_deterministic(deterministic)
     try:
+        if _is_fp8_qkv(q, k, v):
+            _check_fp8_no_grad(q, k, v)
+            out, lse, dmask, _, _, _ = _dense_forward(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
+                                                      alibi_slopes, return_attn_probs)
+            return (out, lse, dmask) if return_attn_probs else out
         return FlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
                                    alibi_slopes, deterministic, return_attn_probs,
                                    torch.is_grad_enabled())
@@ -453,8 +544,9 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: float = None
 def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p,
                     softmax_scale, causal, window_size, softcap, alibi_slopes, return_attn_probs,
                     block_table, seqused_k=None, leftpad_k=None, zero_tensors=False, out=None,
-                    k_descale=None, v_descale=None):
+                    k_descale=None, v_descale=None, q_descale=None):
     """One fa_varlen_fwd call on [T, H, D] tensors (K/V optionally paged [nblk, page, Hk, D]).
+    float8_e4m3fn q, k, v (non-paged) run the fp8 forward: bf16 out, value = code * q/k/v_descale.
     seqused_k clamps the keys of each sequence (include/template.h:65-68); zero_tensors pre-fills out / lse / dmask
     (fused_mha_forward_varlen.cu:538-542); leftpad_k is validated and, like in the reference kernel (the pointer is a
     parameter that is never read, fused_mha_forward_varlen.cu:37), not applied."""
@@ -464,9 +556,15 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
             raise RuntimeError("cu_seqlens_k may be omitted only for paged k / v with seqused_k")
         cu_seqlens_k = torch.nn.functional.pad(seqused_k.cumsum(0, dtype=torch.int32), (1, 0))
     _check_device(q, k, v, cu_seqlens_q, cu_seqlens_k, seqused_k, leftpad_k)
-    if q.dtype not in _DTYPES:
+    fp8_q = q.dtype == _FP8
+    if fp8_q:
+        _is_fp8_qkv(q, k, v)
+        _check_fp8_options(q.shape[-1], dropout_p, softcap, alibi_slopes, paged=block_table is not None)
+        if out is not None:
+            raise RuntimeError("fp8 forward: no caller-allocated out")
+    elif q.dtype not in _DTYPES:
         raise RuntimeError("q must be fp16 or bf16")
-    fp8 = k.dtype == torch.float8_e4m3fn
+    fp8 = not fp8_q and k.dtype == torch.float8_e4m3fn
     if fp8:
         # this build's extension (as in flash_attn_with_kvcache): a paged fp8-e4m3 cache, value = code * descale; forward only
         if v.dtype != k.dtype or block_table is None:
@@ -503,9 +601,10 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     cu_seqlens_q = cu_seqlens_q.to(torch.int32).contiguous()
     cu_seqlens_k = cu_seqlens_k.to(torch.int32).contiguous()
     head_size_og = q.size(-1)
-    dpad = (head_size_og + 7) // 8 * 8
+    dpad = (head_size_og + 15) // 16 * 16 if fp8_q else (head_size_og + 7) // 8 * 8
     _padded_head_dim(dpad)                                   # raises above 256
-    q_, k_, v_ = _prep(q, dpad), _prep(k, dpad), _prep(v, dpad)
+    prep = _prep8 if fp8_q else _prep
+    q_, k_, v_ = prep(q, dpad), prep(k, dpad), prep(v, dpad)
     if softmax_scale is None:
         softmax_scale = head_size_og ** -0.5
     T_Q, H_Q = q_.shape[0], q_.shape[1]
@@ -513,14 +612,21 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     B = cu_seqlens_q.numel() - 1
     paged = block_table is not None
 
+    o_dtype = torch.bfloat16 if fp8_q else q.dtype           # (the fp8 forward writes bf16)
     if out is not None:
         _check_out(out, q)
-    out_ = out if _usable_out(out, dpad, head_size_og) else torch.empty((T_Q, H_Q, dpad), dtype=q.dtype, device=q.device)
+    out_ = out if _usable_out(out, dpad, head_size_og) else torch.empty((T_Q, H_Q, dpad), dtype=o_dtype, device=q.device)
     lse = torch.empty((H_Q, T_Q), dtype=torch.float32, device=q.device)
     if zero_tensors:
         out_.zero_()
         lse.fill_(float("-inf"))
-    p = _base_params(q_, q.dtype, softmax_scale, causal, window_size, softcap)
+    p = _base_params(q_, o_dtype, softmax_scale, causal, window_size, softcap)
+    if fp8_q:
+        p.dtype = p.kv_dtype = _lib.FA_FP8_E4M3
+        p.o_dtype = _lib.FA_BF16
+        p.q_descale = 1.0 if q_descale is None else float(q_descale)
+        p.k_descale = 1.0 if k_descale is None else float(k_descale)
+        p.v_descale = 1.0 if v_descale is None else float(v_descale)
     if fp8:
         p.kv_dtype = _lib.FA_FP8_E4M3
         p.k_descale = 1.0 if k_descale is None else float(k_descale)
@@ -543,7 +649,7 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
         p.page_block_size = k_.shape[1]
     _alibi(p, alibi_slopes, B, H_Q, q.device)
     rng = _philox(p, dropout_p, B, H_Q, q.device)
-    dmask = torch.empty((0,), dtype=q.dtype, device=q.device)
+    dmask = torch.empty((0,), dtype=o_dtype, device=q.device)
     if return_attn_probs and dropout_p > 0.0:
         dmask = torch.zeros((T_Q, H_Q, max_seqlen_k), dtype=q.dtype, device=q.device)
         p.dmask = _ptr(dmask)
@@ -652,20 +758,23 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: in
                            deterministic: bool = False, return_attn_probs: bool = False,
                            block_table: Optional[torch.Tensor] = None, *,
                            seqused_k: Optional[torch.Tensor] = None,
-                           k_descale: Optional[float] = None, v_descale: Optional[float] = None):
+                           k_descale: Optional[float] = None, v_descale: Optional[float] = None,
+                           q_descale: Optional[float] = None):
     """Varlen Flash Attention (T, H, D).  seqused_k ([B] int32, forward only): use only the first seqused_k[b] keys
     of sequence b (the op-level argument of the reference, include/mha.h:116-139).  Paged k / v may be float8_e4m3fn
-    (value = code * k_descale / v_descale; forward only) - this build's extension, as in flash_attn_with_kvcache."""
+    (value = code * k_descale / v_descale; forward only) - this build's extension, as in flash_attn_with_kvcache.
+    q, k and v may all be float8_e4m3fn (non-paged; value = code * q_descale / k_descale / v_descale, None = 1): the
+    fp8 forward of flash_attn_func, bfloat16 `out`, forward only."""
     deterministic = _warn_deterministic(deterministic)
     try:
-        fp8 = k.dtype == torch.float8_e4m3fn
+        fp8 = k.dtype == torch.float8_e4m3fn or q.dtype == torch.float8_e4m3fn
         if seqused_k is not None or fp8:
             if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v)):
                 raise RuntimeError("seqused_k / fp8 k, v are forward-only (the reference's backward op has neither)")
             out, lse, dmask, _, _, _ = _varlen_forward(
                 q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
                 window_size, softcap, alibi_slopes, return_attn_probs, block_table, seqused_k=seqused_k,
-                k_descale=k_descale, v_descale=v_descale)
+                k_descale=k_descale, v_descale=v_descale, q_descale=q_descale)
             return (out, lse, dmask) if return_attn_probs else out
         return FlashAttnVarlenFunc.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
                                          max_seqlen_k, dropout_p, softmax_scale, causal,

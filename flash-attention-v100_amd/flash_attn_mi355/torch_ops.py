@@ -10,7 +10,8 @@ The optional in-place outputs of the reference (`out` of fwd / varlen_fwd, `dq`,
 include/mha.h:31,73-75) live in the separate ops `fwd_out`, `varlen_fwd_out` and `bwd_out`, which MUTATE
 caller-allocated tensors (a torch.library op may not return an alias of an input); the plain ops return fresh
 tensors.  `varlen_fwd` carries the reference's op-level extras `seqused_k`, `leftpad_k`, `zero_tensors`,
-`num_splits` (include/mha.h:116-139).  Every op has a fake (meta) implementation so the path is traceable by
+`num_splits` (include/mha.h:116-139).  `fwd` / `varlen_fwd` also take float8_e4m3fn q, k, v (the fp8 forward, descales 1,
+forward only) and return a bf16 `out` for them.  Every op has a fake (meta) implementation so the path is traceable by
 torch.compile / FakeTensorMode, and `fwd` / `varlen_fwd` carry autograd formulas that call the
 `bwd` ops.
 
@@ -32,6 +33,16 @@ def _rng_tensor(rng, device):
     if seed >= 1 << 63:                         # int64 carrier: two's complement, lossless
         seed -= 1 << 64
     return torch.tensor([seed, int(rng[1])], dtype=torch.int64, device=device)
+
+
+def _out_dtype(q: Tensor):
+    """float8_e4m3fn q, k, v: the fp8 forward writes bf16 out (flash_attn_interface._dense_forward_fp8)"""
+    return torch.bfloat16 if q.dtype == torch.float8_e4m3fn else q.dtype
+
+
+def _no_fp8_backward(q: Tensor):
+    if q.dtype == torch.float8_e4m3fn:
+        raise RuntimeError("the fp8 (float8_e4m3fn) forward is forward-only: no backward")
 
 
 def _rng_tuple(rng_state: Optional[Tensor]):
@@ -59,9 +70,10 @@ def _(q, k, v, alibi_slopes, p_dropout, softmax_scale, is_causal, window_size_le
       window_size_right, softcap, return_softmax):
     B, M, H, D = q.shape
     N = k.shape[1]
-    out = q.new_empty((B, M, H, D))
+    o_dtype = _out_dtype(q)
+    out = q.new_empty((B, M, H, D), dtype=o_dtype)
     lse = q.new_empty((B, H, M), dtype=torch.float32)
-    dmask = q.new_empty((B, H, M, N) if (return_softmax and p_dropout > 0.0) else (0,))
+    dmask = q.new_empty((B, H, M, N) if (return_softmax and p_dropout > 0.0) else (0,), dtype=o_dtype)
     return out, lse, dmask, q.new_empty((2,), dtype=torch.int64)
 
 
@@ -101,6 +113,7 @@ def _fwd_setup(ctx, inputs, output):
 
 def _fwd_backward(ctx, dout, dlse, ddmask, drng):
     q, k, v, out, lse, rng_state, alibi_slopes = ctx.saved_tensors
+    _no_fp8_backward(q)
     p_dropout, softmax_scale, is_causal, wl, wr, softcap = ctx.args
     dq, dk, dv, _ = bwd(dout, q, k, v, out, lse, alibi_slopes, p_dropout, softmax_scale, is_causal,
                         wl, wr, softcap, False, rng_state)
@@ -134,8 +147,9 @@ def _(q, k, v, cu_seqlens_q, cu_seqlens_k, block_table, alibi_slopes, max_seqlen
       p_dropout, softmax_scale, is_causal, window_size_left, window_size_right, softcap,
       return_softmax, seqused_k=None, leftpad_k=None, zero_tensors=False, num_splits=0):
     T, H, D = q.shape
-    dmask = q.new_empty((T, H, max_seqlen_k) if (return_softmax and p_dropout > 0.0) else (0,))
-    return (q.new_empty((T, H, D)), q.new_empty((H, T), dtype=torch.float32), dmask,
+    o_dtype = _out_dtype(q)
+    dmask = q.new_empty((T, H, max_seqlen_k) if (return_softmax and p_dropout > 0.0) else (0,), dtype=o_dtype)
+    return (q.new_empty((T, H, D), dtype=o_dtype), q.new_empty((H, T), dtype=torch.float32), dmask,
             q.new_empty((2,), dtype=torch.int64))
 
 
@@ -185,6 +199,7 @@ def _varlen_setup(ctx, inputs, output):
 
 def _varlen_backward_formula(ctx, dout, dlse, ddmask, drng):
     q, k, v, out, lse, cu_q, cu_k, rng_state, alibi_slopes = ctx.saved_tensors
+    _no_fp8_backward(q)
     max_q, max_k, p_dropout, softmax_scale, is_causal, wl, wr, softcap = ctx.args
     dq, dk, dv, _ = varlen_bwd(dout, q, k, v, out, lse, cu_q, cu_k, alibi_slopes, max_q, max_k,
                                p_dropout, softmax_scale, is_causal, wl, wr, softcap, False, rng_state)

@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 3   /* 2: fa_bwd / fa_varlen_bwd skip outputs passed as NULL; 3: fa_params::flags (was reserved0) */
+#define FA_ABI_VERSION 4   /* 2: fa_bwd / fa_varlen_bwd skip outputs passed as NULL; 3: fa_params::flags (was reserved0);
+                              4: fa_params::q_descale, fa_params::o_dtype (fp8-e4m3 q in fa_fwd / fa_varlen_fwd) */
 
 /* fa_params::flags.  The reference drops a window of >= seqlen_k keys before anything else (fused_mha_forward.cu:343-352); so
  * do the five ops.  With seqlen_q > seqlen_k that also drops right windows that still hide keys from the first rows - the
@@ -57,7 +58,8 @@ extern "C" {
 typedef enum fa_dtype {
     FA_FP16 = 0,      /* IEEE half */
     FA_BF16 = 1,      /* bfloat16 */
-    FA_FP8_E4M3 = 2   /* OCP e4m3fn, KV cache only */
+    FA_FP8_E4M3 = 2   /* OCP e4m3fn: k/v of fa_fwd_kvcache and of paged fa_varlen_fwd; q, k and v together in fa_fwd /
+                         fa_varlen_fwd (forward only, 16-bit o of fa_params::o_dtype) */
 } fa_dtype;
 
 typedef enum fa_status {
@@ -166,6 +168,15 @@ typedef struct fa_params {
     int32_t flags;                  /* FA_FLAG_* bits, 0 for the reference's semantics (unknown bits are rejected) */
     void*   workspace;              /* >= fa_*_workspace_bytes(params) bytes, or NULL if 0 */
     size_t  workspace_bytes;
+
+    /* ---- fp8-e4m3 q, k, v (ABI 4: fa_fwd / fa_varlen_fwd with dtype == kv_dtype == FA_FP8_E4M3) ----
+     * Both products run on the block-scaled e4m3 matrix pipe; value = code * descale for each of q, k, v (k_descale and
+     * v_descale above).  A descale of 0 means 1.0; a negative or non-finite one is FA_ERR_INVALID_ARGUMENT.
+     * q_descale * k_descale joins softmax_scale, v_descale the final normalisation.  Head dims 64 and 128 (head_dim_v: a
+     * multiple of 16), causal / window masks, GQA / MQA, dense and varlen (non-paged); ALiBi, softcap, dropout, paged K/V
+     * and head dims above 128 are FA_ERR_UNSUPPORTED.  No backward: fa_bwd / fa_varlen_bwd / fa_fwd_kvcache reject fp8 q. */
+    float   q_descale;              /* fp8 q: value = code * q_descale (0 = 1.0); ignored otherwise */
+    int32_t o_dtype;                /* fp8 q: fa_dtype of o, FA_FP16 or FA_BF16; ignored for 16-bit q (o has `dtype`) */
 } fa_params;
 
 /* ABI self-description (checked by the Python ctypes mirror at load time). */
