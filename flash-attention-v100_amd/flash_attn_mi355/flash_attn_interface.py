@@ -99,8 +99,11 @@ def _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes, paged=Fal
         raise RuntimeError("fp8 forward: paged k / v (block_table) is not supported with fp8 q")
 
 
-def _check_fp8_no_grad(*tensors):
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+def _check_fp8_no_grad(*tensors, grad_enabled=None):
+    """grad_enabled: the caller's grad mode (inside an autograd.Function's forward torch.is_grad_enabled() is False)"""
+    if grad_enabled is None:
+        grad_enabled = torch.is_grad_enabled()
+    if grad_enabled and any(t is not None and t.requires_grad for t in tensors):
         raise RuntimeError("the fp8 (float8_e4m3fn) forward is forward-only: no backward")
 
 
@@ -445,6 +448,8 @@ class FlashAttnQKVPackedFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                 deterministic, return_softmax, is_grad_enabled):
+        if qkv.dtype == _FP8:
+            _check_fp8_no_grad(qkv, grad_enabled=is_grad_enabled)
         is_grad = is_grad_enabled and qkv.requires_grad
         q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
         out, lse, dmask, saved, rng, softmax_scale = _dense_forward(
@@ -475,6 +480,8 @@ class FlashAttnKVPackedFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, kv, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                 deterministic, return_softmax, is_grad_enabled):
+        if _is_fp8_qkv(q, kv, kv):
+            _check_fp8_no_grad(q, kv, grad_enabled=is_grad_enabled)
         is_grad = is_grad_enabled and any(x.requires_grad for x in [q, kv])
         k, v = kv[:, :, 0], kv[:, :, 1]
         out, lse, dmask, saved, rng, softmax_scale = _dense_forward(

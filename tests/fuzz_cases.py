@@ -3,6 +3,8 @@
 Shapes are drawn around the tile edges of the kernels (multiples of 32 / 64 / 128 / 256, +-1), features are drawn
 independently (causal / one- and two-sided windows, GQA / MQA, ALiBi, softcap, dropout, head dims 32..256, ragged and
 empty sequences, paged caches, rotary, left padding), sizes stay where the fp64 oracle finishes in well under a second.
+The fp8_* kinds run the fp8-e4m3 q / k / v forward (input magnitudes, softmax scales, descales, seqused_k, packed and
+head-sliced views) inside the gate of tests/fp8_gate.py and report the worst error / gate ratio per kind.
 
   pytest runs a fixed sample (tests/test_fuzz_gpu.py);  more:   python tests/fuzz_cases.py --seed 7 --n 400
 """
@@ -357,12 +359,180 @@ def kvcache_case(rng, idx):
     return desc
 
 
+# ------------------------------------------------------------------------------------------------ fp8-e4m3 q, k, v forward
+# csrc/fa_fwd_fp8.hip against the oracle on the dequantised inputs, `out` inside the derived gate of tests/fp8_gate.py
+# (forward only: the fp8 path has no backward).  Head dims that are not a multiple of 16 go through the Python zero-pad;
+# views into packed / wider buffers (D a multiple of 16) reach the kernel without a copy.
+# LSE: the -inf pattern and finiteness are asserted; its value is REPORTED, not gated.  The block-scaled MFMA does not sum
+# the exact e4m3 products as fp32 would: one visible key per row (LSE = the score) measured score errors up to
+# 6.6e-5 x sum_d |q_d k_d| (D 16) and 1.2e-5 x (D 128) at every magnitude, 10 - 70 x the fp32 bound of fp8_gate.py, which
+# the LSE sees in full (out, a ratio of weights, passes the gate).  The worst |LSE - ref| / (scale sum_d |q_d k_d|) is
+# printed per kind.
+HEAD_DIMS_FP8 = (16, 32, 40, 48, 64, 64, 72, 80, 96, 112, 120, 128, 128)
+MAGS_FP8 = (2.0 ** -3, 1.0, 2.0 ** 3, 2.0 ** 5)
+WORST = {}                                  # kind -> (largest out err / gate, case)
+WORST_LSE = {}                              # kind -> (largest |LSE - ref| / (scale sum_d |q_d k_d|), case)
+
+
+def _e4m3(shape, seed, mag):
+    """N(0, mag^2) clamped to +-448 before the cast (torch's cast to float8_e4m3fn does not saturate: 480 -> NaN)"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return (torch.randn(shape, generator=g, dtype=torch.float32) * mag).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).cuda()
+
+
+def _fp8_layout(rng, D):
+    return str(rng.choice(["contiguous", "packed", "head_slice"])) if D % 16 == 0 else "contiguous"
+
+
+def _fp8_qkv(layout, lead_q, lead_k, Hq, Hk, D, seed, mag, rng):
+    """q [*lead_q, Hq, D], k / v [*lead_k, Hk, D] as contiguous tensors, views into one packed [*lead, 3, H, D] (or a
+    [*lead_k, 2, Hk, D] kv buffer beside a contiguous q when the shapes differ), or head slices of wider buffers"""
+    if layout == "packed":
+        if lead_q == lead_k and Hq == Hk:
+            qkv = _e4m3((*lead_q, 3, Hq, D), seed, mag)
+            return qkv.select(-3, 0), qkv.select(-3, 1), qkv.select(-3, 2)
+        kv = _e4m3((*lead_k, 2, Hk, D), seed + 1, mag)
+        return _e4m3((*lead_q, Hq, D), seed, mag), kv.select(-3, 0), kv.select(-3, 1)
+    if layout == "head_slice":
+        out = []
+        for i, (lead, H) in enumerate(((lead_q, Hq), (lead_k, Hk), (lead_k, Hk))):
+            extra = int(rng.integers(1, 4))
+            a = int(rng.integers(0, extra + 1))
+            out.append(_e4m3((*lead, H + extra, D), seed + i, mag).narrow(-2, a, H))
+        return tuple(out)
+    return tuple(_e4m3((*lead, H, D), seed + i, mag) for i, (lead, H) in enumerate(((lead_q, Hq), (lead_k, Hk), (lead_k, Hk))))
+
+
+def _fp8_scale(rng):
+    return None if rng.random() < 0.5 else float(rng.uniform(0.02, 2.0))
+
+
+def _fp8_record(kind, ratio, desc):
+    if ratio > WORST.get(kind, (-1.0, ""))[0]:
+        WORST[kind] = (ratio, desc)
+
+
+def _fp8_lse(kind, got, ref, delta, D, desc):
+    """-inf pattern and finiteness; the error in units of scale sum_d |q_d k_d| (delta / ((D - 1) 2^-24)) is recorded"""
+    inf_ref = np.isneginf(ref)
+    assert (np.isneginf(got) == inf_ref).all(), f"lse: -inf pattern differs  [{desc}]"
+    assert np.isfinite(got[~inf_ref]).all(), f"lse: non-finite values  [{desc}]"
+    if D > 1 and (~inf_ref).any():
+        unit = np.maximum(np.asarray(delta)[~inf_ref] / ((D - 1) * 2.0 ** -24), 1e-30)
+        e = float((np.abs(got[~inf_ref] - ref[~inf_ref]) / unit).max())
+        if e > WORST_LSE.get(kind, (-1.0, ""))[0]:
+            WORST_LSE[kind] = (e, desc)
+
+
+def fp8_dense_case(rng, idx, long=False):
+    import fp8_gate
+    B = int(rng.integers(1, 3))
+    Hk = int(rng.choice([1, 2, 4]))
+    Hq = Hk * int(rng.choice([1, 1, 2, 4]))
+    D = int(rng.choice(HEAD_DIMS_FP8))
+    Sq, Sk = _len(rng), _len(rng)
+    if long:
+        B, Hk = 1, 1
+        Hq = int(rng.choice([1, 1, 2]))
+        Sq, Sk = _len(rng, 4097), _len(rng, 4097)
+    if rng.random() < 0.4:
+        Sk = Sq
+    causal, window = _mask(rng, Sq, Sk)
+    mag = float(rng.choice(MAGS_FP8))
+    scale = _fp8_scale(rng)
+    layout = _fp8_layout(rng, D)
+    kind = "fp8_dense_long" if long else "fp8_dense"
+    desc = f"{kind}#{idx} B{B} Hq{Hq} Hk{Hk} Sq{Sq} Sk{Sk} D{D} causal={causal} window={window} mag={mag} " \
+           f"scale={scale} layout={layout}"
+    q8, k8, v8 = _fp8_qkv(layout, (B, Sq), (B, Sk), Hq, Hk, D, 11000 + 10 * idx, mag, rng)
+    out, lse, _ = _fa().flash_attn_func(q8, k8, v8, softmax_scale=scale, causal=causal, window_size=window,
+                                        return_attn_probs=True)
+    torch.cuda.synchronize()
+    assert out.dtype == torch.bfloat16 and out.shape == (B, Sq, Hq, D), f"out {out.dtype} {tuple(out.shape)}  [{desc}]"
+    assert lse.dtype == torch.float32 and lse.shape == (B, Hq, Sq), f"lse {lse.dtype} {tuple(lse.shape)}  [{desc}]"
+    sc = D ** -0.5 if scale is None else scale
+    t = lambda x: f64(x).transpose(0, 2, 1, 3)
+    q, k, v = t(q8), t(k8), t(v8)
+    o_ref, lse_ref, _ = oracle.attn_fwd(q, k, v, sc, causal=causal, window=window)
+    bnd, delta = fp8_gate.dense_bound(q, k, v, sc, causal, window)
+    r = fp8_gate.check_out(t(out), o_ref, bnd, f"out  [{desc}]")
+    _fp8_lse(kind, f64(lse), lse_ref, delta, D, desc)
+    _fp8_record(kind, r, desc)
+    return desc
+
+
+def _fp8_descale(rng):
+    r = rng.random()
+    if r < 0.4:
+        return None
+    if r < 0.7:
+        return float(2.0 ** int(rng.integers(-4, 3)))
+    return float(rng.choice([0.013, 0.37, 3.0]))
+
+
+def fp8_varlen_case(rng, idx, long=False):
+    import fp8_gate
+    B = int(rng.integers(1, 6))
+    Hk = int(rng.choice([1, 2, 4]))
+    Hq = Hk * int(rng.choice([1, 1, 2, 4]))
+    D = int(rng.choice(HEAD_DIMS_FP8))
+    hi = 400
+    if long:
+        B, Hk, hi = int(rng.integers(1, 3)), 1, 4097
+        Hq = int(rng.choice([1, 2]))
+    lens_q = [0 if rng.random() < 0.1 else _len(rng, hi) for _ in range(B)]
+    if rng.random() < 0.5:
+        lens_k = list(lens_q)
+    else:
+        lens_k = [0 if rng.random() < 0.1 else _len(rng, hi) for _ in range(B)]
+    if sum(lens_q) == 0:
+        lens_q[0] = 17
+    if sum(lens_k) == 0:
+        lens_k[-1] = 9
+    causal, window = _mask(rng, max(lens_q), max(lens_k))
+    used = [int(rng.integers(0, l + 1)) for l in lens_k] if rng.random() < 0.15 else None
+    mag = float(rng.choice(MAGS_FP8))
+    scale = _fp8_scale(rng)
+    qd, kd, vd = _fp8_descale(rng), _fp8_descale(rng), _fp8_descale(rng)
+    layout = _fp8_layout(rng, D)
+    kind = "fp8_varlen_long" if long else "fp8_varlen"
+    desc = f"{kind}#{idx} lens_q={lens_q} lens_k={lens_k} Hq{Hq} Hk{Hk} D{D} causal={causal} window={window} " \
+           f"seqused_k={used} mag={mag} scale={scale} descales={(qd, kd, vd)} layout={layout}"
+    Tq, Tk = sum(lens_q), sum(lens_k)
+    q8, k8, v8 = _fp8_qkv(layout, (Tq,), (Tk,), Hq, Hk, D, 15000 + 10 * idx, mag, rng)
+    cu = lambda l: torch.tensor(np.concatenate([[0], np.cumsum(l)]), dtype=torch.int32, device="cuda")
+    cu_q, cu_k = cu(lens_q), cu(lens_k)
+    mq, mk = max(lens_q), max(lens_k)
+    extra = {} if used is None else {"seqused_k": torch.tensor(used, dtype=torch.int32, device="cuda")}
+    out, lse, _ = _fa().flash_attn_varlen_func(q8, k8, v8, cu_q, cu_k, mq, mk, softmax_scale=scale, causal=causal,
+                                               window_size=window, return_attn_probs=True, q_descale=qd, k_descale=kd,
+                                               v_descale=vd, **extra)
+    torch.cuda.synchronize()
+    assert out.dtype == torch.bfloat16 and out.shape == (Tq, Hq, D), f"out {out.dtype} {tuple(out.shape)}  [{desc}]"
+    assert lse.dtype == torch.float32 and lse.shape == (Hq, Tq), f"lse {lse.dtype} {tuple(lse.shape)}  [{desc}]"
+    sc = D ** -0.5 if scale is None else scale
+    q, k, v = (f64(x) * (1.0 if d is None else d) for x, d in ((q8, qd), (k8, kd), (v8, vd)))
+    cq, ck = cu_q.cpu().numpy(), cu_k.cpu().numpy()
+    o_ref, lse_ref = oracle.varlen_fwd(q, k, v, cq, ck, mq, mk, sc, causal=causal, window=window,
+                                       seqused_k=None if used is None else np.asarray(used, dtype=np.int32))
+    bnd, delta = fp8_gate.varlen_bound(q, k, v, cq, ck, mq, mk, sc, causal, window, seqused_k=used)
+    r = fp8_gate.check_out(f64(out), o_ref, bnd, f"out  [{desc}]")
+    _fp8_lse(kind, f64(lse), lse_ref, delta, D, desc)
+    _fp8_record(kind, r, desc)
+    return desc
+
+
 KINDS = {"dense": dense_case, "varlen": varlen_case, "kvcache": kvcache_case,
          "dense_long": lambda rng, i: dense_case(rng, i, long=True),
-         "varlen_long": lambda rng, i: varlen_case(rng, i, long=True)}
+         "varlen_long": lambda rng, i: varlen_case(rng, i, long=True),
+         "fp8_dense": fp8_dense_case, "fp8_varlen": fp8_varlen_case,
+         "fp8_dense_long": lambda rng, i: fp8_dense_case(rng, i, long=True),
+         "fp8_varlen_long": lambda rng, i: fp8_varlen_case(rng, i, long=True)}
 
 
-KIND_ID = {"dense": 0, "kvcache": 1, "varlen": 2, "dense_long": 3, "varlen_long": 4}
+# (appended only: a kind's id seeds its random stream, and pinned cases replay by (kind, seed, i))
+KIND_ID = {"dense": 0, "kvcache": 1, "varlen": 2, "dense_long": 3, "varlen_long": 4,
+           "fp8_dense": 5, "fp8_varlen": 6, "fp8_dense_long": 7, "fp8_varlen_long": 8}
 
 
 def run_one(kind, seed, i):
@@ -390,6 +560,11 @@ def run(kind, seed, n, verbose=False, keep_going=False):
                 raise
             failures.append(f"{kind}#{i}: {type(e).__name__}: {e}")
             print("FAIL", failures[-1], flush=True)
+    if kind in WORST:
+        print(f"{kind}: worst out error / gate {WORST[kind][0]:.3f}  [{WORST[kind][1]}]", flush=True)
+    if kind in WORST_LSE:
+        print(f"{kind}: worst |LSE - ref| / (scale sum_d |q_d k_d|) {WORST_LSE[kind][0]:.2e}  [{WORST_LSE[kind][1]}]",
+              flush=True)
     return failures
 
 

@@ -171,3 +171,115 @@ def test_python_rejections_before_launch():
         with pytest.raises(RuntimeError, match=match):
             fi._check_fp8_options(**args)
     assert "q_descale" in __import__("inspect").signature(fa.flash_attn_varlen_func).parameters
+
+
+def test_packed_entry_points_reject_fp8_with_grad_before_launch():
+    """the packed autograd Functions refuse fp8 inputs that require grad at forward time (the check comes before the device
+    check, so CPU tensors reach it), as flash_attn_func does"""
+    import flash_attn_mi355 as fa
+    qkv = torch.zeros(1, 16, 3, 2, 64, dtype=torch.float8_e4m3fn).requires_grad_()
+    with pytest.raises(RuntimeError, match="forward-only"):
+        fa.flash_attn_qkvpacked_func(qkv)
+    q = torch.zeros(1, 16, 2, 64, dtype=torch.float8_e4m3fn)
+    kv = torch.zeros(1, 16, 2, 2, 64, dtype=torch.float8_e4m3fn).requires_grad_()
+    with pytest.raises(RuntimeError, match="forward-only"):
+        fa.flash_attn_kvpacked_func(q, kv)
+    with pytest.raises(RuntimeError, match="forward-only"):
+        fa.flash_attn_kvpacked_func(q.clone().requires_grad_(), kv.detach())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the shared fp8 gate (tests/fp8_gate.py) against an emulation of the kernel's arithmetic
+# ---------------------------------------------------------------------------------------------------------------------
+def _emulate(q8, k8, v8, scale, causal, wl, wr, qd=1.0, kd=1.0, vd=1.0, o_dtype=torch.bfloat16, mutate=None):
+    """fa_fwd_fp8.hip on one head, in torch: scores in fp32 from the e4m3 codes, 64-key tiles, waves of 32 rows with the
+    deferred rescale (a wave keeps its maxima unless one row would exceed its own by more than 2^8), P = exp2(s c - m) in
+    fp32, l from the fp32 P, P quantised through float8_e4m3fn for O += P V in fp32, out = O v_descale / l.
+    mutate: 'drop' - the P of each row's highest-scoring visible key is left out of O; 'swap' - the P of keys 2t and 2t + 1 trade
+    places in O."""
+    from oracle.attention import visible_mask
+    sq, sk = q8.shape[0], k8.shape[0]
+    s = q8.float() @ k8.float().T
+    vis = torch.from_numpy(visible_mask(sq, sk, causal, wl, wr))
+    c = torch.tensor(scale * 1.4426950408889634, dtype=torch.float32) * torch.tensor(qd * kd, dtype=torch.float32)
+    m_run = torch.full((sq,), -torch.inf)
+    l_run = torch.zeros(sq)
+    o = torch.zeros(sq, v8.shape[1])
+    heavy = torch.where(vis.any(1), torch.where(vis, s, -torch.inf).argmax(1), -1)
+    for n0 in range(0, sk, 64):
+        st = torch.where(vis[:, n0:n0 + 64], s[:, n0:n0 + 64], -torch.inf)
+        mx = st.max(dim=1).values * c
+        for w0 in range(0, sq, 32):
+            w = slice(w0, w0 + 32)
+            if not bool(((mx[w] - m_run[w]) <= 8.0).all()):
+                m_new = torch.maximum(m_run[w], mx[w])
+                alpha = torch.exp2(m_run[w] - torch.where(m_new == -torch.inf, 0.0, m_new))
+                m_run[w], l_run[w] = m_new, l_run[w] * alpha
+                o[w] *= alpha[:, None]
+        m_use = torch.where(m_run == -torch.inf, 0.0, m_run)
+        p = torch.exp2(st * c - m_use[:, None])
+        assert float(p.max()) <= 256.0
+        l_run += p.sum(dim=1)
+        pq = p.to(torch.float8_e4m3fn).float()
+        if mutate == "drop":
+            j = heavy - n0
+            rows = torch.nonzero((j >= 0) & (j < pq.shape[1]))[:, 0]
+            pq[rows, j[rows]] = 0.0
+        elif mutate == "swap":
+            n = pq.shape[1] // 2 * 2
+            pq[:, 0:n] = pq[:, 0:n].reshape(sq, -1, 2).flip(2).reshape(sq, n)
+        o += pq @ v8[n0:n0 + 64].float()
+    inv = torch.where(l_run > 0, torch.tensor(vd, dtype=torch.float32) / l_run, 0.0)
+    out = (o * inv[:, None]).to(o_dtype)
+    lse = torch.where(l_run > 0, (m_run + torch.log2(l_run)) * 0.6931471805599453, -torch.inf)
+    return out, lse
+
+
+def _e4m3(shape, seed, mag):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=g) * mag).clamp(-448, 448).to(torch.float8_e4m3fn)
+
+
+EMULATED = [
+    # (Sq, Sk, D, causal, window, magnitude, descales (q, k, v), out dtype)
+    (130, 200, 64, True, (-1, -1), 1.0, (1.0, 1.0, 1.0), "bf16"),
+    (96, 300, 128, False, (-1, -1), 8.0, (1.0, 1.0, 1.0), "bf16"),     # P up to 2^8, both rescale paths
+    (100, 100, 16, False, (20, 5), 1.0, (0.5, 0.25, 2.0), "fp16"),
+    (65, 257, 80, False, (-1, -1), 32.0, (1.0, 1.0, 1.0), "bf16"),     # large scores: the accumulation term
+    (200, 70, 48, True, (-1, -1), 0.125, (0.013, 3.0, 0.013), "fp16"),  # Sq > Sk: rows without keys
+]
+
+
+@pytest.mark.parametrize("Sq,Sk,D,causal,window,mag,ds,odt", EMULATED)
+def test_fp8_gate_holds_for_the_emulated_kernel(Sq, Sk, D, causal, window, mag, ds, odt):
+    import fp8_gate
+    import oracle
+    from oracle.attention import normalize_flags
+    q8, k8, v8 = _e4m3((Sq, D), Sq + D, mag), _e4m3((Sk, D), Sk + 1, mag), _e4m3((Sk, D), Sk + 2, mag)
+    scale = D ** -0.5
+    c, wl, wr = normalize_flags(Sq, Sk, causal, window[0], window[1], False)
+    out, lse = _emulate(q8, k8, v8, scale, c, wl, wr, *ds, o_dtype=fp8_gate.DTYPE_OF[odt])
+    q, k, v = (t.double().numpy() * d for t, d in zip((q8, k8, v8), ds))
+    o_ref, lse_ref, _ = oracle.attn_fwd(q[None, None], k[None, None], v[None, None], scale, causal=causal, window=window)
+    bnd, delta = fp8_gate.bound(q, k, v, scale, causal, window)
+    r = fp8_gate.check_out(out.double().numpy(), o_ref[0, 0], bnd, "emulated out", o_dtype=odt)
+    rl = fp8_gate.check_lse(lse.double().numpy(), lse_ref[0, 0], delta, "emulated lse")
+    print(f"Sq{Sq} Sk{Sk} D{D} mag {mag}: out {r:.3f}, lse {rl:.3f} of the gate")
+
+
+@pytest.mark.parametrize("mutate", ["drop", "swap"])
+def test_fp8_gate_rejects_a_wrong_emulation(mutate):
+    """each case of EMULATED with one visible key dropped or two adjacent keys' P swapped lands outside the gate"""
+    import fp8_gate
+    import oracle
+    from oracle.attention import normalize_flags
+    for Sq, Sk, D, causal, window, mag, ds, odt in EMULATED:
+        q8, k8, v8 = _e4m3((Sq, D), Sq + D, mag), _e4m3((Sk, D), Sk + 1, mag), _e4m3((Sk, D), Sk + 2, mag)
+        scale = D ** -0.5
+        c, wl, wr = normalize_flags(Sq, Sk, causal, window[0], window[1], False)
+        out, _ = _emulate(q8, k8, v8, scale, c, wl, wr, *ds, o_dtype=fp8_gate.DTYPE_OF[odt], mutate=mutate)
+        q, k, v = (t.double().numpy() * d for t, d in zip((q8, k8, v8), ds))
+        o_ref, _, _ = oracle.attn_fwd(q[None, None], k[None, None], v[None, None], scale, causal=causal, window=window)
+        bnd, _ = fp8_gate.bound(q, k, v, scale, causal, window)
+        with pytest.raises(AssertionError, match="fp8 gate"):
+            fp8_gate.check_out(out.double().numpy(), o_ref[0, 0], bnd, f"{mutate} Sq{Sq} Sk{Sk} D{D}", o_dtype=odt)

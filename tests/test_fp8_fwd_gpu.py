@@ -4,26 +4,16 @@ inputs, bf16 out.
 Exact-data layout tests catch row / column / key-order permutations in both products (S^T = K Q^T and O^T = V^T P^T on the
 block-scaled K = 64 MFMA); random data is held against the fp64 oracle on the dequantised inputs.
 
-The out gate (derived, not fitted).  Both products are exact up to fp32 accumulation: an e4m3 x e4m3 product has 8
-significant bits.  The one rounding the fp8 path adds is P -> e4m3 (v_cvt_pk_fp8_f32, round to nearest): P is at most
-2^8 under the deferred rescale, so |q(P) - P| <= max(2^-4 P, 2^-10) - half an ulp of 3 mantissa bits for normal values,
-half the subnormal spacing 2^-9 below 2^-6.  The row sum l is taken from the fp32 P, so with p = P / l (the exact
-probabilities) the error of one output element is bounded by
-    |out_i - ref_i| <= 2^-4 sum_j p_ij |v_jd| + 2^-10 sum_j |v_jd| / l_i  +  bf16 rounding of out (2^-9 |ref|),
-and l_i >= 1 (the row's largest P is exp2(s_max - m_run) with m_run <= s_max), i.e. 1 / l_i <= max_j p_ij.  The gate is
-that bound with the bf16 term doubled (2^-8 |ref|) and 1e-6 for fp32 accumulation; the tests assert every element inside
-it and report the largest ratio error / bound.  It is never widened to make a case pass.  One MI355X run of this file: the
-largest ratio over all random, varlen and bf16-consistency cases was 0.71 (the P roundings do not all line up as the bound
-assumes), the smallest 0.16.
-The LSE gate is tests/util.py's LSE_ATOL: the scores are exact e4m3 products summed in fp32 and P's rounding does not
-enter l."""
+The out / LSE gate is tests/fp8_gate.py's (derived there, shared with the fp8 kinds of tests/fuzz_cases.py).  The fixed
+unit-magnitude tests keep their LSE at LSE_ATOL alone."""
 
 import numpy as np
 import pytest
 import torch
 
+import fp8_gate
 import oracle
-from oracle.attention import normalize_flags, score_matrix, visible_mask
+from oracle.attention import normalize_flags, visible_mask
 from util import LSE_ATOL, assert_lse_close
 
 pytestmark = pytest.mark.gpu
@@ -59,41 +49,15 @@ def _vcodes(B, S, H, D, seed=0):
 
 
 def _bound(qh, kh, vh, scale, causal, window):
-    """per element (rows x D) gate of one head, see the module docstring"""
-    sq, sk = qh.shape[0], kh.shape[0]
-    if sk == 0:
-        return np.zeros((sq, vh.shape[1]))
-    c, wl, wr = normalize_flags(sq, sk, causal, window[0], window[1], False)
-    s, vis = score_matrix(qh, kh, scale, c, wl, wr, 0.0, None)
-    m = np.max(s, axis=1, keepdims=True)
-    m = np.where(np.isfinite(m), m, 0.0)
-    e = np.where(vis, np.exp(s - m), 0.0)
-    l = e.sum(axis=1, keepdims=True)
-    p = e / np.where(l > 0, l, 1.0)
-    av = np.abs(vh)
-    return 2.0 ** -4 * (p @ av) + 2.0 ** -10 * p.max(axis=1, keepdims=True) * (vis @ av)
+    """per element (rows x D) out bound of one head, see tests/fp8_gate.py"""
+    return fp8_gate.bound(qh, kh, vh, scale, causal, window)[0]
 
 
-def _check_out(got, ref, bound, name):
-    """got / ref [..., D]; bound of the same shape (without the output-rounding term)"""
-    tol = bound + 2.0 ** -8 * np.abs(ref) + 1e-6
-    err = np.abs(got - ref)
-    assert np.isfinite(got).all(), f"{name}: non-finite output"
-    ratio = float((err / tol).max()) if err.size else 0.0
-    print(f"{name}: max |err| {err.max() if err.size else 0:.3e}, max err / gate {ratio:.3f}")
-    assert ratio <= 1.0, f"{name}: error {ratio:.3f} x the P-rounding gate"
-    return ratio
+_check_out = fp8_gate.check_out
 
 
 def _dense_bound(q8, k8, v8, scale, causal, window):
-    q, k, v = _bhsd(q8), _bhsd(k8), _bhsd(v8)
-    B, H, S, D = q.shape
-    G = H // k.shape[1]
-    out = np.zeros_like(q)
-    for b in range(B):
-        for h in range(H):
-            out[b, h] = _bound(q[b, h], k[b, h // G], v[b, h // G], scale, causal, window)
-    return out
+    return fp8_gate.dense_bound(_bhsd(q8), _bhsd(k8), _bhsd(v8), scale, causal, window)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -210,6 +174,11 @@ RANDOM_CASES = [
     (2, 190, 190, 4, 4, 80, True, (-1, -1)),       # narrow rows: kernel width 128, 80 valid columns
     (1, 260, 130, 4, 2, 112, False, (-1, -1)),
     (1, 130, 260, 2, 2, 48, False, (32, 0)),       # width 64, 48 valid columns
+    (1, 300, 300, 4, 2, 128, False, (-1, 40)),     # right-only window: q-block pairing
+    (2, 260, 390, 4, 1, 64, True, (50, -1)),       # causal + left window
+    (1, 200, 200, 2, 2, 16, True, (-1, -1)),       # width 64, 16 valid columns
+    (1, 129, 200, 2, 1, 32, False, (-1, -1)),
+    (1, 150, 150, 2, 2, 72, False, (-1, -1)),      # D 72: zero-padded to 80 in Python
 ]
 
 
@@ -251,17 +220,9 @@ def test_varlen_with_empty_sequences_and_descales(D, causal, window):
     o_ref, lse_ref = oracle.varlen_fwd(q, k, v, cu_q.cpu().numpy(), cu_k.cpu().numpy(), max(lq), max(lk), scale,
                                        causal=causal, window=window)
     assert_lse_close(_d(lse), lse_ref, "lse")
-    got = _d(out)
-    bound = np.zeros_like(o_ref)
-    cq, ck = cu_q.cpu().numpy(), cu_k.cpu().numpy()
-    for b in range(len(lq)):
-        if lq[b] == 0:
-            continue
-        for h in range(H):
-            g = h // (H // Hk)
-            bound[cq[b]:cq[b + 1], h] = _bound(q[cq[b]:cq[b + 1], h], k[ck[b]:ck[b + 1], g], v[ck[b]:ck[b + 1], g], scale,
-                                               causal, window)
-    _check_out(got, o_ref, bound, "varlen out")
+    bound, _ = fp8_gate.varlen_bound(q, k, v, cu_q.cpu().numpy(), cu_k.cpu().numpy(), max(lq), max(lk), scale, causal,
+                                     window)
+    _check_out(_d(out), o_ref, bound, "varlen out")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -389,3 +350,278 @@ def test_graph_replay_equals_eager():
     out_e, lse_e = fn()
     torch.cuda.synchronize()
     assert torch.equal(out_g, out_e) and torch.equal(lse_g, lse_e)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the C ABI: fp16 out (o_dtype = FA_FP16), descales, strided heads / batches
+# ---------------------------------------------------------------------------------------------------------------------
+def _abi_call(op, q8, k8, v8, o, lse, D, scale, causal, window, ds, o_dtype, cu=None):
+    """fa_fwd ([B, S, H, D] views) or fa_varlen_fwd ([T, H, D] views, cu = (cu_q, cu_k, max_q, max_k)) straight through
+    ctypes; o [.., H, D] 16-bit, lse [B, H, S] / [H, T]"""
+    from flash_attn_mi355 import _lib
+    p = _lib.FaParams()
+    p.q, p.k, p.v, p.o, p.lse = q8.data_ptr(), k8.data_ptr(), v8.data_ptr(), o.data_ptr(), lse.data_ptr()
+    p.dtype = p.kv_dtype = _lib.FA_FP8_E4M3
+    p.o_dtype = o_dtype
+    p.q_descale, p.k_descale, p.v_descale = ds
+    p.softmax_scale = scale
+    p.is_causal = int(causal)
+    p.window_left, p.window_right = window
+    p.head_dim = 64 if D <= 64 else 128
+    p.head_dim_v = D if D != p.head_dim else 0
+    p.nheads_q, p.nheads_k = q8.shape[-2], k8.shape[-2]
+    for name, t in (("q", q8), ("k", k8), ("v", v8), ("o", o)):
+        if cu is None:
+            b, r, h = t.stride(0), t.stride(1), t.stride(2)
+        else:
+            b, r, h = 0, t.stride(0), t.stride(1)
+        setattr(p, name + "_batch_stride", b)
+        setattr(p, name + "_row_stride", r)
+        setattr(p, name + "_head_stride", h)
+    if cu is None:
+        p.batch, p.seqlen_q, p.seqlen_k = q8.shape[0], q8.shape[1], k8.shape[1]
+        p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
+    else:
+        cu_q, cu_k, mq, mk = cu
+        p.batch, p.seqlen_q, p.seqlen_k = cu_q.numel() - 1, mq, mk
+        p.cu_seqlens_q, p.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+        p.total_q, p.total_k = q8.shape[0], k8.shape[0]
+        p.lse_batch_stride, p.lse_head_stride = 0, lse.stride(0)
+    _lib.call(op, p, torch.cuda.current_stream().cuda_stream)
+
+
+def _strided8(shape, seed, mag=1.0):
+    """every other head of a buffer twice as wide (non-contiguous head and batch strides, 16-byte multiples)"""
+    *lead, H, D = shape
+    return _rand8((*lead, 2 * H, D), seed, mag)[..., ::2, :]
+
+
+def _both_roundings_agree(o16, obf, name):
+    """fp16 and bf16 out are roundings of the same fp32 accumulator y: |fp16 - bf16| <= half an ulp of each at y, i.e.
+    (2^-8 + 2^-11) |y| + 2^-25 (fp16's half subnormal spacing), with |y| <= (1 + 2^-8) max(|fp16|, |bf16|)"""
+    a, b = o16.double(), obf.double()
+    tol = (2.0 ** -8 + 2.0 ** -11) * (1 + 2.0 ** -8) * torch.maximum(a.abs(), b.abs()) + 2.0 ** -25
+    bad = ((a - b).abs() > tol)
+    assert not bool(bad.any()), f"{name}: {int(bad.sum())} elements of the fp16 out are not the bf16 out's rounding " \
+                                f"(first at {tuple(torch.nonzero(bad)[0].tolist())})"
+
+
+ABI_CASES = [
+    # (D, causal, window, descales (q, k, v))
+    (64, True, (-1, -1), (0.5, 0.25, 3.0)),
+    (128, False, (-1, -1), (0.013, 2.0, 0.37)),
+    (80, False, (33, 9), (2.0, 0.125, 0.013)),
+]
+
+
+@pytest.mark.parametrize("D,causal,window,ds", ABI_CASES)
+def test_c_abi_fp16_and_bf16_out(D, causal, window, ds):
+    from flash_attn_mi355 import _lib
+    B, Sq, Sk, H, Hk = 2, 200, 263, 4, 2
+    scale = 0.3
+    q8, k8, v8 = _strided8((B, Sq, H, D), 61), _strided8((B, Sk, Hk, D), 62), _strided8((B, Sk, Hk, D), 63)
+    outs = {}
+    for name, odt, tdt in (("fp16", _lib.FA_FP16, torch.float16), ("bf16", _lib.FA_BF16, torch.bfloat16)):
+        o = torch.full((B, Sq, 2 * H, D), float("nan"), dtype=tdt, device="cuda")[:, :, 1::2]
+        lse = torch.empty(B, H, Sq, dtype=torch.float32, device="cuda")
+        _abi_call("fa_fwd", q8, k8, v8, o, lse, D, scale, causal, window, ds, odt)
+        outs[name] = (o, lse)
+    torch.cuda.synchronize()
+    _both_roundings_agree(outs["fp16"][0], outs["bf16"][0], "fa_fwd")
+    assert torch.equal(outs["fp16"][1], outs["bf16"][1])
+    q, k, v = (_bhsd(t) * d for t, d in zip((q8, k8, v8), ds))
+    o_ref, lse_ref, _ = oracle.attn_fwd(q, k, v, scale, causal=causal, window=window)
+    bnd, delta = fp8_gate.dense_bound(q, k, v, scale, causal, window)
+    for name in ("fp16", "bf16"):
+        _check_out(_bhsd(outs[name][0]), o_ref, bnd, f"fa_fwd {name} out", o_dtype=name)
+    fp8_gate.check_lse(_d(outs["bf16"][1]), lse_ref, delta, "fa_fwd lse")
+
+
+@pytest.mark.parametrize("D,causal,window,ds", ABI_CASES)
+def test_c_abi_varlen_fp16_and_bf16_out(D, causal, window, ds):
+    from flash_attn_mi355 import _lib
+    lq, lk = [70, 0, 129, 1, 256], [70, 5, 300, 0, 64]
+    H, Hk = 4, 1
+    scale = 0.21
+    cu_q = torch.tensor(np.concatenate([[0], np.cumsum(lq)]), dtype=torch.int32, device="cuda")
+    cu_k = torch.tensor(np.concatenate([[0], np.cumsum(lk)]), dtype=torch.int32, device="cuda")
+    q8, k8, v8 = _strided8((sum(lq), H, D), 71), _strided8((sum(lk), Hk, D), 72), _strided8((sum(lk), Hk, D), 73)
+    outs = {}
+    for name, odt, tdt in (("fp16", _lib.FA_FP16, torch.float16), ("bf16", _lib.FA_BF16, torch.bfloat16)):
+        o = torch.full((sum(lq), 2 * H, D), float("nan"), dtype=tdt, device="cuda")[:, ::2]
+        lse = torch.empty(H, sum(lq), dtype=torch.float32, device="cuda")
+        _abi_call("fa_varlen_fwd", q8, k8, v8, o, lse, D, scale, causal, window, ds, odt, cu=(cu_q, cu_k, max(lq), max(lk)))
+        outs[name] = (o, lse)
+    torch.cuda.synchronize()
+    _both_roundings_agree(outs["fp16"][0], outs["bf16"][0], "fa_varlen_fwd")
+    assert torch.equal(outs["fp16"][1], outs["bf16"][1])
+    q, k, v = (_d(t) * d for t, d in zip((q8, k8, v8), ds))
+    cq, ck = cu_q.cpu().numpy(), cu_k.cpu().numpy()
+    o_ref, lse_ref = oracle.varlen_fwd(q, k, v, cq, ck, max(lq), max(lk), scale, causal=causal, window=window)
+    bnd, delta = fp8_gate.varlen_bound(q, k, v, cq, ck, max(lq), max(lk), scale, causal, window)
+    for name in ("fp16", "bf16"):
+        _check_out(_d(outs[name][0]), o_ref, bnd, f"fa_varlen_fwd {name} out", o_dtype=name)
+    fp8_gate.check_lse(_d(outs["bf16"][1]), lse_ref, delta, "fa_varlen_fwd lse")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# config 2 in full against an fp64 reference
+# ---------------------------------------------------------------------------------------------------------------------
+def test_config_2_every_row_against_fp64():
+    """B 8, H 16, S 4096, D 128, causal (the bench's forward shape): every output row and LSE against an fp64 reference and
+    the fp8 gate, both computed per (b, h) in torch.float64 on the device"""
+    import time
+    fa = _fa()
+    B, S, H, D = 8, 4096, 16, 128
+    q8, k8, v8 = _rand8((B, S, H, D), 51), _rand8((B, S, H, D), 52), _rand8((B, S, H, D), 53)
+    out, lse, _ = fa.flash_attn_func(q8, k8, v8, causal=True, return_attn_probs=True)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    worst, worst_lse = 0.0, 0.0
+    for b in range(B):
+        for h in range(H):
+            bnd, delta, ref, lref = fp8_gate.head_gate(q8[b, :, h].double(), k8[b, :, h].double(), v8[b, :, h].double(),
+                                                       D ** -0.5, True, -1, -1, with_ref=True)
+            got = out[b, :, h].double()
+            assert bool(torch.isfinite(got).all()), f"b{b} h{h}: non-finite out"
+            r = float(((got - ref).abs() / fp8_gate.gate(ref, bnd)).max())
+            assert r <= 1.0, f"b{b} h{h}: out error {r:.3f} x the fp8 gate"
+            gl = lse[b, h].double()
+            rl = float(((gl - lref).abs() / (LSE_ATOL + delta)).max())
+            assert rl <= 1.0, f"b{b} h{h}: LSE error {rl:.3f} x its gate"
+            worst, worst_lse = max(worst, r), max(worst_lse, rl)
+    torch.cuda.synchronize()
+    print(f"config 2: worst out error / gate {worst:.3f}, LSE {worst_lse:.3f}; fp64 reference + gate {time.time() - t0:.1f} s")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the deferred rescale at its bound, exact data
+# ---------------------------------------------------------------------------------------------------------------------
+def _e4m3_terms(x, n):
+    """x (a multiple of 1/4, 0 <= x < 128) as a sum of n e4m3 values (greedy; exact)"""
+    grid = torch.arange(0, 256, dtype=torch.uint8).view(F8).float()
+    grid = torch.unique(grid[torch.isfinite(grid) & (grid >= 0)]).double().numpy()
+    out, r = [], float(x)
+    for _ in range(n):
+        t = float(grid[grid <= r + 1e-12].max())
+        out.append(t)
+        r -= t
+    assert r == 0.0, (x, out)
+    return out
+
+
+def _rescale_plan(tmax, wave_of_b, ntiles):
+    """host model of the kernel's deferred rescale for waves of 32 rows: per wave and tile, 'keep' or 'rescale' and
+    whether some row alone would have kept (row maxima tmax[type][tile], log2 units)"""
+    plan = {}
+    for w, types in wave_of_b.items():
+        m = np.full(len(types), -np.inf)
+        for t in range(ntiles):
+            mx = np.array([tmax[ty][t] for ty in types])
+            with np.errstate(invalid="ignore"):
+                keep = bool(np.all(mx - m <= 8.0))
+                alone = bool(np.any(mx - m <= 8.0))
+            plan[w, t] = ("keep", float((mx - m).max())) if keep else ("rescale", alone)
+            if not keep:
+                m = np.maximum(m, mx)
+    return plan
+
+
+def test_deferred_rescale_at_its_bound():
+    """scaled log2 scores built from exact e4m3 sums (softmax_scale = ln 2: the kernel's c is 1): row type A raises its
+    maximum by 7.75 every 64-key tile (just under the 2^8 threshold), type B by 8.25 (just over), type C by 8.25 / 7.75
+    alternately.  A wave of A rows keeps the maximum on every other tile (P up to 2^7.75 = 215 of e4m3's 448), a wave of
+    B rows rescales on every tile, a wave of A and C rows takes both paths with its rows disagreeing on the first
+    rescale, and a wave of A rows with one B row rescales on every tile against 31 rows that would keep.  The remaining
+    keys of a tile trail the tile's maximum by 1/4 .. 63/4 so that P covers e4m3's normal and subnormal ranges."""
+    fa = _fa()
+    D, ntiles, H = 64, 9, 2
+    Sq, Sk = 128, 64 * ntiles
+    tmax = {"A": [7.75 * t for t in range(ntiles)], "B": [8.25 * t for t in range(ntiles)], "C": [0.0]}
+    for t in range(1, ntiles):
+        tmax["C"].append(tmax["C"][-1] + (8.25 if t % 2 else 7.75))
+    types = ["A"] * 32 + ["B"] * 32 + ["A", "C"] * 16 + ["A"] * 31 + ["B"]
+    plan = _rescale_plan(tmax, {w: types[32 * w:32 * w + 32] for w in range(4)}, ntiles)
+    for t in range(ntiles):
+        print(f"tile {t}: " + "  ".join(f"wave {w} {plan[w, t]}" for w in range(4)))
+    # (the construction: both paths and a disagreeing rescale in wave 2, the kept path near the bound)
+    assert any(plan[2, t][0] == "keep" and plan[2, t][1] >= 7.5 for t in range(ntiles))
+    assert any(plan[2, t] == ("rescale", True) for t in range(ntiles))
+    assert any(plan[0, t][0] == "keep" for t in range(ntiles)) and all(plan[1, t][0] == "rescale" for t in range(ntiles))
+    assert all(plan[3, t] == ("rescale", True) for t in range(1, ntiles))
+    q = torch.zeros(1, Sq, H, D)
+    k = torch.zeros(1, Sk, 1, D)
+    dims = {"A": 0, "B": 8, "C": 16}
+    for i, ty in enumerate(types):
+        q[0, i, :, dims[ty]:dims[ty] + 8] = 1.0
+    for j in range(Sk):
+        t, pos = divmod(j, 64)
+        peak = (5 * t + 3) % 64                                     # the tile's maximum moves around the tile
+        trail = 0.25 * ((pos - peak) % 64)
+        for ty, d0 in dims.items():                                 # (+16 keeps every sum >= 0; a row-wise shift)
+            k[0, j, 0, d0:d0 + 4] = torch.tensor(_e4m3_terms(tmax[ty][t] - trail + 16.0, 4))
+    q8, k8 = q.to(F8).cuda(), k.to(F8).cuda()
+    assert torch.equal(q8.float().cpu(), q) and torch.equal(k8.float().cpu(), k)
+    v8 = _rand8((1, Sk, 1, D), 81)
+    scale = float(np.log(2.0))
+    out, lse, _ = fa.flash_attn_func(q8, k8, v8, softmax_scale=scale, return_attn_probs=True)
+    torch.cuda.synchronize()
+    qd, kd, vd = _bhsd(q8), _bhsd(k8), _bhsd(v8)
+    o_ref, lse_ref, _ = oracle.attn_fwd(qd, kd, vd, scale)
+    bnd, delta = fp8_gate.dense_bound(qd, kd, vd, scale, False, (-1, -1))
+    _check_out(_bhsd(out), o_ref, bnd, "rescale-bound out")
+    fp8_gate.check_lse(_d(lse), lse_ref, delta, "rescale-bound lse")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# edges and entry points
+# ---------------------------------------------------------------------------------------------------------------------
+def test_dense_without_keys_or_queries():
+    fa = _fa()
+    q8 = _rand8((2, 70, 4, 128), 1)
+    e8 = torch.empty(2, 0, 2, 128, dtype=F8, device="cuda")
+    for causal in (False, True):
+        out, lse, _ = fa.flash_attn_func(q8, e8, e8, causal=causal, return_attn_probs=True)
+        torch.cuda.synchronize()
+        assert out.shape == (2, 70, 4, 128) and out.dtype == torch.bfloat16
+        assert bool((out == 0).all()) and bool(torch.isneginf(lse).all()), "Sk = 0: out 0, LSE -inf"
+    k8 = _rand8((2, 33, 2, 64), 2)
+    out, lse, _ = fa.flash_attn_func(q8[:, :0, :, :64], k8, k8, causal=True, return_attn_probs=True)
+    torch.cuda.synchronize()
+    assert out.shape == (2, 0, 4, 64) and lse.shape == (2, 4, 0)
+
+
+def test_packed_entry_points_match_the_unpacked_call():
+    """fp8 through the four packed entry points (views into the packed buffer, passed to the kernel without a copy) gives
+    bit for bit what flash_attn_func / flash_attn_varlen_func give on contiguous copies; with requires_grad they raise
+    the forward-only error at forward time"""
+    fa = _fa()
+    B, S, H, D = 2, 300, 4, 128
+    qkv = _rand8((B, S, 3, H, D), 91)
+    c = lambda t: t.contiguous()
+    got = fa.flash_attn_qkvpacked_func(qkv, causal=True, return_attn_probs=True)
+    want = fa.flash_attn_func(c(qkv[:, :, 0]), c(qkv[:, :, 1]), c(qkv[:, :, 2]), causal=True, return_attn_probs=True)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), "qkvpacked"
+    q8, kv = _rand8((B, 200, 2 * H, D), 92), _rand8((B, S, 2, H, D), 93)
+    got = fa.flash_attn_kvpacked_func(q8, kv, window_size=(40, 7), return_attn_probs=True)
+    want = fa.flash_attn_func(q8, c(kv[:, :, 0]), c(kv[:, :, 1]), window_size=(40, 7), return_attn_probs=True)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), "kvpacked"
+    lens = [100, 0, 257, 64]
+    cu = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int32, device="cuda")
+    tqkv = _rand8((sum(lens), 3, H, D), 94)
+    got = fa.flash_attn_varlen_qkvpacked_func(tqkv, cu, max(lens), causal=True, return_attn_probs=True)
+    want = fa.flash_attn_varlen_func(c(tqkv[:, 0]), c(tqkv[:, 1]), c(tqkv[:, 2]), cu, cu, max(lens), max(lens),
+                                     causal=True, return_attn_probs=True)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), "varlen qkvpacked"
+    tq, tkv = _rand8((sum(lens), 2 * H, D), 95), _rand8((sum(lens), 2, H, D), 96)
+    got = fa.flash_attn_varlen_kvpacked_func(tq, tkv, cu, cu, max(lens), max(lens), return_attn_probs=True)
+    want = fa.flash_attn_varlen_func(tq, c(tkv[:, 0]), c(tkv[:, 1]), cu, cu, max(lens), max(lens), return_attn_probs=True)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), "varlen kvpacked"
+    torch.cuda.synchronize()
+    for call in (lambda: fa.flash_attn_qkvpacked_func(qkv.clone().requires_grad_()),
+                 lambda: fa.flash_attn_kvpacked_func(q8, kv.clone().requires_grad_()),
+                 lambda: fa.flash_attn_kvpacked_func(q8.clone().requires_grad_(), kv),
+                 lambda: fa.flash_attn_varlen_qkvpacked_func(tqkv.clone().requires_grad_(), cu, max(lens)),
+                 lambda: fa.flash_attn_varlen_kvpacked_func(tq, tkv.clone().requires_grad_(), cu, cu, max(lens), max(lens))):
+        with pytest.raises(RuntimeError, match="forward-only"):
+            call()
