@@ -22,6 +22,7 @@ int launch_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t n
 int launch_scatter_rows(const void* src, const int64_t* idx, void* dst, int64_t n_idx, int64_t n_dst_rows,
                         int64_t row_bytes, int sorted_unique, hipStream_t stream);
 int launch_bwd(const KArgs& a, hipStream_t stream);
+int launch_bwd_dsinks(const KArgs& a, float* dsinks, hipStream_t stream);   // fa_bwd.hip: gradient of the attention sinks
 size_t bwd_workspace_bytes(const fa_params& p);
 int launch_kvcache_append(const KArgs& a, hipStream_t stream);
 int launch_decode(const KArgs& a, hipStream_t stream);
@@ -135,6 +136,27 @@ static int check_fp8_q(fa_params& p) {
     if (p.block_table) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: paged K/V is not supported");
     if (p.head_dim > 128) return fail(FA_ERR_UNSUPPORTED, "fp8-e4m3 q: head dimension %d is not supported (64, 128)", p.head_dim);
     FA_CHECK(p.head_dim_v % 16 == 0, "fp8-e4m3 q: head_dim_v must be a multiple of 16");
+    return FA_OK;
+}
+
+// fa_ext_params (the *_ext entry points): checked before anything else, so that a bad block fails without a launch.
+// fwd: a forward op (dsinks is a backward output).  On success *sinks / *dsinks are the pointers to use (NULL: none).
+static int check_ext(const fa_ext_params* ext, const fa_params* p, bool bwd, const float** sinks, float** dsinks) {
+    *sinks = nullptr;
+    *dsinks = nullptr;
+    if (!ext) return FA_OK;
+    FA_CHECK(ext->struct_size >= sizeof(fa_ext_params), "fa_ext_params::struct_size %zu is smaller than this library's fa_ext_params (%zu)",
+             ext->struct_size, sizeof(fa_ext_params));
+    FA_CHECK(bwd || !ext->dsinks, "fa_ext_params::dsinks is a backward output: set it only for fa_bwd_ext / fa_varlen_bwd_ext");
+    FA_CHECK(!ext->dsinks || ext->sinks, "fa_ext_params::dsinks needs fa_ext_params::sinks");
+    if (!ext->sinks) return FA_OK;
+    FA_CHECK(p, "params is NULL");
+    FA_CHECK((reinterpret_cast<uintptr_t>(ext->sinks) & 3) == 0 && (reinterpret_cast<uintptr_t>(ext->dsinks) & 3) == 0,
+             "attention sinks: sinks / dsinks must be 4-byte aligned fp32 arrays");
+    if (p->dtype == FA_FP8_E4M3) return fail(FA_ERR_UNSUPPORTED, "attention sinks are not supported with fp8-e4m3 q/k/v");
+    if (p->p_dropout > 0.f || p->dmask) return fail(FA_ERR_UNSUPPORTED, "attention sinks are not supported with dropout");
+    *sinks = ext->sinks;
+    *dsinks = ext->dsinks;
     return FA_OK;
 }
 
@@ -255,12 +277,18 @@ size_t fa_fwd_kvcache_workspace_bytes(const fa_params* pp) {
     return fa::decode_workspace_bytes(p);
 }
 
-int fa_fwd(const fa_params* pp, void* stream) {
+int fa_fwd(const fa_params* pp, void* stream) { return fa_fwd_ext(pp, nullptr, stream); }
+
+int fa_fwd_ext(const fa_params* pp, const fa_ext_params* ext, void* stream) {
+    const float* sinks;
+    float* dsinks;
+    int rc = check_ext(ext, pp, false, &sinks, &dsinks);
+    if (rc) return rc;
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
     p.cu_seqlens_q = p.cu_seqlens_k = p.seqused_k = nullptr;
     p.block_table = nullptr;
-    int rc = check_common(p, true, true);
+    rc = check_common(p, true, true);
     if (rc) return rc;
     const bool q8 = p.dtype == FA_FP8_E4M3;
     if (q8) {
@@ -272,15 +300,22 @@ int fa_fwd(const fa_params* pp, void* stream) {
     if (p.seqlen_q == 0) return FA_OK;
     normalize(p, false);
     fa::KArgs a = make_args(p, 128);
+    a.sinks = sinks;
     rc = q8 ? fa::launch_fwd_fp8(a, static_cast<hipStream_t>(stream)) : fa::launch_fwd(a, static_cast<hipStream_t>(stream));
     if (rc) return fail(FA_ERR_UNSUPPORTED, "no forward kernel for this configuration");
     return check_hip("fa_fwd launch");
 }
 
-int fa_varlen_fwd(const fa_params* pp, void* stream) {
+int fa_varlen_fwd(const fa_params* pp, void* stream) { return fa_varlen_fwd_ext(pp, nullptr, stream); }
+
+int fa_varlen_fwd_ext(const fa_params* pp, const fa_ext_params* ext, void* stream) {
+    const float* sinks;
+    float* dsinks;
+    int rc = check_ext(ext, pp, false, &sinks, &dsinks);
+    if (rc) return rc;
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
-    int rc = check_common(p, true, true);
+    rc = check_common(p, true, true);
     if (rc) return rc;
     if (p.dtype == FA_FP8_E4M3) {
         // fp8-e4m3 q, k, v (fa_fwd_fp8.hip): non-paged, flat work list
@@ -323,6 +358,7 @@ int fa_varlen_fwd(const fa_params* pp, void* stream) {
                 fa::KArgs ad = make_args(d, 128);
                 ad.seqlens_k = d.cache_seqlens;
                 ad.kv_mode = 1;
+                ad.sinks = sinks;
                 rc = fa::launch_decode(ad, static_cast<hipStream_t>(stream));
                 if (rc) return fail(FA_ERR_UNSUPPORTED, "no decode kernel for this varlen configuration");
                 return check_hip("fa_varlen_fwd (decode kernels) launch");
@@ -338,6 +374,7 @@ int fa_varlen_fwd(const fa_params* pp, void* stream) {
                 fa::KArgs ad = make_args(d, 128);
                 ad.seqlens_k = d.cache_seqlens;
                 ad.kv_mode = 1;
+                ad.sinks = sinks;
                 rc = fa::launch_decode(ad, static_cast<hipStream_t>(stream));
                 if (rc) return fail(FA_ERR_UNSUPPORTED, "no decode kernel for the short sequences of this varlen batch");
                 skip_short = d.seqlen_q;             // the general kernel below leaves those sequences out
@@ -348,6 +385,7 @@ int fa_varlen_fwd(const fa_params* pp, void* stream) {
     fa::KArgs a = make_args(p, 128);
     a.seqlens_k = p.seqused_k;
     a.skip_short_q = skip_short;
+    a.sinks = sinks;
     if (p.total_q > 0 && !varlen_grid_env()) {     // flat work list (fa_common.h: decode_work_flat)
         a.flat_blocks = p.total_q / 128 + p.batch;
         a.pair_qblocks = 0;
@@ -358,11 +396,17 @@ int fa_varlen_fwd(const fa_params* pp, void* stream) {
     return check_hip("fa_varlen_fwd launch");
 }
 
-int fa_fwd_kvcache(const fa_params* pp, void* stream) {
+int fa_fwd_kvcache(const fa_params* pp, void* stream) { return fa_fwd_kvcache_ext(pp, nullptr, stream); }
+
+int fa_fwd_kvcache_ext(const fa_params* pp, const fa_ext_params* ext, void* stream) {
+    const float* sinks;
+    float* dsinks;
+    int rc = check_ext(ext, pp, false, &sinks, &dsinks);
+    if (rc) return rc;
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
     p.cu_seqlens_q = p.cu_seqlens_k = p.seqused_k = nullptr;
-    int rc = check_common(p, true);
+    rc = check_common(p, true);
     if (rc) return rc;
     FA_CHECK(p.kv_dtype == p.dtype || p.kv_dtype == FA_FP8_E4M3, "kcache/vcache must match q dtype or be fp8-e4m3");
     FA_CHECK(p.p_dropout == 0.f, "kvcache attention has no dropout");
@@ -406,6 +450,7 @@ int fa_fwd_kvcache(const fa_params* pp, void* stream) {
     a.kv_batch_idx = p.cache_batch_idx;
     a.leftpad_k = p.cache_leftpad;
     a.kv_mode = 1;
+    a.sinks = sinks;
     rc = fa::launch_decode(a, s);
     if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no kvcache kernel for this configuration (fp8 caches: head_dim 64 or 128)");
     if (rc == -1) return fail(FA_ERR_INVALID_ARGUMENT, "workspace too small: query fa_fwd_kvcache_workspace_bytes()");
@@ -413,30 +458,60 @@ int fa_fwd_kvcache(const fa_params* pp, void* stream) {
     return check_hip("fa_fwd_kvcache launch");
 }
 
-int fa_bwd(const fa_params* pp, void* stream) {
+// The sinks' gradient (fa_bwd_ext / fa_varlen_bwd_ext): after launch_bwd on the same stream, when softmax_d is final
+// whichever kernel wrote it; zeros when there are no query rows.
+static int dsinks_launch(const fa::KArgs& a, const float* sinks, float* dsinks, bool no_rows, hipStream_t s) {
+    if (!dsinks) return FA_OK;
+    if (no_rows) {
+        if (hipMemsetAsync(dsinks, 0, (size_t)a.p.nheads_q * sizeof(float), s) != hipSuccess)
+            return fail(FA_ERR_LAUNCH, "hipMemsetAsync(dsinks) failed");
+        return FA_OK;
+    }
+    fa::KArgs a2 = a;
+    a2.sinks = sinks;
+    fa::launch_bwd_dsinks(a2, dsinks, s);
+    return check_hip("dsinks launch");
+}
+
+int fa_bwd(const fa_params* pp, void* stream) { return fa_bwd_ext(pp, nullptr, stream); }
+
+int fa_bwd_ext(const fa_params* pp, const fa_ext_params* ext, void* stream) {
+    const float* sinks;
+    float* dsinks;
+    int rc = check_ext(ext, pp, true, &sinks, &dsinks);
+    if (rc) return rc;
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
     p.cu_seqlens_q = p.cu_seqlens_k = p.seqused_k = nullptr;
     p.block_table = nullptr;
-    int rc = check_common(p, true);
+    rc = check_common(p, true);
     if (rc) return rc;
     FA_CHECK(p.dout && p.softmax_d, "dout and softmax_d must not be NULL");
     FA_CHECK((p.dk == nullptr) == (p.dv == nullptr), "dk and dv must be given (or left NULL) together");
     FA_CHECK(p.kv_dtype == p.dtype, "k/v must have the same dtype as q");
-    if (p.seqlen_q == 0 && p.seqlen_k == 0) return FA_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.seqlen_q == 0 && p.seqlen_k == 0) return dsinks_launch(make_args(p, 128), sinks, dsinks, true, s);
     normalize(p, false);
     fa::KArgs a = make_args(p, 128);
-    rc = fa::launch_bwd(a, static_cast<hipStream_t>(stream));
+    rc = fa::launch_bwd(a, s);
     if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no backward kernel for this configuration");
     if (rc) return rc;
-    return check_hip("fa_bwd launch");
+    rc = check_hip("fa_bwd launch");
+    if (rc) return rc;
+    return dsinks_launch(a, sinks, dsinks, p.seqlen_q == 0, s);
 }
 
-int fa_varlen_bwd(const fa_params* pp, void* stream) {
+int fa_varlen_bwd(const fa_params* pp, void* stream) { return fa_varlen_bwd_ext(pp, nullptr, stream); }
+
+int fa_varlen_bwd_ext(const fa_params* pp, const fa_ext_params* ext, void* stream) {
+    const float* sinks;
+    float* dsinks;
+    int rc = check_ext(ext, pp, true, &sinks, &dsinks);
+    if (rc) return rc;
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
     p.block_table = nullptr;
-    int rc = check_common(p, true);
+    rc = check_common(p, true);
     if (rc) return rc;
     FA_CHECK(p.dout && p.softmax_d, "dout and softmax_d must not be NULL");
     FA_CHECK((p.dk == nullptr) == (p.dv == nullptr), "dk and dv must be given (or left NULL) together");
@@ -452,7 +527,7 @@ int fa_varlen_bwd(const fa_params* pp, void* stream) {
                 hipMemset2DAsync(reinterpret_cast<uint16_t*>(p.dv) + (int64_t)h * p.dv_head_stride, (size_t)p.dv_row_stride * 2, 0, width, (size_t)rows, s) != hipSuccess)
                 return fail(FA_ERR_LAUNCH, "hipMemset2DAsync(dk / dv) failed");
         }
-        return FA_OK;
+        return dsinks_launch(make_args(p, 128), sinks, dsinks, true, s);
     }
     normalize(p, false);
     fa::KArgs a = make_args(p, 128);
@@ -464,7 +539,9 @@ int fa_varlen_bwd(const fa_params* pp, void* stream) {
     rc = fa::launch_bwd(a, static_cast<hipStream_t>(stream));
     if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no varlen backward kernel for this configuration");
     if (rc) return rc;
-    return check_hip("fa_varlen_bwd launch");
+    rc = check_hip("fa_varlen_bwd launch");
+    if (rc) return rc;
+    return dsinks_launch(a, sinks, dsinks, false, static_cast<hipStream_t>(stream));
 }
 
 int fa_gather_rows(const void* src, const int64_t* indices, void* dst, int64_t n_idx, int64_t row_bytes,

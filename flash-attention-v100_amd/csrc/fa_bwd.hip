@@ -68,6 +68,73 @@ __global__ void __launch_bounds__(256) bwd_preprocess_kernel(const KArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// 1b. attention sinks: dL/ds_h = -sum_{b,i} exp(s_h - LSE_{b,h,i}) D_{b,h,i}
+// ---------------------------------------------------------------------------------------------
+// One workgroup per query head over every row of that head, after softmax_d is final (stream order: launch_bwd has
+// returned).  Each thread walks a fixed stride of rows with four independent accumulators (four loads in flight: the
+// kernel is latency-bound, ~8 rows per thread at B x Sq = 8 k), and the partial sums meet in a fixed tree: bitwise
+// repeatable, no atomics.  Dense rows are B x Sq of the [B, H, Sq] layout, packed rows the first cu_seqlens_q[B] of
+// [H, total_q] (rows behind the last sequence hold no results).  The LSE is the sink-inclusive one: exp(s_h - LSE) <= 1.
+constexpr int DSINK_THREADS = 1024;
+__global__ void __launch_bounds__(DSINK_THREADS) bwd_dsinks_kernel(const KArgs a, float* __restrict__ dsinks) {
+    const fa_params& p = a.p;
+    const int h = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float s = a.sinks[h];
+    int nb;
+    int64_t per_b;
+    if (p.cu_seqlens_q) {
+        const int64_t used = p.cu_seqlens_q[p.batch];
+        nb = 1;
+        per_b = used < (int64_t)p.total_q ? used : (int64_t)p.total_q;
+    } else {
+        nb = p.batch;
+        per_b = p.seqlen_q;
+    }
+    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+    if (s > -INFINITY) {                                    // (a sink of -inf has no gradient)
+        constexpr int T = DSINK_THREADS;
+        for (int b = 0; b < nb; ++b) {
+            const int64_t at = (int64_t)b * p.lse_batch_stride + (int64_t)h * p.lse_head_stride;
+            const float* L = p.lse + at;
+            const float* Dd = p.softmax_d + at;
+            int64_t i = tid;
+            for (; i + 3 * T < per_b; i += 4 * T) {
+                const float l0 = L[i], l1 = L[i + T], l2 = L[i + 2 * T], l3 = L[i + 3 * T];
+                const float d0 = Dd[i], d1 = Dd[i + T], d2 = Dd[i + 2 * T], d3 = Dd[i + 3 * T];
+                acc0 = fmaf(__expf(s - l0), d0, acc0);
+                acc1 = fmaf(__expf(s - l1), d1, acc1);
+                acc2 = fmaf(__expf(s - l2), d2, acc2);
+                acc3 = fmaf(__expf(s - l3), d3, acc3);
+            }
+            for (; i < per_b; i += T) acc0 = fmaf(__expf(s - L[i]), Dd[i], acc0);
+        }
+    }
+    float acc = (acc0 + acc1) + (acc2 + acc3);
+    __shared__ float red[DSINK_THREADS / 64];
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        float t[DSINK_THREADS / 64];
+#pragma unroll
+        for (int w = 0; w < DSINK_THREADS / 64; ++w) t[w] = red[w];
+#pragma unroll
+        for (int n = DSINK_THREADS / 128; n > 0; n >>= 1)
+#pragma unroll
+            for (int w = 0; w < n; ++w) t[w] += t[w + n];
+        dsinks[h] = -t[0];
+    }
+}
+
+int launch_bwd_dsinks(const KArgs& a, float* dsinks, hipStream_t stream) {
+    if (a.p.nheads_q <= 0) return 0;
+    hipLaunchKernelGGL(bwd_dsinks_kernel, dim3(a.p.nheads_q), dim3(DSINK_THREADS), 0, stream, a, dsinks);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // shared geometry
 // ---------------------------------------------------------------------------------------------
 // (SeqGeom / seq_geom / DKV_BN: fa_common.h - shared with fa_bwd_d256.hip)

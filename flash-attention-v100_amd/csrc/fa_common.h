@@ -512,7 +512,26 @@ struct KArgs {
     // dK / dV and dkv_reduce_kernel sums them (fa_bwd.hip: dkv_split_factor)
     int dkv_split;                 // 0 / 1: one workgroup per key block
     void* dkv_part;                // fp32 [dK | dV][dkv_split][B][Sk][Hk][head_dim]
+    // attention sinks (fa_ext_params::sinks): [nheads_q] fp32 logits, natural log; NULL = none.  Read only where a FINAL
+    // output is normalised (sink_fold below); split partials and the backward kernels never see it
+    const float* sinks;
 };
+
+// Attention sink of a row of head h: one more term e^{s_h} of the softmax denominator, with no value.  m is the kernel's
+// reference maximum in log2 units (the one O and l are relative to - under the deferred rescale the stale one), l the
+// row's denominator.  On return m and l are the sink-inclusive reference and denominator, and O is scaled by the result:
+// out = O * result / l', LSE = (m' + log2 l') ln2.  A row without keys (m = -inf, l = 0) gives the factor 0, l' = 1 and
+// LSE = s_h; no sink, or a sink of -inf, changes nothing (factor 1, m and l untouched: bit-identical to no sink).
+__device__ __forceinline__ float sink_fold(const float* sinks, int h, float& m, float& l) {
+    if (!sinks) return 1.0f;
+    const float sg = sinks[h] * kLog2e;
+    if (!(sg > -INFINITY)) return 1.0f;
+    const float mn = fmaxf(m, sg);
+    const float alpha = fast_exp2(m - mn);                 // (m = -inf: 0)
+    l = fmaf(l, alpha, fast_exp2(sg - mn));
+    m = mn;
+    return alpha;
+}
 
 // the query tiles [mt0, mt1) of a dK/dV pass that split `s` of `n` walks
 __device__ __forceinline__ void dkv_split_range(int s, int n, int& mt0, int& mt1) {

@@ -710,9 +710,12 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
 
     if constexpr (HPW) {
         // ---- every wave stores its own head: row l31, 8-byte pieces of the C layout (d = 32 dblk + 8 rq + 4 g .. + 3) ----
-        const float l_w = xhalf_sum(l_run);
-        const float inv = l_w > 0.f ? (KV8 ? p.v_descale : 1.0f) / (l_w * P_UP) : 0.f;
-        const float lse = l_w > 0.f ? (m_run + fast_log2(l_w)) * kLn2 : -INFINITY;
+        float l_w = xhalf_sum(l_run);
+        float m_w = m_run;
+        // (the final output only: split partials stay sink-free, the combine kernel adds the sink once)
+        const float o_sc = da.n_splits == 1 ? sink_fold(da.a.sinks, h, m_w, l_w) : 1.0f;
+        const float inv = l_w > 0.f ? (KV8 ? p.v_descale : 1.0f) * o_sc / (l_w * P_UP) : 0.f;
+        const float lse = l_w > 0.f ? (m_w + fast_log2(l_w)) * kLn2 : -INFINITY;
         if (row_ok) {
             if (da.n_splits == 1) {
                 uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + (int64_t)b * p.o_batch_stride + (int64_t)(q_row0 + t_row) * p.o_row_stride +
@@ -773,9 +776,12 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
             float l_all = 0.f, sc[NW];
 #pragma unroll
             for (int w2 = 0; w2 < NW; ++w2) { sc[w2] = fast_exp2(mw[w2] - m_s); l_all = fmaf(lw[w2], sc[w2], l_all); }
-            const float inv = l_all > 0.f ? (KV8 ? p.v_descale : 1.0f) / (l_all * P_UP) : 0.f;
-            const float lse = l_all > 0.f ? (m_all + fast_log2(l_all)) * kLn2 : -INFINITY;
             const int hq = hk * G + gq3;
+            // attention sink (final output only: split partials stay sink-free, the combine kernel adds the sink once)
+            float m_ref = m_all;                            // (the merged O and l refer to m_s = m_all, or hold zeros)
+            const float o_sc = da.n_splits == 1 ? sink_fold(da.a.sinks, hq, m_ref, l_all) : 1.0f;
+            const float inv = l_all > 0.f ? (KV8 ? p.v_descale : 1.0f) * o_sc / (l_all * P_UP) : 0.f;
+            const float lse = l_all > 0.f ? (m_ref + fast_log2(l_all)) * kLn2 : -INFINITY;
             if (da.n_splits == 1) {
                 uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + (int64_t)b * p.o_batch_stride + (int64_t)(q_row0 + t3) * p.o_row_stride +
                                (int64_t)hq * p.o_head_stride + cs;
@@ -820,11 +826,15 @@ __global__ void __launch_bounds__(256) decode_combine_kernel(const DecArgs da) {
     const int64_t row = idx / cpr;
     const int cc = idx % cpr;
     if (row >= rows) return;
+    // attention sink: one more partial with O = 0 and LSE = s_h (-inf: none, nothing changes)
+    const float sink = da.a.sinks ? da.a.sinks[(row / p.seqlen_q) % p.nheads_q] : -INFINITY;
     float m = -INFINITY;
     for (int s = 0; s < da.n_splits; ++s) m = fmaxf(m, da.lse_partial[(int64_t)s * rows + row]);
+    if (sink > -INFINITY) m = fmaxf(m, sink);
     const float m_s = (m == -INFINITY) ? 0.f : m;
     float den = 0.f;
     for (int s = 0; s < da.n_splits; ++s) den += __expf(da.lse_partial[(int64_t)s * rows + row] - m_s);
+    if (sink > -INFINITY) den += __expf(sink - m_s);
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int s = 0; s < da.n_splits; ++s) {
         const float wgt = den > 0.f ? __expf(da.lse_partial[(int64_t)s * rows + row] - m_s) / den : 0.f;
@@ -886,6 +896,9 @@ __global__ void __launch_bounds__(256) decode_combine_wide_kernel(const DecArgs 
     if (lane == 0) s_red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    // attention sink: one more partial with O = 0 and LSE = s_h (-inf: none, nothing changes)
+    const float sink = da.a.sinks ? da.a.sinks[hq_] : -INFINITY;
+    if (sink > -INFINITY) m = fmaxf(m, sink);
     const float m_s = (m == -INFINITY) ? 0.f : m;
     float den = 0.f;
     for (int s = tid; s < n; s += 256) den += __expf(da.lse_partial[(int64_t)s * rows + row] - m_s);
@@ -894,6 +907,7 @@ __global__ void __launch_bounds__(256) decode_combine_wide_kernel(const DecArgs 
     if (lane == 0) s_red[4 + wave] = den;
     __syncthreads();
     den = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
+    if (sink > -INFINITY) den += __expf(sink - m_s);
     const float rden = den > 0.f ? 1.0f / den : 0.f;
     const int cg = tid % ncg, pl = tid / ncg;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -1179,9 +1193,11 @@ __global__ void __launch_bounds__(GEMV_THREADS) fa_decode_gemv_fp8_kernel(const 
             l_all = fmaf(red[g2 * (D + 2) + D + 1], sc, l_all);
             acc = fmaf(red[g2 * (D + 2) + tid], sc, acc);
         }
-        const float inv = l_all > 0.f ? p.v_descale / l_all : 0.f;
-        const float lse = l_all > 0.f ? (m_all + fast_log2(l_all)) * kLn2 : -INFINITY;
         const int hq = hk;
+        float m_ref = m_all;                                // attention sink: final output only (see fa_decode_kernel)
+        const float o_sc = da.n_splits == 1 ? sink_fold(da.a.sinks, hq, m_ref, l_all) : 1.0f;
+        const float inv = l_all > 0.f ? p.v_descale * o_sc / l_all : 0.f;
+        const float lse = l_all > 0.f ? (m_ref + fast_log2(l_all)) * kLn2 : -INFINITY;
         if (da.n_splits == 1) {
             uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + (int64_t)b * p.o_batch_stride + q_row0 * p.o_row_stride +
                            (int64_t)hq * p.o_head_stride;
@@ -1457,8 +1473,10 @@ __global__ void __launch_bounds__(GEMV_THREADS) fa_decode_gemv_tm_kernel(const D
 #pragma unroll
         for (int gi = 0; gi < G; ++gi) {
             const int hq = h * G + gi;
-            const float inv = l_run[gi] > 0.f ? p.v_descale / l_run[gi] : 0.f;
-            const float lse = l_run[gi] > 0.f ? (m_run[gi] + fast_log2(l_run[gi])) * kLn2 : -INFINITY;
+            float m_ref = m_run[gi], l_ref = l_run[gi];     // attention sink: final output only (see fa_decode_kernel)
+            const float o_sc = da.n_splits == 1 ? sink_fold(da.a.sinks, hq, m_ref, l_ref) : 1.0f;
+            const float inv = l_ref > 0.f ? p.v_descale * o_sc / l_ref : 0.f;
+            const float lse = l_ref > 0.f ? (m_ref + fast_log2(l_ref)) * kLn2 : -INFINITY;
             if (da.n_splits == 1) {
                 uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + (int64_t)b * p.o_batch_stride + q_row0 * p.o_row_stride +
                                (int64_t)hq * p.o_head_stride + CPL * sub;

@@ -765,8 +765,10 @@ __global__ void __launch_bounds__(FWD_THREADS, (D > 128 ? 1 : FA_FWD_OCC)) fa_fw
     }
 
     // ---- epilogue: O / l, LSE ---------------------------------------------------------------
-    const float l_tot = xhalf_sum(l_run);
-    const float inv = l_tot > 0.f ? (DROPOUT ? a.rp_dropout : (KV8 ? p.v_descale : 1.0f)) / l_tot : 0.f;
+    float l_tot = xhalf_sum(l_run);
+    float m_fin = m_run;
+    const float o_sc = sink_fold(a.sinks, w.h, m_fin, l_tot);   // attention sink (fa_common.h; none with dropout)
+    const float inv = l_tot > 0.f ? (DROPOUT ? a.rp_dropout : (KV8 ? p.v_descale : 1.0f)) * o_sc / l_tot : 0.f;
     if (my_row < seqlen_q) {
         // (the store addresses are formed HERE from opaque copies of the lane's row and half: left visible, hipcc computes the 64-bit lane
         //  pointers in front of the tile loop and parks them in scratch / AGPRs across it - csrc/spill_budget.json)
@@ -786,7 +788,7 @@ __global__ void __launch_bounds__(FWD_THREADS, (D > 128 ? 1 : FA_FWD_OCC)) fa_fw
                 if (d * 32 + 8 * rq + 4 * g_e < dv) *reinterpret_cast<u32x2*>(op + d * 32 + 8 * rq + 4 * g_e) = o2;
             }
         if (g_e == 0) {
-            const float lse = l_tot > 0.f ? (m_run + fast_log2(l_tot)) * kLn2 : -INFINITY;
+            const float lse = l_tot > 0.f ? (m_fin + fast_log2(l_tot)) * kLn2 : -INFINITY;
             p.lse[(int64_t)w.b * p.lse_batch_stride + (int64_t)w.h * p.lse_head_stride + q_row0 + row_e] = lse;
         }
     }

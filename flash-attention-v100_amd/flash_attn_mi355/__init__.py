@@ -15,6 +15,7 @@ from .flash_attn_interface import (
     flash_attn_kvpacked_func,
     flash_attn_varlen_qkvpacked_func,
     flash_attn_varlen_kvpacked_func,
+    flash_attn_sinks_func,
 )
 
 __all__ = [
@@ -28,4 +29,5 @@ __all__ = [
     "flash_attn_kvpacked_func",
     "flash_attn_varlen_qkvpacked_func",
     "flash_attn_varlen_kvpacked_func",
+    "flash_attn_sinks_func",
 ]

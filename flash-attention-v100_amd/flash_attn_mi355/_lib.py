@@ -58,10 +58,31 @@ class FaParams(ctypes.Structure):
     ]
 
 
+class FaExtParams(ctypes.Structure):
+    """Mirror of `struct fa_ext_params` (include/fa_mi355.h): the extension block of the *_ext entry points
+    (attention sinks).  struct_size must be set to sizeof(FaExtParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("sinks", _ptr),                 # [nheads_q] fp32, NULL = none
+        ("dsinks", _ptr),                # backward: [nheads_q] fp32 gradient (written), NULL = not wanted
+    ]
+
+
+def ext_params(sinks=None, dsinks=None):
+    """an FaExtParams with struct_size filled in; sinks / dsinks: fp32 GPU tensors or None"""
+    e = FaExtParams()
+    e.struct_size = ctypes.sizeof(FaExtParams)
+    e.sinks = None if sinks is None else sinks.data_ptr()
+    e.dsinks = None if dsinks is None else dsinks.data_ptr()
+    return e
+
+
+EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
+
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd_workspace_bytes", "fa_bwd_workspace_bytes", "fa_fwd_kvcache_workspace_bytes",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
-           "fa_gather_rows", "fa_scatter_rows"]
+           "fa_gather_rows", "fa_scatter_rows"] + EXT_OPS
 
 
 def _load():
@@ -86,6 +107,10 @@ def _load():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.POINTER(FaParams), ctypes.c_void_p]
+    for name in EXT_OPS:
+        fn = getattr(lib, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(FaParams), ctypes.POINTER(FaExtParams), ctypes.c_void_p]
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -109,6 +134,16 @@ def call(name, params, stream):
     if rc != 0:
         msg = lib.fa_last_error().decode(errors="replace")
         raise RuntimeError(f"{name} failed ({rc}): {msg}")
+
+
+def call_ext(name, params, ext, stream):
+    """call() for the *_ext entry points: `name` is the ABI-4 op; with ext None the ABI-4 op itself runs"""
+    if ext is None:
+        return call(name, params, stream)
+    rc = getattr(lib, name + "_ext")(ctypes.byref(params), ctypes.byref(ext), ctypes.c_void_p(stream))
+    if rc != 0:
+        msg = lib.fa_last_error().decode(errors="replace")
+        raise RuntimeError(f"{name}_ext failed ({rc}): {msg}")
 
 
 def call_rows(name, *args):

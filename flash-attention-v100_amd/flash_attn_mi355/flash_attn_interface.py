@@ -12,7 +12,10 @@ deliberate (DESIGN.md "divergences"):
     raising (kernel/fused_mha_forward.cu:371);
   * `flash_attn_with_kvcache` accepts fp8-e4m3 caches with `k_descale` / `v_descale`;
   * `flash_attn_func` / `flash_attn_varlen_func` accept float8_e4m3fn q, k AND v (forward only, bf16 out; the varlen
-    function takes `q_descale` / `k_descale` / `v_descale`).
+    function takes `q_descale` / `k_descale` / `v_descale`);
+  * attention sinks (one learned logit per query head in the softmax denominator, no value: gpt-oss):
+    `flash_attn_sinks_func` for the dense layout, keyword `sinks` of `flash_attn_varlen_func` and
+    `flash_attn_with_kvcache` (the C ABI's *_ext entry points).
 There is no CPU fallback: tensors must live on an AMD GPU and the HIP library must load.
 """
 import collections
@@ -85,8 +88,10 @@ def _is_fp8_qkv(q, k, v):
     return n == 3
 
 
-def _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes, paged=False):
+def _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes, paged=False, sinks=None):
     """what the fp8 forward does not cover: raised here, before anything is allocated or launched"""
+    if sinks is not None:
+        raise RuntimeError("fp8 forward: attention sinks are not supported")
     if head_size_og > 128:
         raise RuntimeError(f"fp8 forward: head dimension {head_size_og} is not supported (at most 128)")
     if dropout_p > 0.0:
@@ -97,6 +102,27 @@ def _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes, paged=Fal
         raise RuntimeError("fp8 forward: ALiBi is not supported")
     if paged:
         raise RuntimeError("fp8 forward: paged k / v (block_table) is not supported with fp8 q")
+
+
+def _check_sinks(sinks, nheads_q, q, dropout_p=0.0):
+    """attention sinks ([H_Q], any floating dtype, on q's device) -> the contiguous fp32 tensor the kernels read, or None.
+    Raised here, before anything is allocated: a wrong shape, dtype or device, fp8 q / k / v, dropout.  The cast is
+    differentiable, so a gradient returns in the caller's dtype (a bf16 nn.Parameter gets a bf16 gradient)."""
+    if sinks is None:
+        return None
+    if not isinstance(sinks, torch.Tensor):
+        raise RuntimeError("sinks must be a tensor of shape [nheads_q]")
+    if q.dtype == _FP8:
+        raise RuntimeError("attention sinks are not supported with fp8 (float8_e4m3fn) q / k / v")
+    if dropout_p > 0.0:
+        raise RuntimeError("attention sinks are not supported with dropout")
+    if not sinks.is_floating_point() or sinks.dtype == _FP8:
+        raise RuntimeError(f"sinks must have a floating dtype (fp32, bf16, fp16), got {sinks.dtype}")
+    if tuple(sinks.shape) != (nheads_q,):
+        raise RuntimeError(f"sinks must have shape ({nheads_q},) (one logit per query head), got {tuple(sinks.shape)}")
+    if sinks.device != q.device:
+        raise RuntimeError(f"sinks must be on q's device ({q.device}), got {sinks.device}")
+    return sinks.to(torch.float32).contiguous()
 
 
 def _check_fp8_no_grad(*tensors, grad_enabled=None):
@@ -288,12 +314,15 @@ def _dense_forward_fp8(q, k, v, dropout_p, softmax_scale, causal, window_size, s
 
 
 def _dense_forward(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                   return_softmax, out=None, keep_window=False):
+                   return_softmax, out=None, keep_window=False, sinks=None):
     """One fa_fwd call on [B, S, H, D] views (any strides with a contiguous last dim).  keep_window (sharding.py only):
     FA_FLAG_KEEP_WINDOW - a right window of >= seqlen_k keys stays a window where it still hides keys (seqlen_q >
-    seqlen_k); the public functions keep the reference's normalisation, which drops it."""
+    seqlen_k); the public functions keep the reference's normalisation, which drops it.  sinks: contiguous fp32 [H_Q]
+    attention sinks (_check_sinks) or None - with sinks the call goes through fa_fwd_ext."""
     _check_device(q, k, v)
     if _is_fp8_qkv(q, k, v):
+        if sinks is not None:
+            raise RuntimeError("fp8 forward: attention sinks are not supported")
         if out is not None or keep_window:
             raise RuntimeError("fp8 forward: no caller-allocated out / sharding window")
         return _dense_forward_fp8(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
@@ -339,7 +368,7 @@ def _dense_forward(q, k, v, dropout_p, softmax_scale, causal, window_size, softc
             ws = _workspace(_lib.lib.fa_fwd_workspace_bytes(ctypes.byref(p)), q.device) if (FWD_SPLIT and N > 0) else None
             if ws is not None:
                 p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
-            _lib.call("fa_fwd", p, _stream(q.device))
+            _lib.call_ext("fa_fwd", p, None if sinks is None else _lib.ext_params(sinks), _stream(q.device))
     if out is not None and out_ is not out:              # caller-allocated out the kernel could not write directly
         out.copy_(out_[..., :head_size_og])
         res = out
@@ -354,14 +383,18 @@ DS_HANDOFF = os.environ.get("FA_BWD_DS", "0") == "1"
 
 
 def _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, dropout_p, softmax_scale, causal,
-                    window_size, softcap, rng, dq_, dk_, dv_, keep_window=False, deterministic=False):
+                    window_size, softcap, rng, dq_, dk_, dv_, keep_window=False, deterministic=False, sinks=None,
+                    dsinks=None):
     """One fa_bwd call; dq_/dk_/dv_ are caller-allocated [B, S, H, dpad] views (written in place).  dq_ = None, or
     dk_ = dv_ = None, skips that gradient's kernel (autograd's needs_input_grad).
 
     `deterministic`: every backward form is atomic-free and run-to-run repeatable; what the flag adds is BATCH INVARIANCE -
     small dK/dV launches (batch x kv-heads x key blocks < the CUs' slots) otherwise split their query rows over several
     workgroups and sum fp32 partials, so the last bit of dK / dV depends on batch x heads and the CU count.  True sets
-    FA_FLAG_NO_DKV_SPLIT (include/fa_mi355.h): one workgroup per key block, the same bits at every batch size."""
+    FA_FLAG_NO_DKV_SPLIT (include/fa_mi355.h): one workgroup per key block, the same bits at every batch size.
+
+    sinks / dsinks: the forward's fp32 [H_Q] attention sinks and a caller-allocated fp32 [H_Q] for their gradient (or
+    None): fa_bwd_ext.  dq_ = dk_ = dv_ = None with dsinks given computes the sinks' gradient only."""
     B, M, H_Q, dpad = q_.shape
     N, H_K = k_.shape[1], k_.shape[2]
     dout_ = _prep(dout, dpad)
@@ -371,6 +404,8 @@ def _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, dropout_p, softma
     if q_.numel() == 0:                                  # no queries: nothing flows into K / V
         if dk_ is not None:
             dk_.zero_(); dv_.zero_()
+        if dsinks is not None:
+            dsinks.zero_()
         return softmax_d
     p = _base_params(q_, q_.dtype, softmax_scale, causal, window_size, softcap)
     p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
@@ -395,7 +430,8 @@ def _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, dropout_p, softma
         ws = _workspace(_lib.lib.fa_bwd_workspace_bytes(ctypes.byref(p)), q_.device)
         if ws is not None:
             p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
-        _lib.call("fa_bwd", p, _stream(q_.device))
+        ext = None if sinks is None else _lib.ext_params(sinks, dsinks)
+        _lib.call_ext("fa_bwd", p, ext, _stream(q_.device))
     return softmax_d
 
 
@@ -439,6 +475,40 @@ class FlashAttnFunc(torch.autograd.Function):
                         ctx.causal, ctx.window_size, ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic)
         cut = lambda t, need: t[..., :d] if (t is not None and need) else None
         return (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2])) + (None,) * 10
+
+
+class FlashAttnSinksFunc(torch.autograd.Function):
+    """FlashAttnFunc with attention sinks (fp32 [H_Q], already checked and cast: _check_sinks): the same dense forward and
+    backward host code through fa_fwd_ext / fa_bwd_ext; the sinks' gradient when they require grad.  No dropout."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, sinks, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
+                return_softmax, is_grad_enabled):
+        is_grad = is_grad_enabled and any(x.requires_grad for x in [q, k, v, sinks])
+        out, lse, dmask, saved, rng, softmax_scale = _dense_forward(
+            q, k, v, 0.0, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax, sinks=sinks)
+        if is_grad:
+            _save_dense(ctx, saved + (sinks,), lse, alibi_slopes, 0.0, softmax_scale, causal, window_size,
+                        softcap, deterministic, q.shape[-1], rng)
+        if return_softmax:
+            ctx.mark_non_differentiable(lse, dmask)
+            return out, lse, dmask
+        return out
+
+    @staticmethod
+    def backward(ctx, dout, *args):
+        q_, k_, v_, out_, sinks, lse, alibi_slopes = ctx.saved_tensors
+        d = ctx.head_size_og
+        need_q, need_kv = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        need_s = ctx.needs_input_grad[3]
+        new = lambda t: _prep(torch.empty_like(t), q_.shape[-1])
+        dq_ = new(q_) if need_q else None
+        dk_, dv_ = (new(k_), new(v_)) if need_kv else (None, None)
+        dsinks = torch.empty_like(sinks) if need_s else None
+        _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, 0.0, ctx.softmax_scale, ctx.causal, ctx.window_size,
+                        ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic, sinks=sinks, dsinks=dsinks)
+        cut = lambda t, need: t[..., :d] if (t is not None and need) else None
+        return (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2]), dsinks) + (None,) * 8
 
 
 class FlashAttnQKVPackedFunc(torch.autograd.Function):
@@ -545,18 +615,42 @@ def flash_attn_func(q, k, v, dropout_p: float = 0.0, softmax_scale: float = None
         raise
 
 
+def flash_attn_sinks_func(q, k, v, sinks, *, softmax_scale: float = None, causal: bool = False,
+                          window_size: Tuple[int, int] = (-1, -1), softcap: float = 0.0,
+                          alibi_slopes: Optional[torch.Tensor] = None, deterministic: bool = False,
+                          return_attn_probs: bool = False):
+    """Dense attention (B, M, H, D) with attention sinks: `sinks` [H_Q] (any floating dtype, on q's device; natural-log
+    units) holds one logit per query head that joins the softmax denominator and carries no value (gpt-oss):
+        out_i = sum_j e^{x_ij} v_j / (e^{s_h} + sum_j e^{x_ij}),   LSE_i = log(e^{s_h} + sum_j e^{x_ij})
+    with x_ij the final score (softmax_scale q.k, softcap, ALiBi).  Otherwise flash_attn_func without dropout: the other
+    arguments mean the same, return_attn_probs returns (out, sink-inclusive LSE, empty dmask).  Differentiable in q, k,
+    v and sinks (the sinks' gradient in their own dtype).  Not with fp8 q / k / v."""
+    deterministic = _warn_deterministic(deterministic)
+    try:
+        s32 = _check_sinks(sinks, q.shape[-2], q)
+        if s32 is None:
+            raise RuntimeError("flash_attn_sinks_func needs sinks (flash_attn_func is the function without them)")
+        return FlashAttnSinksFunc.apply(q, k, v, s32, softmax_scale, causal, window_size, softcap, alibi_slopes,
+                                        deterministic, return_attn_probs, torch.is_grad_enabled())
+    except Exception as e:
+        print(f"[MI355X FA2 SINKS FAILED] {type(e).__name__}: {e}")
+        traceback.print_exc()
+        raise
+
+
 # ======================================================================================
 # VARLEN ATTENTION (T, H, D)
 # ======================================================================================
 def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p,
                     softmax_scale, causal, window_size, softcap, alibi_slopes, return_attn_probs,
                     block_table, seqused_k=None, leftpad_k=None, zero_tensors=False, out=None,
-                    k_descale=None, v_descale=None, q_descale=None):
+                    k_descale=None, v_descale=None, q_descale=None, sinks=None):
     """One fa_varlen_fwd call on [T, H, D] tensors (K/V optionally paged [nblk, page, Hk, D]).
     float8_e4m3fn q, k, v (non-paged) run the fp8 forward: bf16 out, value = code * q/k/v_descale.
     seqused_k clamps the keys of each sequence (include/template.h:65-68); zero_tensors pre-fills out / lse / dmask
     (fused_mha_forward_varlen.cu:538-542); leftpad_k is validated and, like in the reference kernel (the pointer is a
-    parameter that is never read, fused_mha_forward_varlen.cu:37), not applied."""
+    parameter that is never read, fused_mha_forward_varlen.cu:37), not applied.  sinks: contiguous fp32 [H_Q]
+    attention sinks (_check_sinks) or None - with sinks the call goes through fa_varlen_fwd_ext."""
     if cu_seqlens_k is None:
         # paged callers that carry lengths only (seqused_k, as vLLM-style wrappers do): the prefix sums the op wants
         if block_table is None or seqused_k is None:
@@ -566,7 +660,7 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     fp8_q = q.dtype == _FP8
     if fp8_q:
         _is_fp8_qkv(q, k, v)
-        _check_fp8_options(q.shape[-1], dropout_p, softcap, alibi_slopes, paged=block_table is not None)
+        _check_fp8_options(q.shape[-1], dropout_p, softcap, alibi_slopes, paged=block_table is not None, sinks=sinks)
         if out is not None:
             raise RuntimeError("fp8 forward: no caller-allocated out")
     elif q.dtype not in _DTYPES:
@@ -667,7 +761,7 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
         p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
     if q_.numel() > 0:
         with _on_device(q.device):
-            _lib.call("fa_varlen_fwd", p, _stream(q.device))
+            _lib.call_ext("fa_varlen_fwd", p, None if sinks is None else _lib.ext_params(sinks), _stream(q.device))
     if out is not None and out_ is not out:
         out.copy_(out_[..., :head_size_og])
         res = out
@@ -678,7 +772,8 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
 
 def _varlen_backward(dout, q_, k_, v_, out_, lse, cu_seqlens_q, cu_seqlens_k, alibi_slopes,
                      max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal, window_size,
-                     softcap, rng, dq_, dk_, dv_, deterministic=False):
+                     softcap, rng, dq_, dk_, dv_, deterministic=False, sinks=None, dsinks=None):
+    """One fa_varlen_bwd call (fa_varlen_bwd_ext with attention sinks; see _dense_backward for sinks / dsinks)."""
     T_Q, H_Q, dpad = q_.shape
     H_K = k_.shape[1]
     B = cu_seqlens_q.numel() - 1
@@ -689,6 +784,8 @@ def _varlen_backward(dout, q_, k_, v_, out_, lse, cu_seqlens_q, cu_seqlens_k, al
     if q_.numel() == 0:
         if dk_ is not None:
             dk_.zero_(); dv_.zero_()
+        if dsinks is not None:
+            dsinks.zero_()
         return softmax_d
     p = _base_params(q_, q_.dtype, softmax_scale, causal, window_size, softcap)
     p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
@@ -711,7 +808,8 @@ def _varlen_backward(dout, q_, k_, v_, out_, lse, cu_seqlens_q, cu_seqlens_k, al
         ws = _workspace(_lib.lib.fa_bwd_workspace_bytes(ctypes.byref(p)), q_.device)
         if ws is not None:
             p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
-        _lib.call("fa_varlen_bwd", p, _stream(q_.device))
+        ext = None if sinks is None else _lib.ext_params(sinks, dsinks)
+        _lib.call_ext("fa_varlen_bwd", p, ext, _stream(q_.device))
     return softmax_d
 
 
@@ -719,15 +817,15 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p,
                 softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
-                return_attn_probs, block_table, is_grad_enabled):
-        is_grad = is_grad_enabled and any(x.requires_grad for x in [q, k, v])
+                return_attn_probs, block_table, is_grad_enabled, sinks=None):
+        is_grad = is_grad_enabled and any(x is not None and x.requires_grad for x in [q, k, v, sinks])
         out, lse, dmask, saved, rng, softmax_scale = _varlen_forward(
             q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
-            causal, window_size, softcap, alibi_slopes, return_attn_probs, block_table)
+            causal, window_size, softcap, alibi_slopes, return_attn_probs, block_table, sinks=sinks)
         if is_grad:
             if block_table is not None:
                 raise RuntimeError("backward through paged K/V (block_table) is not supported")
-            ctx.save_for_backward(*saved, lse, alibi_slopes)
+            ctx.save_for_backward(*saved, lse, alibi_slopes, sinks)
             ctx.dropout_p = dropout_p
             ctx.softmax_scale = softmax_scale
             ctx.causal = causal
@@ -745,17 +843,21 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q_, k_, v_, out_, cu_seqlens_q, cu_seqlens_k, lse, alibi_slopes = ctx.saved_tensors
+        q_, k_, v_, out_, cu_seqlens_q, cu_seqlens_k, lse, alibi_slopes, sinks = ctx.saved_tensors
         d = ctx.head_size_og
         need_q, need_kv = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        need_s = len(ctx.needs_input_grad) > 17 and ctx.needs_input_grad[17]
         new = lambda t: _prep(torch.empty_like(t), q_.shape[-1])
         dq_ = new(q_) if need_q else None
         dk_, dv_ = (new(k_), new(v_)) if need_kv else (None, None)
+        dsinks = torch.empty_like(sinks) if need_s else None
         _varlen_backward(dout, q_, k_, v_, out_, lse, cu_seqlens_q, cu_seqlens_k, alibi_slopes,
                          ctx.max_seqlen_q, ctx.max_seqlen_k, ctx.dropout_p, ctx.softmax_scale,
-                         ctx.causal, ctx.window_size, ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic)
+                         ctx.causal, ctx.window_size, ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic,
+                         sinks=sinks, dsinks=dsinks)
         cut = lambda t, need: t[..., :d] if (t is not None and need) else None
-        return (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2])) + (None,) * 14
+        grads = (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2])) + (None,) * 14
+        return grads + (dsinks,) if len(ctx.needs_input_grad) > 17 else grads
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int,
@@ -766,23 +868,32 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: in
                            block_table: Optional[torch.Tensor] = None, *,
                            seqused_k: Optional[torch.Tensor] = None,
                            k_descale: Optional[float] = None, v_descale: Optional[float] = None,
-                           q_descale: Optional[float] = None):
+                           q_descale: Optional[float] = None, sinks: Optional[torch.Tensor] = None):
     """Varlen Flash Attention (T, H, D).  seqused_k ([B] int32, forward only): use only the first seqused_k[b] keys
     of sequence b (the op-level argument of the reference, include/mha.h:116-139).  Paged k / v may be float8_e4m3fn
     (value = code * k_descale / v_descale; forward only) - this build's extension, as in flash_attn_with_kvcache.
     q, k and v may all be float8_e4m3fn (non-paged; value = code * q_descale / k_descale / v_descale, None = 1): the
-    fp8 forward of flash_attn_func, bfloat16 `out`, forward only."""
+    fp8 forward of flash_attn_func, bfloat16 `out`, forward only.
+    sinks ([H_Q], any floating dtype): attention sinks, one logit per query head in the softmax denominator with no value
+    (flash_attn_sinks_func); differentiable like q, k, v; not with fp8 q / k / v or dropout.  The LSE returned is the
+    sink-inclusive one."""
     deterministic = _warn_deterministic(deterministic)
     try:
+        s32 = _check_sinks(sinks, q.shape[-2], q, dropout_p)
         fp8 = k.dtype == torch.float8_e4m3fn or q.dtype == torch.float8_e4m3fn
         if seqused_k is not None or fp8:
-            if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v)):
+            if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (q, k, v, sinks)):
                 raise RuntimeError("seqused_k / fp8 k, v are forward-only (the reference's backward op has neither)")
             out, lse, dmask, _, _, _ = _varlen_forward(
                 q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
                 window_size, softcap, alibi_slopes, return_attn_probs, block_table, seqused_k=seqused_k,
-                k_descale=k_descale, v_descale=v_descale, q_descale=q_descale)
+                k_descale=k_descale, v_descale=v_descale, q_descale=q_descale, sinks=s32)
             return (out, lse, dmask) if return_attn_probs else out
+        if s32 is not None:
+            return FlashAttnVarlenFunc.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                             max_seqlen_k, dropout_p, softmax_scale, causal,
+                                             window_size, softcap, alibi_slopes, deterministic,
+                                             return_attn_probs, block_table, torch.is_grad_enabled(), s32)
         return FlashAttnVarlenFunc.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
                                          max_seqlen_k, dropout_p, softmax_scale, causal,
                                          window_size, softcap, alibi_slopes, deterministic,
@@ -806,16 +917,20 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                             rotary_interleaved: bool = True,
                             alibi_slopes: Optional[torch.Tensor] = None, num_splits: int = 0,
                             return_softmax_lse: bool = False, *,
-                            k_descale: Optional[float] = None, v_descale: Optional[float] = None):
+                            k_descale: Optional[float] = None, v_descale: Optional[float] = None,
+                            sinks: Optional[torch.Tensor] = None):
     """FlashAttention with KV cache (B, M, H, D). k_cache / v_cache are updated in place.
 
     A decode step is launch-bound at small batch (two kernels of 10-15 us), so the host side matters: the argument checks
     and the ~60 fields of fa_params depend only on the tensors' GEOMETRY (dtypes, shapes, strides, which optionals are
     given) and the scalar options - a serving loop repeats one geometry thousands of times.  The filled struct is kept per
-    geometry (`_KV_PLANS`); a repeat call copies it and writes the dozen pointers (tools/host_overhead.py)."""
+    geometry (`_KV_PLANS`); a repeat call copies it and writes the dozen pointers (tools/host_overhead.py).
+
+    sinks ([H_Q], any floating dtype, on q's device): attention sinks, one logit per query head in the softmax
+    denominator with no value (flash_attn_sinks_func); the LSE returned is the sink-inclusive one.  Forward only."""
     key = _kv_plan_key(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad,
                        block_table, softmax_scale, causal, window_size, softcap, rotary_interleaved, alibi_slopes,
-                       num_splits, k_descale, v_descale)
+                       num_splits, k_descale, v_descale, sinks)
     plan = _KV_PLANS.get(key) if key is not None else None
     if plan is not None:
         _KV_PLANS.move_to_end(key)
@@ -834,11 +949,14 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         if ws_bytes:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
             pp.workspace = ws.data_ptr()
+        # (the sinks' geometry is part of the key; their pointer is written on every call, like the others)
+        s32 = None if sinks is None else sinks.to(torch.float32).contiguous()
         with _on_device(q.device):
-            _lib.call("fa_fwd_kvcache", pp, _stream(q.device))
+            _lib.call_ext("fa_fwd_kvcache", pp, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
         return (out, lse) if return_softmax_lse else out
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
+    s32 = _check_sinks(sinks, q.shape[-2], q)
     _check_device(q, k_cache, v_cache, k, v)
     if q.dtype not in _DTYPES:
         raise RuntimeError("q must be fp16 or bf16")
@@ -942,7 +1060,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if ws is not None:
         p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
     with _on_device(q.device):
-        _lib.call("fa_fwd_kvcache", p, _stream(q.device))
+        _lib.call_ext("fa_fwd_kvcache", p, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
     if key is not None:                                  # (the call went through: this geometry passes every check)
         while len(_KV_PLANS) >= _KV_PLANS_MAX:           # least recently used geometry out (a workload whose geometry keeps
             _KV_PLANS.popitem(last=False)                # changing must not wipe the plans of the steady ones)
@@ -962,7 +1080,7 @@ def _geom(t):
 
 def _kv_plan_key(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad,
                  block_table, softmax_scale, causal, window_size, softcap, rotary_interleaved, alibi_slopes, num_splits,
-                 k_descale, v_descale):
+                 k_descale, v_descale, sinks=None):
     """Everything flash_attn_with_kvcache's checks and fa_params fields depend on, except the data pointers - or None
     when the call needs the slow path anyway: an int cache_seqlens, descales given as tensors, or ANY input the slow path
     would route through maybe_contiguous() (the template holds the strides of the tensors the kernel was launched on: a
@@ -978,7 +1096,8 @@ def _kv_plan_key(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlen
     return (_geom(q), _geom(k_cache), _geom(v_cache), _geom(k), _geom(v), _geom(rotary_cos), _geom(rotary_sin),
             _geom(cache_seqlens), _geom(cache_batch_idx), _geom(cache_leftpad), _geom(block_table), _geom(alibi_slopes),
             softmax_scale, bool(causal), tuple(window_size), float(softcap), bool(rotary_interleaved), int(num_splits),
-            None if k_descale is None else float(k_descale), None if v_descale is None else float(v_descale))
+            None if k_descale is None else float(k_descale), None if v_descale is None else float(v_descale),
+            _geom(sinks))
 
 
 # ======================================================================================

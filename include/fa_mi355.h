@@ -241,6 +241,30 @@ int fa_varlen_bwd(const fa_params* p, void* stream);
 int fa_fwd_kvcache(const fa_params* p, void* stream);
 
 /*
+ * Extension block of the *_ext entry points (additive: fa_params and FA_ABI_VERSION are unchanged).
+ *
+ * Attention sinks: one learned logit s_h per query head joins the softmax denominator and carries no value,
+ *   out_i = sum_j e^{x_ij} v_j / (e^{s_h} + sum_j e^{x_ij}),   LSE_i = log(e^{s_h} + sum_j e^{x_ij}),
+ * x_ij the final score (softmax_scale q.k, then softcap, then ALiBi).  The LSE written is the sink-inclusive one; a row
+ * without visible keys gives out = 0, LSE = s_h; a sink of -inf is no sink (bit for bit).  The backward's dq / dk / dv
+ * follow from the sink-inclusive LSE; dsinks_h = -sum_{b,i} exp(s_h - LSE_{b,h,i}) D_{b,h,i} (D = rowsum(dO o O)) is a
+ * fixed-order reduction (bitwise repeatable, no atomics).
+ * Not covered (FA_ERR_UNSUPPORTED): fp8-e4m3 q/k/v and dropout.  The workspace queries are unchanged.
+ */
+typedef struct fa_ext_params {
+    size_t       struct_size;  /* sizeof(fa_ext_params) as the caller compiled it */
+    const float* sinks;        /* [nheads_q] fp32 sink logits (natural-log units), contiguous; NULL = none */
+    float*       dsinks;       /* fa_bwd_ext / fa_varlen_bwd_ext: [nheads_q] fp32 gradient, written (not accumulated); NULL = not wanted */
+} fa_ext_params;
+
+/* The ABI-4 ops with an extension block.  ext == NULL, or sinks == dsinks == NULL: exactly the op without _ext. */
+int fa_fwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
+int fa_varlen_fwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
+int fa_fwd_kvcache_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
+int fa_bwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
+int fa_varlen_bwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
