@@ -8,12 +8,14 @@ A "step" = one forward + one backward of that batch through the public Python AP
 (flash_attn.flash_attn_func -> C ABI -> HIP kernels).  FLOPs use the FlashAttention
 convention: fwd = 4*B*H*S*S*D/2 (causal), bwd = 2.5 x fwd.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU); the
 path shards batch x heads with no collective, so every rank runs the full per-GPU workload
 (weak scaling, `value`) and the only distributed calls are the timing barrier and a MAX over ranks.
 
-Besides the contract fields the JSON line carries
+A plain run measures the headline only: input set-up, ~0.3 s of the step to bring the socket to its sustained state (the
+state `value` is quoted in, see cold_start below), the W warm-up and K timed steps, --dump-outputs, and the JSON line with
+the contract fields.  --full measures everything else as well; its line also carries
   roofline        - the dominant kernel of the step (by measured launch duration), its ALGORITHMIC FLOPs per launch /
                     that duration vs the 2.5 PFLOP/s dense bf16 MFMA peak; durations measured here with HIP events on
                     the stream the kernels run on (torch's current stream).  `achieved` / `frac` use the MEAN launch
@@ -30,14 +32,16 @@ Besides the contract fields the JSON line carries
                     (35-40 ms of work) to reach its sustained clock state and loses it again after 5 ms of idling
                     (profiles/r06_step_ramp.txt), so a 45 ms region behind 13 ms of warm-up times the ramp - 2-3 % below the
                     rate every later step runs at.  `value` is the same region timed again behind the per-kernel legs
-                    (0.3 s of the same launches), i.e. in the state a training loop runs in; rounds 1-5 reported the cold figure;
-  other_configs   - BASELINE configs 3, 4 (fp8 and fp16 KV) and the config-5 shard, measured in the same run (rank 0);
+                    (0.3 s of the same launches; in a plain run, 0.3 s of the step), i.e. in the state a training loop
+                    runs in; rounds 1-5 reported the cold figure;
+  other_configs   - BASELINE configs 3, 4 (fp8 and fp16 KV) and the config-5 shard, measured in the same run (rank 0;
+                    --no-other-configs leaves them and strong_scaling_config5 out);
   strong_scaling_config5 - BASELINE configs[4]: dense fwd bf16 causal + ALiBi, B64 H32 S8192 D128 with the 32 heads
                     sharded over the N ranks (flash_attn_mi355.sharding.shard_units / shard_alibi): total TFLOP/s at
                     this N - the 1/2/4/8 curve north_star asks for comes from the driver's runs at each N;
   cpu_baseline    - the reference's CPU comparator, PyTorch SDPA on the host cores of this box
                     (rank 0, N = 1 only), on the largest batch x heads sample of config 2 that fits ~12 s; the numpy fp64
-                    oracle port is timed next to it (`oracle_port_tflops`).
+                    oracle port is timed next to it (`oracle_port_tflops`); --no-cpu-baseline leaves it out.
 
   --dump-outputs DIR  after the timed steps, rank 0 writes what the LAST timed step returned to its caller - the attention
                     output and the gradients of q, k and v - as DIR/{out,dq,dk,dv}.npy (float32, flattened).  Each array holds
@@ -533,8 +537,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed steps (ms_per_step is their mean)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: cold start, per-kernel roofline, MFMA ceiling, other configs, "
+                         "CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without configs 3, 4 and 5")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: exercise the launch / rendezvous / barrier / MAX-over-ranks / JSON path only (CPU test of N > 1)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -595,44 +602,51 @@ def main():
     ff = fwd_flops(c)
     step_flops = 3.5 * ff
 
-    # ---- (1) the K steps from a COLD socket: straight behind the input set-up, the first warm-up step loads the code objects
-    #      (~150 ms of host time with the GPU idle) and W = 5 steps are 13 ms.  An idle MI355X socket needs ~15 steps (35-40 ms
-    #      of work) to reach its sustained clock state - and an idle gap of 5 ms is enough to lose it again (tools/step_profile.py,
-    #      profiles/r06_step_ramp.txt: 2.99, 2.72, 2.55, 2.45, 2.40 ... 2.19 ms) - so this region times the RAMP.  Reported as
-    #      `cold_start`; it is what rounds 1-5 reported as `value`.
-    cold_elapsed = timed_region()
-
-    # ---- (2) per-kernel durations (HIP events on the launch stream) on EVERY rank - only rank 0 reports them, but every socket has
-    #      to stay busy: ~0.3 s of back-to-back launches, the same kernels as the steps, which also brings the socket to the state
-    #      a training loop runs in --------------------------------------------------------------------------------------------
-    kern, kmin, kmean = {}, {}, {}
-    it = 30
-    with torch.no_grad():
-        st = med_min(event_times_ms(lambda: flash_attn.flash_attn_func(q, k, v, causal=c["causal"]), it, warm=3))
-        kern["fwd"], kmin["fwd"], kmean["fwd"] = st[0], st[1], st.mean
-    # which backward kernels run follows from the gradients the op has to produce (autograd's needs_input_grad ->
-    # fa_bwd with dq == NULL or dk == dv == NULL): q alone = the dQ kernel, k and v = preprocess + dK/dV kernel,
-    # all three = dQ kernel + dK/dV kernel (the step's backward)
-    qd, kd, vd = q.detach(), k.detach(), v.detach()
-    graphs = {"bwd_all": (flash_attn.flash_attn_func(q, k, v, causal=c["causal"]), (q, k, v)),
-              "bwd_dq": (flash_attn.flash_attn_func(q, kd, vd, causal=c["causal"]), (q,)),
-              "bwd_dkdv_pre": (flash_attn.flash_attn_func(qd, k, v, causal=c["causal"]), (k, v))}
-    for name, (o, ins) in graphs.items():
-        st = med_min(event_times_ms(lambda: torch.autograd.grad(o, ins, do, retain_graph=True), it, warm=3))
-        kern[name], kmin[name], kmean[name] = st[0], st[1], st.mean
-    del graphs, o
-
     def fb():
         oo = flash_attn.flash_attn_func(q, k, v, causal=c["causal"])
         oo.backward(do)
         q.grad = k.grad = v.grad = None
-    st = med_min(event_times_ms(fb, it, warm=3))
-    kern["step"], kmin["step"], kmean["step"] = st[0], st[1], st.mean
 
-    # ---- (3) `value`: the contract's timed region again, now on a socket in its sustained state - W warm-up steps, barrier +
-    #      synchronize, EXACTLY K steps, barrier + synchronize, MAX over ranks.  With N > 1 a rendezvous first, so that the ranks
-    #      enter their warm-up steps together and the bracketing barrier finds them aligned (a rank waiting 5 ms in a barrier would
-    #      start its timed steps on a socket that has dropped its clocks).
+    if args.full:
+        # ---- (1) the K steps from a COLD socket: straight behind the input set-up, the first warm-up step loads the code objects
+        #      (~150 ms of host time with the GPU idle) and W = 5 steps are 13 ms.  An idle MI355X socket needs ~15 steps (35-40 ms
+        #      of work) to reach its sustained clock state - and an idle gap of 5 ms is enough to lose it again (tools/step_profile.py,
+        #      profiles/r06_step_ramp.txt: 2.99, 2.72, 2.55, 2.45, 2.40 ... 2.19 ms) - so this region times the RAMP.  Reported as
+        #      `cold_start`; it is what rounds 1-5 reported as `value`.
+        cold_elapsed = timed_region()
+
+        # ---- (2) per-kernel durations (HIP events on the launch stream) on EVERY rank - only rank 0 reports them, but every socket
+        #      has to stay busy: ~0.3 s of back-to-back launches, the same kernels as the steps, which also brings the socket to the
+        #      state a training loop runs in ------------------------------------------------------------------------------------
+        kern, kmin, kmean = {}, {}, {}
+        it = 30
+        with torch.no_grad():
+            st = med_min(event_times_ms(lambda: flash_attn.flash_attn_func(q, k, v, causal=c["causal"]), it, warm=3))
+            kern["fwd"], kmin["fwd"], kmean["fwd"] = st[0], st[1], st.mean
+        # which backward kernels run follows from the gradients the op has to produce (autograd's needs_input_grad ->
+        # fa_bwd with dq == NULL or dk == dv == NULL): q alone = the dQ kernel, k and v = preprocess + dK/dV kernel,
+        # all three = dQ kernel + dK/dV kernel (the step's backward)
+        qd, kd, vd = q.detach(), k.detach(), v.detach()
+        graphs = {"bwd_all": (flash_attn.flash_attn_func(q, k, v, causal=c["causal"]), (q, k, v)),
+                  "bwd_dq": (flash_attn.flash_attn_func(q, kd, vd, causal=c["causal"]), (q,)),
+                  "bwd_dkdv_pre": (flash_attn.flash_attn_func(qd, k, v, causal=c["causal"]), (k, v))}
+        for name, (o, ins) in graphs.items():
+            st = med_min(event_times_ms(lambda: torch.autograd.grad(o, ins, do, retain_graph=True), it, warm=3))
+            kern[name], kmin[name], kmean[name] = st[0], st[1], st.mean
+        del graphs, o
+        st = med_min(event_times_ms(fb, it, warm=3))
+        kern["step"], kmin["step"], kmean["step"] = st[0], st[1], st.mean
+    else:
+        # ---- a plain run skips (1) and (2), but `value` is quoted for the socket state they leave behind: one step (it loads the
+        #      code objects with the GPU idle), then ~0.3 s of the step back to back, with no idle gap in front of (3).
+        fb()
+        torch.cuda.synchronize()
+        settle(fb, 300.0)
+
+    # ---- (3) `value`: the contract's timed region on a socket in its sustained state - W warm-up steps, barrier + synchronize,
+    #      EXACTLY K steps, barrier + synchronize, MAX over ranks.  With N > 1 a rendezvous first, so that the ranks enter their
+    #      warm-up steps together and the bracketing barrier finds them aligned (a rank waiting 5 ms in a barrier would start its
+    #      timed steps on a socket that has dropped its clocks).
     if dist is not None:
         dist.barrier()
     elapsed = timed_region()
@@ -641,6 +655,28 @@ def main():
     last.clear()
     ms_per_step = elapsed / args.steps * 1e3
     value = world * step_flops / (elapsed / args.steps) / 1e12
+
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "attention TFLOPS fwd+bwd (seqlen 4096, hd128, causal)",
+            "value": round(value, 2), "unit": "TFLOP/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "config": {"workload": "dense fwd+bwd bf16 causal B8 H16 S4096 D128 (BASELINE configs[1])",
+                       "batch_per_gpu": B, "nheads": H, "nheads_k": Hk, "seqlen": S, "head_dim": D,
+                       "causal": True, "sharding": "batch x heads per GPU, no collective"},
+            "frac_of_mfma_peak": round(value / world / PEAK_BF16_TFLOPS, 4),
+        }
+        if world > 1:
+            out["dist_backend"] = dist_backend      # barrier + MAX only (no data-path collective): "nccl" = RCCL, "gloo" = the CPU fallback
+    if not args.full:
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return 0
     cold_ms = cold_elapsed / args.steps * 1e3
 
     if rank == 0:
@@ -673,7 +709,6 @@ def main():
                   "tflops_total": round(total5 / ms5max / 1e9, 1),
                   "frac_of_mfma_peak": round(total5 / ms5max / 1e9 / (world * PEAK_BF16_TFLOPS), 4), "scaling": "strong"}
 
-    out = None
     if rank == 0:
         # the dK/dV kernel's own duration: the full backward launches exactly two kernels (dQ, then dK/dV)
         kern["bwd_dkdv"] = kern["bwd_all"] - kern["bwd_dq"]
@@ -736,24 +771,14 @@ def main():
             roofline["traffic"] = tr[0]
             roofline["traffic_unit"] = "bytes of HBM per launch (FETCH_SIZE x2 + WRITE_SIZE)"
             roofline["traffic_source"] = f"NOT measured in this run: committed rocprofv3 PMC passes, {tr[1]}"
-        out = {
-            "metric": "attention TFLOPS fwd+bwd (seqlen 4096, hd128, causal)",
-            "value": round(value, 2), "unit": "TFLOP/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "dense fwd+bwd bf16 causal B8 H16 S4096 D128 (BASELINE configs[1])",
-                       "batch_per_gpu": B, "nheads": H, "nheads_k": Hk, "seqlen": S, "head_dim": D,
-                       "causal": True, "sharding": "batch x heads per GPU, no collective"},
-            "frac_of_mfma_peak": round(value / world / PEAK_BF16_TFLOPS, 4),
+        out.update({
             "fwd_tflops": kernels["fwd"]["achieved"], "fwd_frac_of_mfma_peak": kernels["fwd"]["frac"],
             "roofline": roofline, "kernels": kernels,
             "cold_start": {"ms_per_step": round(cold_ms, 4), "value": round(world * step_flops / (cold_ms * 1e-3) / 1e12, 2),
                            "note": "the same W warm-up + K timed steps straight behind the input set-up, on an idle socket (clock ramp: "
                                    "profiles/r06_step_ramp.txt); `value` is the region timed again behind the per-kernel legs - every "
                                    "rank runs them -, the state every step of a training loop after the first 40 ms runs in"},
-        }
-        if world > 1:
-            out["dist_backend"] = dist_backend      # barrier + MAX only (no data-path collective): "nccl" = RCCL, "gloo" = the CPU fallback
+        })
         if strong is not None:
             out["strong_scaling_config5"] = strong
         if not args.no_other_configs:

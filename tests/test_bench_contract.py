@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -60,7 +61,7 @@ def test_bench_rejects_a_run_without_timed_steps():
 
 @pytest.mark.gpu
 def test_bench_json_line_contract(tmp_path):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full",
                           "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, cwd=ROOT,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -108,6 +109,42 @@ def test_bench_json_line_contract(tmp_path):
     assert d["ms_per_step"] <= 1.02 * cs["ms_per_step"], (d["ms_per_step"], cs)
     for name in ("fwd", "bwd_dq", "bwd_all"):
         assert d["kernels"][name]["ms_min"] <= d["kernels"][name]["ms"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_only(tmp_path):
+    """Without --full a run times the headline's W + K steps, dumps, prints the contract fields and nothing measured besides
+    them, and spends at most 30 s of the whole process outside its steps."""
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    import numpy as np
+    dumped = {f: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert set(dumped) == {"out.npy", "dq.npy", "dk.npy", "dv.npy"}, set(dumped)
+    for f, a in dumped.items():
+        assert a.dtype == np.float32 and a.size > 1_000_000 and np.isfinite(a).all() and np.abs(a).max() > 0, f
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True
+    assert d["unit"] == "TFLOP/s" and d["dtype"] == "bf16" and d["data"] == "synthetic"
+    assert abs(d["value"] - 1924.16e9 / (d["ms_per_step"] * 1e-3) / 1e12) / d["value"] < 1e-2
+    for key in ("roofline", "kernels", "cold_start", "other_configs", "strong_scaling_config5", "cpu_baseline"):
+        assert key not in d, key
+    assert wall - (20 + 5) * d["ms_per_step"] * 1e-3 <= 30.0, wall
+
+
+def test_full_is_an_option():
+    """--full selects everything besides the headline; the dry run (no GPU work) takes it like any other run."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dry-run", "--steps", "2", "--warmup", "0"],
+                         capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert json.loads(out.stdout.strip().splitlines()[-1])["steps"] == 2
 
 
 def _free_port():

@@ -6,7 +6,7 @@ for a in sys.argv[1:]:
     if path != "default":
         env["FA_MI355_LIB"] = os.path.abspath(path)
     for r in range(2):
-        out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bench.py"), "--no-cpu-baseline"],
+        out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bench.py"), "--full", "--no-cpu-baseline"],
                              env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])
