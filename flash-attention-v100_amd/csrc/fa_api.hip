@@ -23,7 +23,7 @@ int launch_scatter_rows(const void* src, const int64_t* idx, void* dst, int64_t 
                         int64_t row_bytes, int sorted_unique, hipStream_t stream);
 int launch_bwd(const KArgs& a, hipStream_t stream);
 int launch_bwd_dsinks(const KArgs& a, float* dsinks, hipStream_t stream);   // fa_bwd.hip: gradient of the attention sinks
-size_t bwd_workspace_bytes(const fa_params& p);
+size_t bwd_workspace_bytes(const fa_params& p, bool flat);
 int launch_kvcache_append(const KArgs& a, hipStream_t stream);
 int launch_decode(const KArgs& a, hipStream_t stream);
 size_t decode_workspace_bytes(const fa_params& p);
@@ -180,6 +180,13 @@ static fa::KArgs make_args(const fa_params& p, int block_m) {
     return a;
 }
 
+// Packed sequences on the flat work list of 128-row blocks (fa_common.h: decode_work_flat): no mirrored pairs
+static void set_flat_qblocks(fa::KArgs& a) {
+    a.flat_blocks = a.p.total_q / 128 + a.p.batch;
+    a.pair_qblocks = 0;
+    a.n_qblocks = a.n_qblocks_total;
+}
+
 extern "C" {
 
 int fa_abi_version(void) { return FA_ABI_VERSION; }
@@ -192,18 +199,26 @@ const char* fa_build_info(void) {
 }
 
 
-// Decode issued through the varlen op (vLLM-style callers: every sequence brings the same few query tokens, K / V are
-// paged with a block_table, lengths come from seqused_k or cu_seqlens_k): the layout is the kv-cache op's - q [B, T_q, H, D]
-// with batch stride T_q rows, LSE [H, B T_q] - so the decode kernels (GQA packing, split-KV) can serve it instead of
-// fa_fwd_kernel's one workgroup per sequence and head (B 1, H 32/8, 8 k context: 240 -> 32 us; tools/varlen_decode_probe.py).
-// Needs the split-KV workspace: fa_fwd_workspace_bytes() reports it, and without it the general path runs as before.
-static bool varlen_decode_route(const fa_params& p, fa_params& d) {
-    if (!p.block_table || !p.cu_seqlens_q || !p.cu_seqlens_k || p.p_dropout > 0.f || p.dmask) return false;
-    if (p.batch <= 0 || p.seqlen_q <= 0 || p.total_q != (int64_t)p.batch * p.seqlen_q) return false;   // uniform T_q (host-checkable)
-    if ((p.kv_dtype != p.dtype && p.kv_dtype != FA_FP8_E4M3) || p.page_block_size <= 0 || p.page_block_size % 16 != 0) return false;
-    d = p;
+// The varlen forward's routes to the decode kernels.  Both hand them paged K / V in the kv-cache op's layout - q [B, T_q, H, D]
+// with batch stride T_q rows, LSE [H, B T_q] - and need the split-KV workspace: fa_fwd_workspace_bytes() reports it, and without
+// it the general path runs as before.
+//  * uniform decode (vLLM-style callers: every sequence brings the same few query tokens, lengths from seqused_k or
+//    cu_seqlens_k): the decode kernels (GQA packing, split-KV) serve the whole call instead of fa_fwd_kernel's one workgroup per
+//    sequence and head (B 1, H 32/8, 8 k context: 240 -> 32 us; tools/varlen_decode_probe.py);
+//  * a MIXED batch (vLLM-style unified step: many sequences with one - or a few - query tokens next to a prefill chunk): the
+//    host cannot see the lengths, but it can see that most sequences must be short ((total_q - max_seqlen_q) / (batch - 1) <=
+//    64).  Then the decode kernels run over ALL sequences in varlen-q mode and keep the ones with 1 .. T query rows
+//    (DecArgs::cu_q; the others' workgroups leave at once), and fa_fwd_kernel runs with KArgs::skip_short_q = T for the rest:
+//    32 decode sequences + a 512-token chunk over 8 k contexts 792 -> ~350 us (tools/mixed_batch_probe.py).  T = 32 / G query
+//    rows (at most 8): one 32-row block per kv-head.
+enum class VarlenRoute { General, Decode, Mixed };
+
+// the decode launch's params: T query rows per sequence at most (the class bound; rows per sequence come from cu_seqlens_q)
+static fa_params varlen_decode_params(const fa_params& p, int T, bool uniform) {
+    fa_params d = p;
     d.cache_seqlens = p.seqused_k;                       // NULL: cu_seqlens_k differences (dec_cache_len in fa_decode.hip)
     d.seqused_k = nullptr;
+    d.seqlen_q = T;
     // cu_seqlens_q stays: the kernels run in varlen-q mode (DecArgs::cu_q, class bound T = seqlen_q) and take every
     // sequence's rows and row count from the device.  total_q == batch x max_seqlen_q does NOT prove cu_seqlens_q[-1] ==
     // total_q - q may carry padding rows behind the last sequence (graph-captured serving steps), and then sequence b is
@@ -213,47 +228,37 @@ static bool varlen_decode_route(const fa_params& p, fa_params& d) {
     d.rotary_cos = d.rotary_sin = nullptr; d.rotary_dim = 0;
     d.cache_batch_idx = nullptr; d.cache_leftpad = nullptr;
     d.num_splits = 0;
-    if (d.seqlen_q == 1 && !d.alibi_slopes) d.is_causal = 0;
+    if (uniform && d.seqlen_q == 1 && !d.alibi_slopes) d.is_causal = 0;
     if (d.is_causal) d.window_right = 0;
-    return fa::decode_takes(d);
+    return d;
 }
 
-// A MIXED batch through the varlen op (vLLM-style unified step: many sequences with one - or a few - query tokens next to a
-// prefill chunk, paged K / V): the host cannot see the lengths, but it can see that most sequences must be short
-// ((total_q - max_seqlen_q) / (batch - 1) <= 64).  Then the decode kernels run over ALL sequences in varlen-q mode and keep
-// the ones with 1 .. T query rows (DecArgs::cu_q; the others' workgroups leave at once), and fa_fwd_kernel runs with
-// KArgs::skip_short_q = T for the rest: 32 decode sequences + a 512-token chunk over 8 k contexts 792 -> ~350 us
-// (tools/mixed_batch_probe.py).  T = 32 / G query rows (at most 8): one 32-row block per kv-head.
-static bool varlen_mixed_route(const fa_params& p, fa_params& d) {
-    if (!p.block_table || !p.cu_seqlens_q || !p.cu_seqlens_k || p.p_dropout > 0.f || p.dmask) return false;
-    if ((p.kv_dtype != p.dtype && p.kv_dtype != FA_FP8_E4M3) || p.page_block_size <= 0 || p.page_block_size % 16 != 0) return false;
-    if (p.batch < 4 || p.nheads_k <= 0 || p.total_q >= (int64_t)p.batch * p.seqlen_q) return false;    // uniform batches: above
+// d: the decode launch's params (Decode, Mixed)
+static VarlenRoute varlen_route(const fa_params& p, fa_params& d) {
+    if (!p.block_table || !p.cu_seqlens_q || !p.cu_seqlens_k || p.p_dropout > 0.f || p.dmask) return VarlenRoute::General;
+    if ((p.kv_dtype != p.dtype && p.kv_dtype != FA_FP8_E4M3) || p.page_block_size <= 0 || p.page_block_size % 16 != 0)
+        return VarlenRoute::General;
+    if (p.batch > 0 && p.seqlen_q > 0 && p.total_q == (int64_t)p.batch * p.seqlen_q) {     // uniform T_q (host-checkable)
+        d = varlen_decode_params(p, p.seqlen_q, true);
+        return fa::decode_takes(d) ? VarlenRoute::Decode : VarlenRoute::General;
+    }
+    if (p.batch < 4 || p.nheads_k <= 0 || p.total_q >= (int64_t)p.batch * p.seqlen_q) return VarlenRoute::General;   // uniform: above
     const int G = p.nheads_q / p.nheads_k;
     int T = 32 / (G > 0 ? G : 1);
     T = T < 1 ? 1 : (T > 8 ? 8 : T);
-    if (p.seqlen_q <= T) return false;                                           // everything is short: the uniform route or the general kernel
+    if (p.seqlen_q <= T) return VarlenRoute::General;                  // everything is short: the uniform route or the general kernel
     // (the other sequences average more than 64 rows: few of them can be decode steps.  A wrong yes costs one launch of
     //  workgroups that leave at once, ~10 us; a wrong no costs the decode sequences a 128-row tile and a full stream each)
-    if ((p.total_q - p.seqlen_q) > (int64_t)(p.batch - 1) * 64) return false;
-    d = p;
-    d.cache_seqlens = p.seqused_k;                       // NULL: cu_seqlens_k differences
-    d.seqused_k = nullptr;
-    d.seqlen_q = T;                                      // the class bound; rows per sequence come from cu_seqlens_q (kept)
-    d.q_batch_stride = 0; d.o_batch_stride = 0; d.lse_batch_stride = 0;
-    d.k_new = d.v_new = nullptr; d.seqlen_new = 0;
-    d.rotary_cos = d.rotary_sin = nullptr; d.rotary_dim = 0;
-    d.cache_batch_idx = nullptr; d.cache_leftpad = nullptr;
-    d.num_splits = 0;
-    if (d.is_causal) d.window_right = 0;
-    return fa::decode_takes(d);
+    if ((p.total_q - p.seqlen_q) > (int64_t)(p.batch - 1) * 64) return VarlenRoute::General;
+    d = varlen_decode_params(p, T, false);
+    return fa::decode_takes(d) ? VarlenRoute::Mixed : VarlenRoute::General;
 }
 
 size_t fa_fwd_workspace_bytes(const fa_params* p) {
     fa_params d;
     if (!p) return 0;
     if (p->dtype == FA_FP8_E4M3) return 0;               // fp8 q: one kernel, no split, no decode route
-    if (varlen_decode_route(*p, d)) return fa::decode_workspace_bytes(d);
-    if (varlen_mixed_route(*p, d)) return fa::decode_workspace_bytes(d);
+    if (varlen_route(*p, d) != VarlenRoute::General) return fa::decode_workspace_bytes(d);
     if (!p->cu_seqlens_q && !p->cu_seqlens_k && !p->block_table && p->seqlen_q > 0 && p->seqlen_k > 0 && p->kv_dtype == p->dtype) {
         // fa_fwd: partial outputs of a key-split one-wave causal launch (the struct as fa_fwd will see it)
         fa_params q = *p;
@@ -268,7 +273,7 @@ size_t fa_bwd_workspace_bytes(const fa_params* pp) {
     fa_params p = *pp;
     // the flags as fa_bwd / fa_varlen_bwd will see them (the split of small dK/dV launches depends on the mask's shape)
     if (p.seqlen_q > 0 && p.seqlen_k > 0) normalize(p, false);
-    return fa::bwd_workspace_bytes(p);
+    return fa::bwd_workspace_bytes(p, p.cu_seqlens_q && !varlen_grid_env());
 }
 size_t fa_fwd_kvcache_workspace_bytes(const fa_params* pp) {
     if (!pp) return 0;
@@ -326,11 +331,7 @@ int fa_varlen_fwd_ext(const fa_params* pp, const fa_ext_params* ext, void* strea
         normalize(p, false);
         fa::KArgs a = make_args(p, 128);
         a.seqlens_k = p.seqused_k;
-        if (p.total_q > 0) {
-            a.flat_blocks = p.total_q / 128 + p.batch;
-            a.pair_qblocks = 0;
-            a.n_qblocks = a.n_qblocks_total;
-        }
+        if (p.total_q > 0) set_flat_qblocks(a);
         rc = fa::launch_fwd_fp8(a, static_cast<hipStream_t>(stream));
         if (rc) return fail(FA_ERR_UNSUPPORTED, "no fp8 varlen forward kernel for this configuration");
         return check_hip("fa_varlen_fwd (fp8) launch");
@@ -350,35 +351,23 @@ int fa_varlen_fwd_ext(const fa_params* pp, const fa_ext_params* ext, void* strea
     }
     if (p.p_dropout > 0.f && p.block_table) return fail(FA_ERR_UNSUPPORTED, "dropout with paged K/V is not supported");
     if (p.total_q == 0 || p.seqlen_q == 0) return FA_OK;
-    {
-        fa_params d;
-        if (varlen_decode_route(p, d)) {
-            const size_t need = fa::decode_workspace_bytes(d);
-            if (need == 0 || (d.workspace && d.workspace_bytes >= need)) {
-                fa::KArgs ad = make_args(d, 128);
-                ad.seqlens_k = d.cache_seqlens;
-                ad.kv_mode = 1;
-                ad.sinks = sinks;
-                rc = fa::launch_decode(ad, static_cast<hipStream_t>(stream));
+    int skip_short = 0;
+    fa_params d;
+    const VarlenRoute route = varlen_route(p, d);
+    if (route != VarlenRoute::General) {
+        const size_t need = fa::decode_workspace_bytes(d);
+        if (need == 0 || (d.workspace && d.workspace_bytes >= need)) {
+            fa::KArgs ad = make_args(d, 128);
+            ad.seqlens_k = d.cache_seqlens;
+            ad.kv_mode = 1;
+            ad.sinks = sinks;
+            rc = fa::launch_decode(ad, static_cast<hipStream_t>(stream));
+            if (route == VarlenRoute::Decode) {
                 if (rc) return fail(FA_ERR_UNSUPPORTED, "no decode kernel for this varlen configuration");
                 return check_hip("fa_varlen_fwd (decode kernels) launch");
             }
-        }
-    }
-    int skip_short = 0;
-    {
-        fa_params d;
-        if (varlen_mixed_route(p, d)) {
-            const size_t need = fa::decode_workspace_bytes(d);
-            if (need == 0 || (d.workspace && d.workspace_bytes >= need)) {
-                fa::KArgs ad = make_args(d, 128);
-                ad.seqlens_k = d.cache_seqlens;
-                ad.kv_mode = 1;
-                ad.sinks = sinks;
-                rc = fa::launch_decode(ad, static_cast<hipStream_t>(stream));
-                if (rc) return fail(FA_ERR_UNSUPPORTED, "no decode kernel for the short sequences of this varlen batch");
-                skip_short = d.seqlen_q;             // the general kernel below leaves those sequences out
-            }
+            if (rc) return fail(FA_ERR_UNSUPPORTED, "no decode kernel for the short sequences of this varlen batch");
+            skip_short = d.seqlen_q;                 // the general kernel below leaves those sequences out
         }
     }
     normalize(p, false);
@@ -386,11 +375,7 @@ int fa_varlen_fwd_ext(const fa_params* pp, const fa_ext_params* ext, void* strea
     a.seqlens_k = p.seqused_k;
     a.skip_short_q = skip_short;
     a.sinks = sinks;
-    if (p.total_q > 0 && !varlen_grid_env()) {     // flat work list (fa_common.h: decode_work_flat)
-        a.flat_blocks = p.total_q / 128 + p.batch;
-        a.pair_qblocks = 0;
-        a.n_qblocks = a.n_qblocks_total;
-    }
+    if (p.total_q > 0 && !varlen_grid_env()) set_flat_qblocks(a);
     rc = fa::launch_fwd(a, static_cast<hipStream_t>(stream));
     if (rc) return fail(FA_ERR_UNSUPPORTED, "no varlen forward kernel for this configuration");
     return check_hip("fa_varlen_fwd launch");
@@ -531,11 +516,7 @@ int fa_varlen_bwd_ext(const fa_params* pp, const fa_ext_params* ext, void* strea
     }
     normalize(p, false);
     fa::KArgs a = make_args(p, 128);
-    if (!varlen_grid_env()) {                      // flat work lists (fa_common.h: decode_work_flat)
-        a.flat_blocks = p.total_q / 128 + p.batch;
-        a.pair_qblocks = 0;
-        a.n_qblocks = a.n_qblocks_total;
-    }
+    if (!varlen_grid_env()) set_flat_qblocks(a);
     rc = fa::launch_bwd(a, static_cast<hipStream_t>(stream));
     if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no varlen backward kernel for this configuration");
     if (rc) return rc;

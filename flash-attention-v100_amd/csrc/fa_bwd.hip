@@ -1860,9 +1860,11 @@ int launch_bwd_dkdv_split(const KArgs& a, int grid, hipStream_t stream);
 bool bwd_ds2_applicable(const fa_params& p);             // fa_bwd_dq_ds.hip: dS hand-off between the generated dK/dV kernel and a one-GEMM dQ kernel
 size_t bwd_ds2_bytes(const fa_params& p);
 int launch_bwd_dq_ds(const KArgs& a, hipStream_t stream);
-bool bwd_asm_applicable(const KArgs& a);
+bool bwd_asm_applicable(const fa_params& p, bool flat);
 size_t bwd_asm_workspace_bytes(const fa_params& p);
-int launch_bwd_dkdv_asm(const KArgs& a, hipStream_t stream);
+int launch_bwd_dkdv_asm(const KArgs& a, int grid, hipStream_t stream);
+bool bwd_dq_asm_applicable(const fa_params& p, bool flat);
+int launch_bwd_dq_asm(const KArgs& a, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // dK/dV launches smaller than the chip.  A dK/dV workgroup owns 128 keys of one (batch, kv-head) and walks every query
@@ -1990,68 +1992,121 @@ static size_t bwd_ds_workspace_bytes(const fa_params& p) {
     if (total > max_gb * 1073741824.0) return 0;
     return (size_t)total;
 }
-// workspace of the backward ops: the dS hand-off (measurement builds) or the statistics planes of the asm dK/dV kernel
-static KArgs bwd_probe_args(const fa_params& p) {
-    KArgs a;
-    memset(&a, 0, sizeof(a));
-    a.p = p;
-    a.has_bias = (p.alibi_slopes != nullptr) || (p.softcap > 0.f);
-    a.flat_blocks = p.cu_seqlens_q ? 1 : 0;           // (packed sequences run through the flat work lists unless FA_VARLEN_GRID=1)
-    return a;
-}
-// which dK/dV kernel a dense call takes decides the slots per CU and the stage height behind dkv_split_factor
-static int bwd_dkv_split_for(const KArgs& a, bool asm_kernel) {
-    const fa_params& p = a.p;
-    const bool drop = p.p_dropout > 0.f;
-    const bool lin_alibi = p.alibi_slopes && p.softcap <= 0.f && (p.is_causal || p.window_right == 0);
-    const bool cap_only = p.softcap > 0.f && !p.alibi_slopes;
-    // the predicate of fa_api.hip: make_args (block_m = 128) - the kernels pair key blocks only when a.pair_qblocks is set: a
-    // causal call with seqlen_q <= 128 over long keys is NOT paired (the model would otherwise see half its workgroups)
-    const int pair = ((p.is_causal || p.window_right >= 0) && p.window_left < 0 && (p.seqlen_q + 127) / 128 >= 2) ? 1 : 0;
-    if (asm_kernel) return p.alibi_slopes ? 1 : dkv_split_factor(p, pair, 1, 32, 8);     // (the ALiBi bodies have no partial epilogue)
-    if (a.ds_ws) return 1;
-    if (p.head_dim > 128)                                  // two waves per key block (fa_bwd_d256.hip): one workgroup per CU
-        return ((!a.has_bias || cap_only) && !drop) ? dkv_split_factor(p, pair, 1, 32, 8) : 1;
-    if (a.has_bias || drop) return 1;                      // the split (PART) instantiations: the plain scores
-    return p.head_dim <= 64 ? dkv_split_factor(p, pair, FA_DKV2_OCC64, 64, 4) : dkv_split_factor(p, pair, 2, 32, 8);
-}
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-// dS hand-off (fa_bwd_dq_ds.hip): where both generated kernels would run, the launch fills the chip (no split) and the caller asked
-// for all three gradients
-static bool bwd_takes_ds2(const KArgs& a, bool asm_kernel, int split) {
-    return asm_kernel && split <= 1 && bwd_ds2_applicable(a.p);
-}
-size_t bwd_workspace_bytes(const fa_params& p) {
-    const size_t ds = bwd_ds_workspace_bytes(p);
-    if (ds > 0) return ds;
-    const KArgs a = bwd_probe_args(p);
-    const bool asm_kernel = bwd_asm_applicable(a);
-    const size_t stats = asm_kernel ? bwd_asm_workspace_bytes(p) : 0;
-    const int split = bwd_dkv_split_for(a, asm_kernel);
-    if (bwd_takes_ds2(a, asm_kernel, split)) return align256(stats) + bwd_ds2_bytes(p);
-    const size_t part = dkv_split_bytes(p, split);
-    return part ? align256(stats) + part : stats;
-}
 #ifdef FA_TIMERS
 extern "C" int fa_debug_read_timers(unsigned long long* out, int n) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_timers), (size_t)n * 8);
 }
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// The backward's plan: which kernel runs each phase, the dK/dV split and grid, and where each workspace region lies.  The query
+// asks it with an unlimited workspace and launch_bwd with the caller's, so the fallbacks for a missing or short workspace are
+// decided here.  Layout: the measurement-only dS region alone, or the statistics planes of the asm dK/dV kernel followed
+// (256-byte aligned) by the dS hand-off tiles or the dK/dV partials.
+// ---------------------------------------------------------------------------------------------
+enum class BwdDkv { None, Asm, Gen2, Gen2Part, D256Split, Gen1 };   // asm | fa_bwd_dkdv2_kernel (PART) | fa_bwd_d256.hip | fa_bwd_dkdv_kernel
+enum class BwdDq { None, FromDs, Ds2, Asm, Gen };                   // measurement-only dS | dS hand-off | asm | fa_bwd_dq_kernel
+struct BwdRegion { size_t off, bytes; };                            // bytes == 0: not used
+struct BwdPlan {
+    bool fuse_pre;          // the dQ kernel computes D = rowsum(dO o O) in its prologue and runs first (else a preprocess launch)
+    BwdDkv dkv;
+    BwdDq dq;
+    int dkv_split, dkv_grid, flat_kblocks;      // KArgs::dkv_split (0: unsplit), dK/dV workgroups, KArgs::flat_kblocks
+    BwdRegion stats, ds2, part, ds;
+    size_t bytes;
+};
 
-bool bwd_dq_asm_applicable(const KArgs& a);
-int launch_bwd_dq_asm(const KArgs& a, hipStream_t stream);
+// flat: packed sequences on the flat work lists; want_dq / want_dkv: the gradients the call computes
+static BwdPlan plan_bwd(const fa_params& p, bool flat, size_t avail, bool want_dq, bool want_dkv) {
+    BwdPlan pl = {};
+    const int D = p.head_dim;
+    const bool drop = p.p_dropout > 0.f, bias = p.alibi_slopes || p.softcap > 0.f;
+    const bool lin_alibi = p.alibi_slopes && p.softcap <= 0.f && (p.is_causal || p.window_right == 0);
+    const bool cap_only = p.softcap > 0.f && !p.alibi_slopes;
+    // make_args' pairing test (block_m = 128; flat lists do not pair); the split model halves a packed pass's stages with it
+    const bool pair = (p.is_causal || p.window_right >= 0) && p.window_left < 0 && (p.seqlen_q + 127) / 128 >= 2;
+    const int n_kblocks = (p.seqlen_k + DKV_BN - 1) / DKV_BN;
+    const int n_kb_grid = (pair && !flat && n_kblocks >= 2) ? (n_kblocks + 1) / 2 : n_kblocks;
+    const int units = p.batch * p.nheads_k, grid = unit_grid(units, n_kb_grid);
+
+    const size_t ds = bwd_ds_workspace_bytes(p);
+    const bool from_ds = ds > 0 && want_dq && want_dkv && avail >= ds;
+    const bool asm_ok = !from_ds && bwd_asm_applicable(p, flat);
+    const size_t stats = asm_ok ? bwd_asm_workspace_bytes(p) : 0;
+    const size_t tail = align256(stats);                           // the dS tiles / dK/dV partials lie behind the planes
+    // every path whose dQ kernel recomputes S / dP: D = rowsum(dO o O) comes out of that kernel's prologue, it runs first, and
+    // there is no preprocess launch (one pass over dO and O less: 0.10 of 1.97 ms at config 3)
+#ifndef FA_NO_FUSE_PRE
+    pl.fuse_pre = !from_ds && want_dq;
+#endif
+    // (without a workspace the hipcc kernels run; packed sequences: the preprocess kernel only knows the dense statistics layout)
+    if (asm_ok && avail >= stats && (!p.cu_seqlens_q || pl.fuse_pre)) pl.stats = {0, stats};
+
+    // dK/dV: the two-workgroups-per-CU kernel where it applies (6 % faster at config 2); FA_DKDV1 forces the other one
+#ifdef FA_MEASURE
+    static const bool dkv2_env = getenv("FA_DKDV1") == nullptr;
+#else
+    constexpr bool dkv2_env = true;
+#endif
+    if (!want_dkv || grid <= 0) pl.dkv = BwdDkv::None;
+    else if (pl.stats.bytes) pl.dkv = BwdDkv::Asm;
+    else if (D <= 128 && dkv2_env && (!bias || ((lin_alibi || cap_only) && !drop))) pl.dkv = BwdDkv::Gen2;
+    else if (D == 256 && (!bias || cap_only) && !drop) pl.dkv = BwdDkv::D256Split;     // two waves per key block, one sweep
+    else pl.dkv = BwdDkv::Gen1;
+
+    // a dK/dV launch smaller than the chip: query tiles split over several workgroups + a reduction (dkv_split_factor); the
+    // kernel sets the model's slots per CU and stage height.  No partial epilogue: the ALiBi asm bodies, the biased / dropout
+    // fa_bwd_dkdv2_kernel, fa_bwd_dkdv_kernel.
+    int split = 1;
+    if (!from_ds && (!(p.cu_seqlens_q || p.cu_seqlens_k) || (flat && p.cu_seqlens_q && p.cu_seqlens_k))) {
+        if (pl.dkv == BwdDkv::Asm || pl.dkv == BwdDkv::D256Split)
+            split = p.alibi_slopes ? 1 : dkv_split_factor(p, pair, 1, 32, 8);
+        else if (pl.dkv == BwdDkv::Gen2 && !bias && !drop)
+            split = D <= 64 ? dkv_split_factor(p, pair, FA_DKV2_OCC64, 64, 4) : dkv_split_factor(p, pair, 2, 32, 8);
+    }
+    // dS hand-off (fa_bwd_dq_ds.hip): where both generated kernels would run, the launch fills the chip (no split) and the caller
+    // asked for all three gradients: preprocess -> asm dK/dV kernel (+ tile stores) -> one-GEMM dQ kernel
+    if (pl.dkv == BwdDkv::Asm && split <= 1 && bwd_ds2_applicable(p) && avail >= tail + bwd_ds2_bytes(p)) {
+        pl.ds2 = {tail, bwd_ds2_bytes(p)};
+        pl.fuse_pre = false;                                       // the dK/dV kernel runs first: statistics from the preprocess kernel
+    } else if (split > 1 && avail >= tail + dkv_split_bytes(p, split)) {
+        pl.part = {tail, dkv_split_bytes(p, split)};
+        pl.dkv_split = split;
+        if (pl.dkv == BwdDkv::Gen2) pl.dkv = BwdDkv::Gen2Part;
+    }
+    const int splits = pl.dkv_split > 1 ? pl.dkv_split : 1;
+    if (pl.dkv == BwdDkv::Gen1 || pl.dkv == BwdDkv::None) {
+        pl.dkv_grid = grid;
+    } else if (flat && p.cu_seqlens_k && p.total_k > 0) {
+        pl.flat_kblocks = p.total_k / DKV_BN + p.batch;
+        pl.dkv_grid = pl.flat_kblocks * p.nheads_k * splits;
+    } else {
+        pl.dkv_grid = splits > 1 ? unit_grid(units, n_kb_grid * splits) : grid;
+    }
+
+    if (!want_dq) pl.dq = BwdDq::None;
+    else if (from_ds) pl.dq = BwdDq::FromDs;
+    else if (pl.ds2.bytes) pl.dq = BwdDq::Ds2;
+    else if (pl.fuse_pre && bwd_dq_asm_applicable(p, flat)) pl.dq = BwdDq::Asm;
+    else pl.dq = BwdDq::Gen;
+
+    if (from_ds) pl.ds = {0, ds};
+    pl.bytes = from_ds ? ds : pl.ds2.bytes ? tail + pl.ds2.bytes : pl.part.bytes ? tail + pl.part.bytes : pl.stats.bytes;
+    return pl;
+}
+
+// A struct that names no gradient is sized for all of them; the dS hand-off still needs the three pointers (bwd_ds2_applicable).
+size_t bwd_workspace_bytes(const fa_params& p, bool flat) {
+    const bool all = !p.dq && !p.dk;
+    return plan_bwd(p, flat, SIZE_MAX, all || p.dq, all || p.dk).bytes;
+}
 
 template <typename T, int D>
-static int launch_bwd_td(const KArgs& a, hipStream_t stream) {
+static int launch_bwd_td(const KArgs& a, const BwdPlan& pl, hipStream_t stream) {
     const fa_params& p = a.p;
-    // outputs the caller did not ask for are not computed (include/fa_mi355.h: dq == NULL, dk == dv == NULL)
-    const int g_bwd_phase_mask = 1 | (p.dk ? 2 : 0) | (p.dq ? 4 : 0);
-    // no preprocess launch when the dQ kernel recomputes S / dP (every path but the dS hand-off): it computes D in its
-    // prologue, runs first and leaves softmax_d (+ the asm dK/dV kernel's statistics planes) behind
-    const bool fused_pre = a.fuse_pre != 0;
-    // 1. preprocess
-    if ((g_bwd_phase_mask & 1) && !fused_pre) {
+    // 1. preprocess (outputs the caller did not ask for are not computed: include/fa_mi355.h, dq == NULL, dk == dv == NULL)
+    if (!pl.fuse_pre) {
         const int cpr = D / 8, rows_per_block = 256 / cpr;
         const int64_t total_rows = p.cu_seqlens_q ? (int64_t)p.total_q : (int64_t)p.batch * p.seqlen_q;
         if (total_rows > 0) {
@@ -2064,11 +2119,7 @@ static int launch_bwd_td(const KArgs& a, hipStream_t stream) {
     const bool lin_alibi = p.alibi_slopes && p.softcap <= 0.f && (p.is_causal || p.window_right == 0);
     // 2. dK/dV
     auto launch_dkdv = [&]() {
-    if (g_bwd_phase_mask & 2) {
-        const int n_kblocks = (p.seqlen_k + DKV_BN - 1) / DKV_BN;
-        const int n_kb_grid = (a.pair_qblocks && n_kblocks >= 2) ? (n_kblocks + 1) / 2 : n_kblocks;
-        const int units = p.batch * p.nheads_k;
-        const int grid = unit_grid(units, n_kb_grid);
+        const int grid = pl.dkv_grid;
         const size_t smem = DkvSmem<D>::TOTAL;
 #define FA_LAUNCH_DKV(BIAS, DROP)                                                                                 \
         do {                                                                                                      \
@@ -2076,53 +2127,35 @@ static int launch_bwd_td(const KArgs& a, hipStream_t stream) {
             FA_SET_LDS_ONCE(kern, smem); \
             hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);                             \
         } while (0)
-        // two-workgroups-per-CU kernel where it applies (6 % faster at config 2); FA_DKDV1 forces the other one
-#ifdef FA_MEASURE
-        static const bool dkv2_env = getenv("FA_DKDV1") == nullptr;
-#else
-        constexpr bool dkv2_env = true;
-#endif
-        bool done = false;
         if constexpr (D == 128) {
-            if (a.stats_ws && grid > 0) {
-                launch_bwd_dkdv_asm(a, stream);             // (grid x a.dkv_split workgroups)
+            if (pl.dkv == BwdDkv::Asm) {
+                launch_bwd_dkdv_asm(a, grid, stream);
                 if (a.dkv_split > 1) launch_dkv_reduce<T>(a, stream);
-                done = true;
             }
         }
         if constexpr (D <= 128) {
-            if (done) {} else {
-            const bool cap_only = p.softcap > 0.f && !p.alibi_slopes;
-            if (dkv2_env && (!a.has_bias || ((lin_alibi || cap_only) && !drop)) && grid > 0) {
+            if (pl.dkv == BwdDkv::Gen2 || pl.dkv == BwdDkv::Gen2Part) {
                 const size_t smem2 = Dkv2Smem<D>::TOTAL;
-                KArgs a2 = a;                     // varlen: flat list of key blocks for this kernel
-                int grid2 = grid;
-                if (a.flat_blocks && p.cu_seqlens_k && p.total_k > 0) {
-                    a2.flat_kblocks = p.total_k / DKV_BN + p.batch;
-                    grid2 = a2.flat_kblocks * p.nheads_k * (a.dkv_split > 1 ? a.dkv_split : 1);
-                } else if (a.dkv_split > 1) {
-                    grid2 = unit_grid(units, n_kb_grid * a.dkv_split);   // the query tiles of a pass over dkv_split workgroups (dkv_split_factor)
-                }
 #define FA_LAUNCH_DKV2(BIAS, DROP)                                                                                \
                 do {                                                                                              \
-                    if (BIAS == 0 && !(DROP) && a.dkv_split > 1) {         /* split launch: the PART instantiations */ \
+                    if (pl.dkv == BwdDkv::Gen2Part) {                  /* split launch: the PART instantiations */ \
                         if (D == 128 && valid_cols(p) <= 96) {                                                    \
                             auto kern = fa_bwd_dkdv2_kernel<T, D, 0, false, (D == 128 ? 96 : D), true>;           \
                             FA_SET_LDS_ONCE(kern, smem2);                                                         \
-                            hipLaunchKernelGGL(kern, dim3(grid2), dim3(BWD_THREADS), smem2, stream, a2);          \
+                            hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem2, stream, a);            \
                         } else {                                                                                  \
                             auto kern = fa_bwd_dkdv2_kernel<T, D, 0, false, D, true>;                             \
                             FA_SET_LDS_ONCE(kern, smem2);                                                         \
-                            hipLaunchKernelGGL(kern, dim3(grid2), dim3(BWD_THREADS), smem2, stream, a2);          \
+                            hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem2, stream, a);            \
                         }                                                                                         \
                     } else if (D == 128 && valid_cols(p) <= 96) {                                                 \
                         auto kern = fa_bwd_dkdv2_kernel<T, D, BIAS, DROP, (D == 128 ? 96 : D)>;                   \
                         FA_SET_LDS_ONCE(kern, smem2);                                                             \
-                        hipLaunchKernelGGL(kern, dim3(grid2), dim3(BWD_THREADS), smem2, stream, a2);              \
+                        hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem2, stream, a);                \
                     } else {                                                                                      \
                         auto kern = fa_bwd_dkdv2_kernel<T, D, BIAS, DROP>;                                        \
                         FA_SET_LDS_ONCE(kern, smem2);                                                             \
-                        hipLaunchKernelGGL(kern, dim3(grid2), dim3(BWD_THREADS), smem2, stream, a2);              \
+                        hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem2, stream, a);                \
                     }                                                                                             \
                 } while (0)
                 if (a.has_bias && lin_alibi) FA_LAUNCH_DKV2(2, false);
@@ -2131,138 +2164,88 @@ static int launch_bwd_td(const KArgs& a, hipStream_t stream) {
                 else FA_LAUNCH_DKV2(0, false);
 #undef FA_LAUNCH_DKV2
                 if (a.dkv_split > 1) launch_dkv_reduce<T>(a, stream);
-                done = true;
-            }
             }
         }
         if constexpr (D == 256) {
-            // no bias or softcap only, no dropout: two waves per key block (fa_bwd_dkdv_split_kernel), one sweep instead of two
-            if ((!a.has_bias || (p.softcap > 0.f && !p.alibi_slopes)) && !drop && !a.ds_ws && grid > 0) {
-                KArgs a2 = a;
-                int grid2 = grid;
-                if (a.flat_blocks && p.cu_seqlens_k && p.total_k > 0) {
-                    a2.flat_kblocks = p.total_k / DKV_BN + p.batch;
-                    grid2 = a2.flat_kblocks * p.nheads_k * (a.dkv_split > 1 ? a.dkv_split : 1);
-                } else if (a.dkv_split > 1) {
-                    grid2 = unit_grid(units, n_kb_grid * a.dkv_split);
-                }
-                launch_bwd_dkdv_split(a2, grid2, stream);         // fa_bwd_d256.hip
+            if (pl.dkv == BwdDkv::D256Split) {
+                launch_bwd_dkdv_split(a, grid, stream);         // fa_bwd_d256.hip
                 if (a.dkv_split > 1) launch_dkv_reduce<T>(a, stream);
-                done = true;
             }
         }
-        if (grid > 0 && !done) {
+        if (pl.dkv == BwdDkv::Gen1) {
             if (drop) { if (a.has_bias) FA_LAUNCH_DKV(1, true); else FA_LAUNCH_DKV(0, true); }
             else if (a.has_bias) { if (lin_alibi) FA_LAUNCH_DKV(2, false); else FA_LAUNCH_DKV(1, false); }
             else      FA_LAUNCH_DKV(0, false);
         }
 #undef FA_LAUNCH_DKV
-    }
     };
     // 3. dQ
     auto launch_dq = [&]() {
-    if ((g_bwd_phase_mask & 4) && a.ds_ws) {
-        if constexpr (D <= 128) {
-            const int grid = work_grid(p.batch, p.nheads_q, p.nheads_k, a.n_qblocks);
-            const size_t smem = DqdsSmem<D>::TOTAL;
-            auto kern = fa_bwd_dq_from_ds_kernel<T, D>;
-            FA_SET_LDS_ONCE(kern, smem);
-            if (grid > 0) hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);
-        }
-    } else if ((g_bwd_phase_mask & 4) && D == 128 && a.ds2_ws) {
-        launch_bwd_dq_ds(a, stream);                      // one GEMM over the handed-off dS tiles (fa_bwd_dq_ds.hip)
-    } else if ((g_bwd_phase_mask & 4) && D == 128 && bwd_dq_asm_applicable(a)) {
-        launch_bwd_dq_asm(a, stream);                     // hand-scheduled body (fa_bwd_dq_asm.hip)
-    } else if (g_bwd_phase_mask & 4) {
-        const int grid = a.flat_blocks ? a.flat_blocks * p.nheads_q : work_grid(p.batch, p.nheads_q, p.nheads_k, a.n_qblocks);
-        const size_t smem = DqSmem<D>::TOTAL;
-        // D = 128: two waves per SIMD spill ~10 registers but measure 11 % faster than one wave
-        constexpr int OCC = (D > 128) ? 1 : (D <= 64 ? FA_DQ_OCC64 : 2);
-#define FA_LAUNCH_DQ(BIAS, DROP)                                                                                  \
-        do {                                                                                                      \
-            /* dropout needs the Philox registers: two waves per SIMD spill 84 of them (4.0 ms), one wave none */ \
-            if ((D == 256 && valid_cols(p) <= 192) || (D == 128 && valid_cols(p) <= 96)) {                          \
-                auto kern = fa_bwd_dq_kernel<T, D, BIAS, (DROP) ? 1 : OCC, DROP, (D == 256 ? 192 : (D == 128 ? 96 : D))>; \
-                FA_SET_LDS_ONCE(kern, smem);                                                                      \
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);                         \
-            } else {                                                                                              \
-                auto kern = fa_bwd_dq_kernel<T, D, BIAS, (DROP) ? 1 : OCC, DROP>;                                 \
-                FA_SET_LDS_ONCE(kern, smem);                                                                      \
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);                         \
-            }                                                                                                     \
-        } while (0)
-        if (grid > 0) {
-            if (drop) { if (a.has_bias) FA_LAUNCH_DQ(1, true); else FA_LAUNCH_DQ(0, true); }
-            else if (a.has_bias) {
-                if (lin_alibi) FA_LAUNCH_DQ(2, false);
-                else if (!p.alibi_slopes) FA_LAUNCH_DQ(3, false);            // softcap only
-                else FA_LAUNCH_DQ(1, false);
+        if (pl.dq == BwdDq::FromDs) {
+            if constexpr (D <= 128) {
+                const int grid = work_grid(p.batch, p.nheads_q, p.nheads_k, a.n_qblocks);
+                const size_t smem = DqdsSmem<D>::TOTAL;
+                auto kern = fa_bwd_dq_from_ds_kernel<T, D>;
+                FA_SET_LDS_ONCE(kern, smem);
+                if (grid > 0) hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);
             }
-            else      FA_LAUNCH_DQ(0, false);
-        }
+        } else if (pl.dq == BwdDq::Ds2) {
+            launch_bwd_dq_ds(a, stream);                      // one GEMM over the handed-off dS tiles (fa_bwd_dq_ds.hip)
+        } else if (pl.dq == BwdDq::Asm) {
+            launch_bwd_dq_asm(a, stream);                     // hand-scheduled body (fa_bwd_dq_asm.hip)
+        } else if (pl.dq == BwdDq::Gen) {
+            const int grid = a.flat_blocks ? a.flat_blocks * p.nheads_q : work_grid(p.batch, p.nheads_q, p.nheads_k, a.n_qblocks);
+            const size_t smem = DqSmem<D>::TOTAL;
+            // D = 128: two waves per SIMD spill ~10 registers but measure 11 % faster than one wave
+            constexpr int OCC = (D > 128) ? 1 : (D <= 64 ? FA_DQ_OCC64 : 2);
+#define FA_LAUNCH_DQ(BIAS, DROP)                                                                                  \
+            do {                                                                                                  \
+                /* dropout needs the Philox registers: two waves per SIMD spill 84 of them (4.0 ms), one wave none */ \
+                if ((D == 256 && valid_cols(p) <= 192) || (D == 128 && valid_cols(p) <= 96)) {                      \
+                    auto kern = fa_bwd_dq_kernel<T, D, BIAS, (DROP) ? 1 : OCC, DROP, (D == 256 ? 192 : (D == 128 ? 96 : D))>; \
+                    FA_SET_LDS_ONCE(kern, smem);                                                                  \
+                    hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);                     \
+                } else {                                                                                          \
+                    auto kern = fa_bwd_dq_kernel<T, D, BIAS, (DROP) ? 1 : OCC, DROP>;                             \
+                    FA_SET_LDS_ONCE(kern, smem);                                                                  \
+                    hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), smem, stream, a);                     \
+                }                                                                                                 \
+            } while (0)
+            if (grid > 0) {
+                if (drop) { if (a.has_bias) FA_LAUNCH_DQ(1, true); else FA_LAUNCH_DQ(0, true); }
+                else if (a.has_bias) {
+                    if (lin_alibi) FA_LAUNCH_DQ(2, false);
+                    else if (!p.alibi_slopes) FA_LAUNCH_DQ(3, false);            // softcap only
+                    else FA_LAUNCH_DQ(1, false);
+                }
+                else      FA_LAUNCH_DQ(0, false);
+            }
 #undef FA_LAUNCH_DQ
-    }
+        }
     };
-    if (fused_pre) { launch_dq(); launch_dkdv(); } else { launch_dkdv(); launch_dq(); }
+    if (pl.fuse_pre) { launch_dq(); launch_dkdv(); } else { launch_dkdv(); launch_dq(); }
     return 0;
 }
 
 int launch_bwd(const KArgs& a_in, hipStream_t stream) {
     KArgs a = a_in;
-    a.ds_ws = nullptr;
-    a.stats_ws = nullptr;
-    a.fuse_pre = 0;
-    const size_t need = bwd_ds_workspace_bytes(a.p);
-    if (need > 0 && a.p.dq && a.p.dk && a.p.workspace && a.p.workspace_bytes >= need) {
-        a.ds_ws = a.p.workspace;
-        a.ds_nqb = (a.p.seqlen_q + 31) / 32;
-        a.ds_nkb = (a.p.seqlen_k + 31) / 32;
-    } else {
-        if (bwd_asm_applicable(a) && a.p.workspace && a.p.workspace_bytes >= bwd_asm_workspace_bytes(a.p))
-            a.stats_ws = reinterpret_cast<float*>(a.p.workspace);     // (without a workspace the hipcc kernels run)
-        // every path whose dQ kernel recomputes S / dP: D = rowsum(dO o O) comes out of that kernel's prologue, it runs
-        // first, and there is no preprocess launch (one pass over dO and O less: 0.10 of 1.97 ms at config 3)
-#ifndef FA_NO_FUSE_PRE
-        a.fuse_pre = 1;
-#else
-        if (a.p.cu_seqlens_q) a.stats_ws = nullptr;      // (A/B build: the preprocess kernel only knows the dense statistics layout)
-#endif
-        if (!a.p.dq) {
-            // dQ not requested: its kernel - and with it the fused row-dot - does not run, so the preprocess kernel
-            // provides softmax_d and the statistics planes (dense layout only; packed sequences take the hipcc dK/dV kernel)
-            a.fuse_pre = 0;
-            if (a.p.cu_seqlens_q) a.stats_ws = nullptr;
-        }
-    }
-    // dS hand-off: preprocess -> generated dK/dV kernel (+ tile stores) -> one-GEMM dQ kernel
-    a.ds2_ws = nullptr;
-    if (a.stats_ws && !a.ds_ws && bwd_takes_ds2(a, true, bwd_dkv_split_for(a, true))) {
-        const size_t off = align256(bwd_asm_workspace_bytes(a.p));
-        if (a.p.workspace_bytes >= off + bwd_ds2_bytes(a.p)) {
-            a.ds2_ws = reinterpret_cast<char*>(a.p.workspace) + off;
-            a.ds2_nqb = (a.p.seqlen_q + 31) / 32;
-            a.ds2_nkb = 4 * ((a.p.seqlen_k + 127) / 128);
-            a.fuse_pre = 0;                               // the dK/dV kernel runs first: statistics from the preprocess kernel
-        }
-    }
-    // a dense dK/dV launch smaller than the chip: query tiles split over several workgroups + a reduction (dkv_split_factor)
-    a.dkv_split = 0;
-    a.dkv_part = nullptr;
-    const bool packed = a.p.cu_seqlens_q || a.p.cu_seqlens_k;
-    if (a.p.dk && !a.ds_ws && !a.ds2_ws && (!packed || (a.flat_blocks && a.p.cu_seqlens_q && a.p.cu_seqlens_k))) {
-        const bool asm_kernel = a.p.head_dim == 128 && a.stats_ws != nullptr;
-        const int split = bwd_dkv_split_for(a, asm_kernel);
-        const size_t off = align256(bwd_asm_applicable(a) ? bwd_asm_workspace_bytes(a.p) : 0);      // as bwd_workspace_bytes lays it out
-        if (split > 1 && a.p.workspace && a.p.workspace_bytes >= off + dkv_split_bytes(a.p, split)) {
-            a.dkv_split = split;
-            a.dkv_part = reinterpret_cast<char*>(a.p.workspace) + off;
-        }
-    }
-    const bool bf = a.p.dtype == FA_BF16;
-    switch (a.p.head_dim) {
-        case 64:  return bf ? launch_bwd_td<bf16_tag, 64>(a, stream) : launch_bwd_td<fp16_tag, 64>(a, stream);
-        case 128: return bf ? launch_bwd_td<bf16_tag, 128>(a, stream) : launch_bwd_td<fp16_tag, 128>(a, stream);
-        case 256: return bf ? launch_bwd_td<bf16_tag, 256>(a, stream) : launch_bwd_td<fp16_tag, 256>(a, stream);
+    const fa_params& p = a.p;
+    const BwdPlan pl = plan_bwd(p, a.flat_blocks != 0, p.workspace ? p.workspace_bytes : 0, p.dq != nullptr, p.dk != nullptr);
+    char* ws = reinterpret_cast<char*>(p.workspace);
+    a.fuse_pre = pl.fuse_pre ? 1 : 0;
+    a.stats_ws = pl.stats.bytes ? reinterpret_cast<float*>(ws + pl.stats.off) : nullptr;
+    a.ds_ws = pl.ds.bytes ? ws + pl.ds.off : nullptr;
+    if (a.ds_ws) { a.ds_nqb = (p.seqlen_q + 31) / 32; a.ds_nkb = (p.seqlen_k + 31) / 32; }
+    a.ds2_ws = pl.ds2.bytes ? ws + pl.ds2.off : nullptr;
+    if (a.ds2_ws) { a.ds2_nqb = (p.seqlen_q + 31) / 32; a.ds2_nkb = 4 * ((p.seqlen_k + 127) / 128); }
+    a.dkv_split = pl.dkv_split;
+    a.dkv_part = pl.part.bytes ? ws + pl.part.off : nullptr;
+    a.flat_kblocks = pl.flat_kblocks;
+    const bool bf = p.dtype == FA_BF16;
+    switch (p.head_dim) {
+        case 64:  return bf ? launch_bwd_td<bf16_tag, 64>(a, pl, stream) : launch_bwd_td<fp16_tag, 64>(a, pl, stream);
+        case 128: return bf ? launch_bwd_td<bf16_tag, 128>(a, pl, stream) : launch_bwd_td<fp16_tag, 128>(a, pl, stream);
+        case 256: return bf ? launch_bwd_td<bf16_tag, 256>(a, pl, stream) : launch_bwd_td<fp16_tag, 256>(a, pl, stream);
         default:  return -2;
     }
 }

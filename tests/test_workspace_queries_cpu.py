@@ -91,6 +91,28 @@ def test_backward_split_workspace(lib):
     assert q(ctypes.byref(p)) == 0
 
 
+def test_backward_workspace_follows_the_launch(lib):
+    """The query and fa_bwd / fa_varlen_bwd share one plan (fa_bwd.hip: plan_bwd), so the query asks for the bytes of the kernels
+    the launch runs for the gradients the struct names (a struct that names none is sized for all of them, as above)."""
+    q = lib.lib.fa_bwd_workspace_bytes
+    al = lambda x: (x + 255) & ~255
+    # packed D = 128 without dQ: no dQ kernel computes the row-dot, so the preprocess kernel does - it knows only the dense
+    # statistics layout, and the compiler-built dK/dV kernel runs.  Its model (2 workgroups per CU) splits the 116 workgroups 4
+    # ways, where the asm kernel's (1 per CU) would split them 2 ways; the partials still lie behind the planes' region.
+    p = _dense(lib, 3, 2048, 8, 4, 128)
+    cu = (ctypes.c_int32 * 4)(0, 1000, 1300, 3348)
+    p.cu_seqlens_q = p.cu_seqlens_k = ctypes.addressof(cu)
+    p.total_q = p.total_k = 3348
+    p.dk = p.dv = 4096
+    assert q(ctypes.byref(p)) == al(2 * 8 * 3348 * 4) + 2 * 4 * 3348 * 4 * 128 * 4
+    p.flags = lib.FA_FLAG_NO_DKV_SPLIT                       # ... and unsplit it uses no workspace at all
+    assert q(ctypes.byref(p)) == 0
+    # dQ only: no dK/dV launch to split, the statistics planes alone (the fused dQ prologue writes them)
+    p = _dense(lib, 1, 4096, 32, 8, 128)
+    p.dq = 4096
+    assert q(ctypes.byref(p)) == 2 * 32 * 4096 * 4
+
+
 def _decode(lib, B, H, Hk, L, kv8, num_splits=0):
     p = lib.FaParams()
     p.dtype = lib.FA_FP16
