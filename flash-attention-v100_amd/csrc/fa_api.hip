@@ -25,7 +25,7 @@ int launch_bwd(const KArgs& a, hipStream_t stream);
 int launch_bwd_dsinks(const KArgs& a, float* dsinks, hipStream_t stream);   // fa_bwd.hip: gradient of the attention sinks
 size_t bwd_workspace_bytes(const fa_params& p, bool flat);
 int launch_kvcache_append(const KArgs& a, hipStream_t stream);
-int launch_decode(const KArgs& a, hipStream_t stream);
+int launch_decode(const KArgs& a, hipStream_t stream, const fa_tree_params* tree = nullptr);
 size_t decode_workspace_bytes(const fa_params& p);
 bool decode_applicable(const fa_params& p);
 bool decode_takes(const fa_params& p);
@@ -191,6 +191,7 @@ extern "C" {
 
 int fa_abi_version(void) { return FA_ABI_VERSION; }
 size_t fa_params_size(void) { return sizeof(fa_params); }
+size_t fa_tree_params_size(void) { return sizeof(fa_tree_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -384,13 +385,53 @@ int fa_varlen_fwd_ext(const fa_params* pp, const fa_ext_params* ext, void* strea
 int fa_fwd_kvcache(const fa_params* pp, void* stream) { return fa_fwd_kvcache_ext(pp, nullptr, stream); }
 
 int fa_fwd_kvcache_ext(const fa_params* pp, const fa_ext_params* ext, void* stream) {
+    return fa_fwd_kvcache_tree(pp, ext, nullptr, stream);
+}
+
+// fa_tree_params (fa_fwd_kvcache_tree): the block itself, checked with the extension block before anything else.
+// *on: a tree accompanies the call (mask != NULL)
+static int check_tree_block(const fa_tree_params* tree, const fa_params* p, bool* on) {
+    *on = false;
+    const bool flag = p && (p->flags & FA_FLAG_TREE_MASK) != 0;
+    if (tree) {
+        FA_CHECK(tree->struct_size >= sizeof(fa_tree_params), "fa_tree_params::struct_size %zu is smaller than this library's fa_tree_params (%zu)",
+                 tree->struct_size, sizeof(fa_tree_params));
+        *on = tree->mask != nullptr;
+    }
+    FA_CHECK(!flag || *on, "FA_FLAG_TREE_MASK is set but no tree block (fa_tree_params::mask) accompanies the call");
+    FA_CHECK(!*on || flag, "a tree block accompanies the call but FA_FLAG_TREE_MASK is not set in fa_params::flags "
+                           "(fa_fwd_kvcache_workspace_bytes() needs it to answer for the decode route)");
+    return FA_OK;
+}
+
+// the tree call's own argument checks (after the op's: p is normalised apart from the mask fields); all on the host
+static int check_tree_call(const fa_tree_params& t, const fa_params& p) {
+    FA_CHECK(p.seqlen_q >= 2 && p.seqlen_q <= 64, "tree mask: seqlen_q must be in [2, 64] (got %d)", p.seqlen_q);
+    FA_CHECK(t.mask_words == (p.seqlen_q + 31) / 32, "tree mask: mask_words must be ceil(seqlen_q / 32) = %d (got %d)",
+             (p.seqlen_q + 31) / 32, t.mask_words);
+    FA_CHECK((reinterpret_cast<uintptr_t>(t.mask) & 3) == 0 && (reinterpret_cast<uintptr_t>(t.depths) & 3) == 0,
+             "tree mask: mask and depths must be 4-byte aligned");
+    FA_CHECK(t.mask_batch_stride >= 0 && t.depths_batch_stride >= 0, "tree mask: batch strides must be >= 0 (0 = shared by the batch)");
+    FA_CHECK(p.seqlen_new == 0 || p.seqlen_new == p.seqlen_q, "tree mask: seqlen_new must be 0 or seqlen_q (the tree's nodes are the new tokens)");
+    FA_CHECK(p.window_left < 0 && p.window_right < 0, "tree mask: window_size must be (-1, -1)");
+    if (p.alibi_slopes) return fail(FA_ERR_UNSUPPORTED, "tree mask: ALiBi is not supported (its distance term needs tree positions)");
+    FA_CHECK(p.rotary_dim <= 0 || t.depths, "tree mask: depths are required with rotary_cos / rotary_sin (node t sits at cache_seqlens + depths[t])");
+    if (!fa::decode_applicable(p)) return fail(FA_ERR_UNSUPPORTED, "tree mask: no decode kernel for this head dimension / cache dtype");
+    return FA_OK;
+}
+
+int fa_fwd_kvcache_tree(const fa_params* pp, const fa_ext_params* ext, const fa_tree_params* tree, void* stream) {
     const float* sinks;
     float* dsinks;
     int rc = check_ext(ext, pp, false, &sinks, &dsinks);
     if (rc) return rc;
+    bool tree_on;
+    rc = check_tree_block(tree, pp, &tree_on);
+    if (rc) return rc;
     if (!pp) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
     fa_params p = *pp;
     p.cu_seqlens_q = p.cu_seqlens_k = p.seqused_k = nullptr;
+    p.flags &= ~FA_FLAG_TREE_MASK;                       // (this op's own bit: check_common rejects it for every other op)
     rc = check_common(p, true);
     if (rc) return rc;
     FA_CHECK(p.kv_dtype == p.dtype || p.kv_dtype == FA_FP8_E4M3, "kcache/vcache must match q dtype or be fp8-e4m3");
@@ -421,6 +462,13 @@ int fa_fwd_kvcache_ext(const fa_params* pp, const fa_ext_params* ext, void* stre
         FA_CHECK(p.seqlen_ro >= p.seqlen_k, "rotary_cos / rotary_sin must cover the cache capacity (seqlen_ro >= seqlen_k)");
     }
     if (p.num_splits < 0) return fail(FA_ERR_INVALID_ARGUMENT, "num_splits must be >= 0");
+    if (tree_on) {
+        // the mask replaces the causal rule (windows are checked as the caller gave them: causal alone sets none)
+        p.is_causal = 0;
+        rc = check_tree_call(*tree, p);
+        if (rc) return rc;
+        p.flags |= FA_FLAG_TREE_MASK;                    // decode_takes(): every tree call runs on the decode kernels
+    }
     // reference: fused_mha_forward_kvcache.cu:465-472
     normalize(p, true);
     if (p.softcap > 0.f) {
@@ -436,7 +484,7 @@ int fa_fwd_kvcache_ext(const fa_params* pp, const fa_ext_params* ext, void* stre
     a.leftpad_k = p.cache_leftpad;
     a.kv_mode = 1;
     a.sinks = sinks;
-    rc = fa::launch_decode(a, s);
+    rc = fa::launch_decode(a, s, tree_on ? tree : nullptr);
     if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no kvcache kernel for this configuration (fp8 caches: head_dim 64 or 128)");
     if (rc == -1) return fail(FA_ERR_INVALID_ARGUMENT, "workspace too small: query fa_fwd_kvcache_workspace_bytes()");
     if (rc) return rc;

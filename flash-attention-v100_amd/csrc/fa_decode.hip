@@ -15,6 +15,9 @@
 //     window masks, and fp8-e4m3 K/V (dequantised while staging; k_descale folds into the softmax
 //     scale, v_descale into the final normalisation).
 // ALiBi / softcap: per-element score path of fa_decode_kernel (the token-major kernels step aside).
+// Tree masks (speculative decoding, fa_tree_params): the T_q <= 64 query tokens are the nodes of a draft tree; a lane owns one
+// query row in the S^T layout, so the row's visibility among the new keys is one or two 32-bit words of that lane, applied in
+// a wave-uniform branch by the tiles that overlap the last T_q keys (fa_decode_kernel only: T_q >= 2).
 // Head dims: widths 64 / 128 / 256 (256: 16-key tiles), narrower rows through the NARROW instantiations.
 #include <atomic>
 #include "fa_common.h"
@@ -46,6 +49,8 @@ template <int D, int NW = 4> struct DecSmem {
     static constexpr int QOFF = NW * WAVE;
     static constexpr int QBYTES = (D > 128 || NW == 8) ? (D / 16) * 64 * 16 : 0;
     static constexpr int TOTAL = QOFF + QBYTES > MERGE ? QOFF + QBYTES : MERGE;
+    // tree decode: the 32 rows' visibility words (2 x 4 bytes each) sit behind whatever else the launch asks for
+    static constexpr int TREE = 32 * 8;
 };
 
 // keys in the cache of batch entry b: cache_seqlens[b] (kv-cache op), or - decode issued through the varlen op - the
@@ -74,6 +79,12 @@ struct DecArgs {
     int ksub;                  // token-major kernel: waves per head group = partial rows per grid split (1, 2, 4)
     float* o_partial;          // [n_splits, B, Hq, T_q, D] fp32 (n_splits > 1)
     float* lse_partial;        // [n_splits, B, Hq, T_q]
+    // tree decode (fa_tree_params; fa_decode_kernel only): key off + c is visible to query token t iff bit c & 31 of
+    // tree_mask[b * stride + t * words + (c >> 5)] is set; the cache below off is visible to every row
+    const uint32_t* tree_mask; // NULL: no tree
+    const int32_t* tree_depths;// RoPE position of token t = L + leftpad + depths[b * stride + t]; NULL: none (no rotary)
+    int64_t tree_mask_stride, tree_depths_stride;         // per batch entry, 0 = shared
+    int tree_words;            // words per row: 1 or 2
 };
 
 // F8M (fp8 cache, D = 128, eight waves): the cache bytes feed the matrix pipe AS STORED - v_mfma_f32_32x32x16_fp8_fp8 for both
@@ -156,6 +167,25 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
     int lo = 0, hi = seqlen_k - 1;
     if (wr >= 0) { const int h2 = t_row + off + wr; hi = h2 < hi ? h2 : hi; }
     if (wl >= 0) { const int l2 = t_row + off - wl; lo = l2 > lo ? l2 : lo; }
+    // tree decode: the row's visibility words over the T_q new keys (lanes of one token - a GQA group - share them; no
+    // windows, not causal: the host clears them).  Here they give hi = the row's last visible key, which trims the tile range
+    // below exactly as the causal rule does for a chain.  The words do NOT stay in registers across the tile loop (the 16-bit
+    // D = 128 eight-wave instantiations have none to spare: two more spilled five, and a pointer to read them again from
+    // memory pushed the scalar spills into a second register): they wait in LDS behind the launch's other areas for the
+    // few tiles that overlap the new keys (T_q <= 64: at most three 32-key tiles, five of D = 256's 16-key tiles).  Every wave writes the same 32 rows' words and reads back what it wrote
+    // itself (LDS is in order per wave): no barrier.
+    constexpr int TREE_OFF = HPW ? DecSmem<D, NW>::QOFF
+                                 : (F8M ? DecSmem<D, NW>::QOFF + DecSmem<D, NW>::QBYTES + (D / 16) * 64 * 8 : DecSmem<D, NW>::TOTAL);
+    const bool tree = da.tree_mask != nullptr;
+    if (tree) {
+        const uint32_t* mrow = da.tree_mask + (int64_t)b * da.tree_mask_stride + (int64_t)(t_row < Tq ? t_row : 0) * da.tree_words;
+        uint32_t tm0 = mrow[0], tm1 = da.tree_words > 1 ? mrow[1] : 0u;             // (rows past R: masked by hi = -1 below)
+        if (Tq < 32) tm0 &= (1u << Tq) - 1u;                // (bits past the tree do not name keys)
+        else if (Tq < 64) tm1 &= (1u << (Tq - 32)) - 1u;
+        const int top = tm1 ? 63 - __builtin_clz(tm1) : (tm0 ? 31 - __builtin_clz(tm0) : -1);
+        hi = off + top;
+        *reinterpret_cast<u32x2*>(smem + TREE_OFF + l31 * 8) = u32x2{tm0, tm1};
+    }
     // wave-uniform bounds for mask elision: a tile inside [max lo, min hi] of the wave's valid rows needs no per-element
     // compare / select (64 of the ~540 instructions of a tile step); rows past R see unmasked garbage that is never stored
     int w_lo_max = row_ok ? lo : 0, w_hi_min = row_ok ? hi : 0x7fffffff;
@@ -167,6 +197,15 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
     }
     w_lo_max = __builtin_amdgcn_readfirstlane(w_lo_max);
     w_hi_min = __builtin_amdgcn_readfirstlane(w_hi_min);
+    int w_hi_max = 0;                                       // tree: last key any valid row of the block sees
+    if (tree) {
+        w_hi_max = row_ok ? hi : -1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const int a2 = __shfl_xor(w_hi_max, o); w_hi_max = a2 > w_hi_max ? a2 : w_hi_max; }
+        w_hi_max = __builtin_amdgcn_readfirstlane(w_hi_max);
+        // tiles below off keep the elided fast path; the ones that overlap [off, seqlen_k) take the per-element branch
+        w_hi_min = w_hi_min < off - 1 ? w_hi_min : off - 1;
+    }
     const bool any_row = __builtin_amdgcn_readfirstlane((int)(__ballot(row_ok) != 0ull));
     if (!row_ok) { lo = 0x7fffffff; hi = -1; }
 
@@ -191,7 +230,8 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
         const uint16_t* qrow = reinterpret_cast<const uint16_t*>(p.q) + (int64_t)b * p.q_batch_stride +
                                (int64_t)(q_row0 + t_row) * p.q_row_stride + (int64_t)h * p.q_head_stride;
         const int half = p.rotary_dim >> 1;
-        const int pos = L + lp + (da.local ? t_row : 0);
+        int pos = L + lp + (da.local ? t_row : 0);
+        if (da.tree_depths) pos = L + lp + (row_ok ? da.tree_depths[(int64_t)b * da.tree_depths_stride + t_row] : 0);
         const uint16_t* cosp = reinterpret_cast<const uint16_t*>(p.rotary_cos) + (int64_t)pos * half;
         const uint16_t* sinp = reinterpret_cast<const uint16_t*>(p.rotary_sin) + (int64_t)pos * half;
         u32x4 xq[F8M ? KSTEPS : 1];
@@ -250,6 +290,7 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
     if (wl >= 0) { const int kmin = t_first + off - wl; if (kmin > 0) tile_lo = kmin / BN; }
     int tile_hi = (seqlen_k + BN - 1) / BN;
     if (wr >= 0) { const int kmax = t_last + off + wr; const int t2 = kmax < 0 ? 0 : kmax / BN + 1; tile_hi = t2 < tile_hi ? t2 : tile_hi; }
+    if (tree) { const int t2 = w_hi_max < 0 ? 0 : w_hi_max / BN + 1; tile_hi = t2 < tile_hi ? t2 : tile_hi; }
     const int n_all = tile_hi > tile_lo ? tile_hi - tile_lo : 0;
     const int per_split = HPW ? (n_all + da.n_splits - 1) / da.n_splits
                               : ((n_all + da.n_splits - 1) / da.n_splits + NW - 1) / NW * NW;     // multiple of the waves
@@ -474,6 +515,20 @@ __global__ void __launch_bounds__(64 * NW, 1) fa_decode_kernel(const DecArgs da)
             for (int i = 0; i < 16; ++i) {
                 const int j = n0 + (i & 3) + 8 * (i >> 2) + 4 * g;
                 if (j < lo || j > hi) s[i] = -INFINITY;
+            }
+            if (tree && n0 + BN > off) {                    // (wave-uniform; inside: these tiles always take the branch above)
+                // (the lane's slot from the lane id, behind an opaque copy: as a loop invariant the address took a register
+                //  for the whole tile loop)
+                int tl = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                FA_DEC_PIN(tl);
+                const u32x2 tw = *reinterpret_cast<const u32x2*>(smem + TREE_OFF + (tl & 31) * 8);
+                const uint32_t tm0 = tw[0], tm1 = tw[1];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int cN = n0 + (i & 3) + 8 * (i >> 2) + 4 * g - off;      // new key c = j - off
+                    const uint32_t wbits = cN < 32 ? tm0 : tm1;
+                    if (cN >= 0 && !((wbits >> (cN & 31)) & 1u)) s[i] = -INFINITY;
+                }
             }
         }
         if (BN == 16) {                                     // (16-key tiles: key rows 16..31 are not there)
@@ -1522,6 +1577,8 @@ bool decode_applicable(const fa_params& p) {
 // 8 x the passes (B 1, H 32/8, T_q 128 over 8 k: 72 us against 240).  fp8 caches with two row blocks stay here too.
 bool decode_takes(const fa_params& p) {
     if (!decode_applicable(p)) return false;
+    // a tree mask (fa_fwd_kvcache_tree) lives in fa_decode_kernel alone: every tree call runs row blocks of 32 packed rows
+    if (p.flags & FA_FLAG_TREE_MASK) return true;
     const int G = p.nheads_q / p.nheads_k;
     const int row_blocks = (p.seqlen_q * G + 31) / 32;
     const int fwd_blocks = (p.seqlen_q + 127) / 128;
@@ -1655,7 +1712,7 @@ static int launch_decode_td(DecArgs& da, hipStream_t stream) {
     if constexpr (D == 128) {
         if (decode_hpw(p)) {
             const dim3 grid_h(p.batch * (p.nheads_k / 8), da.n_splits, 1);
-            const size_t smem_ = DecSmem<D, 8>::QOFF;                       // the waves' tile regions only: Q in registers, no merge
+            const size_t smem_ = DecSmem<D, 8>::QOFF + DecSmem<D, 8>::TREE;   // the waves' tile regions (Q in registers, no merge) + the tree words
 #define FA_LAUNCH_HPW(KV8_, PAGED_, F8M_)                                                                          \
             do {                                                                                                    \
                 auto kern = fa_decode_kernel<T, D, KV8_, PAGED_, false, 8, F8M_, true>;                            \
@@ -1676,7 +1733,7 @@ static int launch_decode_td(DecArgs& da, hipStream_t stream) {
 #define FA_LAUNCH_DEC(KV8, PAGED, NARROW, NW_)                                                                      \
     do {                                                                                                            \
         auto kern = fa_decode_kernel<T, D, KV8, PAGED, NARROW, NW_>;                                                \
-        const size_t smem_ = DecSmem<D, NW_>::TOTAL;                                                                \
+        const size_t smem_ = DecSmem<D, NW_>::TOTAL + DecSmem<D, NW_>::TREE;                                        \
         FA_SET_LDS_ONCE(kern, smem_);                                                                               \
         hipLaunchKernelGGL(kern, grid, dim3(64 * NW_), smem_, stream, da);                                          \
     } while (0)
@@ -1690,7 +1747,7 @@ static int launch_decode_td(DecArgs& da, hipStream_t stream) {
                 // the fp8 cache feeds v_mfma_f32_32x32x16_fp8_fp8 as stored (F8M above); FA_DEC_F8M=0 builds keep the dequantising form
                 if (w8) {
                     auto kern = paged ? fa_decode_kernel<T, D, true, true, false, 8, true> : fa_decode_kernel<T, D, true, false, false, 8, true>;
-                    const size_t smem_ = DecSmem<D, 8>::QOFF + DecSmem<D, 8>::QBYTES + (D / 16) * 64 * 8;    // (+ the third Q term)
+                    const size_t smem_ = DecSmem<D, 8>::QOFF + DecSmem<D, 8>::QBYTES + (D / 16) * 64 * 8 + DecSmem<D, 8>::TREE;    // (+ the third Q term, + the tree words)
                     static_assert(DecSmem<D, 8>::QOFF + DecSmem<D, 8>::QBYTES + (D / 16) * 64 * 8 >= DecSmem<D, 8>::MERGE, "merge area");
                     if (paged) { FA_SET_LDS_ONCE((fa_decode_kernel<T, D, true, true, false, 8, true>), smem_); }
                     else       { FA_SET_LDS_ONCE((fa_decode_kernel<T, D, true, false, false, 8, true>), smem_); }
@@ -1723,7 +1780,7 @@ static int launch_decode_td(DecArgs& da, hipStream_t stream) {
 }
 
 // workspace layout: [o_partial | lse_partial] at `ws`
-int launch_decode_splitkv(const KArgs& a, void* ws, hipStream_t stream) {
+int launch_decode_splitkv(const KArgs& a, void* ws, hipStream_t stream, const fa_tree_params* tree) {
     const fa_params& p = a.p;
     DecArgs da;
     da.a = a;
@@ -1732,6 +1789,13 @@ int launch_decode_splitkv(const KArgs& a, void* ws, hipStream_t stream) {
     da.local = (p.is_causal || p.window_left >= 0 || p.window_right >= 0) ? 1 : 0;
     da.bias = (p.alibi_slopes != nullptr || p.softcap > 0.f) ? 1 : 0;
     da.cu_q = p.cu_seqlens_q;                         // (NULL except for the routes of the varlen op)
+    da.tree_mask = nullptr; da.tree_depths = nullptr;
+    da.tree_mask_stride = da.tree_depths_stride = 0; da.tree_words = 0;
+    if (tree && tree->mask) {
+        if (p.seqlen_q < 2 || p.seqlen_q > 64 || da.cu_q) return -2;      // (fa_decode_kernel's row blocks only)
+        da.tree_mask = tree->mask; da.tree_mask_stride = tree->mask_batch_stride; da.tree_words = tree->mask_words;
+        if (p.rotary_dim > 0) { da.tree_depths = tree->depths; da.tree_depths_stride = tree->depths_batch_stride; }
+    }
     da.n_splits = decode_num_partials(p);             // (token-major kernel: grid splits x key sub-ranges; else the grid's y)
     da.ksub = gemv_tm_applicable(p) ? gemv_tm_ksub(p) : 1;
     da.page_shift = -1;

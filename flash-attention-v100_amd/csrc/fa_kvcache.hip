@@ -18,7 +18,7 @@ int launch_fwd(const KArgs& a, hipStream_t stream);
 bool decode_applicable(const fa_params& p);
 bool decode_takes(const fa_params& p);
 size_t decode_split_workspace_bytes(const fa_params& p);
-int launch_decode_splitkv(const KArgs& a, void* ws, hipStream_t stream);
+int launch_decode_splitkv(const KArgs& a, void* ws, hipStream_t stream, const fa_tree_params* tree);
 
 // 8 x 16-bit -> 8 x fp8-e4m3 (OCP), value / descale, saturating at +-448
 template <typename T>
@@ -38,8 +38,9 @@ __device__ __forceinline__ u32x2 to_fp8x8(const u32x4& x, float inv_descale) {
 }
 
 // One thread per 16-byte chunk of one new (b, r, hk) row; K and V.
+// depths (tree decode, fa_tree_params): new token r is rotated at position L + leftpad + depths[b, r]; its cache slot stays L + r
 template <typename T, bool KV8>
-__global__ void __launch_bounds__(256) kv_append_kernel(const KArgs a) {
+__global__ void __launch_bounds__(256) kv_append_kernel(const KArgs a, const int32_t* depths, int64_t depths_batch_stride) {
     const fa_params& p = a.p;
     const int cpr = valid_cols(p) / 8;
     const int64_t total = (int64_t)p.batch * p.seqlen_new * p.nheads_k * cpr;
@@ -61,15 +62,16 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const KArgs a) {
                          (int64_t)r * p.vnew_row_stride + (int64_t)hk * p.vnew_head_stride;
     u32x4 kx = *reinterpret_cast<const u32x4*>(kn + d_base);
     const u32x4 vx = *reinterpret_cast<const u32x4*>(vn + d_base);
-    if (p.rotary_dim > 0 && d_base < p.rotary_dim && pos < p.seqlen_ro) {
+    const int rpos = depths ? L + lp + depths[(int64_t)b * depths_batch_stride + r] : pos;
+    if (p.rotary_dim > 0 && d_base < p.rotary_dim && rpos >= 0 && rpos < p.seqlen_ro) {
         const int half = p.rotary_dim >> 1;
         u32x4 kp = kx;
         if (!p.rotary_interleaved) {
             const int pd = d_base < half ? d_base + half : d_base - half;
             kp = *reinterpret_cast<const u32x4*>(kn + pd);
         }
-        const uint16_t* cosp = reinterpret_cast<const uint16_t*>(p.rotary_cos) + (int64_t)pos * half;
-        const uint16_t* sinp = reinterpret_cast<const uint16_t*>(p.rotary_sin) + (int64_t)pos * half;
+        const uint16_t* cosp = reinterpret_cast<const uint16_t*>(p.rotary_cos) + (int64_t)rpos * half;
+        const uint16_t* sinp = reinterpret_cast<const uint16_t*>(p.rotary_sin) + (int64_t)rpos * half;
         rope_chunk<T>(kx, kp, cosp, sinp, d_base, p.rotary_dim, p.rotary_interleaved != 0);
     }
     int64_t koff, voff;
@@ -99,7 +101,7 @@ size_t decode_workspace_bytes(const fa_params& p) {
     return 0;                       // the general path rotates Q inside fa_fwd_kernel (KArgs::rope_q): no scratch
 }
 
-int launch_decode(const KArgs& a_in, hipStream_t stream) {
+int launch_decode(const KArgs& a_in, hipStream_t stream, const fa_tree_params* tree) {
     KArgs a = a_in;
     fa_params& p = a.p;
     const bool bf = p.dtype == FA_BF16;
@@ -109,21 +111,24 @@ int launch_decode(const KArgs& a_in, hipStream_t stream) {
     // chunked prefill, long speculative blocks -: fa_fwd_kernel on the cache, which dequantises an fp8 tile once per 128
     // query rows.  decode_takes() (fa_decode.hip) holds the rule and the measurements behind it.
     const bool fast = decode_takes(p);
+    if (tree && !fast) return -2;                       // (a tree never reaches the general kernel; refused before the append touches the cache)
     if (p.k_new) {
         const int64_t total = (int64_t)p.batch * p.seqlen_new * p.nheads_k * (valid_cols(p) / 8);
         const int grid = (int)((total + 255) / 256);
+        const int32_t* depths = (tree && p.rotary_dim > 0) ? tree->depths : nullptr;
+        const int64_t dstride = tree ? tree->depths_batch_stride : 0;
         if (kv8) {
-            if (bf) hipLaunchKernelGGL((kv_append_kernel<bf16_tag, true>), dim3(grid), dim3(256), 0, stream, a);
-            else    hipLaunchKernelGGL((kv_append_kernel<fp16_tag, true>), dim3(grid), dim3(256), 0, stream, a);
+            if (bf) hipLaunchKernelGGL((kv_append_kernel<bf16_tag, true>), dim3(grid), dim3(256), 0, stream, a, depths, dstride);
+            else    hipLaunchKernelGGL((kv_append_kernel<fp16_tag, true>), dim3(grid), dim3(256), 0, stream, a, depths, dstride);
         } else {
-            if (bf) hipLaunchKernelGGL((kv_append_kernel<bf16_tag, false>), dim3(grid), dim3(256), 0, stream, a);
-            else    hipLaunchKernelGGL((kv_append_kernel<fp16_tag, false>), dim3(grid), dim3(256), 0, stream, a);
+            if (bf) hipLaunchKernelGGL((kv_append_kernel<bf16_tag, false>), dim3(grid), dim3(256), 0, stream, a, depths, dstride);
+            else    hipLaunchKernelGGL((kv_append_kernel<fp16_tag, false>), dim3(grid), dim3(256), 0, stream, a, depths, dstride);
         }
     }
     if (fast) {
         const size_t need = decode_split_workspace_bytes(p);
         if (need > 0 && (!p.workspace || p.workspace_bytes < need)) return -1;
-        return launch_decode_splitkv(a, p.workspace, stream);
+        return launch_decode_splitkv(a, p.workspace, stream, tree);
     }
     a.rope_q = p.rotary_dim > 0 ? 1 : 0;
     return launch_fwd(a, stream);

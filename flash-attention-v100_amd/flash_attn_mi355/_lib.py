@@ -14,6 +14,7 @@ FA_FLAG_KEEP_WINDOW = 1
 FA_FLAG_NO_DKV_SPLIT = 2
 FA_FLAG_DS_HANDOFF = 4
 FA_FLAG_FWD_KEY_SPLIT = 8
+FA_FLAG_TREE_MASK = 16
 
 _i64, _i32, _f32, _u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
 _ptr = ctypes.c_void_p
@@ -77,12 +78,39 @@ def ext_params(sinks=None, dsinks=None):
     return e
 
 
+class FaTreeParams(ctypes.Structure):
+    """Mirror of `struct fa_tree_params` (include/fa_mi355.h): the tree-mask block of fa_fwd_kvcache_tree.
+    struct_size must be set to sizeof(FaTreeParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("mask", _ptr),                  # uint32 [B, T_q, W] / [T_q, W] visibility words, NULL = no tree
+        ("mask_batch_stride", _i64),     # in words, 0 = one tree for the whole batch
+        ("mask_words", _i32),            # W = ceil(T_q / 32)
+        ("depths", _ptr),                # int32 [B, T_q] / [T_q] node depths, NULL = none
+        ("depths_batch_stride", _i64),   # in elements, 0 = shared
+    ]
+
+
+def tree_params(mask=None, depths=None):
+    """an FaTreeParams with struct_size filled in; mask: packed int32 [B, T, W] / [T, W] GPU tensor, depths: int32 [B, T] / [T]"""
+    t = FaTreeParams()
+    t.struct_size = ctypes.sizeof(FaTreeParams)
+    if mask is not None:
+        t.mask = mask.data_ptr()
+        t.mask_words = mask.shape[-1]
+        t.mask_batch_stride = mask.stride(0) if mask.dim() == 3 else 0
+    if depths is not None:
+        t.depths = depths.data_ptr()
+        t.depths_batch_stride = depths.stride(0) if depths.dim() == 2 else 0
+    return t
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd_workspace_bytes", "fa_bwd_workspace_bytes", "fa_fwd_kvcache_workspace_bytes",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
-           "fa_gather_rows", "fa_scatter_rows"] + EXT_OPS
+           "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size"] + EXT_OPS
 
 
 def _load():
@@ -111,6 +139,10 @@ def _load():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.POINTER(FaParams), ctypes.POINTER(FaExtParams), ctypes.c_void_p]
+    lib.fa_fwd_kvcache_tree.restype = ctypes.c_int
+    lib.fa_fwd_kvcache_tree.argtypes = [ctypes.POINTER(FaParams), ctypes.POINTER(FaExtParams), ctypes.POINTER(FaTreeParams),
+                                        ctypes.c_void_p]
+    lib.fa_tree_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -121,6 +153,9 @@ def _load():
     if lib.fa_params_size() != ctypes.sizeof(FaParams):
         raise ImportError(f"fa_params size mismatch: library {lib.fa_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaParams)}")
+    if lib.fa_tree_params_size() != ctypes.sizeof(FaTreeParams):
+        raise ImportError(f"fa_tree_params size mismatch: library {lib.fa_tree_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaTreeParams)}")
     return lib
 
 
@@ -144,6 +179,15 @@ def call_ext(name, params, ext, stream):
     if rc != 0:
         msg = lib.fa_last_error().decode(errors="replace")
         raise RuntimeError(f"{name}_ext failed ({rc}): {msg}")
+
+
+def call_tree(params, ext, tree, stream):
+    """fa_fwd_kvcache_tree: the kv-cache op with an optional extension block and an optional tree block (None: NULL)"""
+    rc = lib.fa_fwd_kvcache_tree(ctypes.byref(params), None if ext is None else ctypes.byref(ext),
+                                 None if tree is None else ctypes.byref(tree), ctypes.c_void_p(stream))
+    if rc != 0:
+        msg = lib.fa_last_error().decode(errors="replace")
+        raise RuntimeError(f"fa_fwd_kvcache_tree failed ({rc}): {msg}")
 
 
 def call_rows(name, *args):

@@ -918,7 +918,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                             alibi_slopes: Optional[torch.Tensor] = None, num_splits: int = 0,
                             return_softmax_lse: bool = False, *,
                             k_descale: Optional[float] = None, v_descale: Optional[float] = None,
-                            sinks: Optional[torch.Tensor] = None):
+                            sinks: Optional[torch.Tensor] = None,
+                            tree_mask: Optional[torch.Tensor] = None, tree_depths: Optional[torch.Tensor] = None):
     """FlashAttention with KV cache (B, M, H, D). k_cache / v_cache are updated in place.
 
     A decode step is launch-bound at small batch (two kernels of 10-15 us), so the host side matters: the argument checks
@@ -927,10 +928,18 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     geometry (`_KV_PLANS`); a repeat call copies it and writes the dozen pointers (tools/host_overhead.py).
 
     sinks ([H_Q], any floating dtype, on q's device): attention sinks, one logit per query head in the softmax
-    denominator with no value (flash_attn_sinks_func); the LSE returned is the sink-inclusive one.  Forward only."""
+    denominator with no value (flash_attn_sinks_func); the LSE returned is the sink-inclusive one.  Forward only.
+
+    tree_mask: the T_q (2 .. 64) query tokens are the nodes of a speculative-decoding draft tree.  Every node sees the
+    committed cache plus the new tokens its mask row names: bool [B, T_q, T_q] or [T_q, T_q] (row = query node, column = key
+    node; packed to words on the device), or already packed int32 [B, T_q, W] / [T_q, W] with W = ceil(T_q / 32) (bit c & 31
+    of word c >> 5 = key node c).  The mask replaces the causal rule (`causal` has no further effect); `window_size` must be
+    (-1, -1) and ALiBi is not supported.  The nodes' K / V come with the call (k, v with T_q tokens) or already sit at the end
+    of the cache.  tree_depths (int32 [B, T_q] or [T_q]): node t is rotated at position cache_seqlens + depth[t] while its
+    cache slot stays cache_seqlens + t; required with rotary_cos, ignored without."""
     key = _kv_plan_key(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad,
                        block_table, softmax_scale, causal, window_size, softcap, rotary_interleaved, alibi_slopes,
-                       num_splits, k_descale, v_descale, sinks)
+                       num_splits, k_descale, v_descale, sinks, tree_mask, tree_depths)
     plan = _KV_PLANS.get(key) if key is not None else None
     if plan is not None:
         _KV_PLANS.move_to_end(key)
@@ -952,11 +961,18 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         # (the sinks' geometry is part of the key; their pointer is written on every call, like the others)
         s32 = None if sinks is None else sinks.to(torch.float32).contiguous()
         with _on_device(q.device):
-            _lib.call_ext("fa_fwd_kvcache", pp, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
+            if tree_mask is not None:
+                # (the tree tensors' geometry is part of the key too; bool masks are packed on the device on every call)
+                words = _pack_tree_mask(tree_mask) if tree_mask.dtype == torch.bool else tree_mask
+                _lib.call_tree(pp, None if s32 is None else _lib.ext_params(s32),
+                               _lib.tree_params(words, tree_depths if rotary_cos is not None else None), _stream(q.device))
+            else:
+                _lib.call_ext("fa_fwd_kvcache", pp, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
         return (out, lse) if return_softmax_lse else out
     assert k_cache.stride(-1) == 1, "k_cache must have contiguous last dimension"
     assert v_cache.stride(-1) == 1, "v_cache must have contiguous last dimension"
     s32 = _check_sinks(sinks, q.shape[-2], q)
+    tree_words, tree_depths = _check_tree(tree_mask, tree_depths, q, k, window_size, alibi_slopes, rotary_cos)
     _check_device(q, k_cache, v_cache, k, v)
     if q.dtype not in _DTYPES:
         raise RuntimeError("q must be fp16 or bf16")
@@ -1055,12 +1071,18 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
         p.rotary_interleaved = int(bool(rotary_interleaved))
     _alibi(p, alibi_slopes, B, H_Q, q.device)
     p.num_splits = int(num_splits)
+    if tree_words is not None:
+        p.flags |= _lib.FA_FLAG_TREE_MASK               # (the workspace query answers for the route a tree call takes)
     ws_bytes = int(_lib.lib.fa_fwd_kvcache_workspace_bytes(ctypes.byref(p)))
     ws = _workspace(ws_bytes, q.device)
     if ws is not None:
         p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
     with _on_device(q.device):
-        _lib.call_ext("fa_fwd_kvcache", p, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
+        if tree_words is not None:
+            _lib.call_tree(p, None if s32 is None else _lib.ext_params(s32), _lib.tree_params(tree_words, tree_depths),
+                           _stream(q.device))
+        else:
+            _lib.call_ext("fa_fwd_kvcache", p, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
     if key is not None:                                  # (the call went through: this geometry passes every check)
         while len(_KV_PLANS) >= _KV_PLANS_MAX:           # least recently used geometry out (a workload whose geometry keeps
             _KV_PLANS.popitem(last=False)                # changing must not wipe the plans of the steady ones)
@@ -1072,6 +1094,64 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
 
 _KV_PLANS = collections.OrderedDict()
 _KV_PLANS_MAX = 256
+_TREE_BITS = {}                                          # device -> int32 [32]: 1 << i (bit 31 as the sign bit)
+
+
+def _pack_tree_mask(mask: torch.Tensor) -> torch.Tensor:
+    """bool [..., T, T] (row = query node, column = key node) -> int32 [..., T, ceil(T / 32)] visibility words, bit c & 31 of
+    word c >> 5 = column c.  A few device ops and no host sync, so the call stays capturable in a HIP graph."""
+    T = mask.shape[-1]
+    W = (T + 31) // 32
+    bits = _TREE_BITS.get(mask.device)
+    if bits is None:
+        sh = torch.arange(32, dtype=torch.int32, device=mask.device)
+        bits = _TREE_BITS[mask.device] = torch.bitwise_left_shift(torch.ones_like(sh), sh)
+    m = mask
+    if W * 32 != T:
+        m = torch.nn.functional.pad(m, (0, W * 32 - T))
+    # (distinct powers of two: the int32 sum is exact, bit 31 being -2^31)
+    return (m.reshape(*m.shape[:-1], W, 32).to(torch.int32) * bits).sum(-1, dtype=torch.int32)
+
+
+def _check_tree(tree_mask, tree_depths, q, k, window_size, alibi_slopes, rotary_cos):
+    """flash_attn_with_kvcache's tree arguments: (packed int32 words, depths or None), or (None, None) without a tree"""
+    if tree_mask is None:
+        if tree_depths is not None:
+            raise RuntimeError("tree_depths needs tree_mask")
+        return None, None
+    if q.dim() != 4:
+        raise RuntimeError("q must be (B, T, H, D)")
+    B, T = q.shape[0], q.shape[1]
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.device != q.device:
+        raise RuntimeError("tree_mask must be a tensor on the same device as q")
+    if not 2 <= T <= 64:
+        raise RuntimeError(f"tree_mask: the tree must have 2 .. 64 query tokens (got {T})")
+    W = (T + 31) // 32
+    if tree_mask.dtype == torch.bool:
+        if tuple(tree_mask.shape) not in ((B, T, T), (T, T)):
+            raise RuntimeError(f"tree_mask (bool) must have shape ({B}, {T}, {T}) or ({T}, {T})")
+        words = _pack_tree_mask(tree_mask)
+    elif tree_mask.dtype == torch.int32:
+        if tuple(tree_mask.shape) not in ((B, T, W), (T, W)):
+            raise RuntimeError(f"tree_mask (packed int32) must have shape ({B}, {T}, {W}) or ({T}, {W})")
+        words = tree_mask.contiguous()
+    else:
+        raise RuntimeError("tree_mask must have dtype bool or (packed) int32")
+    if tuple(window_size) != (-1, -1):
+        raise RuntimeError("tree_mask: window_size must be (-1, -1)")
+    if alibi_slopes is not None:
+        raise RuntimeError("tree_mask: ALiBi is not supported (its distance term needs tree positions)")
+    if k is not None and k.shape[1] != T:
+        raise RuntimeError(f"tree_mask: k / v must bring the tree's {T} tokens (or be None: the nodes already sit in the cache)")
+    if rotary_cos is None:
+        return words, None                               # (depths only feed the in-kernel RoPE)
+    if tree_depths is None:
+        raise RuntimeError("tree_mask with rotary_cos needs tree_depths (node t sits at position cache_seqlens + depth[t])")
+    if not isinstance(tree_depths, torch.Tensor) or tree_depths.device != q.device or tree_depths.dtype != torch.int32:
+        raise RuntimeError("tree_depths must be an int32 tensor on the same device as q")
+    if tuple(tree_depths.shape) not in ((B, T), (T,)):
+        raise RuntimeError(f"tree_depths must have shape ({B}, {T}) or ({T},)")
+    return words, tree_depths.contiguous()
 
 
 def _geom(t):
@@ -1080,7 +1160,7 @@ def _geom(t):
 
 def _kv_plan_key(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens, cache_batch_idx, cache_leftpad,
                  block_table, softmax_scale, causal, window_size, softcap, rotary_interleaved, alibi_slopes, num_splits,
-                 k_descale, v_descale, sinks=None):
+                 k_descale, v_descale, sinks=None, tree_mask=None, tree_depths=None):
     """Everything flash_attn_with_kvcache's checks and fa_params fields depend on, except the data pointers - or None
     when the call needs the slow path anyway: an int cache_seqlens, descales given as tensors, or ANY input the slow path
     would route through maybe_contiguous() (the template holds the strides of the tensors the kernel was launched on: a
@@ -1090,14 +1170,14 @@ def _kv_plan_key(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlen
         return None
     if isinstance(k_descale, torch.Tensor) or isinstance(v_descale, torch.Tensor):
         return None
-    for t in (q, k, v, cache_seqlens, cache_batch_idx, cache_leftpad, block_table):
-        if t is not None and (t.dim() == 0 or not t.is_contiguous()):
+    for t in (q, k, v, cache_seqlens, cache_batch_idx, cache_leftpad, block_table, tree_mask, tree_depths):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() == 0 or not t.is_contiguous()):
             return None
     return (_geom(q), _geom(k_cache), _geom(v_cache), _geom(k), _geom(v), _geom(rotary_cos), _geom(rotary_sin),
             _geom(cache_seqlens), _geom(cache_batch_idx), _geom(cache_leftpad), _geom(block_table), _geom(alibi_slopes),
             softmax_scale, bool(causal), tuple(window_size), float(softcap), bool(rotary_interleaved), int(num_splits),
             None if k_descale is None else float(k_descale), None if v_descale is None else float(v_descale),
-            _geom(sinks))
+            _geom(sinks), _geom(tree_mask), _geom(tree_depths))
 
 
 # ======================================================================================

@@ -1,5 +1,5 @@
 """torch.library registration of the five operators: `torch.ops.flash_attn_mi355.{fwd, bwd,
-varlen_fwd, varlen_bwd, fwd_kvcache}`.
+varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -315,4 +315,30 @@ def _(q, kcache, vcache, k, v, seqlens_k, rotary_cos, rotary_sin, cache_batch_id
     return torch.empty_like(q), q.new_empty((B, H, T), dtype=torch.float32)
 
 
-__all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_out", "varlen_fwd_out", "bwd_out"]
+@torch.library.custom_op(f"{_NS}::fwd_kvcache_tree", mutates_args=("kcache", "vcache"), device_types="cuda")
+def fwd_kvcache_tree(q: Tensor, kcache: Tensor, vcache: Tensor, k: Optional[Tensor], v: Optional[Tensor],
+                     seqlens_k: Optional[Tensor], rotary_cos: Optional[Tensor], rotary_sin: Optional[Tensor],
+                     cache_batch_idx: Optional[Tensor], leftpad_k: Optional[Tensor],
+                     block_table: Optional[Tensor], tree_mask: Tensor, tree_depths: Optional[Tensor],
+                     softmax_scale: float, softcap: float, is_rotary_interleaved: bool,
+                     num_splits: int) -> Tuple[Tensor, Tensor]:
+    """fwd_kvcache for the nodes of a speculative-decoding draft tree: `tree_mask` (bool [B, T, T] / [T, T] or packed int32
+    [B, T, W] / [T, W]) replaces the causal rule among the T new tokens, `tree_depths` gives their rotary positions
+    (flash_attn_with_kvcache).  No ALiBi, no windows."""
+    out, lse = _fi.flash_attn_with_kvcache(
+        q, kcache, vcache, k=k, v=v, rotary_cos=rotary_cos, rotary_sin=rotary_sin,
+        cache_seqlens=seqlens_k, cache_batch_idx=cache_batch_idx, cache_leftpad=leftpad_k,
+        block_table=block_table, softmax_scale=softmax_scale, causal=False, softcap=softcap,
+        rotary_interleaved=is_rotary_interleaved, num_splits=num_splits, return_softmax_lse=True,
+        tree_mask=tree_mask, tree_depths=tree_depths)
+    return out, lse
+
+
+@fwd_kvcache_tree.register_fake
+def _(q, kcache, vcache, k, v, seqlens_k, rotary_cos, rotary_sin, cache_batch_idx, leftpad_k, block_table,
+      tree_mask, tree_depths, softmax_scale, softcap, is_rotary_interleaved, num_splits):
+    B, T, H, _ = q.shape
+    return torch.empty_like(q), q.new_empty((B, H, T), dtype=torch.float32)
+
+
+__all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out"]

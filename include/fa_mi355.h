@@ -54,6 +54,11 @@ extern "C" {
  * fa_fwd_workspace_bytes() reports, the heavy blocks' key ranges are cut into 2 - 4 parts whose fp32 partial outputs a merge kernel
  * combines (deterministic; out / LSE equal the unsplit result up to the order of fp32 additions).  Ignored where it does not apply. */
 #define FA_FLAG_FWD_KEY_SPLIT 8
+/* fa_fwd_kvcache_tree only: a tree block (fa_tree_params below) accompanies the call.  The caller sets it whenever it passes one, so
+ * that fa_fwd_kvcache_workspace_bytes() - which sees fa_params alone - answers for the route a tree call takes (always the decode
+ * kernels).  The flag without a tree block, a tree block without the flag, and the flag on any other op are
+ * FA_ERR_INVALID_ARGUMENT. */
+#define FA_FLAG_TREE_MASK 16
 
 typedef enum fa_dtype {
     FA_FP16 = 0,      /* IEEE half */
@@ -263,6 +268,41 @@ int fa_varlen_fwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream
 int fa_fwd_kvcache_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
 int fa_bwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
 int fa_varlen_bwd_ext(const fa_params* p, const fa_ext_params* ext, void* stream);
+
+/*
+ * Tree attention masks for speculative decoding (additive, like the block above: fa_params and FA_ABI_VERSION are unchanged).
+ *
+ * The call brings T_q = seqlen_q query tokens per sequence, 2 <= T_q <= 64: the nodes of a draft tree.  Their K / V are appended
+ * by the same call (k_new / v_new with seqlen_new == T_q) or already sit at the end of the cache (seqlen_new == 0).  With
+ * seqlen_k = cache_seqlens[b] + seqlen_new and off = seqlen_k - T_q:
+ *   - key j < off (the committed cache) is visible to every query row;
+ *   - key off + c, 0 <= c < T_q, is visible to row t iff bit (c & 31) of word (c >> 5) of mask[b, t] is set.
+ * The mask REPLACES the causal rule (is_causal is accepted and has no further effect); it need not be topologically ordered nor
+ * contain the diagonal.  A row without a visible key gives out = 0 and LSE = -inf (with attention sinks: LSE = s_h).
+ * With seqlen_new == 0 the nodes are the LAST T_q keys of the cache, so the caller passes cache_seqlens[b] >= T_q (lengths
+ * live on the device and are not checked): a shorter cache gives off < 0, the bits c < -off then name keys that do not exist
+ * and are ignored, nothing is read out of bounds.
+ * Positions: node t sits at position cache_seqlens[b] + cache_leftpad[b] + depths[b, t] for the in-kernel RoPE of q and of the new
+ * k, while its cache SLOT stays cache_seqlens[b] + t.  depths is required when rotary_dim > 0 and ignored otherwise.
+ * Works with softcap, attention sinks, GQA / MQA, paged and contiguous caches, cache_batch_idx, cache_leftpad, fp8-e4m3 caches,
+ * num_splits and every head width of fa_fwd_kvcache.  Every tree call runs on the split-KV decode kernels (32 packed rows per
+ * workgroup); set FA_FLAG_TREE_MASK in fa_params::flags for the call AND for its fa_fwd_kvcache_workspace_bytes() query.
+ * Windows must be off (window_left == window_right == -1: FA_ERR_INVALID_ARGUMENT otherwise).
+ * Out of scope: ALiBi with a tree (FA_ERR_UNSUPPORTED: its distance term needs tree positions), tree masks through the varlen
+ * op's decode route, T_q > 64, and any backward.
+ */
+typedef struct fa_tree_params {
+    size_t          struct_size;          /* sizeof(fa_tree_params) as the caller compiled it */
+    const uint32_t* mask;                 /* [B, T_q, mask_words] (or [T_q, mask_words]) visibility words, 4-byte aligned; NULL = no tree */
+    int64_t         mask_batch_stride;    /* in words; 0 = one tree for the whole batch */
+    int32_t         mask_words;           /* ceil(T_q / 32): 1 or 2 */
+    const int32_t*  depths;               /* [B, T_q] (or [T_q]) node depths, 4-byte aligned; NULL = none (no rotary) */
+    int64_t         depths_batch_stride;  /* in elements; 0 = one depth array for the whole batch */
+} fa_tree_params;
+
+/* fa_fwd_kvcache_ext with a tree block.  tree == NULL or tree->mask == NULL: exactly fa_fwd_kvcache_ext. */
+int fa_fwd_kvcache_tree(const fa_params* p, const fa_ext_params* ext, const fa_tree_params* tree, void* stream);
+size_t fa_tree_params_size(void);
 
 /*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
