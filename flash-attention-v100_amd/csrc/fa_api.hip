@@ -29,6 +29,8 @@ int launch_decode(const KArgs& a, hipStream_t stream, const fa_tree_params* tree
 size_t decode_workspace_bytes(const fa_params& p);
 bool decode_applicable(const fa_params& p);
 bool decode_takes(const fa_params& p);
+int merge_vec_width(const fa_merge_params& m);           // fa_merge.hip: 8 / 4 values per piece, 0 = o not 8-byte aligned
+void launch_merge_states(const fa_merge_params& m, hipStream_t stream);
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -192,6 +194,7 @@ extern "C" {
 int fa_abi_version(void) { return FA_ABI_VERSION; }
 size_t fa_params_size(void) { return sizeof(fa_params); }
 size_t fa_tree_params_size(void) { return sizeof(fa_tree_params); }
+size_t fa_merge_params_size(void) { return sizeof(fa_merge_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -595,6 +598,32 @@ int fa_scatter_rows(const void* src, const int64_t* indices, void* dst, int64_t 
     if (fa::launch_scatter_rows(src, indices, dst, n_idx, n_dst_rows, row_bytes, sorted_unique, static_cast<hipStream_t>(stream)))
         return fail(FA_ERR_INVALID_ARGUMENT, "hipMemsetAsync failed");
     return check_hip("fa_scatter_rows launch");
+}
+
+int fa_merge_states(const fa_merge_params* m, void* stream) {
+    FA_CHECK(m, "fa_merge_params must not be NULL");
+    FA_CHECK(m->struct_size >= sizeof(fa_merge_params), "fa_merge_params::struct_size %zu is smaller than this library's %zu",
+             m->struct_size, sizeof(fa_merge_params));
+    FA_CHECK(m->n_parts >= 2 && m->n_parts <= FA_MERGE_MAX_PARTS, "n_parts must be 2 .. %d, got %d", FA_MERGE_MAX_PARTS, m->n_parts);
+    FA_CHECK(m->dtype == FA_FP16 || m->dtype == FA_BF16, "merge dtype must be fp16 or bf16");
+    FA_CHECK(m->head_dim > 0 && m->head_dim % 8 == 0 && m->head_dim <= 256, "merge head_dim must be a multiple of 8 and <= 256, got %d",
+             m->head_dim);
+    FA_CHECK(m->batch >= 0 && m->seqlen >= 0 && m->nheads >= 0, "merge sizes must be non-negative");
+    for (int s = 0; s <= m->n_parts; ++s) {
+        const bool is_out = s == m->n_parts;
+        const fa_merge_state& t = is_out ? m->out : m->parts[s];
+        FA_CHECK(t.o && t.lse, "merge %s %d: o and lse must not be NULL", is_out ? "output" : "part", is_out ? 0 : s);
+        FA_CHECK((uintptr_t)t.lse % 4 == 0, "merge %s %d: lse must be 4-byte aligned", is_out ? "output" : "part", is_out ? 0 : s);
+        if (!is_out)
+            FA_CHECK(t.o != m->out.o && t.lse != m->out.lse, "merge output must not alias part %d (no in-place merge)", s);
+    }
+    FA_CHECK(fa::merge_vec_width(*m) != 0, "merge: every o base address and stride must be a multiple of 8 bytes");
+    if (m->batch == 0 || m->seqlen == 0 || m->nheads == 0) return FA_OK;
+    // (one lane per 8-byte piece at the least: the 1-D grid of 256-lane workgroups must fit 31 bits)
+    if ((double)m->batch * m->seqlen * m->nheads * (m->head_dim / 4) >= 256.0 * 2147483647.0)
+        return fail(FA_ERR_UNSUPPORTED, "merge: batch x seqlen x nheads x head_dim is too large for one launch");
+    fa::launch_merge_states(*m, static_cast<hipStream_t>(stream));
+    return check_hip("fa_merge_states launch");
 }
 
 }  // extern "C"

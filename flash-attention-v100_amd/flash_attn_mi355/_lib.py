@@ -105,12 +105,42 @@ def tree_params(mask=None, depths=None):
     return t
 
 
+FA_MERGE_MAX_PARTS = 8
+
+
+class FaMergeState(ctypes.Structure):
+    """Mirror of `struct fa_merge_state` (include/fa_mi355.h): one (o, lse) pair of fa_merge_states, strides in elements."""
+    _fields_ = [
+        ("o", _ptr), ("lse", _ptr),
+        ("o_batch_stride", _i64), ("o_row_stride", _i64), ("o_head_stride", _i64),
+        ("lse_batch_stride", _i64), ("lse_head_stride", _i64), ("lse_row_stride", _i64),
+    ]
+
+
+class FaMergeParams(ctypes.Structure):
+    """Mirror of `struct fa_merge_params` (include/fa_mi355.h).  struct_size must be set to sizeof(FaMergeParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("n_parts", _i32), ("batch", _i32), ("seqlen", _i32), ("nheads", _i32), ("head_dim", _i32), ("dtype", _i32),
+        ("parts", FaMergeState * FA_MERGE_MAX_PARTS),
+        ("out", FaMergeState),
+    ]
+
+
+def merge_state(st, o, lse):
+    """fill an FaMergeState from o [B, S, H, D] (last dimension contiguous) and fp32 lse [B, H, S], both taken as strided views"""
+    st.o, st.lse = o.data_ptr(), lse.data_ptr()
+    st.o_batch_stride, st.o_row_stride, st.o_head_stride = o.stride(0), o.stride(1), o.stride(2)
+    st.lse_batch_stride, st.lse_head_stride, st.lse_row_stride = lse.stride(0), lse.stride(1), lse.stride(2)
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd_workspace_bytes", "fa_bwd_workspace_bytes", "fa_fwd_kvcache_workspace_bytes",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
-           "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size"] + EXT_OPS
+           "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
+           "fa_merge_states", "fa_merge_params_size"] + EXT_OPS
 
 
 def _load():
@@ -143,6 +173,9 @@ def _load():
     lib.fa_fwd_kvcache_tree.argtypes = [ctypes.POINTER(FaParams), ctypes.POINTER(FaExtParams), ctypes.POINTER(FaTreeParams),
                                         ctypes.c_void_p]
     lib.fa_tree_params_size.restype = ctypes.c_size_t
+    lib.fa_merge_states.restype = ctypes.c_int
+    lib.fa_merge_states.argtypes = [ctypes.POINTER(FaMergeParams), ctypes.c_void_p]
+    lib.fa_merge_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -156,6 +189,9 @@ def _load():
     if lib.fa_tree_params_size() != ctypes.sizeof(FaTreeParams):
         raise ImportError(f"fa_tree_params size mismatch: library {lib.fa_tree_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaTreeParams)}")
+    if lib.fa_merge_params_size() != ctypes.sizeof(FaMergeParams):
+        raise ImportError(f"fa_merge_params size mismatch: library {lib.fa_merge_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaMergeParams)}")
     return lib
 
 
@@ -188,6 +224,13 @@ def call_tree(params, ext, tree, stream):
     if rc != 0:
         msg = lib.fa_last_error().decode(errors="replace")
         raise RuntimeError(f"fa_fwd_kvcache_tree failed ({rc}): {msg}")
+
+
+def call_merge(params, stream):
+    """fa_merge_states"""
+    rc = lib.fa_merge_states(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_merge_states failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
 
 
 def call_rows(name, *args):

@@ -1,5 +1,6 @@
 """torch.library registration of the five operators: `torch.ops.flash_attn_mi355.{fwd, bwd,
-varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask).
+varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask; `merge_states`: the
+LSE merge of attention states over disjoint key sets, fa_merge_states).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -18,11 +19,12 @@ torch.compile / FakeTensorMode, and `fwd` / `varlen_fwd` carry autograd formulas
 Import this module to register the ops (flash_attn_mi355/__init__.py does NOT import it, so
 that plain users of the functional API pay nothing).
 """
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
+from . import cascade as _cascade
 from . import flash_attn_interface as _fi
 
 _NS = "flash_attn_mi355"
@@ -341,4 +343,21 @@ def _(q, kcache, vcache, k, v, seqlens_k, rotary_cos, rotary_sin, cache_batch_id
     return torch.empty_like(q), q.new_empty((B, H, T), dtype=torch.float32)
 
 
-__all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out"]
+# ------------------------------------------------------------------------------------------
+# merge of attention states over disjoint key sets (shared-prefix decode, context parallelism)
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::merge_states", mutates_args=(), device_types="cuda")
+def merge_states(outs: List[Tensor], lses: List[Tensor]) -> Tuple[Tensor, Tensor]:
+    """cascade.merge_attention_states: outs[s] [B, S, H, D] fp16 / bf16, lses[s] [B, H, S] fp32, 2 .. 8 parts -> (out, lse).
+    Forward only (no autograd formula)."""
+    return _cascade.merge_attention_states(outs, lses)
+
+
+@merge_states.register_fake
+def _(outs, lses):
+    B, S, H, D = outs[0].shape
+    return outs[0].new_empty((B, S, H, D)), outs[0].new_empty((B, H, S), dtype=torch.float32)
+
+
+__all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",
+           "merge_states"]

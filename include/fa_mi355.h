@@ -305,6 +305,52 @@ int fa_fwd_kvcache_tree(const fa_params* p, const fa_ext_params* ext, const fa_t
 size_t fa_tree_params_size(void);
 
 /*
+ * fa_merge_states - combine attention computed over DISJOINT key sets into attention over their union (additive, like the blocks
+ * above: fa_params and FA_ABI_VERSION are unchanged).
+ *
+ * Every part s is the (o, lse) pair a forward op of this library wrote for the same queries over its own keys.  Per (batch, row,
+ * head), in fp32:
+ *   LSE = logsumexp_s(lse_s),   out = sum_s exp(lse_s - LSE) out_s.
+ * A part whose lse_s is -inf (no visible key) contributes nothing, even where its out_s holds NaN; if every part is -inf the row
+ * gives out = 0 and LSE = -inf.  With exactly one finite part the row's out and LSE are that part's, bit for bit.
+ * With attention sinks, pass the sink to ONE of the forward calls only: its sink-inclusive LSE then makes the merged LSE the
+ * sink-inclusive LSE of the whole problem (a sink in two parts would be counted twice).
+ * Use: shared-prefix ("cascade") decode - one fa_fwd of all queries of a batch over the common prefix, one fa_fwd_kvcache over
+ * each sequence's own tokens, then this merge - and the per-step reduction of context / ring parallelism.
+ * Element (b, i, h, d) of a part's o = o[b*o_batch_stride + i*o_row_stride + h*o_head_stride + d] (strides in elements, the last
+ * dimension contiguous); element (b, h, i) of its lse = lse[b*lse_batch_stride + h*lse_head_stride + i*lse_row_stride].  The
+ * three explicit LSE strides let one call take the [1, H, B*T] LSE of an fa_fwd over all B*T query rows as one sequence (batch
+ * stride T, head stride B*T, row stride 1) next to fa_fwd_kvcache's [B, H, T] LSE, or a row-major [B, T, H] one, without a copy.
+ * One kernel launch on `stream`: byte movement (16-byte loads and stores where every o base and stride is a multiple of 16 bytes,
+ * 8-byte ones where they are multiples of 8), no atomics, no workspace, bitwise repeatable.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; n_parts outside 2 .. FA_MERGE_MAX_PARTS; a NULL o or lse;
+ * head_dim not a multiple of 8 or above 256; a dtype other than FA_FP16 / FA_BF16; negative sizes; an lse that is not 4-byte
+ * aligned; an o base or stride that is not a multiple of 8 bytes; an output o or lse whose base equals a part's (no in-place
+ * merge).  Other overlap between the output and a part is not detected and not supported.
+ */
+#define FA_MERGE_MAX_PARTS 8
+
+typedef struct fa_merge_state {
+    void*   o;                 /* [batch, seqlen, nheads, head_dim] of fa_merge_params::dtype (parts: read only) */
+    float*  lse;               /* fp32 [batch, nheads, seqlen], natural log (parts: read only) */
+    int64_t o_batch_stride, o_row_stride, o_head_stride;
+    int64_t lse_batch_stride, lse_head_stride, lse_row_stride;
+} fa_merge_state;
+
+typedef struct fa_merge_params {
+    size_t         struct_size;   /* sizeof(fa_merge_params) as the caller compiled it */
+    int32_t        n_parts;       /* 2 .. FA_MERGE_MAX_PARTS */
+    int32_t        batch, seqlen, nheads;
+    int32_t        head_dim;      /* a multiple of 8, <= 256 */
+    int32_t        dtype;         /* FA_FP16 or FA_BF16: every part's o and the output o */
+    fa_merge_state parts[FA_MERGE_MAX_PARTS];
+    fa_merge_state out;           /* written */
+} fa_merge_params;
+
+int    fa_merge_states(const fa_merge_params* m, void* stream);
+size_t fa_merge_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
