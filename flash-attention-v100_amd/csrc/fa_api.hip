@@ -31,6 +31,7 @@ bool decode_applicable(const fa_params& p);
 bool decode_takes(const fa_params& p);
 int merge_vec_width(const fa_merge_params& m);           // fa_merge.hip: 8 / 4 values per piece, 0 = o not 8-byte aligned
 void launch_merge_states(const fa_merge_params& m, hipStream_t stream);
+void launch_rotary(const fa_rotary_params& r, hipStream_t stream);          // fa_rotary.hip: standalone rotary embedding
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -195,6 +196,7 @@ int fa_abi_version(void) { return FA_ABI_VERSION; }
 size_t fa_params_size(void) { return sizeof(fa_params); }
 size_t fa_tree_params_size(void) { return sizeof(fa_tree_params); }
 size_t fa_merge_params_size(void) { return sizeof(fa_merge_params); }
+size_t fa_rotary_params_size(void) { return sizeof(fa_rotary_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -624,6 +626,52 @@ int fa_merge_states(const fa_merge_params* m, void* stream) {
         return fail(FA_ERR_UNSUPPORTED, "merge: batch x seqlen x nheads x head_dim is too large for one launch");
     fa::launch_merge_states(*m, static_cast<hipStream_t>(stream));
     return check_hip("fa_merge_states launch");
+}
+
+// bytes from the first to one past the last element of x / out as fa_rotary addresses it (strides >= 0, sizes > 0)
+static uint64_t rotary_span_bytes(const fa_rotary_params& r, int64_t bs, int64_t rs, int64_t hs) {
+    const int64_t rows = r.cu_seqlens ? r.total_rows : r.seqlen;
+    const int64_t last = (r.cu_seqlens ? 0 : (int64_t)(r.batch - 1) * bs) + (rows - 1) * rs + (int64_t)(r.nheads - 1) * hs + r.head_dim;
+    return (uint64_t)last * 2;
+}
+
+int fa_rotary(const fa_rotary_params* r, void* stream) {
+    FA_CHECK(r, "fa_rotary_params must not be NULL");
+    FA_CHECK(r->struct_size >= sizeof(fa_rotary_params), "fa_rotary_params::struct_size %zu is smaller than this library's %zu",
+             r->struct_size, sizeof(fa_rotary_params));
+    FA_CHECK(r->x && r->out && r->cos && r->sin, "rotary: x, out, cos and sin must not be NULL");
+    FA_CHECK(r->dtype == FA_FP16 || r->dtype == FA_BF16, "rotary dtype must be fp16 or bf16");
+    FA_CHECK(r->batch >= 0 && r->seqlen >= 0 && r->nheads >= 0 && r->head_dim >= 0 && r->seqlen_ro >= 0 && r->total_rows >= 0 &&
+             r->seqlen_offset >= 0, "rotary sizes and seqlen_offset must be non-negative");
+    FA_CHECK(r->rotary_dim > 0 && r->rotary_dim % 2 == 0, "rotary_dim must be positive and even, got %d", r->rotary_dim);
+    FA_CHECK(r->rotary_dim <= r->head_dim, "rotary_dim must be <= head_dim (%d > %d)", r->rotary_dim, r->head_dim);
+    FA_CHECK(r->x_batch_stride >= 0 && r->x_row_stride >= 0 && r->x_head_stride >= 0 && r->o_batch_stride >= 0 &&
+             r->o_row_stride >= 0 && r->o_head_stride >= 0, "rotary strides must be non-negative");
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(r->x), oa = reinterpret_cast<uintptr_t>(r->out);
+    FA_CHECK(xa % 2 == 0 && oa % 2 == 0, "rotary: x and out must be 2-byte aligned");
+    const uintptr_t cs_al = r->cos_sin_fp32 ? 4 : 2;
+    FA_CHECK(reinterpret_cast<uintptr_t>(r->cos) % cs_al == 0 && reinterpret_cast<uintptr_t>(r->sin) % cs_al == 0,
+             "rotary: cos / sin must be aligned to their element size (%d bytes)", (int)cs_al);
+    FA_CHECK(reinterpret_cast<uintptr_t>(r->seqlen_offsets) % 4 == 0 && reinterpret_cast<uintptr_t>(r->cu_seqlens) % 4 == 0,
+             "rotary: seqlen_offsets and cu_seqlens must be 4-byte aligned int32 arrays");
+    if ((int64_t)r->nheads * r->head_dim > ((int64_t)1 << 24))
+        return fail(FA_ERR_UNSUPPORTED, "rotary: nheads x head_dim is too large for one launch");
+    const bool empty = r->batch == 0 || r->nheads == 0 || (r->cu_seqlens ? r->total_rows == 0 : r->seqlen == 0);
+    if (!empty) {
+        const bool same_strides = r->x_row_stride == r->o_row_stride && r->x_head_stride == r->o_head_stride &&
+                                  (r->cu_seqlens || r->x_batch_stride == r->o_batch_stride);
+        if (xa == oa) {
+            FA_CHECK(same_strides, "rotary: out shares x's base address but not its strides (in place needs both equal)");
+        } else {
+            const uint64_t xe = rotary_span_bytes(*r, r->x_batch_stride, r->x_row_stride, r->x_head_stride);
+            const uint64_t oe = rotary_span_bytes(*r, r->o_batch_stride, r->o_row_stride, r->o_head_stride);
+            FA_CHECK((uint64_t)oa >= (uint64_t)xa + xe || (uint64_t)xa >= (uint64_t)oa + oe,
+                     "rotary: out overlaps x without being x itself (in place: the same base address and strides)");
+        }
+    }
+    if (empty) return FA_OK;
+    fa::launch_rotary(*r, static_cast<hipStream_t>(stream));
+    return check_hip("fa_rotary launch");
 }
 
 }  // extern "C"

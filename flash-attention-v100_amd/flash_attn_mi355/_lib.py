@@ -134,13 +134,31 @@ def merge_state(st, o, lse):
     st.lse_batch_stride, st.lse_head_stride, st.lse_row_stride = lse.stride(0), lse.stride(1), lse.stride(2)
 
 
+class FaRotaryParams(ctypes.Structure):
+    """Mirror of `struct fa_rotary_params` (include/fa_mi355.h): the standalone rotary embedding fa_rotary.
+    struct_size must be set to sizeof(FaRotaryParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("x", _ptr), ("out", _ptr),
+        ("x_batch_stride", _i64), ("x_row_stride", _i64), ("x_head_stride", _i64),
+        ("o_batch_stride", _i64), ("o_row_stride", _i64), ("o_head_stride", _i64),
+        ("batch", _i32), ("seqlen", _i32), ("nheads", _i32), ("head_dim", _i32),
+        ("rotary_dim", _i32), ("dtype", _i32),
+        ("cos", _ptr), ("sin", _ptr),
+        ("cos_sin_fp32", _i32), ("seqlen_ro", _i32), ("interleaved", _i32), ("conjugate", _i32),
+        ("seqlen_offset", _i32), ("total_rows", _i32),
+        ("seqlen_offsets", _ptr),        # int32 [batch] on the device, NULL = none
+        ("cu_seqlens", _ptr),            # int32 [batch + 1] on the device, NULL = dense
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd_workspace_bytes", "fa_bwd_workspace_bytes", "fa_fwd_kvcache_workspace_bytes",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
            "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
-           "fa_merge_states", "fa_merge_params_size"] + EXT_OPS
+           "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size"] + EXT_OPS
 
 
 def _load():
@@ -176,6 +194,9 @@ def _load():
     lib.fa_merge_states.restype = ctypes.c_int
     lib.fa_merge_states.argtypes = [ctypes.POINTER(FaMergeParams), ctypes.c_void_p]
     lib.fa_merge_params_size.restype = ctypes.c_size_t
+    lib.fa_rotary.restype = ctypes.c_int
+    lib.fa_rotary.argtypes = [ctypes.POINTER(FaRotaryParams), ctypes.c_void_p]
+    lib.fa_rotary_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -192,6 +213,9 @@ def _load():
     if lib.fa_merge_params_size() != ctypes.sizeof(FaMergeParams):
         raise ImportError(f"fa_merge_params size mismatch: library {lib.fa_merge_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaMergeParams)}")
+    if lib.fa_rotary_params_size() != ctypes.sizeof(FaRotaryParams):
+        raise ImportError(f"fa_rotary_params size mismatch: library {lib.fa_rotary_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaRotaryParams)}")
     return lib
 
 
@@ -231,6 +255,13 @@ def call_merge(params, stream):
     rc = lib.fa_merge_states(ctypes.byref(params), ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"fa_merge_states failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_rotary(params, stream):
+    """fa_rotary"""
+    rc = lib.fa_rotary(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_rotary failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
 
 
 def call_rows(name, *args):

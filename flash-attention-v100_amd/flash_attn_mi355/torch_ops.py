@@ -1,6 +1,7 @@
 """torch.library registration of the five operators: `torch.ops.flash_attn_mi355.{fwd, bwd,
 varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask; `merge_states`: the
-LSE merge of attention states over disjoint key sets, fa_merge_states).
+LSE merge of attention states over disjoint key sets, fa_merge_states; `rotary` / `rotary_`: the standalone rotary embedding,
+fa_rotary).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -26,6 +27,7 @@ from torch import Tensor
 
 from . import cascade as _cascade
 from . import flash_attn_interface as _fi
+from . import rotary as _rotary
 
 _NS = "flash_attn_mi355"
 
@@ -359,5 +361,59 @@ def _(outs, lses):
     return outs[0].new_empty((B, S, H, D)), outs[0].new_empty((B, H, S), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------
+# standalone rotary embedding (flash_attn.layers.rotary; csrc/fa_rotary.hip)
+# ------------------------------------------------------------------------------------------
+def _rotary_offsets(seqlen_offsets, seqlen_offset):
+    return seqlen_offset if seqlen_offsets is None else seqlen_offsets
+
+
+@torch.library.custom_op(f"{_NS}::rotary", mutates_args=(), device_types="cuda")
+def rotary(x: Tensor, cos: Tensor, sin: Tensor, seqlen_offsets: Optional[Tensor], cu_seqlens: Optional[Tensor],
+           seqlen_offset: int, max_seqlen: int, interleaved: bool, conjugate: bool) -> Tensor:
+    """rotary.apply_rotary out of place: x [B, S, H, D] (or [T, H, D] with cu_seqlens and max_seqlen) fp16 / bf16, cos / sin
+    [seqlen_ro, rotary_dim / 2]; positions i + seqlen_offset, or i + seqlen_offsets[b] with the int32 [B] tensor.  Returns a
+    fresh contiguous tensor.  Differentiable in x: the backward is the same op with `not conjugate`."""
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    return _rotary._launch(x, out, cos, sin, interleaved, conjugate, _rotary_offsets(seqlen_offsets, seqlen_offset),
+                           cu_seqlens, max_seqlen if cu_seqlens is not None else None)
+
+
+@rotary.register_fake
+def _(x, cos, sin, seqlen_offsets, cu_seqlens, seqlen_offset, max_seqlen, interleaved, conjugate):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op(f"{_NS}::rotary_", mutates_args=("x",), device_types="cuda")
+def rotary_(x: Tensor, cos: Tensor, sin: Tensor, seqlen_offsets: Optional[Tensor], cu_seqlens: Optional[Tensor],
+            seqlen_offset: int, max_seqlen: int, interleaved: bool, conjugate: bool) -> None:
+    """`rotary` in place on x (a view with a contiguous last dimension is rotated where it lies)"""
+    _rotary._launch(x, x, cos, sin, interleaved, conjugate, _rotary_offsets(seqlen_offsets, seqlen_offset),
+                    cu_seqlens, max_seqlen if cu_seqlens is not None else None)
+
+
+@rotary_.register_fake
+def _(x, cos, sin, seqlen_offsets, cu_seqlens, seqlen_offset, max_seqlen, interleaved, conjugate):
+    return None
+
+
+def _rotary_setup(ctx, inputs, output):
+    (_, cos, sin, seqlen_offsets, cu_seqlens, seqlen_offset, max_seqlen, interleaved, conjugate) = inputs
+    ctx.save_for_backward(cos, sin, seqlen_offsets, cu_seqlens)
+    ctx.args = (seqlen_offset, max_seqlen, interleaved, conjugate)
+
+
+def _rotary_backward(ctx, dout):
+    cos, sin, seqlen_offsets, cu_seqlens = ctx.saved_tensors
+    seqlen_offset, max_seqlen, interleaved, conjugate = ctx.args
+    if dout.stride(-1) != 1:
+        dout = dout.contiguous()
+    dx = rotary(dout, cos, sin, seqlen_offsets, cu_seqlens, seqlen_offset, max_seqlen, interleaved, not conjugate)
+    return (dx,) + (None,) * 8
+
+
+rotary.register_autograd(_rotary_backward, setup_context=_rotary_setup)
+
+
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",
-           "merge_states"]
+           "merge_states", "rotary", "rotary_"]

@@ -351,6 +351,55 @@ int    fa_merge_states(const fa_merge_params* m, void* stream);
 size_t fa_merge_params_size(void);
 
 /*
+ * fa_rotary - standalone rotary position embedding (additive, like the blocks above: fa_params and FA_ABI_VERSION are unchanged).
+ *
+ * out = rope(x, pos) for every (batch, row, head) of x, with the pair rule and the arithmetic of fa_fwd_kvcache's in-kernel RoPE
+ * (fp32 math, c = cos[pos, t], s = sin[pos, t], the result rounded once to the 16-bit io type):
+ *   interleaved:  (x[2t], x[2t+1])         -> (x0 c - x1 s, x0 s + x1 c)      t < rotary_dim / 2
+ *   otherwise:    (x[t], x[t+rotary_dim/2]) -> likewise                         (GPT-NeoX)
+ * conjugate != 0 negates s first (exactly): the inverse rotation, which is also the backward of the op.
+ * Element (b, i, h, d) of x = x[b*x_batch_stride + i*x_row_stride + h*x_head_stride + d] (strides in elements, the last dimension
+ * contiguous); with cu_seqlens the tensor is packed, [total_rows, nheads, head_dim]: row r = x[r*x_row_stride + ...], it belongs to
+ * the sequence b with cu_seqlens[b] <= r < cu_seqlens[b+1] and i is its index inside that sequence (batch strides are unused,
+ * seqlen = max_seqlen is informative; rows behind cu_seqlens[batch] belong to no sequence and are left unrotated).
+ * Position of row i of batch b: i + seqlen_offset + (seqlen_offsets ? seqlen_offsets[b] : 0).  A position < 0 or >= seqlen_ro
+ * leaves the row unrotated - copied when out != x, untouched in place - and nothing outside cos / sin is read (fa_fwd_kvcache's
+ * rule).  Columns [rotary_dim, head_dim) are copied when out != x and neither read nor written when out == x.
+ * out == x (the same base address AND strides) is in place and is the common case.
+ * One kernel launch on `stream`: byte movement, no atomics, no workspace, no host synchronisation, bitwise repeatable.  16-byte
+ * streamed loads and stores where every x / out base address and stride is a multiple of 16 bytes, rotary_dim % 16 == 0
+ * (interleaved: % 8 == 0), cos / sin are of `dtype` and 16-byte aligned, and - for out != x - (head_dim - rotary_dim) % 8 == 0;
+ * one pair per lane otherwise (any even rotary_dim, 2-byte aligned views, fp32 cos / sin).  Both forms give the same bits.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL x / out / cos / sin; a dtype other than FA_FP16 /
+ * FA_BF16; rotary_dim odd, <= 0 or > head_dim; negative sizes, strides or seqlen_offset; x / out not 2-byte aligned; cos / sin
+ * not aligned to their element size; seqlen_offsets / cu_seqlens not 4-byte aligned; an out whose address range overlaps x's
+ * without out being x itself (base address and strides).  An empty problem returns FA_OK without a launch.
+ */
+typedef struct fa_rotary_params {
+    size_t         struct_size;      /* sizeof(fa_rotary_params) as the caller compiled it */
+    const void*    x;                /* [batch, seqlen, nheads, head_dim] (cu_seqlens: [total_rows, nheads, head_dim]) of `dtype` */
+    void*          out;              /* same shape, own strides; may equal x */
+    int64_t        x_batch_stride, x_row_stride, x_head_stride;   /* elements, the last dimension contiguous */
+    int64_t        o_batch_stride, o_row_stride, o_head_stride;
+    int32_t        batch, seqlen, nheads, head_dim;   /* cu_seqlens: seqlen = max_seqlen */
+    int32_t        rotary_dim;       /* even, 0 < rotary_dim <= head_dim */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    const void*    cos;              /* [seqlen_ro, rotary_dim / 2] contiguous */
+    const void*    sin;
+    int32_t        cos_sin_fp32;     /* 0: cos / sin of `dtype`; 1: fp32 */
+    int32_t        seqlen_ro;
+    int32_t        interleaved;
+    int32_t        conjugate;
+    int32_t        seqlen_offset;    /* host scalar, >= 0 */
+    int32_t        total_rows;       /* cu_seqlens: rows of the packed tensor */
+    const int32_t* seqlen_offsets;   /* device [batch], or NULL */
+    const int32_t* cu_seqlens;       /* device [batch + 1], or NULL (dense) */
+} fa_rotary_params;
+
+int    fa_rotary(const fa_rotary_params* r, void* stream);
+size_t fa_rotary_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
