@@ -11,6 +11,7 @@
 //   NeoX:        (x[t], x[t+rd/2]) -> (x0 c - x1 s, x0 s + x1 c)
 #include "fa_common.h"
 #include "fa_rope.h"
+#include "fa_fp8_cvt.h"
 
 namespace fa {
 
@@ -19,23 +20,6 @@ bool decode_applicable(const fa_params& p);
 bool decode_takes(const fa_params& p);
 size_t decode_split_workspace_bytes(const fa_params& p);
 int launch_decode_splitkv(const KArgs& a, void* ws, hipStream_t stream, const fa_tree_params* tree);
-
-// 8 x 16-bit -> 8 x fp8-e4m3 (OCP), value / descale, saturating at +-448
-template <typename T>
-__device__ __forceinline__ u32x2 to_fp8x8(const u32x4& x, float inv_descale) {
-    using E = Elem<T>;
-    u32x2 r = {0, 0};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float a0 = fminf(fmaxf(E::lo(x[i]) * inv_descale, -448.f), 448.f);
-        const float a1 = fminf(fmaxf(E::hi(x[i]) * inv_descale, -448.f), 448.f);
-        if (i == 0) r[0] = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, r[0], false);
-        if (i == 1) r[0] = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, r[0], true);
-        if (i == 2) r[1] = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, r[1], false);
-        if (i == 3) r[1] = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, r[1], true);
-    }
-    return r;
-}
 
 // One thread per 16-byte chunk of one new (b, r, hk) row; K and V.
 // depths (tree decode, fa_tree_params): new token r is rotated at position L + leftpad + depths[b, r]; its cache slot stays L + r
@@ -88,8 +72,8 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const KArgs a, const int
     koff += (int64_t)hk * p.k_head_stride + d_base;
     voff += (int64_t)hk * p.v_head_stride + d_base;
     if (KV8) {
-        *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(const_cast<void*>(p.k)) + koff) = to_fp8x8<T>(kx, 1.0f / p.k_descale);
-        *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(const_cast<void*>(p.v)) + voff) = to_fp8x8<T>(vx, 1.0f / p.v_descale);
+        *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(const_cast<void*>(p.k)) + koff) = to_fp8x8<T>(kx, fp8_inv_descale(p.k_descale));
+        *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(const_cast<void*>(p.v)) + voff) = to_fp8x8<T>(vx, fp8_inv_descale(p.v_descale));
     } else {
         *reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(const_cast<void*>(p.k)) + koff) = kx;
         *reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(const_cast<void*>(p.v)) + voff) = vx;

@@ -152,13 +152,39 @@ class FaRotaryParams(ctypes.Structure):
     ]
 
 
+class FaKvStoreParams(ctypes.Structure):
+    """Mirror of `struct fa_kv_store_params` (include/fa_mi355.h): fa_kv_store, a ragged packed batch of K / V rows into a KV
+    cache.  struct_size must be set to sizeof(FaKvStoreParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("k", _ptr), ("v", _ptr),
+        ("k_row_stride", _i64), ("k_head_stride", _i64), ("v_row_stride", _i64), ("v_head_stride", _i64),
+        ("k_cache", _ptr), ("v_cache", _ptr),
+        ("kc_batch_stride", _i64), ("kc_row_stride", _i64), ("kc_head_stride", _i64),
+        ("vc_batch_stride", _i64), ("vc_row_stride", _i64), ("vc_head_stride", _i64),
+        ("total_rows", _i32), ("nheads", _i32), ("head_dim", _i32), ("dtype", _i32), ("cache_dtype", _i32),
+        ("paged", _i32), ("num_blocks", _i32), ("page_block_size", _i32),
+        ("slot_mapping", _ptr),          # int64 [total_rows] on the device: slot mode
+        ("cu_seqlens", _ptr),            # int32 [batch + 1] on the device: sequence mode
+        ("cache_seqlens", _ptr),         # int32 [batch], NULL = zeros
+        ("block_table", _ptr), ("block_table_batch_stride", _i64),
+        ("cache_batch_idx", _ptr),
+        ("batch", _i32), ("max_blocks", _i32),
+        ("k_descale", _f32), ("v_descale", _f32),
+        ("rotary_dim", _i32), ("rotary_interleaved", _i32),
+        ("rotary_cos", _ptr), ("rotary_sin", _ptr),
+        ("seqlen_ro", _i32), ("reserved", _i32),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd_workspace_bytes", "fa_bwd_workspace_bytes", "fa_fwd_kvcache_workspace_bytes",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
            "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
-           "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size"] + EXT_OPS
+           "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size",
+           "fa_kv_store", "fa_kv_store_params_size"] + EXT_OPS
 
 
 def _load():
@@ -197,6 +223,9 @@ def _load():
     lib.fa_rotary.restype = ctypes.c_int
     lib.fa_rotary.argtypes = [ctypes.POINTER(FaRotaryParams), ctypes.c_void_p]
     lib.fa_rotary_params_size.restype = ctypes.c_size_t
+    lib.fa_kv_store.restype = ctypes.c_int
+    lib.fa_kv_store.argtypes = [ctypes.POINTER(FaKvStoreParams), ctypes.c_void_p]
+    lib.fa_kv_store_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -216,6 +245,9 @@ def _load():
     if lib.fa_rotary_params_size() != ctypes.sizeof(FaRotaryParams):
         raise ImportError(f"fa_rotary_params size mismatch: library {lib.fa_rotary_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaRotaryParams)}")
+    if lib.fa_kv_store_params_size() != ctypes.sizeof(FaKvStoreParams):
+        raise ImportError(f"fa_kv_store_params size mismatch: library {lib.fa_kv_store_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaKvStoreParams)}")
     return lib
 
 
@@ -262,6 +294,13 @@ def call_rotary(params, stream):
     rc = lib.fa_rotary(ctypes.byref(params), ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"fa_rotary failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_kv_store(params, stream):
+    """fa_kv_store"""
+    rc = lib.fa_kv_store(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_kv_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
 
 
 def call_rows(name, *args):

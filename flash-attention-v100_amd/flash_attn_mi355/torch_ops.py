@@ -1,7 +1,7 @@
 """torch.library registration of the five operators: `torch.ops.flash_attn_mi355.{fwd, bwd,
 varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask; `merge_states`: the
 LSE merge of attention states over disjoint key sets, fa_merge_states; `rotary` / `rotary_`: the standalone rotary embedding,
-fa_rotary).
+fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_kv_store).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -27,6 +27,7 @@ from torch import Tensor
 
 from . import cascade as _cascade
 from . import flash_attn_interface as _fi
+from . import kv_store as _kv_store
 from . import rotary as _rotary
 
 _NS = "flash_attn_mi355"
@@ -415,5 +416,29 @@ def _rotary_backward(ctx, dout):
 rotary.register_autograd(_rotary_backward, setup_context=_rotary_setup)
 
 
+# ------------------------------------------------------------------------------------------
+# KV-cache store (flash_attn_mi355.kv_store; csrc/fa_kv_store.hip)
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::kv_store", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def kv_store(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, slot_mapping: Optional[Tensor],
+             cu_seqlens: Optional[Tensor], cache_seqlens: Optional[Tensor], block_table: Optional[Tensor],
+             cache_batch_idx: Optional[Tensor], rotary_cos: Optional[Tensor], rotary_sin: Optional[Tensor],
+             rotary_interleaved: bool, k_descale: float, v_descale: float) -> None:
+    """kv_store.store_kv_cache: k / v [T, Hk, D] into k_cache / v_cache (in place) by slot_mapping, or by cu_seqlens with
+    cache_seqlens and block_table / cache_batch_idx (optionally rotating K).  k_descale / v_descale are read for float8_e4m3fn
+    caches only (pass 1.0 otherwise)."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    _kv_store.store_kv_cache(k, v, k_cache, v_cache, slot_mapping=slot_mapping, cu_seqlens=cu_seqlens, cache_seqlens=cache_seqlens,
+                             block_table=block_table, cache_batch_idx=cache_batch_idx, rotary_cos=rotary_cos,
+                             rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved,
+                             k_descale=k_descale if fp8 else None, v_descale=v_descale if fp8 else None)
+
+
+@kv_store.register_fake
+def _(k, v, k_cache, v_cache, slot_mapping, cu_seqlens, cache_seqlens, block_table, cache_batch_idx, rotary_cos, rotary_sin,
+      rotary_interleaved, k_descale, v_descale):
+    return None
+
+
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",
-           "merge_states", "rotary", "rotary_"]
+           "merge_states", "rotary", "rotary_", "kv_store"]

@@ -400,6 +400,87 @@ int    fa_rotary(const fa_rotary_params* r, void* stream);
 size_t fa_rotary_params_size(void);
 
 /*
+ * fa_kv_store - write a ragged packed batch of K / V rows into a KV cache (additive, like the blocks above: fa_params and
+ * FA_ABI_VERSION are unchanged).  The step between a ragged prefill (fa_varlen_fwd) and everything that reads a cache
+ * (fa_fwd_kvcache, fa_varlen_fwd with a block_table); fa_fwd_kvcache's own append takes a uniform [B, T_new] block only.
+ *
+ * k, v: [total_rows, nheads, head_dim] of `dtype` (FA_FP16 / FA_BF16); element (r, h, d) of k = k[r*k_row_stride + h*k_head_stride
+ * + d] (strides in elements, the last dimension contiguous) - the K and V heads of a packed [T, Hq + 2 Hk, D] qkv are such views.
+ * k_cache, v_cache: [num_blocks, page_block_size, nheads, head_dim] of `cache_dtype` (= dtype, or FA_FP8_E4M3) with explicit
+ * batch (page), row and head strides in elements of the cache type, K and V each their own.  A contiguous cache
+ * [Bc, S_max, nheads, head_dim] is num_blocks = Bc, page_block_size = S_max, paged = 0.
+ * Exactly one of two addressing modes:
+ *   slot mode (slot_mapping != NULL): row r goes to block slot_mapping[r] / page_block_size, row slot_mapping[r] % page_block_size.
+ *     A slot < 0 or >= num_blocks * page_block_size skips the row (padding rows of a captured graph).  cu_seqlens, cache_seqlens,
+ *     block_table, cache_batch_idx and the rotary fields must be unset.
+ *   sequence mode (cu_seqlens != NULL): row r belongs to the sequence b with cu_seqlens[b] <= r < cu_seqlens[b+1], has the index
+ *     i = r - cu_seqlens[b] and goes to position cache_seqlens[b] + i (cache_seqlens NULL: i) - fa_fwd_kvcache's append rule for
+ *     a ragged batch.  paged != 0: page block_table[b*block_table_batch_stride + pos / page_block_size], row pos % page_block_size,
+ *     capacity max_blocks * page_block_size; paged == 0: batch slot cache_batch_idx[b] (NULL: b, which needs batch <= num_blocks),
+ *     row pos, capacity page_block_size.  A position < 0 or >= the capacity is dropped without a write, as in the append; rows
+ *     behind cu_seqlens[batch] belong to no sequence and are dropped; empty sequences are legal; a block-table entry is read only
+ *     for a row that is stored (entries are not range-checked, as in fa_fwd_kvcache).
+ * Two rows with the same destination: one of them wins (unspecified, as in fa_scatter_rows).
+ * fp8 cache: stored code = e4m3(clamp(x * (1 / descale), -448, 448)), round to nearest even - the expression, the reciprocal and
+ * the conversion are fa_fwd_kvcache's append's own (one shared header), so both write the same codes.  k_descale / v_descale: host
+ * floats, 0 = 1.0; ignored for a 16-bit cache.
+ * RoPE on K (sequence mode only, rotary_dim > 0): row i of sequence b is rotated at its cache position cache_seqlens[b] + i with
+ * fa_fwd_kvcache's in-kernel rule and arithmetic (fp32 math, one rounding to `dtype`, then - fp8 cache - the quantisation above);
+ * rotary_cos / rotary_sin: [seqlen_ro, rotary_dim / 2] of `dtype`, contiguous.  A position outside [0, seqlen_ro) stores the row
+ * unrotated and reads nothing outside the tables.  V is never rotated.
+ * One kernel launch on `stream` stores K and V: byte movement, no LDS, no atomics, no workspace, no host synchronisation, bitwise
+ * repeatable.  16-byte loads; 16-byte stores (fp8 caches: 16-byte stores where head_dim % 16 == 0 and every cache base and stride
+ * is a multiple of 16 bytes, 8-byte stores otherwise).
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL k, v, k_cache or v_cache; both addressing modes or
+ * neither; block_table together with cache_batch_idx; block_table without paged, or sequence mode with paged and no block_table;
+ * sequence-mode or rotary fields in slot mode; a dtype other than FA_FP16 / FA_BF16; a cache_dtype other than dtype or
+ * FA_FP8_E4M3; head_dim not a multiple of 8 or above 256; negative sizes or strides; page_block_size <= 0; a contiguous cache
+ * without cache_batch_idx and batch > num_blocks; k / v bases or strides that are not multiples of 16 bytes; cache bases or
+ * strides that are not multiples of 16 bytes (fp8: 8 bytes); a slot_mapping that is not 8-byte aligned; int32 side arrays that
+ * are not 4-byte aligned; a negative or non-finite descale; rotary_cos / rotary_sin not both given, rotary_dim > head_dim or
+ * not a multiple of 16, tables not 16-byte aligned.  total_rows == 0, nheads == 0 or (sequence mode) batch == 0: FA_OK without
+ * a launch.
+ */
+typedef struct fa_kv_store_params {
+    size_t         struct_size;      /* sizeof(fa_kv_store_params) as the caller compiled it */
+    const void*    k;                /* [total_rows, nheads, head_dim] of `dtype`, read only */
+    const void*    v;
+    int64_t        k_row_stride, k_head_stride;        /* elements, the last dimension contiguous */
+    int64_t        v_row_stride, v_head_stride;
+    void*          k_cache;          /* [num_blocks, page_block_size, nheads, head_dim] of `cache_dtype`, written */
+    void*          v_cache;
+    int64_t        kc_batch_stride, kc_row_stride, kc_head_stride;   /* elements of the cache type */
+    int64_t        vc_batch_stride, vc_row_stride, vc_head_stride;
+    int32_t        total_rows;       /* rows of k / v */
+    int32_t        nheads;           /* KV heads */
+    int32_t        head_dim;         /* a multiple of 8, <= 256 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        cache_dtype;      /* dtype, or FA_FP8_E4M3 */
+    int32_t        paged;            /* != 0: pages addressed through block_table (sequence mode); slot mode ignores it */
+    int32_t        num_blocks;       /* pages, or batch slots of a contiguous cache */
+    int32_t        page_block_size;  /* rows per page, or S_max of a contiguous cache; > 0 */
+    const int64_t* slot_mapping;     /* slot mode: device [total_rows], 8-byte aligned */
+    const int32_t* cu_seqlens;       /* sequence mode: device [batch + 1] */
+    const int32_t* cache_seqlens;    /* device [batch], NULL = zeros */
+    const int32_t* block_table;      /* device [batch, max_blocks], paged caches */
+    int64_t        block_table_batch_stride;           /* elements */
+    const int32_t* cache_batch_idx;  /* device [batch], contiguous caches; NULL = identity */
+    int32_t        batch;            /* sequence mode: sequences */
+    int32_t        max_blocks;       /* columns of block_table */
+    float          k_descale;        /* fp8 cache: value = code * descale; 0 = 1.0 */
+    float          v_descale;
+    int32_t        rotary_dim;       /* 0 = no rotary; else a multiple of 16, <= head_dim */
+    int32_t        rotary_interleaved;
+    const void*    rotary_cos;       /* [seqlen_ro, rotary_dim / 2] of `dtype`, contiguous, 16-byte aligned */
+    const void*    rotary_sin;
+    int32_t        seqlen_ro;
+    int32_t        reserved;         /* 0 */
+} fa_kv_store_params;
+
+int    fa_kv_store(const fa_kv_store_params* s, void* stream);
+size_t fa_kv_store_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
