@@ -33,6 +33,7 @@ int merge_vec_width(const fa_merge_params& m);           // fa_merge.hip: 8 / 4 
 void launch_merge_states(const fa_merge_params& m, hipStream_t stream);
 void launch_rotary(const fa_rotary_params& r, hipStream_t stream);          // fa_rotary.hip: standalone rotary embedding
 void launch_kv_store(const fa_kv_store_params& s, hipStream_t stream);      // fa_kv_store.hip: ragged K / V rows into a KV cache
+void launch_kv_gather(const fa_kv_gather_params& s, hipStream_t stream);    // fa_kv_gather.hip: ragged K / V rows out of a KV cache
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -199,6 +200,7 @@ size_t fa_tree_params_size(void) { return sizeof(fa_tree_params); }
 size_t fa_merge_params_size(void) { return sizeof(fa_merge_params); }
 size_t fa_rotary_params_size(void) { return sizeof(fa_rotary_params); }
 size_t fa_kv_store_params_size(void) { return sizeof(fa_kv_store_params); }
+size_t fa_kv_gather_params_size(void) { return sizeof(fa_kv_gather_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -742,6 +744,81 @@ int fa_kv_store(const fa_kv_store_params* sp, void* stream) {
     if (s.total_rows == 0 || s.nheads == 0 || s.head_dim == 0 || (seq_mode && s.batch == 0)) return FA_OK;
     fa::launch_kv_store(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_kv_store launch");
+}
+
+// bytes from the first to one past the last element of a [rows, nheads, head_dim] tensor (sizes > 0, strides >= 0, in elements)
+static uint64_t kv_span_bytes(int64_t blocks, int64_t bs, int64_t rows, int64_t rs, int64_t heads, int64_t hs, int64_t d, int esize) {
+    return (uint64_t)((blocks - 1) * bs + (rows - 1) * rs + (heads - 1) * hs + d) * (uint64_t)esize;
+}
+
+int fa_kv_gather(const fa_kv_gather_params* sp, void* stream) {
+    FA_CHECK(sp, "fa_kv_gather_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_kv_gather_params), "fa_kv_gather_params::struct_size %zu is smaller than this library's %zu",
+             sp->struct_size, sizeof(fa_kv_gather_params));
+    fa_kv_gather_params s = *sp;
+    FA_CHECK(s.k && s.v && s.k_cache && s.v_cache, "kv_gather: k, v, k_cache and v_cache must not be NULL");
+    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "kv_gather: k / v dtype must be fp16 or bf16");
+    FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "kv_gather: the cache dtype must be the k / v dtype or fp8-e4m3");
+    const bool slot_mode = s.slot_mapping != nullptr, seq_mode = s.cu_seqlens != nullptr;
+    FA_CHECK(slot_mode != seq_mode, "kv_gather: exactly one addressing mode - slot_mapping, or cu_seqlens (%s given)",
+             slot_mode ? "both" : "neither");
+    FA_CHECK(!(s.block_table && s.cache_batch_idx), "kv_gather: block_table and cache_batch_idx exclude each other (paged caches have no cache_batch_idx)");
+    FA_CHECK(s.total_rows >= 0 && s.nheads >= 0 && s.head_dim >= 0 && s.num_blocks >= 0 && s.batch >= 0 && s.max_blocks >= 0,
+             "kv_gather sizes must be non-negative");
+    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "kv_gather head_dim must be a multiple of 8 and <= 256, got %d", s.head_dim);
+    FA_CHECK(s.page_block_size > 0, "kv_gather: page_block_size must be positive (a contiguous cache: S_max)");
+    FA_CHECK(s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.v_row_stride >= 0 && s.v_head_stride >= 0 && s.kc_batch_stride >= 0 &&
+             s.kc_row_stride >= 0 && s.kc_head_stride >= 0 && s.vc_batch_stride >= 0 && s.vc_row_stride >= 0 &&
+             s.vc_head_stride >= 0 && s.block_table_batch_stride >= 0, "kv_gather strides must be non-negative");
+    if (slot_mode) {
+        FA_CHECK(!s.seq_offsets && !s.block_table && !s.cache_batch_idx,
+                 "kv_gather: slot mode takes no seq_offsets, block_table or cache_batch_idx (the slot is the whole address)");
+        FA_CHECK(reinterpret_cast<uintptr_t>(s.slot_mapping) % 8 == 0, "kv_gather: slot_mapping must be an 8-byte aligned int64 array");
+    } else {
+        if (s.paged) FA_CHECK(s.block_table, "kv_gather: sequence mode on a paged cache needs a block_table");
+        else         FA_CHECK(!s.block_table, "kv_gather: a block_table needs paged != 0");
+        FA_CHECK(s.paged || s.cache_batch_idx || s.batch <= s.num_blocks,
+                 "kv_gather: the cache has %d batch slots for %d sequences (pass cache_batch_idx)", s.num_blocks, s.batch);
+        FA_CHECK(reinterpret_cast<uintptr_t>(s.cu_seqlens) % 4 == 0 && reinterpret_cast<uintptr_t>(s.seq_offsets) % 4 == 0 &&
+                 reinterpret_cast<uintptr_t>(s.block_table) % 4 == 0 && reinterpret_cast<uintptr_t>(s.cache_batch_idx) % 4 == 0,
+                 "kv_gather: cu_seqlens, seq_offsets, block_table and cache_batch_idx must be 4-byte aligned int32 arrays");
+    }
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.v)) & 15) == 0 &&
+             ((s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride) & 7) == 0,
+             "kv_gather: k / v base addresses and strides must be multiples of 16 bytes");
+    const bool kv8 = s.cache_dtype == FA_FP8_E4M3;
+    {
+        const uintptr_t cal = kv8 ? 7 : 15;               // bytes; strides are in elements of 1 / 2 bytes
+        const int64_t sal = 7;
+        FA_CHECK(((reinterpret_cast<uintptr_t>(s.k_cache) | reinterpret_cast<uintptr_t>(s.v_cache)) & cal) == 0 &&
+                 ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
+                 "kv_gather: cache base addresses and strides must be multiples of %d bytes", kv8 ? 8 : 16);
+    }
+    {
+        float* ds[2] = {&s.k_descale, &s.v_descale};      // (checked for every cache type, used by fp8 caches)
+        for (float* d : ds) {
+            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "kv_gather: k / v descales must be finite and >= 0 (0 = 1.0)");
+            if (*d == 0.f) *d = 1.0f;
+        }
+    }
+    if ((int64_t)s.nheads * s.head_dim > ((int64_t)1 << 24))
+        return fail(FA_ERR_UNSUPPORTED, "kv_gather: nheads x head_dim is too large for one launch");
+    if (s.total_rows == 0 || s.nheads == 0 || s.head_dim == 0) return FA_OK;
+    if (s.num_blocks > 0) {
+        // the output must not lie inside what is read: the rows are written while other workgroups still read the cache
+        const uint64_t ce[2] = {kv_span_bytes(s.num_blocks, s.kc_batch_stride, s.page_block_size, s.kc_row_stride, s.nheads, s.kc_head_stride, s.head_dim, kv8 ? 1 : 2),
+                                kv_span_bytes(s.num_blocks, s.vc_batch_stride, s.page_block_size, s.vc_row_stride, s.nheads, s.vc_head_stride, s.head_dim, kv8 ? 1 : 2)};
+        const uint64_t oe[2] = {kv_span_bytes(1, 0, s.total_rows, s.k_row_stride, s.nheads, s.k_head_stride, s.head_dim, 2),
+                                kv_span_bytes(1, 0, s.total_rows, s.v_row_stride, s.nheads, s.v_head_stride, s.head_dim, 2)};
+        const uint64_t ca[2] = {(uint64_t)reinterpret_cast<uintptr_t>(s.k_cache), (uint64_t)reinterpret_cast<uintptr_t>(s.v_cache)};
+        const uint64_t oa[2] = {(uint64_t)reinterpret_cast<uintptr_t>(s.k), (uint64_t)reinterpret_cast<uintptr_t>(s.v)};
+        for (int o = 0; o < 2; ++o)
+            for (int c = 0; c < 2; ++c)
+                FA_CHECK(oa[o] >= ca[c] + ce[c] || ca[c] >= oa[o] + oe[o], "kv_gather: %s overlaps %s (gather into a separate buffer)",
+                         o ? "v" : "k", c ? "v_cache" : "k_cache");
+    }
+    fa::launch_kv_gather(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_kv_gather launch");
 }
 
 }  // extern "C"

@@ -177,6 +177,28 @@ class FaKvStoreParams(ctypes.Structure):
     ]
 
 
+class FaKvGatherParams(ctypes.Structure):
+    """Mirror of `struct fa_kv_gather_params` (include/fa_mi355.h): fa_kv_gather, ragged K / V rows out of a KV cache into a packed
+    pair.  struct_size must be set to sizeof(FaKvGatherParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("k_cache", _ptr), ("v_cache", _ptr),
+        ("kc_batch_stride", _i64), ("kc_row_stride", _i64), ("kc_head_stride", _i64),
+        ("vc_batch_stride", _i64), ("vc_row_stride", _i64), ("vc_head_stride", _i64),
+        ("k", _ptr), ("v", _ptr),
+        ("k_row_stride", _i64), ("k_head_stride", _i64), ("v_row_stride", _i64), ("v_head_stride", _i64),
+        ("total_rows", _i32), ("nheads", _i32), ("head_dim", _i32), ("dtype", _i32), ("cache_dtype", _i32),
+        ("paged", _i32), ("num_blocks", _i32), ("page_block_size", _i32),
+        ("slot_mapping", _ptr),          # int64 [total_rows] on the device: slot mode
+        ("cu_seqlens", _ptr),            # int32 [batch + 1] on the device: sequence mode
+        ("seq_offsets", _ptr),           # int32 [batch]: first position read, NULL = zeros
+        ("block_table", _ptr), ("block_table_batch_stride", _i64),
+        ("cache_batch_idx", _ptr),
+        ("batch", _i32), ("max_blocks", _i32),
+        ("k_descale", _f32), ("v_descale", _f32),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -184,7 +206,7 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
            "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
            "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size",
-           "fa_kv_store", "fa_kv_store_params_size"] + EXT_OPS
+           "fa_kv_store", "fa_kv_store_params_size", "fa_kv_gather", "fa_kv_gather_params_size"] + EXT_OPS
 
 
 def _load():
@@ -226,6 +248,9 @@ def _load():
     lib.fa_kv_store.restype = ctypes.c_int
     lib.fa_kv_store.argtypes = [ctypes.POINTER(FaKvStoreParams), ctypes.c_void_p]
     lib.fa_kv_store_params_size.restype = ctypes.c_size_t
+    lib.fa_kv_gather.restype = ctypes.c_int
+    lib.fa_kv_gather.argtypes = [ctypes.POINTER(FaKvGatherParams), ctypes.c_void_p]
+    lib.fa_kv_gather_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -248,6 +273,9 @@ def _load():
     if lib.fa_kv_store_params_size() != ctypes.sizeof(FaKvStoreParams):
         raise ImportError(f"fa_kv_store_params size mismatch: library {lib.fa_kv_store_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaKvStoreParams)}")
+    if lib.fa_kv_gather_params_size() != ctypes.sizeof(FaKvGatherParams):
+        raise ImportError(f"fa_kv_gather_params size mismatch: library {lib.fa_kv_gather_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaKvGatherParams)}")
     return lib
 
 
@@ -301,6 +329,13 @@ def call_kv_store(params, stream):
     rc = lib.fa_kv_store(ctypes.byref(params), ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"fa_kv_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_kv_gather(params, stream):
+    """fa_kv_gather"""
+    rc = lib.fa_kv_gather(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_kv_gather failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
 
 
 def call_rows(name, *args):

@@ -7,8 +7,9 @@ One launch stores K and V; paged or contiguous caches of the input dtype or floa
 the ones `flash_attn_with_kvcache(..., k=, v=)` would store: both kernels share the rounding rule and the rotation.
 
 Not covered: `cache_leftpad`, per-token position ids for the rotation, a V-only or K-only store, per-head or device-resident
-descales, fusing the store into the varlen forward, and a cache -> packed gather.  Nothing here is exported through the packages'
-`__all__` lists."""
+descales, and fusing the store into the varlen forward.  The way back, cache -> packed, is `kv_gather.gather_kv_cache`
+(`kv_gather.move_kv_cache` composes the two to move rows inside a cache).  Nothing here is exported through the packages' `__all__`
+lists."""
 import ctypes
 from typing import Optional
 

@@ -1,7 +1,8 @@
 """torch.library registration of the five operators: `torch.ops.flash_attn_mi355.{fwd, bwd,
 varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask; `merge_states`: the
 LSE merge of attention states over disjoint key sets, fa_merge_states; `rotary` / `rotary_`: the standalone rotary embedding,
-fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_kv_store).
+fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_kv_store; `kv_gather` / `kv_move`: ragged K / V
+rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -27,6 +28,7 @@ from torch import Tensor
 
 from . import cascade as _cascade
 from . import flash_attn_interface as _fi
+from . import kv_gather as _kv_gather
 from . import kv_store as _kv_store
 from . import rotary as _rotary
 
@@ -437,6 +439,41 @@ def kv_store(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, slot_mappin
 @kv_store.register_fake
 def _(k, v, k_cache, v_cache, slot_mapping, cu_seqlens, cache_seqlens, block_table, cache_batch_idx, rotary_cos, rotary_sin,
       rotary_interleaved, k_descale, v_descale):
+    return None
+
+
+# ------------------------------------------------------------------------------------------
+# KV-cache gather and move (flash_attn_mi355.kv_gather; csrc/fa_kv_gather.hip).  Reached as torch.ops.flash_attn_mi355.kv_gather /
+# .kv_move; not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::kv_gather", mutates_args=(), device_types="cuda")
+def kv_gather(k_cache: Tensor, v_cache: Tensor, slot_mapping: Optional[Tensor], cu_seqlens: Optional[Tensor],
+              seq_offsets: Optional[Tensor], block_table: Optional[Tensor], cache_batch_idx: Optional[Tensor],
+              total_rows: int, dtype: torch.dtype, k_descale: float, v_descale: float) -> Tuple[Tensor, Tensor]:
+    """kv_gather.gather_kv_cache: (k, v) [total_rows, Hk, D] of `dtype`, fresh contiguous tensors, read out of k_cache / v_cache by
+    slot_mapping, or by cu_seqlens with seq_offsets and block_table / cache_batch_idx.  `dtype` is the cache's for a 16-bit cache;
+    k_descale / v_descale are read for float8_e4m3fn caches only (pass 1.0 otherwise)."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    return _kv_gather.gather_kv_cache(k_cache, v_cache, slot_mapping=slot_mapping, cu_seqlens=cu_seqlens, seq_offsets=seq_offsets,
+                                      block_table=block_table, cache_batch_idx=cache_batch_idx, total_rows=total_rows, dtype=dtype,
+                                      k_descale=k_descale if fp8 else None, v_descale=v_descale if fp8 else None)
+
+
+@kv_gather.register_fake
+def _(k_cache, v_cache, slot_mapping, cu_seqlens, seq_offsets, block_table, cache_batch_idx, total_rows, dtype, k_descale,
+      v_descale):
+    shape = (total_rows, k_cache.shape[2], k_cache.shape[3])
+    return k_cache.new_empty(shape, dtype=dtype), k_cache.new_empty(shape, dtype=dtype)
+
+
+@torch.library.custom_op(f"{_NS}::kv_move", mutates_args=("k_cache", "v_cache"), device_types="cuda")
+def kv_move(k_cache: Tensor, v_cache: Tensor, src_slots: Tensor, dst_slots: Tensor) -> None:
+    """kv_gather.move_kv_cache: rows src_slots[r] -> dst_slots[r] inside k_cache / v_cache (gather, then store)"""
+    _kv_gather.move_kv_cache(k_cache, v_cache, src_slots, dst_slots)
+
+
+@kv_move.register_fake
+def _(k_cache, v_cache, src_slots, dst_slots):
     return None
 
 

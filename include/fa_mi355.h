@@ -481,6 +481,78 @@ int    fa_kv_store(const fa_kv_store_params* s, void* stream);
 size_t fa_kv_store_params_size(void);
 
 /*
+ * fa_kv_gather - read ragged K / V rows out of a KV cache into a packed pair: fa_kv_store read backwards (additive, like the
+ * blocks above: fa_params and FA_ABI_VERSION are unchanged).  What turns cache pages back into the packed tensors that the ops
+ * without a block_table take (the fp8 forward, every backward, fa_merge_states' callers with a dense prefix), and the first half
+ * of moving rows inside a cache: gather by slot into a staging pair, then fa_kv_store by slot.
+ *
+ * k_cache, v_cache: [num_blocks, page_block_size, nheads, head_dim] of `cache_dtype` (FA_FP16, FA_BF16 or FA_FP8_E4M3), read only,
+ * with explicit batch (page), row and head strides in elements of the cache type, K and V each their own.  A contiguous cache
+ * [Bc, S_max, nheads, head_dim] is num_blocks = Bc, page_block_size = S_max, paged = 0.
+ * k, v: [total_rows, nheads, head_dim] of `dtype` (FA_FP16 / FA_BF16), written; element (r, h, d) of k = k[r*k_row_stride +
+ * h*k_head_stride + d] (strides in elements, the last dimension contiguous) - the K and V heads of a packed [T, Hq + 2 Hk, D] qkv
+ * are such views.  A 16-bit cache must have cache_dtype == dtype.
+ * Exactly one of two addressing modes, fa_kv_store's:
+ *   slot mode (slot_mapping != NULL): row r is block slot_mapping[r] / page_block_size, row slot_mapping[r] % page_block_size.
+ *     cu_seqlens, seq_offsets, block_table and cache_batch_idx must be unset.
+ *   sequence mode (cu_seqlens != NULL): row r belongs to the sequence b with cu_seqlens[b] <= r < cu_seqlens[b+1], has the index
+ *     i = r - cu_seqlens[b] and reads position seq_offsets[b] + i (seq_offsets NULL: i) - the counterpart of the store's
+ *     cache_seqlens: the first position of the run that is read.  paged != 0: page block_table[b*block_table_batch_stride + pos /
+ *     page_block_size], row pos % page_block_size, capacity max_blocks * page_block_size; paged == 0: batch slot
+ *     cache_batch_idx[b] (NULL: b, which needs batch <= num_blocks), row pos, capacity page_block_size.
+ * EVERY output row is written exactly once.  A row that names nothing - a slot < 0 or >= num_blocks * page_block_size, a
+ * position < 0 or >= the capacity, a row behind cu_seqlens[batch] - is written as zeros (+0 bits) in k and v: the padding-row
+ * rule of a captured graph turned round, the whole output is defined.  Empty sequences are legal; a block-table entry is read
+ * only for a row that is gathered (entries are not range-checked, as in fa_fwd_kvcache).
+ * 16-bit cache: copied bit for bit (NaN payloads, -0).  fp8 cache: out = round_to_nearest_even_to_dtype(fp32(code) * descale) -
+ * the exact conversion of the code, one fp32 multiply, one rounding; torch: (cache.float() * descale).to(dtype).  k_descale /
+ * v_descale: host floats, 0 = 1.0; ignored for a 16-bit cache.
+ * One kernel launch on `stream` reads K and V: byte movement, no LDS, no atomics, no workspace, no host synchronisation, bitwise
+ * repeatable.  16-byte stores; 16-byte loads (fp8 caches: 16-byte loads where head_dim % 16 == 0 and every cache base and stride
+ * is a multiple of 16 bytes, 8-byte loads otherwise - the same bits either way).
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL k, v, k_cache or v_cache; both addressing modes or
+ * neither; block_table together with cache_batch_idx; block_table without paged, or sequence mode with paged and no block_table;
+ * sequence-mode fields in slot mode; a dtype other than FA_FP16 / FA_BF16; a cache_dtype other than dtype or FA_FP8_E4M3;
+ * head_dim not a multiple of 8 or above 256; negative sizes or strides; page_block_size <= 0; a contiguous cache without
+ * cache_batch_idx and batch > num_blocks; k / v bases or strides that are not multiples of 16 bytes; cache bases or strides that
+ * are not multiples of 16 bytes (fp8: 8 bytes); a slot_mapping that is not 8-byte aligned; int32 side arrays that are not 4-byte
+ * aligned; a negative or non-finite descale; k or v whose address range overlaps k_cache's or v_cache's.  total_rows == 0 or
+ * nheads == 0: FA_OK without a launch; sequence mode with batch == 0 and total_rows > 0 zero-fills the rows.
+ */
+typedef struct fa_kv_gather_params {
+    size_t         struct_size;      /* sizeof(fa_kv_gather_params) as the caller compiled it */
+    const void*    k_cache;          /* [num_blocks, page_block_size, nheads, head_dim] of `cache_dtype`, read only */
+    const void*    v_cache;
+    int64_t        kc_batch_stride, kc_row_stride, kc_head_stride;   /* elements of the cache type */
+    int64_t        vc_batch_stride, vc_row_stride, vc_head_stride;
+    void*          k;                /* [total_rows, nheads, head_dim] of `dtype`, written */
+    void*          v;
+    int64_t        k_row_stride, k_head_stride;        /* elements, the last dimension contiguous */
+    int64_t        v_row_stride, v_head_stride;
+    int32_t        total_rows;       /* rows of k / v */
+    int32_t        nheads;           /* KV heads */
+    int32_t        head_dim;         /* a multiple of 8, <= 256 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        cache_dtype;      /* dtype, or FA_FP8_E4M3 */
+    int32_t        paged;            /* != 0: pages addressed through block_table (sequence mode); slot mode ignores it */
+    int32_t        num_blocks;       /* pages, or batch slots of a contiguous cache */
+    int32_t        page_block_size;  /* rows per page, or S_max of a contiguous cache; > 0 */
+    const int64_t* slot_mapping;     /* slot mode: device [total_rows], 8-byte aligned */
+    const int32_t* cu_seqlens;       /* sequence mode: device [batch + 1] */
+    const int32_t* seq_offsets;      /* device [batch]: first position read of each sequence, NULL = zeros */
+    const int32_t* block_table;      /* device [batch, max_blocks], paged caches */
+    int64_t        block_table_batch_stride;           /* elements */
+    const int32_t* cache_batch_idx;  /* device [batch], contiguous caches; NULL = identity */
+    int32_t        batch;            /* sequence mode: sequences */
+    int32_t        max_blocks;       /* columns of block_table */
+    float          k_descale;        /* fp8 cache: value = code * descale; 0 = 1.0 */
+    float          v_descale;
+} fa_kv_gather_params;
+
+int    fa_kv_gather(const fa_kv_gather_params* s, void* stream);
+size_t fa_kv_gather_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
