@@ -34,6 +34,7 @@ void launch_merge_states(const fa_merge_params& m, hipStream_t stream);
 void launch_rotary(const fa_rotary_params& r, hipStream_t stream);          // fa_rotary.hip: standalone rotary embedding
 void launch_kv_store(const fa_kv_store_params& s, hipStream_t stream);      // fa_kv_store.hip: ragged K / V rows into a KV cache
 void launch_kv_gather(const fa_kv_gather_params& s, hipStream_t stream);    // fa_kv_gather.hip: ragged K / V rows out of a KV cache
+void launch_rope_store(const fa_rope_store_params& s, hipStream_t stream);  // fa_rope_store.hip: RoPE at per-token positions + K / V store
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -201,6 +202,7 @@ size_t fa_merge_params_size(void) { return sizeof(fa_merge_params); }
 size_t fa_rotary_params_size(void) { return sizeof(fa_rotary_params); }
 size_t fa_kv_store_params_size(void) { return sizeof(fa_kv_store_params); }
 size_t fa_kv_gather_params_size(void) { return sizeof(fa_kv_gather_params); }
+size_t fa_rope_store_params_size(void) { return sizeof(fa_rope_store_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -819,6 +821,103 @@ int fa_kv_gather(const fa_kv_gather_params* sp, void* stream) {
     }
     fa::launch_kv_gather(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_kv_gather launch");
+}
+
+
+int fa_rope_store(const fa_rope_store_params* sp, void* stream) {
+    FA_CHECK(sp, "fa_rope_store_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_rope_store_params), "fa_rope_store_params::struct_size %zu is smaller than this library's %zu",
+             sp->struct_size, sizeof(fa_rope_store_params));
+    fa_rope_store_params s = *sp;
+    FA_CHECK(s.k && s.positions && s.rotary_cos && s.rotary_sin, "rope_store: k, positions, rotary_cos and rotary_sin must not be NULL");
+    FA_CHECK((s.q != nullptr) == (s.q_out != nullptr), "rope_store: q and q_out go together (%s given)", s.q ? "q without q_out" : "q_out without q");
+    FA_CHECK((s.k_cache != nullptr) == (s.v_cache != nullptr), "rope_store: k_cache and v_cache go together (both, or neither: rotate only)");
+    const bool cached = s.k_cache != nullptr;
+    if (cached) {
+        FA_CHECK(s.v && s.slot_mapping, "rope_store: caches need v and slot_mapping");
+    } else {
+        FA_CHECK(!s.v && !s.slot_mapping, "rope_store: v and slot_mapping need caches (the rotate-only form takes neither)");
+        FA_CHECK(s.q || s.k_out, "rope_store: the rotate-only form needs q or k_out (nothing would be written)");
+    }
+    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "rope_store: q / k / v dtype must be fp16 or bf16");
+    if (cached)
+        FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "rope_store: the cache dtype must be the k / v dtype or fp8-e4m3");
+    FA_CHECK(s.total_rows >= 0 && s.nheads_q >= 0 && s.nheads_k >= 0 && s.head_dim >= 0 && s.seqlen_ro >= 0 && s.num_blocks >= 0,
+             "rope_store sizes must be non-negative");
+    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "rope_store head_dim must be a multiple of 8 and <= 256, got %d", s.head_dim);
+    FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "rope_store: rotary_dim must be positive and divisible by 16, got %d", s.rotary_dim);
+    FA_CHECK(s.rotary_dim <= s.head_dim, "rope_store: rotary_dim must be <= head_dim (%d > %d)", s.rotary_dim, s.head_dim);
+    FA_CHECK(s.q_row_stride >= 0 && s.q_head_stride >= 0 && s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.v_row_stride >= 0 &&
+             s.v_head_stride >= 0 && s.qo_row_stride >= 0 && s.qo_head_stride >= 0 && s.ko_row_stride >= 0 && s.ko_head_stride >= 0 &&
+             s.kc_batch_stride >= 0 && s.kc_row_stride >= 0 && s.kc_head_stride >= 0 && s.vc_batch_stride >= 0 &&
+             s.vc_row_stride >= 0 && s.vc_head_stride >= 0, "rope_store strides must be non-negative");
+    if (cached) FA_CHECK(s.page_block_size > 0, "rope_store: page_block_size must be positive (a contiguous cache: S_max)");
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.q) | reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.v) |
+               reinterpret_cast<uintptr_t>(s.q_out) | reinterpret_cast<uintptr_t>(s.k_out)) & 15) == 0 &&
+             ((s.q_row_stride | s.q_head_stride | s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride |
+               s.qo_row_stride | s.qo_head_stride | s.ko_row_stride | s.ko_head_stride) & 7) == 0,
+             "rope_store: q / k / v / q_out / k_out base addresses and strides must be multiples of 16 bytes");
+    const bool kv8 = cached && s.cache_dtype == FA_FP8_E4M3;
+    if (cached) {
+        const uintptr_t cal = kv8 ? 7 : 15;               // bytes; strides are in elements of 1 / 2 bytes
+        const int64_t sal = 7;
+        FA_CHECK(((reinterpret_cast<uintptr_t>(s.k_cache) | reinterpret_cast<uintptr_t>(s.v_cache)) & cal) == 0 &&
+                 ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
+                 "rope_store: cache base addresses and strides must be multiples of %d bytes", kv8 ? 8 : 16);
+    }
+    FA_CHECK(reinterpret_cast<uintptr_t>(s.positions) % 8 == 0 && reinterpret_cast<uintptr_t>(s.slot_mapping) % 8 == 0,
+             "rope_store: positions and slot_mapping must be 8-byte aligned int64 arrays");
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.rotary_cos) | reinterpret_cast<uintptr_t>(s.rotary_sin)) & 15) == 0,
+             "rope_store: rotary_cos / rotary_sin must be 16-byte aligned");
+    {
+        float* ds[2] = {&s.k_descale, &s.v_descale};      // (checked for every cache type, used by fp8 caches)
+        for (float* d : ds) {
+            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "rope_store: k / v descales must be finite and >= 0 (0 = 1.0)");
+            if (*d == 0.f) *d = 1.0f;
+        }
+    }
+    if ((int64_t)(s.nheads_q + 2 * (int64_t)s.nheads_k) * s.head_dim > ((int64_t)1 << 24))
+        return fail(FA_ERR_UNSUPPORTED, "rope_store: (nheads_q + 2 nheads_k) x head_dim is too large for one launch");
+    if (!s.q) s.nheads_q = 0;
+    const bool q_inplace = s.q && s.q_out == s.q, k_inplace = s.k_out == s.k;
+    if (q_inplace)
+        FA_CHECK(s.q_row_stride == s.qo_row_stride && s.q_head_stride == s.qo_head_stride,
+                 "rope_store: q_out shares q's base address but not its strides (in place needs both equal)");
+    if (k_inplace)
+        FA_CHECK(s.k_row_stride == s.ko_row_stride && s.k_head_stride == s.ko_head_stride,
+                 "rope_store: k_out shares k's base address but not its strides (in place needs both equal)");
+    if (s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0)) return FA_OK;
+    {
+        // an out-of-place output must not lie inside anything that is read or inside a cache: other workgroups still read and write them
+        struct Span { const char* name; uint64_t at, bytes; };
+        const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
+        const Span in[] = {
+            {"q", (uint64_t)reinterpret_cast<uintptr_t>(s.q), (s.q && Hq) ? kv_span_bytes(1, 0, T, s.q_row_stride, Hq, s.q_head_stride, D, 2) : 0},
+            {"k", (uint64_t)reinterpret_cast<uintptr_t>(s.k), Hk ? kv_span_bytes(1, 0, T, s.k_row_stride, Hk, s.k_head_stride, D, 2) : 0},
+            {"v", (uint64_t)reinterpret_cast<uintptr_t>(s.v), (s.v && Hk) ? kv_span_bytes(1, 0, T, s.v_row_stride, Hk, s.v_head_stride, D, 2) : 0},
+            {"positions", (uint64_t)reinterpret_cast<uintptr_t>(s.positions), (uint64_t)T * 8},
+            {"slot_mapping", (uint64_t)reinterpret_cast<uintptr_t>(s.slot_mapping), s.slot_mapping ? (uint64_t)T * 8 : 0},
+            {"rotary_cos", (uint64_t)reinterpret_cast<uintptr_t>(s.rotary_cos), (uint64_t)s.seqlen_ro * half * 2},
+            {"rotary_sin", (uint64_t)reinterpret_cast<uintptr_t>(s.rotary_sin), (uint64_t)s.seqlen_ro * half * 2},
+            {"k_cache", (uint64_t)reinterpret_cast<uintptr_t>(s.k_cache), (cached && Hk && s.num_blocks)
+                ? kv_span_bytes(s.num_blocks, s.kc_batch_stride, s.page_block_size, s.kc_row_stride, Hk, s.kc_head_stride, D, kv8 ? 1 : 2) : 0},
+            {"v_cache", (uint64_t)reinterpret_cast<uintptr_t>(s.v_cache), (cached && Hk && s.num_blocks)
+                ? kv_span_bytes(s.num_blocks, s.vc_batch_stride, s.page_block_size, s.vc_row_stride, Hk, s.vc_head_stride, D, kv8 ? 1 : 2) : 0},
+        };
+        const Span out[2] = {
+            {"q_out", (uint64_t)reinterpret_cast<uintptr_t>(s.q_out),
+             (s.q && Hq && !q_inplace) ? kv_span_bytes(1, 0, T, s.qo_row_stride, Hq, s.qo_head_stride, D, 2) : 0},
+            {"k_out", (uint64_t)reinterpret_cast<uintptr_t>(s.k_out),
+             (s.k_out && Hk && !k_inplace) ? kv_span_bytes(1, 0, T, s.ko_row_stride, Hk, s.ko_head_stride, D, 2) : 0},
+        };
+        for (const Span& o : out)
+            for (const Span& i : in)
+                if (o.bytes && i.bytes)
+                    FA_CHECK(o.at >= i.at + i.bytes || i.at >= o.at + o.bytes,
+                             "rope_store: %s overlaps %s without being in place (in place: the same base address and strides)", o.name, i.name);
+    }
+    fa::launch_rope_store(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_rope_store launch");
 }
 
 }  // extern "C"

@@ -199,6 +199,30 @@ class FaKvGatherParams(ctypes.Structure):
     ]
 
 
+class FaRopeStoreParams(ctypes.Structure):
+    """Mirror of `struct fa_rope_store_params` (include/fa_mi355.h): fa_rope_store, q / k rotated at per-token positions and K / V
+    stored into a KV cache by slot, one launch.  struct_size must be set to sizeof(FaRopeStoreParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("q", _ptr), ("k", _ptr), ("v", _ptr),               # q NULL: K / V only; v NULL: rotate only
+        ("q_row_stride", _i64), ("q_head_stride", _i64), ("k_row_stride", _i64), ("k_head_stride", _i64),
+        ("v_row_stride", _i64), ("v_head_stride", _i64),
+        ("q_out", _ptr), ("k_out", _ptr),                     # may equal q / k (in place); k_out NULL: K is only cached
+        ("qo_row_stride", _i64), ("qo_head_stride", _i64), ("ko_row_stride", _i64), ("ko_head_stride", _i64),
+        ("positions", _ptr),             # int64 [total_rows] on the device
+        ("rotary_cos", _ptr), ("rotary_sin", _ptr),
+        ("rotary_dim", _i32), ("seqlen_ro", _i32), ("rotary_interleaved", _i32),
+        ("total_rows", _i32), ("nheads_q", _i32), ("nheads_k", _i32), ("head_dim", _i32), ("dtype", _i32), ("cache_dtype", _i32),
+        ("reserved", _i32),
+        ("k_cache", _ptr), ("v_cache", _ptr),                 # both NULL: rotate only
+        ("kc_batch_stride", _i64), ("kc_row_stride", _i64), ("kc_head_stride", _i64),
+        ("vc_batch_stride", _i64), ("vc_row_stride", _i64), ("vc_head_stride", _i64),
+        ("num_blocks", _i32), ("page_block_size", _i32),
+        ("slot_mapping", _ptr),          # int64 [total_rows] on the device
+        ("k_descale", _f32), ("v_descale", _f32),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -206,7 +230,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_fwd", "fa_bwd", "fa_varlen_fwd", "fa_varlen_bwd", "fa_fwd_kvcache",
            "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
            "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size",
-           "fa_kv_store", "fa_kv_store_params_size", "fa_kv_gather", "fa_kv_gather_params_size"] + EXT_OPS
+           "fa_kv_store", "fa_kv_store_params_size", "fa_kv_gather", "fa_kv_gather_params_size",
+           "fa_rope_store", "fa_rope_store_params_size"] + EXT_OPS
 
 
 def _load():
@@ -251,6 +276,9 @@ def _load():
     lib.fa_kv_gather.restype = ctypes.c_int
     lib.fa_kv_gather.argtypes = [ctypes.POINTER(FaKvGatherParams), ctypes.c_void_p]
     lib.fa_kv_gather_params_size.restype = ctypes.c_size_t
+    lib.fa_rope_store.restype = ctypes.c_int
+    lib.fa_rope_store.argtypes = [ctypes.POINTER(FaRopeStoreParams), ctypes.c_void_p]
+    lib.fa_rope_store_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -276,6 +304,9 @@ def _load():
     if lib.fa_kv_gather_params_size() != ctypes.sizeof(FaKvGatherParams):
         raise ImportError(f"fa_kv_gather_params size mismatch: library {lib.fa_kv_gather_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaKvGatherParams)}")
+    if lib.fa_rope_store_params_size() != ctypes.sizeof(FaRopeStoreParams):
+        raise ImportError(f"fa_rope_store_params size mismatch: library {lib.fa_rope_store_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaRopeStoreParams)}")
     return lib
 
 
@@ -336,6 +367,13 @@ def call_kv_gather(params, stream):
     rc = lib.fa_kv_gather(ctypes.byref(params), ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"fa_kv_gather failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_rope_store(params, stream):
+    """fa_rope_store"""
+    rc = lib.fa_rope_store(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_rope_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
 
 
 def call_rows(name, *args):

@@ -2,7 +2,8 @@
 varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op with a tree attention mask; `merge_states`: the
 LSE merge of attention states over disjoint key sets, fa_merge_states; `rotary` / `rotary_`: the standalone rotary embedding,
 fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_kv_store; `kv_gather` / `kv_move`: ragged K / V
-rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache - registered, but not listed in `__all__`).
+rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache; `rope_store_`: q / k rotated at per-token positions
+and K / V stored by slot in one launch, fa_rope_store - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -30,6 +31,7 @@ from . import cascade as _cascade
 from . import flash_attn_interface as _fi
 from . import kv_gather as _kv_gather
 from . import kv_store as _kv_store
+from . import rope_store as _rope_store
 from . import rotary as _rotary
 
 _NS = "flash_attn_mi355"
@@ -474,6 +476,27 @@ def kv_move(k_cache: Tensor, v_cache: Tensor, src_slots: Tensor, dst_slots: Tens
 
 @kv_move.register_fake
 def _(k_cache, v_cache, src_slots, dst_slots):
+    return None
+
+
+# ------------------------------------------------------------------------------------------
+# RoPE at per-token positions + KV-cache store, one launch (flash_attn_mi355.rope_store; csrc/fa_rope_store.hip).  Reached as
+# torch.ops.flash_attn_mi355.rope_store_; not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::rope_store_", mutates_args=("q", "k", "k_cache", "v_cache"), device_types="cuda")
+def rope_store_(q: Tensor, k: Tensor, v: Tensor, positions: Tensor, rotary_cos: Tensor, rotary_sin: Tensor, k_cache: Tensor,
+                v_cache: Tensor, slot_mapping: Tensor, interleaved: bool, k_descale: float, v_descale: float) -> None:
+    """rope_store.rope_and_store_kv in place: q / k [T, H, D] are rotated at positions[T] where they are, the rotated k and v go
+    into k_cache / v_cache by slot_mapping[T].  k_descale / v_descale are read for float8_e4m3fn caches only (pass 1.0 otherwise).
+    The optional forms (no q, no write-back of k, no caches, out of place) stay with the Python function."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    _rope_store.rope_and_store_kv(q, k, v, positions, rotary_cos, rotary_sin, k_cache, v_cache, slot_mapping,
+                                  interleaved=interleaved, inplace=True, k_out=True,
+                                  k_descale=k_descale if fp8 else None, v_descale=v_descale if fp8 else None)
+
+
+@rope_store_.register_fake
+def _(q, k, v, positions, rotary_cos, rotary_sin, k_cache, v_cache, slot_mapping, interleaved, k_descale, v_descale):
     return None
 
 

@@ -553,6 +553,86 @@ int    fa_kv_gather(const fa_kv_gather_params* s, void* stream);
 size_t fa_kv_gather_params_size(void);
 
 /*
+ * fa_rope_store - the prologue of a serving step in one launch: rotate q and k at PER-TOKEN positions and store K / V into the KV
+ * cache by slot (additive, like the blocks above: fa_params and FA_ABI_VERSION are unchanged).  What fa_rotary (positions = row
+ * index + a per-sequence offset) followed by fa_kv_store in slot mode (no rotation) do in two or three launches, for a flat token
+ * batch with positions[T] and slot_mapping[T] - draft-tree nodes, re-packed tokens and padding rows included.
+ *
+ * q: [total_rows, nheads_q, head_dim] of `dtype` (FA_FP16 / FA_BF16), or NULL (a K / V-only call); k, v: [total_rows, nheads_k,
+ * head_dim]; element (r, h, d) of q = q[r*q_row_stride + h*q_head_stride + d] (strides in elements, the last dimension contiguous)
+ * - the q, k and v heads of one packed [T, Hq + 2 Hk, D] qkv are such views.  q_out, k_out: the same shapes with their own strides.
+ * q_out == q (the same base address AND strides) is in place, likewise k_out == k; k_out == NULL: the rotated K is not written
+ * back, only cached; q_out is required whenever q is given.  The caller guarantees that the q, k and v views share no element.
+ * positions: device int64 [total_rows].  pos = positions[r]; row r of q and of k is rotated if and only if 0 <= pos < seqlen_ro,
+ * with fa_rotary's pair rule and arithmetic (fp32 math, c = cos[pos, t], s = sin[pos, t], one rounding to `dtype`;
+ * rotary_interleaved != 0: pairs (2t, 2t+1), otherwise (t, t + rotary_dim/2)).  Any other position leaves the row unrotated -
+ * copied when out != in, untouched in place - and nothing outside rotary_cos / rotary_sin ([seqlen_ro, rotary_dim / 2] of `dtype`,
+ * contiguous) is read.  Columns [rotary_dim, head_dim) are copied when out != in and neither read nor written in place.
+ * q_out[r] and k_out[r] are written for EVERY row, whatever its slot: their bits are fa_rotary's.
+ * k_cache, v_cache, their strides, num_blocks, page_block_size, cache_dtype, k_descale, v_descale and slot_mapping are fa_kv_store's
+ * slot mode: s = slot_mapping[r]; s < 0 or s >= num_blocks * page_block_size skips the cache write of that row (padding rows of a
+ * captured graph); otherwise block s / page_block_size, row s % page_block_size gets k_cache = store(rope(k[r], pos)) and
+ * v_cache = store(v[r]), where store is a bit copy for a 16-bit cache and fa_kv_store's e4m3(clamp(x * (1 / descale), -448, 448))
+ * for an fp8 cache: the cache holds the bits that fa_rotary followed by fa_kv_store by slot would leave.  V is never rotated.  Two
+ * rows with the same slot: one of them wins (unspecified, as in fa_kv_store).
+ * k_cache == v_cache == NULL is the rotate-only form: v and slot_mapping must be NULL too and at least one of q / k_out must be
+ * given - the standalone rotation at per-token positions.
+ * One kernel launch on `stream`: byte movement, no LDS, no atomics, no workspace, no host synchronisation, bitwise repeatable,
+ * capturable in a graph.  One lane owns both partner pieces of a GPT-NeoX pair and loads everything it owns before its first
+ * store, so in place no element is read after its partner was written.  16-byte loads; 16-byte stores to q_out / k_out and to
+ * 16-bit caches; fp8 caches: 16-byte stores where head_dim % 16 == 0, every cache base and stride is a multiple of 16 bytes and
+ * (GPT-NeoX pairs only) rotary_dim % 32 == 0, 8-byte stores otherwise - the same bits either way.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL k, positions, rotary_cos or rotary_sin; q without q_out
+ * or q_out without q; exactly one of the two caches; caches without v or without slot_mapping; v or slot_mapping without caches;
+ * the rotate-only form with neither q nor k_out; a dtype other than FA_FP16 / FA_BF16; a cache_dtype other than dtype or
+ * FA_FP8_E4M3; head_dim not a multiple of 8 or above 256; rotary_dim <= 0, not a multiple of 16 or > head_dim; negative sizes or
+ * strides; page_block_size <= 0 with caches; q / k / v / q_out / k_out bases or strides that are not multiples of 16 bytes; cache
+ * bases or strides that are not multiples of 16 bytes (fp8: 8 bytes); positions or slot_mapping not 8-byte aligned; rotary_cos /
+ * rotary_sin not 16-byte aligned; a negative or non-finite descale; a q_out / k_out that shares its input's base address but not
+ * its strides; an out-of-place q_out or k_out whose address range overlaps that of q, k, v, positions, slot_mapping, rotary_cos,
+ * rotary_sin, k_cache or v_cache.  total_rows == 0 or nheads_q == nheads_k == 0 (a NULL q counts as no q heads): FA_OK without a
+ * launch.
+ */
+typedef struct fa_rope_store_params {
+    size_t         struct_size;      /* sizeof(fa_rope_store_params) as the caller compiled it */
+    const void*    q;                /* [total_rows, nheads_q, head_dim] of `dtype`, or NULL */
+    const void*    k;                /* [total_rows, nheads_k, head_dim] */
+    const void*    v;                /* [total_rows, nheads_k, head_dim]; NULL in the rotate-only form */
+    int64_t        q_row_stride, q_head_stride;        /* elements, the last dimension contiguous */
+    int64_t        k_row_stride, k_head_stride;
+    int64_t        v_row_stride, v_head_stride;
+    void*          q_out;            /* q's shape, own strides; may equal q; required with q */
+    void*          k_out;            /* k's shape, own strides; may equal k; NULL: the rotated K is only cached */
+    int64_t        qo_row_stride, qo_head_stride;
+    int64_t        ko_row_stride, ko_head_stride;
+    const int64_t* positions;        /* device [total_rows], 8-byte aligned */
+    const void*    rotary_cos;       /* [seqlen_ro, rotary_dim / 2] of `dtype`, contiguous, 16-byte aligned */
+    const void*    rotary_sin;
+    int32_t        rotary_dim;       /* a multiple of 16, 0 < rotary_dim <= head_dim */
+    int32_t        seqlen_ro;
+    int32_t        rotary_interleaved;
+    int32_t        total_rows;       /* rows of q / k / v */
+    int32_t        nheads_q;
+    int32_t        nheads_k;
+    int32_t        head_dim;         /* a multiple of 8, <= 256 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        cache_dtype;      /* dtype, or FA_FP8_E4M3; read with caches only */
+    int32_t        reserved;         /* 0 */
+    void*          k_cache;          /* [num_blocks, page_block_size, nheads_k, head_dim] of `cache_dtype`, written; or NULL */
+    void*          v_cache;
+    int64_t        kc_batch_stride, kc_row_stride, kc_head_stride;   /* elements of the cache type */
+    int64_t        vc_batch_stride, vc_row_stride, vc_head_stride;
+    int32_t        num_blocks;       /* pages, or batch slots of a contiguous cache */
+    int32_t        page_block_size;  /* rows per page, or S_max of a contiguous cache; > 0 with caches */
+    const int64_t* slot_mapping;     /* device [total_rows], 8-byte aligned; with caches */
+    float          k_descale;        /* fp8 cache: value = code * descale; 0 = 1.0 */
+    float          v_descale;
+} fa_rope_store_params;
+
+int    fa_rope_store(const fa_rope_store_params* s, void* stream);
+size_t fa_rope_store_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
