@@ -7,6 +7,7 @@
 //   backward kernel/fused_mha_backward.cu:577-692, kernel/fused_mha_backward_varlen.cu:636-765
 // Errors never cross the boundary as exceptions: negative status + fa_last_error().
 #include <cstdarg>
+#include <cstddef>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -35,6 +36,7 @@ void launch_rotary(const fa_rotary_params& r, hipStream_t stream);          // f
 void launch_kv_store(const fa_kv_store_params& s, hipStream_t stream);      // fa_kv_store.hip: ragged K / V rows into a KV cache
 void launch_kv_gather(const fa_kv_gather_params& s, hipStream_t stream);    // fa_kv_gather.hip: ragged K / V rows out of a KV cache
 void launch_rope_store(const fa_rope_store_params& s, hipStream_t stream);  // fa_rope_store.hip: RoPE at per-token positions + K / V store
+void launch_qk_norm_rope_store(const fa_qk_norm_rope_store_params& s, hipStream_t stream);   // fa_qk_norm_rope_store.hip: QK RMSNorm in front of that
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -203,6 +205,7 @@ size_t fa_rotary_params_size(void) { return sizeof(fa_rotary_params); }
 size_t fa_kv_store_params_size(void) { return sizeof(fa_kv_store_params); }
 size_t fa_kv_gather_params_size(void) { return sizeof(fa_kv_gather_params); }
 size_t fa_rope_store_params_size(void) { return sizeof(fa_rope_store_params); }
+size_t fa_qk_norm_rope_store_params_size(void) { return sizeof(fa_qk_norm_rope_store_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -824,78 +827,90 @@ int fa_kv_gather(const fa_kv_gather_params* sp, void* stream) {
 }
 
 
-int fa_rope_store(const fa_rope_store_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_rope_store_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_rope_store_params), "fa_rope_store_params::struct_size %zu is smaller than this library's %zu",
-             sp->struct_size, sizeof(fa_rope_store_params));
-    fa_rope_store_params s = *sp;
-    FA_CHECK(s.k && s.positions && s.rotary_cos && s.rotary_sin, "rope_store: k, positions, rotary_cos and rotary_sin must not be NULL");
-    FA_CHECK((s.q != nullptr) == (s.q_out != nullptr), "rope_store: q and q_out go together (%s given)", s.q ? "q without q_out" : "q_out without q");
-    FA_CHECK((s.k_cache != nullptr) == (s.v_cache != nullptr), "rope_store: k_cache and v_cache go together (both, or neither: rotate only)");
+// The argument rules that fa_rope_store and fa_qk_norm_rope_store share (the second block begins with the fields of the first).
+// `op` names the entry point in the messages.  no_rope_ok: seqlen_ro == 0 means "no rotation" - positions and the tables may be
+// NULL then and rotary_dim is not read (set to 0).  extra: further read-only spans that an out-of-place output must not overlap.
+// Normalises the block (descales of 0 -> 1.0, nheads_q = 0 without q); *empty: nothing to launch.
+struct RsSpan { const char* name; uint64_t at, bytes; };
+static int rope_store_check(fa_rope_store_params& s, const char* op, bool no_rope_ok, const RsSpan* extra, int n_extra, bool* empty) {
+    *empty = false;
+    const bool no_rope = no_rope_ok && s.seqlen_ro == 0;
+    if (no_rope) {
+        FA_CHECK(s.k, "%s: k must not be NULL", op);
+        s.positions = nullptr; s.rotary_cos = s.rotary_sin = nullptr; s.rotary_dim = 0;
+    } else if (no_rope_ok) {
+        FA_CHECK(s.k, "%s: k must not be NULL", op);
+        FA_CHECK(s.seqlen_ro < 0 || (s.positions && s.rotary_cos && s.rotary_sin),         // (< 0: rejected with the sizes below)
+                 "%s: positions, rotary_cos and rotary_sin may be NULL only where seqlen_ro == 0", op);
+    } else {
+        FA_CHECK(s.k && s.positions && s.rotary_cos && s.rotary_sin, "%s: k, positions, rotary_cos and rotary_sin must not be NULL", op);
+    }
+    FA_CHECK((s.q != nullptr) == (s.q_out != nullptr), "%s: q and q_out go together (%s given)", op, s.q ? "q without q_out" : "q_out without q");
+    FA_CHECK((s.k_cache != nullptr) == (s.v_cache != nullptr), "%s: k_cache and v_cache go together (both, or neither: rotate only)", op);
     const bool cached = s.k_cache != nullptr;
     if (cached) {
-        FA_CHECK(s.v && s.slot_mapping, "rope_store: caches need v and slot_mapping");
+        FA_CHECK(s.v && s.slot_mapping, "%s: caches need v and slot_mapping", op);
     } else {
-        FA_CHECK(!s.v && !s.slot_mapping, "rope_store: v and slot_mapping need caches (the rotate-only form takes neither)");
-        FA_CHECK(s.q || s.k_out, "rope_store: the rotate-only form needs q or k_out (nothing would be written)");
+        FA_CHECK(!s.v && !s.slot_mapping, "%s: v and slot_mapping need caches (the rotate-only form takes neither)", op);
+        FA_CHECK(s.q || s.k_out, "%s: the rotate-only form needs q or k_out (nothing would be written)", op);
     }
-    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "rope_store: q / k / v dtype must be fp16 or bf16");
+    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "%s: q / k / v dtype must be fp16 or bf16", op);
     if (cached)
-        FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "rope_store: the cache dtype must be the k / v dtype or fp8-e4m3");
+        FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "%s: the cache dtype must be the k / v dtype or fp8-e4m3", op);
     FA_CHECK(s.total_rows >= 0 && s.nheads_q >= 0 && s.nheads_k >= 0 && s.head_dim >= 0 && s.seqlen_ro >= 0 && s.num_blocks >= 0,
-             "rope_store sizes must be non-negative");
-    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "rope_store head_dim must be a multiple of 8 and <= 256, got %d", s.head_dim);
-    FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "rope_store: rotary_dim must be positive and divisible by 16, got %d", s.rotary_dim);
-    FA_CHECK(s.rotary_dim <= s.head_dim, "rope_store: rotary_dim must be <= head_dim (%d > %d)", s.rotary_dim, s.head_dim);
+             "%s sizes must be non-negative", op);
+    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "%s head_dim must be a multiple of 8 and <= 256, got %d", op, s.head_dim);
+    if (!no_rope) FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "%s: rotary_dim must be positive and divisible by 16, got %d", op, s.rotary_dim);
+    FA_CHECK(s.rotary_dim <= s.head_dim, "%s: rotary_dim must be <= head_dim (%d > %d)", op, s.rotary_dim, s.head_dim);
     FA_CHECK(s.q_row_stride >= 0 && s.q_head_stride >= 0 && s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.v_row_stride >= 0 &&
              s.v_head_stride >= 0 && s.qo_row_stride >= 0 && s.qo_head_stride >= 0 && s.ko_row_stride >= 0 && s.ko_head_stride >= 0 &&
              s.kc_batch_stride >= 0 && s.kc_row_stride >= 0 && s.kc_head_stride >= 0 && s.vc_batch_stride >= 0 &&
-             s.vc_row_stride >= 0 && s.vc_head_stride >= 0, "rope_store strides must be non-negative");
-    if (cached) FA_CHECK(s.page_block_size > 0, "rope_store: page_block_size must be positive (a contiguous cache: S_max)");
+             s.vc_row_stride >= 0 && s.vc_head_stride >= 0, "%s strides must be non-negative", op);
+    if (cached) FA_CHECK(s.page_block_size > 0, "%s: page_block_size must be positive (a contiguous cache: S_max)", op);
     FA_CHECK(((reinterpret_cast<uintptr_t>(s.q) | reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.v) |
                reinterpret_cast<uintptr_t>(s.q_out) | reinterpret_cast<uintptr_t>(s.k_out)) & 15) == 0 &&
              ((s.q_row_stride | s.q_head_stride | s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride |
                s.qo_row_stride | s.qo_head_stride | s.ko_row_stride | s.ko_head_stride) & 7) == 0,
-             "rope_store: q / k / v / q_out / k_out base addresses and strides must be multiples of 16 bytes");
+             "%s: q / k / v / q_out / k_out base addresses and strides must be multiples of 16 bytes", op);
     const bool kv8 = cached && s.cache_dtype == FA_FP8_E4M3;
     if (cached) {
         const uintptr_t cal = kv8 ? 7 : 15;               // bytes; strides are in elements of 1 / 2 bytes
         const int64_t sal = 7;
         FA_CHECK(((reinterpret_cast<uintptr_t>(s.k_cache) | reinterpret_cast<uintptr_t>(s.v_cache)) & cal) == 0 &&
                  ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
-                 "rope_store: cache base addresses and strides must be multiples of %d bytes", kv8 ? 8 : 16);
+                 "%s: cache base addresses and strides must be multiples of %d bytes", op, kv8 ? 8 : 16);
     }
     FA_CHECK(reinterpret_cast<uintptr_t>(s.positions) % 8 == 0 && reinterpret_cast<uintptr_t>(s.slot_mapping) % 8 == 0,
-             "rope_store: positions and slot_mapping must be 8-byte aligned int64 arrays");
+             "%s: positions and slot_mapping must be 8-byte aligned int64 arrays", op);
     FA_CHECK(((reinterpret_cast<uintptr_t>(s.rotary_cos) | reinterpret_cast<uintptr_t>(s.rotary_sin)) & 15) == 0,
-             "rope_store: rotary_cos / rotary_sin must be 16-byte aligned");
+             "%s: rotary_cos / rotary_sin must be 16-byte aligned", op);
     {
         float* ds[2] = {&s.k_descale, &s.v_descale};      // (checked for every cache type, used by fp8 caches)
         for (float* d : ds) {
-            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "rope_store: k / v descales must be finite and >= 0 (0 = 1.0)");
+            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "%s: k / v descales must be finite and >= 0 (0 = 1.0)", op);
             if (*d == 0.f) *d = 1.0f;
         }
     }
     if ((int64_t)(s.nheads_q + 2 * (int64_t)s.nheads_k) * s.head_dim > ((int64_t)1 << 24))
-        return fail(FA_ERR_UNSUPPORTED, "rope_store: (nheads_q + 2 nheads_k) x head_dim is too large for one launch");
+        return fail(FA_ERR_UNSUPPORTED, "%s: (nheads_q + 2 nheads_k) x head_dim is too large for one launch", op);
     if (!s.q) s.nheads_q = 0;
     const bool q_inplace = s.q && s.q_out == s.q, k_inplace = s.k_out == s.k;
     if (q_inplace)
         FA_CHECK(s.q_row_stride == s.qo_row_stride && s.q_head_stride == s.qo_head_stride,
-                 "rope_store: q_out shares q's base address but not its strides (in place needs both equal)");
+                 "%s: q_out shares q's base address but not its strides (in place needs both equal)", op);
     if (k_inplace)
         FA_CHECK(s.k_row_stride == s.ko_row_stride && s.k_head_stride == s.ko_head_stride,
-                 "rope_store: k_out shares k's base address but not its strides (in place needs both equal)");
-    if (s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0)) return FA_OK;
+                 "%s: k_out shares k's base address but not its strides (in place needs both equal)", op);
+    if (s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0)) { *empty = true; return FA_OK; }
     {
         // an out-of-place output must not lie inside anything that is read or inside a cache: other workgroups still read and write them
-        struct Span { const char* name; uint64_t at, bytes; };
+        typedef RsSpan Span;
         const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
         const Span in[] = {
             {"q", (uint64_t)reinterpret_cast<uintptr_t>(s.q), (s.q && Hq) ? kv_span_bytes(1, 0, T, s.q_row_stride, Hq, s.q_head_stride, D, 2) : 0},
             {"k", (uint64_t)reinterpret_cast<uintptr_t>(s.k), Hk ? kv_span_bytes(1, 0, T, s.k_row_stride, Hk, s.k_head_stride, D, 2) : 0},
             {"v", (uint64_t)reinterpret_cast<uintptr_t>(s.v), (s.v && Hk) ? kv_span_bytes(1, 0, T, s.v_row_stride, Hk, s.v_head_stride, D, 2) : 0},
-            {"positions", (uint64_t)reinterpret_cast<uintptr_t>(s.positions), (uint64_t)T * 8},
+            {"positions", (uint64_t)reinterpret_cast<uintptr_t>(s.positions), s.positions ? (uint64_t)T * 8 : 0},
             {"slot_mapping", (uint64_t)reinterpret_cast<uintptr_t>(s.slot_mapping), s.slot_mapping ? (uint64_t)T * 8 : 0},
             {"rotary_cos", (uint64_t)reinterpret_cast<uintptr_t>(s.rotary_cos), (uint64_t)s.seqlen_ro * half * 2},
             {"rotary_sin", (uint64_t)reinterpret_cast<uintptr_t>(s.rotary_sin), (uint64_t)s.seqlen_ro * half * 2},
@@ -910,14 +925,63 @@ int fa_rope_store(const fa_rope_store_params* sp, void* stream) {
             {"k_out", (uint64_t)reinterpret_cast<uintptr_t>(s.k_out),
              (s.k_out && Hk && !k_inplace) ? kv_span_bytes(1, 0, T, s.ko_row_stride, Hk, s.ko_head_stride, D, 2) : 0},
         };
-        for (const Span& o : out)
+        for (const Span& o : out) {
             for (const Span& i : in)
                 if (o.bytes && i.bytes)
                     FA_CHECK(o.at >= i.at + i.bytes || i.at >= o.at + o.bytes,
-                             "rope_store: %s overlaps %s without being in place (in place: the same base address and strides)", o.name, i.name);
+                             "%s: %s overlaps %s without being in place (in place: the same base address and strides)", op, o.name, i.name);
+            for (int e = 0; e < n_extra; ++e)
+                if (o.bytes && extra[e].bytes)
+                    FA_CHECK(o.at >= extra[e].at + extra[e].bytes || extra[e].at >= o.at + o.bytes, "%s: %s overlaps %s", op, o.name, extra[e].name);
+        }
     }
+    return FA_OK;
+}
+
+int fa_rope_store(const fa_rope_store_params* sp, void* stream) {
+    FA_CHECK(sp, "fa_rope_store_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_rope_store_params), "fa_rope_store_params::struct_size %zu is smaller than this library's %zu",
+             sp->struct_size, sizeof(fa_rope_store_params));
+    fa_rope_store_params s = *sp;
+    bool empty;
+    const int rc = rope_store_check(s, "rope_store", false, nullptr, 0, &empty);
+    if (rc != FA_OK || empty) return rc;
     fa::launch_rope_store(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_rope_store launch");
+}
+
+int fa_qk_norm_rope_store(const fa_qk_norm_rope_store_params* sp, void* stream) {
+    // the block begins with fa_rope_store_params, field for field: the shared rules read (and normalise) that part
+    static_assert(offsetof(fa_qk_norm_rope_store_params, q_weight) == sizeof(fa_rope_store_params) &&
+                  offsetof(fa_qk_norm_rope_store_params, v_descale) == offsetof(fa_rope_store_params, v_descale) &&
+                  offsetof(fa_qk_norm_rope_store_params, k_cache) == offsetof(fa_rope_store_params, k_cache) &&
+                  offsetof(fa_qk_norm_rope_store_params, positions) == offsetof(fa_rope_store_params, positions),
+                  "fa_qk_norm_rope_store_params must begin with the fields of fa_rope_store_params");
+    FA_CHECK(sp, "fa_qk_norm_rope_store_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_qk_norm_rope_store_params),
+             "fa_qk_norm_rope_store_params::struct_size %zu is smaller than this library's %zu", sp->struct_size, sizeof(fa_qk_norm_rope_store_params));
+    fa_qk_norm_rope_store_params s = *sp;
+    const char* op = "qk_norm_rope_store";
+    const bool weights = s.q_weight || s.k_weight;
+    if (weights)
+        FA_CHECK(s.weight_dtype == FA_FP32 || (s.weight_dtype == s.dtype && (s.dtype == FA_FP16 || s.dtype == FA_BF16)),
+                 "%s: weight_dtype must be the q / k dtype or fp32", op);
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.q_weight) | reinterpret_cast<uintptr_t>(s.k_weight)) & 15) == 0,
+             "%s: q_weight / k_weight must be 16-byte aligned", op);
+    FA_CHECK(s.eps >= 0.f && s.eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
+    FA_CHECK(s.weight_offset >= -3.402823466e38f && s.weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
+    const uint64_t wbytes = (uint64_t)(s.head_dim > 0 ? s.head_dim : 0) * (s.weight_dtype == FA_FP32 ? 4 : 2);
+    const RsSpan extra[2] = {{"q_weight", (uint64_t)reinterpret_cast<uintptr_t>(s.q_weight), s.q_weight ? wbytes : 0},
+                             {"k_weight", (uint64_t)reinterpret_cast<uintptr_t>(s.k_weight), s.k_weight ? wbytes : 0}};
+    fa_rope_store_params base;
+    memcpy(&base, &s, sizeof(base));
+    bool empty;
+    const int rc = rope_store_check(base, op, true, extra, 2, &empty);
+    if (rc != FA_OK || empty) return rc;
+    memcpy(&s, &base, sizeof(base));
+    s.struct_size = sizeof(s);
+    fa::launch_qk_norm_rope_store(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_qk_norm_rope_store launch");
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FA_MI355_LIB") or os.path.join(_HERE, "libfa_mi355.so")   # env: A/B experiment builds
 
-FA_FP16, FA_BF16, FA_FP8_E4M3 = 0, 1, 2
+FA_FP16, FA_BF16, FA_FP8_E4M3, FA_FP32 = 0, 1, 2, 3
 FA_ABI_VERSION = 4
 FA_FLAG_KEEP_WINDOW = 1
 FA_FLAG_NO_DKV_SPLIT = 2
@@ -223,6 +223,18 @@ class FaRopeStoreParams(ctypes.Structure):
     ]
 
 
+class FaQkNormRopeStoreParams(ctypes.Structure):
+    """Mirror of `struct fa_qk_norm_rope_store_params` (include/fa_mi355.h): fa_qk_norm_rope_store, fa_rope_store with a per-head
+    RMSNorm of q and k in front of the rotation - FaRopeStoreParams' fields, then the norm's.  struct_size must be set to
+    sizeof(FaQkNormRopeStoreParams)."""
+    _fields_ = FaRopeStoreParams._fields_ + [
+        ("q_weight", _ptr), ("k_weight", _ptr),               # [head_dim] of weight_dtype; NULL: that tensor is not normalised
+        ("weight_dtype", _i32),          # the q / k dtype, or FA_FP32
+        ("eps", _f32), ("weight_offset", _f32),
+        ("reserved1", _i32),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -231,7 +243,7 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
            "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size",
            "fa_kv_store", "fa_kv_store_params_size", "fa_kv_gather", "fa_kv_gather_params_size",
-           "fa_rope_store", "fa_rope_store_params_size"] + EXT_OPS
+           "fa_rope_store", "fa_rope_store_params_size", "fa_qk_norm_rope_store", "fa_qk_norm_rope_store_params_size"] + EXT_OPS
 
 
 def _load():
@@ -279,6 +291,9 @@ def _load():
     lib.fa_rope_store.restype = ctypes.c_int
     lib.fa_rope_store.argtypes = [ctypes.POINTER(FaRopeStoreParams), ctypes.c_void_p]
     lib.fa_rope_store_params_size.restype = ctypes.c_size_t
+    lib.fa_qk_norm_rope_store.restype = ctypes.c_int
+    lib.fa_qk_norm_rope_store.argtypes = [ctypes.POINTER(FaQkNormRopeStoreParams), ctypes.c_void_p]
+    lib.fa_qk_norm_rope_store_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -307,6 +322,9 @@ def _load():
     if lib.fa_rope_store_params_size() != ctypes.sizeof(FaRopeStoreParams):
         raise ImportError(f"fa_rope_store_params size mismatch: library {lib.fa_rope_store_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaRopeStoreParams)}")
+    if lib.fa_qk_norm_rope_store_params_size() != ctypes.sizeof(FaQkNormRopeStoreParams):
+        raise ImportError(f"fa_qk_norm_rope_store_params size mismatch: library {lib.fa_qk_norm_rope_store_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaQkNormRopeStoreParams)}")
     return lib
 
 
@@ -374,6 +392,13 @@ def call_rope_store(params, stream):
     rc = lib.fa_rope_store(ctypes.byref(params), ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"fa_rope_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_qk_norm_rope_store(params, stream):
+    """fa_qk_norm_rope_store"""
+    rc = lib.fa_qk_norm_rope_store(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_qk_norm_rope_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
 
 
 def call_rows(name, *args):

@@ -9,8 +9,8 @@ The rotated bits are `apply_rotary_emb`'s and the cache holds what `apply_rotary
 kernels share the rotation and the fp8 rounding rule.  Without caches the call is the standalone rotation at per-token positions.
 
 Not covered: fp32 cos / sin and rotary dims that are not multiples of 16 (`apply_rotary_emb` has them), a backward, sequence-mode
-addressing (`store_kv_cache` has it), per-head or device-resident descales.  Nothing here is exported through the packages'
-`__all__` lists."""
+addressing (`store_kv_cache` has it), per-head or device-resident descales.  QK-norm in front of the rotation is
+`qk_norm.qk_norm_rope_and_store_kv`'s.  Nothing here is exported through the packages' `__all__` lists."""
 import ctypes
 from typing import Optional
 

@@ -3,7 +3,8 @@ varlen_fwd, varlen_bwd, fwd_kvcache}` (and `fwd_kvcache_tree`: the kv-cache op w
 LSE merge of attention states over disjoint key sets, fa_merge_states; `rotary` / `rotary_`: the standalone rotary embedding,
 fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_kv_store; `kv_gather` / `kv_move`: ragged K / V
 rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache; `rope_store_`: q / k rotated at per-token positions
-and K / V stored by slot in one launch, fa_rope_store - registered, but not listed in `__all__`).
+and K / V stored by slot in one launch, fa_rope_store; `qk_norm_rope_store_`: the same behind a per-head RMSNorm of q and k,
+fa_qk_norm_rope_store - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -31,6 +32,7 @@ from . import cascade as _cascade
 from . import flash_attn_interface as _fi
 from . import kv_gather as _kv_gather
 from . import kv_store as _kv_store
+from . import qk_norm as _qk_norm
 from . import rope_store as _rope_store
 from . import rotary as _rotary
 
@@ -497,6 +499,31 @@ def rope_store_(q: Tensor, k: Tensor, v: Tensor, positions: Tensor, rotary_cos: 
 
 @rope_store_.register_fake
 def _(q, k, v, positions, rotary_cos, rotary_sin, k_cache, v_cache, slot_mapping, interleaved, k_descale, v_descale):
+    return None
+
+
+# ------------------------------------------------------------------------------------------
+# QK RMSNorm + RoPE at per-token positions + KV-cache store, one launch (flash_attn_mi355.qk_norm; csrc/fa_qk_norm_rope_store.hip).
+# Reached as torch.ops.flash_attn_mi355.qk_norm_rope_store_; not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::qk_norm_rope_store_", mutates_args=("q", "k", "k_cache", "v_cache"), device_types="cuda")
+def qk_norm_rope_store_(q: Tensor, k: Tensor, v: Tensor, positions: Tensor, rotary_cos: Tensor, rotary_sin: Tensor, k_cache: Tensor,
+                        v_cache: Tensor, slot_mapping: Tensor, q_weight: Optional[Tensor], k_weight: Optional[Tensor], eps: float,
+                        weight_offset: float, interleaved: bool, k_descale: float, v_descale: float) -> None:
+    """qk_norm.qk_norm_rope_and_store_kv in place: every head of q / k [T, H, D] is RMS-normalised with q_weight / k_weight [D]
+    (None: not normalised) and rotated at positions[T] where it is, the normalised, rotated k and v go into k_cache / v_cache by
+    slot_mapping[T].  k_descale / v_descale are read for float8_e4m3fn caches only (pass 1.0 otherwise).  The optional forms (no q,
+    no write-back of k, no caches, no rotation, out of place) stay with the Python function."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    _qk_norm.qk_norm_rope_and_store_kv(q, k, v, positions, rotary_cos, rotary_sin, k_cache, v_cache, slot_mapping,
+                                       q_weight=q_weight, k_weight=k_weight, eps=eps, weight_offset=weight_offset,
+                                       interleaved=interleaved, inplace=True, k_out=True,
+                                       k_descale=k_descale if fp8 else None, v_descale=v_descale if fp8 else None)
+
+
+@qk_norm_rope_store_.register_fake
+def _(q, k, v, positions, rotary_cos, rotary_sin, k_cache, v_cache, slot_mapping, q_weight, k_weight, eps, weight_offset, interleaved,
+      k_descale, v_descale):
     return None
 
 

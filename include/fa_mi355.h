@@ -63,8 +63,9 @@ extern "C" {
 typedef enum fa_dtype {
     FA_FP16 = 0,      /* IEEE half */
     FA_BF16 = 1,      /* bfloat16 */
-    FA_FP8_E4M3 = 2   /* OCP e4m3fn: k/v of fa_fwd_kvcache and of paged fa_varlen_fwd; q, k and v together in fa_fwd /
+    FA_FP8_E4M3 = 2,  /* OCP e4m3fn: k/v of fa_fwd_kvcache and of paged fa_varlen_fwd; q, k and v together in fa_fwd /
                          fa_varlen_fwd (forward only, 16-bit o of fa_params::o_dtype) */
+    FA_FP32 = 3       /* IEEE single: fa_qk_norm_rope_store_params::weight_dtype only */
 } fa_dtype;
 
 typedef enum fa_status {
@@ -631,6 +632,80 @@ typedef struct fa_rope_store_params {
 
 int    fa_rope_store(const fa_rope_store_params* s, void* stream);
 size_t fa_rope_store_params_size(void);
+
+/*
+ * fa_qk_norm_rope_store - fa_rope_store with a per-head RMSNorm of q and k in front of the rotation, still one launch (additive,
+ * like the blocks above: fa_params and FA_ABI_VERSION are unchanged).  The prologue of a serving step for models with QK-norm
+ * (Qwen3, Gemma 3, OLMo 2): norm over head_dim with a learned [head_dim] weight, rotation at per-token positions, K / V store.
+ *
+ * The block is fa_rope_store_params field for field (same order, same meaning, same rules) followed by the norm's fields.  For
+ * every row r and every head h of q (weight q_weight) and of k (weight k_weight):
+ *     ss   = sum_d x[r,h,d]^2                                         fp32
+ *     rstd = 1 / sqrt(ss / head_dim + eps)                            fp32
+ *     y[d] = round_to_dtype((x[d] * rstd) * (weight_offset + w[d]))   fp32 products, ONE rounding to `dtype`
+ * and that 16-bit y is what fa_rope_store's rotation, write-back and cache store then see: the call leaves the bits of "norm-only
+ * call, then fa_rope_store".  The sum has a fixed order (csrc/fa_rmsnorm.h): a head's bits do not depend on what else is in the
+ * batch.  A row whose position is outside [0, seqlen_ro) is normalised and left unrotated; a row whose slot is outside the cache
+ * is normalised and rotated, only its cache write is skipped.  V is neither normalised nor rotated.
+ * q_weight, k_weight: device [head_dim] of `weight_dtype` (FA_FP16 / FA_BF16 - then it must equal `dtype` - or FA_FP32),
+ * contiguous, 16-byte aligned.  Either may be NULL: that tensor is not normalised, only rotated; with both NULL the call leaves
+ * fa_rope_store's bits.  In place (q_out == q, k_out == k) a normalised tensor is rewritten in every column, a tensor without a
+ * weight as in fa_rope_store.  weight_offset: Gemma's (1 + w) is 1.0.
+ * seqlen_ro == 0 is the form without rotation: rotary_dim, rotary_interleaved, positions, rotary_cos and rotary_sin are ignored
+ * (and may be 0 / NULL) - norm only without caches, norm + store with them.
+ * One kernel launch on `stream`: no LDS, no atomics, no workspace, no host synchronisation, bitwise repeatable, capturable in a
+ * graph.  A head is owned by adjacent lanes of one wave, 8 columns each; the row sum and the GPT-NeoX partner piece travel between
+ * lanes, so in place a lane only ever loads its own columns, and it loads them before its first store.  16-byte loads and
+ * stores, 8-byte stores to fp8 caches.
+ * FA_ERR_INVALID_ARGUMENT before any launch: everything fa_rope_store lists (a NULL positions / rotary_cos / rotary_sin and a bad
+ * rotary_dim only where seqlen_ro > 0); a weight_dtype other than `dtype` or FA_FP32 where a weight is given; a weight that is not
+ * 16-byte aligned; a negative or non-finite eps; a non-finite weight_offset; an out-of-place q_out or k_out that overlaps a
+ * weight.  total_rows == 0 or nheads_q == nheads_k == 0 (a NULL q counts as no q heads): FA_OK without a launch.
+ */
+typedef struct fa_qk_norm_rope_store_params {
+    size_t         struct_size;      /* sizeof(fa_qk_norm_rope_store_params) as the caller compiled it */
+    const void*    q;                /* from here to v_descale: fa_rope_store_params */
+    const void*    k;
+    const void*    v;
+    int64_t        q_row_stride, q_head_stride;
+    int64_t        k_row_stride, k_head_stride;
+    int64_t        v_row_stride, v_head_stride;
+    void*          q_out;
+    void*          k_out;
+    int64_t        qo_row_stride, qo_head_stride;
+    int64_t        ko_row_stride, ko_head_stride;
+    const int64_t* positions;        /* may be NULL where seqlen_ro == 0 */
+    const void*    rotary_cos;       /* may be NULL where seqlen_ro == 0 */
+    const void*    rotary_sin;
+    int32_t        rotary_dim;
+    int32_t        seqlen_ro;        /* 0: no rotation */
+    int32_t        rotary_interleaved;
+    int32_t        total_rows;
+    int32_t        nheads_q;
+    int32_t        nheads_k;
+    int32_t        head_dim;
+    int32_t        dtype;
+    int32_t        cache_dtype;
+    int32_t        reserved;         /* 0 */
+    void*          k_cache;
+    void*          v_cache;
+    int64_t        kc_batch_stride, kc_row_stride, kc_head_stride;
+    int64_t        vc_batch_stride, vc_row_stride, vc_head_stride;
+    int32_t        num_blocks;
+    int32_t        page_block_size;
+    const int64_t* slot_mapping;
+    float          k_descale;
+    float          v_descale;
+    const void*    q_weight;         /* device [head_dim] of `weight_dtype`, 16-byte aligned; NULL: q is not normalised */
+    const void*    k_weight;         /* NULL: k is not normalised */
+    int32_t        weight_dtype;     /* `dtype`, or FA_FP32; read where a weight is given */
+    float          eps;              /* >= 0, finite */
+    float          weight_offset;    /* y = x rstd (weight_offset + w) */
+    int32_t        reserved1;        /* 0 */
+} fa_qk_norm_rope_store_params;
+
+int    fa_qk_norm_rope_store(const fa_qk_norm_rope_store_params* s, void* stream);
+size_t fa_qk_norm_rope_store_params_size(void);
 
 /*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
