@@ -37,6 +37,8 @@ void launch_kv_store(const fa_kv_store_params& s, hipStream_t stream);      // f
 void launch_kv_gather(const fa_kv_gather_params& s, hipStream_t stream);    // fa_kv_gather.hip: ragged K / V rows out of a KV cache
 void launch_rope_store(const fa_rope_store_params& s, hipStream_t stream);  // fa_rope_store.hip: RoPE at per-token positions + K / V store
 void launch_qk_norm_rope_store(const fa_qk_norm_rope_store_params& s, hipStream_t stream);   // fa_qk_norm_rope_store.hip: QK RMSNorm in front of that
+void launch_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params& s, hipStream_t stream);       // fa_qk_norm_rope_bwd.hip: its backward (dx, dw)
+size_t qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params& s);                // the dw partial rows of its launch plan
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -206,6 +208,7 @@ size_t fa_kv_store_params_size(void) { return sizeof(fa_kv_store_params); }
 size_t fa_kv_gather_params_size(void) { return sizeof(fa_kv_gather_params); }
 size_t fa_rope_store_params_size(void) { return sizeof(fa_rope_store_params); }
 size_t fa_qk_norm_rope_store_params_size(void) { return sizeof(fa_qk_norm_rope_store_params); }
+size_t fa_qk_norm_rope_bwd_params_size(void) { return sizeof(fa_qk_norm_rope_bwd_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -982,6 +985,143 @@ int fa_qk_norm_rope_store(const fa_qk_norm_rope_store_params* sp, void* stream) 
     s.struct_size = sizeof(s);
     fa::launch_qk_norm_rope_store(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_qk_norm_rope_store launch");
+}
+
+}  // extern "C"
+
+// A [rows, heads, head_dim] view for fa_qk_norm_rope_bwd's overlap rules (bytes; rows, heads, head_dim > 0, strides >= 0)
+struct QnbView { const char* name; uint64_t at, row_stride, row_bytes, bytes; };
+static QnbView qnb_view(const char* name, const void* p, int64_t rows, int64_t rs, int64_t heads, int64_t hs, int64_t d) {
+    QnbView v = {name, (uint64_t)reinterpret_cast<uintptr_t>(p), (uint64_t)rs * 2, 0, 0};
+    if (p && rows > 0 && heads > 0 && d > 0) {
+        v.row_bytes = (uint64_t)((heads - 1) * hs + d) * 2;
+        v.bytes = (uint64_t)(rows - 1) * v.row_stride + v.row_bytes;
+    }
+    return v;
+}
+// no common element: disjoint address ranges, or the heads of one packed buffer - the same row stride, and within a row the
+// one view ends before the other begins
+static bool qnb_disjoint(const QnbView& a, const QnbView& b) {
+    if (!a.bytes || !b.bytes || a.at >= b.at + b.bytes || b.at >= a.at + a.bytes) return true;
+    const QnbView& lo = a.at <= b.at ? a : b;
+    const QnbView& hi = a.at <= b.at ? b : a;
+    const uint64_t delta = hi.at - lo.at;
+    return a.row_stride == b.row_stride && delta < lo.row_stride && lo.row_bytes <= delta && delta + hi.row_bytes <= lo.row_stride;
+}
+
+// fa_qk_norm_rope_bwd's argument rules (the forward's, rope_store_check above, where the two ops share a field); normalises the
+// block (no rotation: the pointers and rotary_dim cleared; no q: nheads_q = 0).  query: the workspace itself is not looked at
+static int qk_norm_rope_bwd_check(fa_qk_norm_rope_bwd_params& s, bool query) {
+    const char* op = "qk_norm_rope_bwd";
+    FA_CHECK(s.k && s.dk_out, "%s: k and dk_out must not be NULL", op);
+    FA_CHECK(!s.q || s.dq_out, "%s: q needs dq_out (a NULL q: no q heads)", op);
+    FA_CHECK(!s.dq || s.q, "%s: dq needs q", op);
+    FA_CHECK(!s.dq_weight || s.q_weight, "%s: dq_weight needs q_weight", op);
+    FA_CHECK(!s.dk_weight || s.k_weight, "%s: dk_weight needs k_weight", op);
+    FA_CHECK(s.reserved == 0 && s.reserved1[0] == 0 && s.reserved1[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    if (s.seqlen_ro == 0) {
+        s.positions = nullptr; s.rotary_cos = s.rotary_sin = nullptr; s.rotary_dim = 0;
+    } else {
+        FA_CHECK(s.seqlen_ro < 0 || (s.positions && s.rotary_cos && s.rotary_sin),                 // (< 0: rejected with the sizes below)
+                 "%s: positions, rotary_cos and rotary_sin may be NULL only where seqlen_ro == 0", op);
+    }
+    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "%s: q / k dtype must be fp16 or bf16", op);
+    if (s.q_weight || s.k_weight)
+        FA_CHECK(s.weight_dtype == FA_FP32 || s.weight_dtype == s.dtype, "%s: weight_dtype must be the q / k dtype or fp32", op);
+    FA_CHECK(s.total_rows >= 0 && s.nheads_q >= 0 && s.nheads_k >= 0 && s.head_dim >= 0 && s.seqlen_ro >= 0, "%s sizes must be non-negative", op);
+    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "%s head_dim must be a multiple of 8 and <= 256, got %d", op, s.head_dim);
+    if (s.seqlen_ro > 0) FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "%s: rotary_dim must be positive and divisible by 16, got %d", op, s.rotary_dim);
+    FA_CHECK(s.rotary_dim <= s.head_dim, "%s: rotary_dim must be <= head_dim (%d > %d)", op, s.rotary_dim, s.head_dim);
+    FA_CHECK(s.dqo_row_stride >= 0 && s.dqo_head_stride >= 0 && s.dko_row_stride >= 0 && s.dko_head_stride >= 0 && s.q_row_stride >= 0 &&
+             s.q_head_stride >= 0 && s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.dq_row_stride >= 0 && s.dq_head_stride >= 0 &&
+             s.dk_row_stride >= 0 && s.dk_head_stride >= 0, "%s strides must be non-negative", op);
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.dq_out) | reinterpret_cast<uintptr_t>(s.dk_out) | reinterpret_cast<uintptr_t>(s.q) |
+               reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.dq) | reinterpret_cast<uintptr_t>(s.dk)) & 15) == 0 &&
+             ((s.dqo_row_stride | s.dqo_head_stride | s.dko_row_stride | s.dko_head_stride | s.q_row_stride | s.q_head_stride |
+               s.k_row_stride | s.k_head_stride | s.dq_row_stride | s.dq_head_stride | s.dk_row_stride | s.dk_head_stride) & 7) == 0,
+             "%s: dq_out / dk_out / q / k / dq / dk base addresses and strides must be multiples of 16 bytes", op);
+    FA_CHECK(reinterpret_cast<uintptr_t>(s.positions) % 8 == 0, "%s: positions must be an 8-byte aligned int64 array", op);
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.rotary_cos) | reinterpret_cast<uintptr_t>(s.rotary_sin)) & 15) == 0,
+             "%s: rotary_cos / rotary_sin must be 16-byte aligned", op);
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.q_weight) | reinterpret_cast<uintptr_t>(s.k_weight) | reinterpret_cast<uintptr_t>(s.dq_weight) |
+               reinterpret_cast<uintptr_t>(s.dk_weight)) & 15) == 0, "%s: q_weight / k_weight / dq_weight / dk_weight must be 16-byte aligned", op);
+    FA_CHECK(s.eps >= 0.f && s.eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
+    FA_CHECK(s.weight_offset >= -3.402823466e38f && s.weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
+    if ((int64_t)(s.nheads_q + (int64_t)s.nheads_k) * s.head_dim > ((int64_t)1 << 24))
+        return fail(FA_ERR_UNSUPPORTED, "%s: (nheads_q + nheads_k) x head_dim is too large for one launch", op);
+    if (!s.q) { s.nheads_q = 0; s.dq_out = nullptr; }
+    const bool q_inplace = s.dq && s.dq == s.dq_out, k_inplace = s.dk && s.dk == s.dk_out;
+    if (q_inplace)
+        FA_CHECK(s.dq_row_stride == s.dqo_row_stride && s.dq_head_stride == s.dqo_head_stride,
+                 "%s: dq shares dq_out's base address but not its strides (in place needs both equal)", op);
+    if (k_inplace)
+        FA_CHECK(s.dk_row_stride == s.dko_row_stride && s.dk_head_stride == s.dko_head_stride,
+                 "%s: dk shares dk_out's base address but not its strides (in place needs both equal)", op);
+    const size_t need = fa::qk_norm_rope_bwd_workspace_bytes(s);
+    if (!query && need) {
+        FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_qk_norm_rope_bwd_workspace_bytes() reports %zu",
+                 op, s.workspace ? s.workspace_bytes : (size_t)0, need);
+        FA_CHECK(reinterpret_cast<uintptr_t>(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+    }
+    if (!query) {                                         // (the query is about sizes: it does not look at where the tensors lie)
+        // an output must share no element with anything that is read (the exact in-place aliasing apart: that output is exempt, the
+        // caller guarantees that its view shares no element with the others), with another output or with the workspace
+        const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
+        const uint64_t wbytes = (uint64_t)D * (s.weight_dtype == FA_FP32 ? 4 : 2);
+        auto flat = [](const char* name, const void* p, uint64_t bytes) {
+            return QnbView{name, (uint64_t)reinterpret_cast<uintptr_t>(p), 0, p ? bytes : 0, p ? bytes : 0};
+        };
+        const QnbView in[] = {
+            qnb_view("dq_out", s.dq_out, T, s.dqo_row_stride, Hq, s.dqo_head_stride, D),
+            qnb_view("dk_out", s.dk_out, T, s.dko_row_stride, Hk, s.dko_head_stride, D),
+            qnb_view("q", s.q, T, s.q_row_stride, Hq, s.q_head_stride, D),
+            qnb_view("k", s.k, T, s.k_row_stride, Hk, s.k_head_stride, D),
+            flat("positions", s.positions, (uint64_t)T * 8),
+            flat("rotary_cos", s.rotary_cos, (uint64_t)s.seqlen_ro * half * 2),
+            flat("rotary_sin", s.rotary_sin, (uint64_t)s.seqlen_ro * half * 2),
+            flat("q_weight", s.q_weight, wbytes),
+            flat("k_weight", s.k_weight, wbytes),
+        };
+        const QnbView out[] = {
+            qnb_view("dq", q_inplace ? nullptr : s.dq, T, s.dq_row_stride, Hq, s.dq_head_stride, D),
+            qnb_view("dk", k_inplace ? nullptr : s.dk, T, s.dk_row_stride, Hk, s.dk_head_stride, D),
+            flat("dq_weight", s.dq_weight, wbytes),
+            flat("dk_weight", s.dk_weight, wbytes),
+            flat("workspace", need ? s.workspace : nullptr, need),
+        };
+        const int n_out = (int)(sizeof(out) / sizeof(out[0]));
+        for (int o = 0; o < n_out; ++o) {
+            for (int i = 0; i < (int)(sizeof(in) / sizeof(in[0])); ++i)
+                FA_CHECK(qnb_disjoint(out[o], in[i]), "%s: %s overlaps %s%s", op, out[o].name, in[i].name,
+                         o < 2 && i < 2 ? " without being in place (in place: the gradient's base address and strides)" : "");
+            for (int p = o + 1; p < n_out; ++p)
+                FA_CHECK(qnb_disjoint(out[o], out[p]), "%s: %s overlaps %s", op, out[o].name, out[p].name);
+        }
+    }
+    return FA_OK;
+}
+
+extern "C" {
+
+size_t fa_qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_qk_norm_rope_bwd_params)) return 0;
+    fa_qk_norm_rope_bwd_params s = *sp;
+    if (qk_norm_rope_bwd_check(s, true) != FA_OK) return 0;
+    return fa::qk_norm_rope_bwd_workspace_bytes(s);
+}
+
+int fa_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params* sp, void* stream) {
+    FA_CHECK(sp, "fa_qk_norm_rope_bwd_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_qk_norm_rope_bwd_params),
+             "fa_qk_norm_rope_bwd_params::struct_size %zu is smaller than this library's %zu", sp->struct_size, sizeof(fa_qk_norm_rope_bwd_params));
+    fa_qk_norm_rope_bwd_params s = *sp;
+    const int rc = qk_norm_rope_bwd_check(s, false);
+    if (rc != FA_OK) return rc;
+    const bool empty = s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0);
+    if (empty && !s.dq_weight && !s.dk_weight) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_qk_norm_rope_bwd(s, static_cast<hipStream_t>(stream));      // (an empty problem: a wanted dw is set to zeros, no kernel)
+    return check_hip("fa_qk_norm_rope_bwd launch");
 }
 
 }  // extern "C"

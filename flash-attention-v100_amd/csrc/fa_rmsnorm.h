@@ -64,4 +64,13 @@ __device__ __forceinline__ void rms_gains(const void* w, int d, bool w_fp32, flo
     }
 }
 
+// the lane's part of sum_d a[d] b[d] (the backward, fa_qk_norm_rope_bwd.hip): its 8 columns in column order, as rms_piece_ss -
+// s = a0 * b0, then s = fmaf(ai, bi, s) for i = 1 .. 7; rms_group_sum adds the lanes
+__device__ __forceinline__ float rms_piece_dot(const float (&a)[8], const float (&b)[8]) {
+    float s = a[0] * b[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) s = fmaf(a[i], b[i], s);
+    return s;
+}
+
 }  // namespace fa

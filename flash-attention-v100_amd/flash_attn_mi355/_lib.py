@@ -235,6 +235,30 @@ class FaQkNormRopeStoreParams(ctypes.Structure):
     ]
 
 
+class FaQkNormRopeBwdParams(ctypes.Structure):
+    """Mirror of `struct fa_qk_norm_rope_bwd_params` (include/fa_mi355.h): fa_qk_norm_rope_bwd, the backward of the norm + rotation
+    of fa_qk_norm_rope_store - dq / dk from the gradients of q_out / k_out and the saved pre-norm q / k, and the two weight
+    gradients.  struct_size must be set to sizeof(FaQkNormRopeBwdParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dq_out", _ptr), ("dk_out", _ptr),                   # the incoming gradients
+        ("dqo_row_stride", _i64), ("dqo_head_stride", _i64), ("dko_row_stride", _i64), ("dko_head_stride", _i64),
+        ("q", _ptr), ("k", _ptr),                             # the saved pre-norm inputs; q NULL: no q heads
+        ("q_row_stride", _i64), ("q_head_stride", _i64), ("k_row_stride", _i64), ("k_head_stride", _i64),
+        ("dq", _ptr), ("dk", _ptr),                           # outputs; may equal dq_out / dk_out (in place); NULL: skipped
+        ("dq_row_stride", _i64), ("dq_head_stride", _i64), ("dk_row_stride", _i64), ("dk_head_stride", _i64),
+        ("positions", _ptr),             # int64 [total_rows] on the device
+        ("rotary_cos", _ptr), ("rotary_sin", _ptr),
+        ("rotary_dim", _i32), ("seqlen_ro", _i32), ("rotary_interleaved", _i32),
+        ("total_rows", _i32), ("nheads_q", _i32), ("nheads_k", _i32), ("head_dim", _i32), ("dtype", _i32),
+        ("q_weight", _ptr), ("k_weight", _ptr),
+        ("weight_dtype", _i32), ("eps", _f32), ("weight_offset", _f32), ("reserved", _i32),
+        ("dq_weight", _ptr), ("dk_weight", _ptr),             # [head_dim] of weight_dtype; NULL: skipped
+        ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("reserved1", _i64 * 2),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -243,7 +267,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_gather_rows", "fa_scatter_rows", "fa_fwd_kvcache_tree", "fa_tree_params_size",
            "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size",
            "fa_kv_store", "fa_kv_store_params_size", "fa_kv_gather", "fa_kv_gather_params_size",
-           "fa_rope_store", "fa_rope_store_params_size", "fa_qk_norm_rope_store", "fa_qk_norm_rope_store_params_size"] + EXT_OPS
+           "fa_rope_store", "fa_rope_store_params_size", "fa_qk_norm_rope_store", "fa_qk_norm_rope_store_params_size",
+           "fa_qk_norm_rope_bwd", "fa_qk_norm_rope_bwd_workspace_bytes", "fa_qk_norm_rope_bwd_params_size"] + EXT_OPS
 
 
 def _load():
@@ -294,6 +319,11 @@ def _load():
     lib.fa_qk_norm_rope_store.restype = ctypes.c_int
     lib.fa_qk_norm_rope_store.argtypes = [ctypes.POINTER(FaQkNormRopeStoreParams), ctypes.c_void_p]
     lib.fa_qk_norm_rope_store_params_size.restype = ctypes.c_size_t
+    lib.fa_qk_norm_rope_bwd.restype = ctypes.c_int
+    lib.fa_qk_norm_rope_bwd.argtypes = [ctypes.POINTER(FaQkNormRopeBwdParams), ctypes.c_void_p]
+    lib.fa_qk_norm_rope_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.fa_qk_norm_rope_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaQkNormRopeBwdParams)]
+    lib.fa_qk_norm_rope_bwd_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -325,6 +355,9 @@ def _load():
     if lib.fa_qk_norm_rope_store_params_size() != ctypes.sizeof(FaQkNormRopeStoreParams):
         raise ImportError(f"fa_qk_norm_rope_store_params size mismatch: library {lib.fa_qk_norm_rope_store_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaQkNormRopeStoreParams)}")
+    if lib.fa_qk_norm_rope_bwd_params_size() != ctypes.sizeof(FaQkNormRopeBwdParams):
+        raise ImportError(f"fa_qk_norm_rope_bwd_params size mismatch: library {lib.fa_qk_norm_rope_bwd_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaQkNormRopeBwdParams)}")
     return lib
 
 
@@ -399,6 +432,18 @@ def call_qk_norm_rope_store(params, stream):
     rc = lib.fa_qk_norm_rope_store(ctypes.byref(params), ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"fa_qk_norm_rope_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_qk_norm_rope_bwd(params, stream):
+    """fa_qk_norm_rope_bwd"""
+    rc = lib.fa_qk_norm_rope_bwd(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_qk_norm_rope_bwd failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def qk_norm_rope_bwd_workspace_bytes(params):
+    """fa_qk_norm_rope_bwd_workspace_bytes: needs no device"""
+    return int(lib.fa_qk_norm_rope_bwd_workspace_bytes(ctypes.byref(params)))
 
 
 def call_rows(name, *args):

@@ -4,7 +4,8 @@ LSE merge of attention states over disjoint key sets, fa_merge_states; `rotary` 
 fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_kv_store; `kv_gather` / `kv_move`: ragged K / V
 rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache; `rope_store_`: q / k rotated at per-token positions
 and K / V stored by slot in one launch, fa_rope_store; `qk_norm_rope_store_`: the same behind a per-head RMSNorm of q and k,
-fa_qk_norm_rope_store - registered, but not listed in `__all__`).
+fa_qk_norm_rope_store; `qk_norm_rope` / `qk_norm_rope_bwd`: that norm + rotation out of place with an autograd formula, and its
+backward, fa_qk_norm_rope_bwd - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -525,6 +526,74 @@ def qk_norm_rope_store_(q: Tensor, k: Tensor, v: Tensor, positions: Tensor, rota
 def _(q, k, v, positions, rotary_cos, rotary_sin, k_cache, v_cache, slot_mapping, q_weight, k_weight, eps, weight_offset, interleaved,
       k_descale, v_descale):
     return None
+
+
+# ------------------------------------------------------------------------------------------
+# QK RMSNorm + RoPE for training: the forward out of place on fa_qk_norm_rope_store's kernel, the backward on fa_qk_norm_rope_bwd
+# (flash_attn_mi355.qk_norm; csrc/fa_qk_norm_rope_bwd.hip).  Reached as torch.ops.flash_attn_mi355.qk_norm_rope / .qk_norm_rope_bwd;
+# not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::qk_norm_rope", mutates_args=(), device_types="cuda")
+def qk_norm_rope(q: Optional[Tensor], k: Tensor, positions: Optional[Tensor], rotary_cos: Optional[Tensor],
+                 rotary_sin: Optional[Tensor], q_weight: Optional[Tensor], k_weight: Optional[Tensor], eps: float,
+                 weight_offset: float, interleaved: bool) -> Tuple[Tensor, Tensor]:
+    """qk_norm.qk_norm_rope_and_store_kv(..., inplace=False) without caches: (q_out, k_out), fresh contiguous tensors; q None:
+    q_out is an empty (0,) tensor.  Differentiable in q, k, q_weight and k_weight (qk_norm_rope_bwd)."""
+    q_out, k_out = _qk_norm.qk_norm_rope_and_store_kv(q, k, None, positions, rotary_cos, rotary_sin, q_weight=q_weight,
+                                                      k_weight=k_weight, eps=eps, weight_offset=weight_offset,
+                                                      interleaved=interleaved, inplace=False)
+    return (k.new_empty((0,)) if q_out is None else q_out), k_out
+
+
+@qk_norm_rope.register_fake
+def _(q, k, positions, rotary_cos, rotary_sin, q_weight, k_weight, eps, weight_offset, interleaved):
+    return (k.new_empty((0,)) if q is None else q.new_empty(q.shape)), k.new_empty(k.shape)
+
+
+@torch.library.custom_op(f"{_NS}::qk_norm_rope_bwd", mutates_args=(), device_types="cuda")
+def qk_norm_rope_bwd(dq_out: Optional[Tensor], dk_out: Tensor, q: Optional[Tensor], k: Tensor, positions: Optional[Tensor],
+                     rotary_cos: Optional[Tensor], rotary_sin: Optional[Tensor], q_weight: Optional[Tensor],
+                     k_weight: Optional[Tensor], eps: float, weight_offset: float, interleaved: bool, need_dq: bool,
+                     need_dk: bool, need_dq_weight: bool, need_dk_weight: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """qk_norm.qk_norm_rope_backward out of place: (dq, dk, dq_weight, dk_weight), fresh tensors; an output that is not needed (or
+    has no tensor: q None, a weight None) is an empty (0,) tensor and is not computed."""
+    dq, dk, dqw, dkw = _qk_norm.qk_norm_rope_backward(dq_out, dk_out, q, k, positions, rotary_cos, rotary_sin, q_weight, k_weight,
+                                                      eps, weight_offset, interleaved, need_dq=need_dq, need_dk=need_dk,
+                                                      need_dw=need_dq_weight or need_dk_weight)
+    none = lambda: k.new_empty((0,))                            # noqa: E731
+    return (none() if dq is None else dq, none() if dk is None else dk,
+            none() if (dqw is None or not need_dq_weight) else dqw, none() if (dkw is None or not need_dk_weight) else dkw)
+
+
+@qk_norm_rope_bwd.register_fake
+def _(dq_out, dk_out, q, k, positions, rotary_cos, rotary_sin, q_weight, k_weight, eps, weight_offset, interleaved, need_dq,
+      need_dk, need_dq_weight, need_dk_weight):
+    none = lambda: k.new_empty((0,))                            # noqa: E731
+    return (q.new_empty(q.shape) if (need_dq and q is not None) else none(),
+            k.new_empty(k.shape) if need_dk else none(),
+            q_weight.new_empty(q_weight.shape) if (need_dq_weight and q_weight is not None) else none(),
+            k_weight.new_empty(k_weight.shape) if (need_dk_weight and k_weight is not None) else none())
+
+
+def _qk_norm_rope_setup(ctx, inputs, output):
+    (q, k, positions, rotary_cos, rotary_sin, q_weight, k_weight, eps, weight_offset, interleaved) = inputs
+    ctx.save_for_backward(q, k, positions, rotary_cos, rotary_sin, q_weight, k_weight)
+    ctx.args = (eps, weight_offset, interleaved)
+
+
+def _qk_norm_rope_backward(ctx, dq_out, dk_out):
+    q, k, positions, rotary_cos, rotary_sin, q_weight, k_weight = ctx.saved_tensors
+    eps, weight_offset, interleaved = ctx.args
+    need = ctx.needs_input_grad                 # (q, k, positions, cos, sin, q_weight, k_weight, ...)
+    dq, dk, dqw, dkw = qk_norm_rope_bwd(None if q is None else dq_out, dk_out, q, k, positions, rotary_cos, rotary_sin, q_weight,
+                                        k_weight, eps, weight_offset, interleaved, need[0] and q is not None, need[1],
+                                        need[5] and q_weight is not None, need[6] and k_weight is not None)
+    pick = lambda g, on: g if on else None                      # noqa: E731
+    return (pick(dq, need[0] and q is not None), pick(dk, need[1]), None, None, None,
+            pick(dqw, need[5] and q_weight is not None), pick(dkw, need[6] and k_weight is not None), None, None, None)
+
+
+qk_norm_rope.register_autograd(_qk_norm_rope_backward, setup_context=_qk_norm_rope_setup)
 
 
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",

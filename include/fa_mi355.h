@@ -708,6 +708,93 @@ int    fa_qk_norm_rope_store(const fa_qk_norm_rope_store_params* s, void* stream
 size_t fa_qk_norm_rope_store_params_size(void);
 
 /*
+ * fa_qk_norm_rope_bwd - the backward of fa_qk_norm_rope_store's norm + rotation (additive: fa_params and FA_ABI_VERSION are
+ * unchanged).  The forward computes, for every row r and every head of q (weight q_weight) and of k (k_weight),
+ *     y = round_to_dtype(x * rstd * g),  g = weight_offset + w,  rstd = 1 / sqrt(mean_d(x^2) + eps),   z = rope(y) at positions[r]
+ * (z = y where the position is outside [0, seqlen_ro), in columns >= rotary_dim, or where seqlen_ro == 0).  From dz - dq_out /
+ * dk_out, the gradients of q_out / k_out - and the saved PRE-NORM inputs q / k this op computes, with BOTH 16-bit roundings of the
+ * forward treated as the identity (straight-through) and all arithmetic in fp32:
+ *     dy = conj_rope(dz)        fa_rotary's pair rule with the sign of sin flipped exactly, NOT rounded; dy = dz where the forward
+ *                               left the element unrotated
+ *   a tensor WITHOUT a weight:  dx = round_to_dtype(dy)       - the bits of fa_rotary with `conjugate` at the same positions
+ *   a tensor WITH a weight:     xhat = x * rstd;  a = dy * g;  c = (sum_d a[d] xhat[d]) / head_dim
+ *                               dx    = round_to_dtype(rstd * (a - xhat * c))      (a - xhat c is one fused multiply-add)
+ *                               dw[d] = sum over ALL rows and all heads of that tensor of dy[d] * xhat[d]
+ * rstd is recomputed from x with the forward's fixed-order sum (csrc/fa_rmsnorm.h): it has the forward's bits, the forward saves
+ * nothing.  The sum for c has the same fixed order, so a head's dx bits do not depend on what else is in the batch.  Every row
+ * enters dw, rows whose position is outside the tables included: there is no notion of a padding row.  eps == 0 with an all-zero
+ * head gives what the arithmetic gives (non-finite values), as in the forward.
+ * dq_out, dk_out, q, k, dq, dk: [total_rows, nheads, head_dim] of `dtype`, each with its own row and head stride (elements, the
+ * last dimension contiguous) - the heads of a packed [T, Hq + 2 Hk, D] gradient are such views.  dq == dq_out and dk == dk_out
+ * (the same base address AND strides) are in place and the only legal overlap.  positions, rotary_cos, rotary_sin, rotary_dim,
+ * seqlen_ro (0: no rotation; the pointers may then be NULL), rotary_interleaved, q_weight, k_weight, weight_dtype, eps and
+ * weight_offset are fa_qk_norm_rope_store's.  dq_weight, dk_weight: device [head_dim] of `weight_dtype`, 16-byte aligned, written
+ * ONCE with one rounding of the final fp32 sum.
+ * Any of the four outputs dq, dk, dq_weight, dk_weight may be NULL and is then skipped; a tensor of which nothing is wanted is not
+ * read.  A NULL q counts as no q heads (dq_out, dq may then be NULL as well).  k and dk_out are required.
+ * dw is deterministic, no atomics: a lane keeps its partial sums in registers over the rows it walks, a workgroup adds its lanes
+ * through LDS in a fixed order and writes one fp32 row [2][head_dim] into `workspace`, and a second small kernel on the same
+ * stream adds the rows in a fixed order.  The grid and with it the order depend on this block alone, never on the device:
+ * fa_qk_norm_rope_bwd_workspace_bytes() needs no device and the bits are the same on every card.  The workspace is 0 bytes where
+ * neither dq_weight nor dk_weight is given (then: one launch, no LDS); otherwise it must be 16-byte aligned and hold the reported
+ * size (at most 2 MB).
+ * No host synchronisation, bitwise repeatable, capturable in a graph.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL k or dk_out; q without dq_out; dq without q; dq_weight
+ * without q_weight or dk_weight without k_weight; non-zero reserved fields; NULL positions / rotary_cos / rotary_sin or a
+ * rotary_dim that is not a positive multiple of 16 <= head_dim where seqlen_ro > 0; a dtype other than FA_FP16 / FA_BF16; a
+ * weight_dtype other than `dtype` or FA_FP32 where a weight is given; head_dim not a multiple of 8 or above 256; negative sizes
+ * or strides; tensor bases or strides, weights, weight gradients, tables or the workspace not 16-byte aligned; positions not
+ * 8-byte aligned; a negative or non-finite eps; a non-finite weight_offset; a dq / dk that shares its gradient's base address but
+ * not its strides; an output (dq, dk, dq_weight, dk_weight) whose address range overlaps an input other than by that exact
+ * aliasing, another output or the workspace; a workspace that overlaps an input; a workspace smaller than reported.
+ * total_rows == 0, or no heads (nheads_k == 0 and no q heads): FA_OK without a kernel launch; a dq_weight / dk_weight that was
+ * asked for is then set to zeros on `stream`.
+ */
+typedef struct fa_qk_norm_rope_bwd_params {
+    size_t         struct_size;      /* sizeof(fa_qk_norm_rope_bwd_params) as the caller compiled it */
+    const void*    dq_out;           /* [total_rows, nheads_q, head_dim] of `dtype`: the gradient of q_out; NULL with a NULL q */
+    const void*    dk_out;           /* [total_rows, nheads_k, head_dim]: the gradient of k_out */
+    int64_t        dqo_row_stride, dqo_head_stride;    /* elements, the last dimension contiguous */
+    int64_t        dko_row_stride, dko_head_stride;
+    const void*    q;                /* the forward's pre-norm q, or NULL: no q heads */
+    const void*    k;                /* the forward's pre-norm k */
+    int64_t        q_row_stride, q_head_stride;
+    int64_t        k_row_stride, k_head_stride;
+    void*          dq;               /* q's shape, own strides; may equal dq_out; NULL: skipped */
+    void*          dk;               /* k's shape, own strides; may equal dk_out; NULL: skipped */
+    int64_t        dq_row_stride, dq_head_stride;
+    int64_t        dk_row_stride, dk_head_stride;
+    const int64_t* positions;        /* device [total_rows], 8-byte aligned; may be NULL where seqlen_ro == 0 */
+    const void*    rotary_cos;       /* [seqlen_ro, rotary_dim / 2] of `dtype`, contiguous, 16-byte aligned */
+    const void*    rotary_sin;
+    int32_t        rotary_dim;       /* a multiple of 16, 0 < rotary_dim <= head_dim (read where seqlen_ro > 0) */
+    int32_t        seqlen_ro;        /* 0: no rotation */
+    int32_t        rotary_interleaved;
+    int32_t        total_rows;
+    int32_t        nheads_q;
+    int32_t        nheads_k;
+    int32_t        head_dim;         /* a multiple of 8, <= 256 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    const void*    q_weight;         /* device [head_dim] of `weight_dtype`, 16-byte aligned; NULL: q was not normalised */
+    const void*    k_weight;         /* NULL: k was not normalised */
+    int32_t        weight_dtype;     /* `dtype`, or FA_FP32; read where a weight is given */
+    float          eps;              /* >= 0, finite: the forward's */
+    float          weight_offset;    /* the forward's */
+    int32_t        reserved;         /* 0 */
+    void*          dq_weight;        /* device [head_dim] of `weight_dtype`, 16-byte aligned; NULL: skipped */
+    void*          dk_weight;
+    void*          workspace;        /* fa_qk_norm_rope_bwd_workspace_bytes() bytes, 16-byte aligned; may be NULL where that is 0 */
+    size_t         workspace_bytes;
+    int64_t        reserved1[2];     /* 0 */
+} fa_qk_norm_rope_bwd_params;
+
+int    fa_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params* s, void* stream);
+/* the workspace of that call; `workspace`, `workspace_bytes` and where the tensors lie are not looked at (the overlap rules are the
+ * call's); 0 for a block that the call rejects for any other reason */
+size_t fa_qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params* s);
+size_t fa_qk_norm_rope_bwd_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
