@@ -39,6 +39,9 @@ void launch_rope_store(const fa_rope_store_params& s, hipStream_t stream);  // f
 void launch_qk_norm_rope_store(const fa_qk_norm_rope_store_params& s, hipStream_t stream);   // fa_qk_norm_rope_store.hip: QK RMSNorm in front of that
 void launch_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params& s, hipStream_t stream);       // fa_qk_norm_rope_bwd.hip: its backward (dx, dw)
 size_t qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params& s);                // the dw partial rows of its launch plan
+void launch_add_norm(const fa_add_norm_params& s, hipStream_t stream);                       // fa_add_norm.hip: residual add + RMSNorm / LayerNorm
+void launch_add_norm_bwd(const fa_add_norm_bwd_params& s, hipStream_t stream);               // fa_add_norm_bwd.hip: its backward (dx, dres, dweight, dbias)
+size_t add_norm_bwd_workspace_bytes(const fa_add_norm_bwd_params& s);                        // the partial rows of its launch plan
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -209,6 +212,8 @@ size_t fa_kv_gather_params_size(void) { return sizeof(fa_kv_gather_params); }
 size_t fa_rope_store_params_size(void) { return sizeof(fa_rope_store_params); }
 size_t fa_qk_norm_rope_store_params_size(void) { return sizeof(fa_qk_norm_rope_store_params); }
 size_t fa_qk_norm_rope_bwd_params_size(void) { return sizeof(fa_qk_norm_rope_bwd_params); }
+size_t fa_add_norm_params_size(void) { return sizeof(fa_add_norm_params); }
+size_t fa_add_norm_bwd_params_size(void) { return sizeof(fa_add_norm_bwd_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1122,6 +1127,186 @@ int fa_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_qk_norm_rope_bwd(s, static_cast<hipStream_t>(stream));      // (an empty problem: a wanted dw is set to zeros, no kernel)
     return check_hip("fa_qk_norm_rope_bwd launch");
+}
+
+}  // extern "C"
+
+// A [rows, n] view for the overlap rules of fa_add_norm / fa_add_norm_bwd (bytes; a NULL pointer or no rows: empty)
+struct AnView { const char* name; uint64_t at, row_stride, row_bytes, bytes; };
+static AnView an_view(const char* name, const void* p, int64_t rows, int64_t rs, int64_t n, int esize) {
+    AnView v = {name, (uint64_t)reinterpret_cast<uintptr_t>(p), (uint64_t)rs * esize, 0, 0};
+    if (p && rows > 0 && n > 0) {
+        v.row_bytes = (uint64_t)n * esize;
+        v.bytes = (uint64_t)(rows - 1) * v.row_stride + v.row_bytes;
+    }
+    return v;
+}
+static AnView an_flat(const char* name, const void* p, uint64_t bytes) {
+    return AnView{name, (uint64_t)reinterpret_cast<uintptr_t>(p), 0, p ? bytes : 0, p ? bytes : 0};
+}
+// no common element: disjoint address ranges, or column ranges of one wider buffer - the same row stride, and within a row the one
+// view ends before the other begins
+static bool an_disjoint(const AnView& a, const AnView& b) {
+    if (!a.bytes || !b.bytes || a.at >= b.at + b.bytes || b.at >= a.at + a.bytes) return true;
+    const AnView& lo = a.at <= b.at ? a : b;
+    const AnView& hi = a.at <= b.at ? b : a;
+    const uint64_t delta = hi.at - lo.at;
+    return a.row_stride == b.row_stride && delta < lo.row_stride && lo.row_bytes <= delta && delta + hi.row_bytes <= lo.row_stride;
+}
+// every output against every input and against the later outputs; (ex_out[k], ex_in[k]), k < n_ex: the exact in-place pairs, exempt
+static int an_overlaps(const char* op, const AnView* out, int n_out, const AnView* in, int n_in, const int* ex_out, const int* ex_in,
+                       int n_ex) {
+    for (int o = 0; o < n_out; ++o) {
+        for (int i = 0; i < n_in; ++i) {
+            bool exempt = false;
+            for (int k = 0; k < n_ex; ++k) exempt = exempt || (ex_out[k] == o && ex_in[k] == i);
+            FA_CHECK(exempt || an_disjoint(out[o], in[i]), "%s: %s overlaps %s (in place needs the same base address, row stride and dtype)",
+                     op, out[o].name, in[i].name);
+        }
+        for (int p = o + 1; p < n_out; ++p) FA_CHECK(an_disjoint(out[o], out[p]), "%s: %s overlaps %s", op, out[o].name, out[p].name);
+    }
+    return FA_OK;
+}
+static bool an_is_io_or_fp32(int t, int dtype) { return t == dtype || t == FA_FP32; }
+static bool an_stride_ok(int64_t rs, int64_t rows, int n) { return rs >= 0 && rs % 8 == 0 && (rows <= 1 || rs >= n); }
+
+// what fa_add_norm and fa_add_norm_bwd share: dtype, n, rows, the weight, eps, weight_offset
+static int add_norm_common_check(const char* op, int dtype, int weight_dtype, int64_t rows, int n, const void* weight, float eps,
+                                 float weight_offset) {
+    FA_CHECK(dtype == FA_FP16 || dtype == FA_BF16, "%s: dtype must be fp16 or bf16", op);
+    FA_CHECK(an_is_io_or_fp32(weight_dtype, dtype), "%s: weight_dtype must be the io dtype or fp32", op);
+    FA_CHECK(weight, "%s: weight must not be NULL", op);
+    FA_CHECK(rows >= 0, "%s: rows must be non-negative", op);
+    FA_CHECK(n >= 8 && n <= 16384 && n % 8 == 0, "%s: n must be a multiple of 8 in [8, 16384], got %d", op, n);
+    FA_CHECK(eps >= 0.f && eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
+    FA_CHECK(weight_offset >= -3.402823466e38f && weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
+    return FA_OK;
+}
+
+// fa_add_norm's argument rules
+static int add_norm_check(const fa_add_norm_params& s) {
+    const char* op = "add_norm";
+    FA_CHECK(s.x && s.out, "%s: x and out must not be NULL", op);
+    FA_CHECK(!s.residual || s.residual_out, "%s: a residual needs residual_out", op);
+    FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    const int rc = add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset);
+    if (rc != FA_OK) return rc;
+    if (s.residual) FA_CHECK(an_is_io_or_fp32(s.residual_dtype, s.dtype), "%s: residual_dtype must be the io dtype or fp32", op);
+    if (s.residual_out) {
+        FA_CHECK(an_is_io_or_fp32(s.residual_out_dtype, s.dtype), "%s: residual_out_dtype must be the io dtype or fp32", op);
+        FA_CHECK(!s.residual || s.residual_dtype != FA_FP32 || s.residual_out_dtype == FA_FP32,
+                 "%s: an fp32 residual needs an fp32 residual_out", op);
+    }
+    FA_CHECK(an_stride_ok(s.x_row_stride, s.rows, s.n) && an_stride_ok(s.out_row_stride, s.rows, s.n) &&
+             (!s.residual || an_stride_ok(s.residual_row_stride, s.rows, s.n)) &&
+             (!s.residual_out || an_stride_ok(s.residual_out_row_stride, s.rows, s.n)),
+             "%s: row strides must be non-negative multiples of 8 elements and (rows > 1) at least n", op);
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.x) | reinterpret_cast<uintptr_t>(s.out) | reinterpret_cast<uintptr_t>(s.residual) |
+               reinterpret_cast<uintptr_t>(s.residual_out) | reinterpret_cast<uintptr_t>(s.weight) | reinterpret_cast<uintptr_t>(s.bias)) & 15) == 0,
+             "%s: x / residual / out / residual_out / weight / bias must be 16-byte aligned", op);
+    if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
+    const bool x_inplace = s.out == s.x, r_inplace = s.residual_out && s.residual_out == s.residual;
+    if (x_inplace) FA_CHECK(s.out_row_stride == s.x_row_stride, "%s: out shares x's base address but not its row stride (in place needs both equal)", op);
+    if (r_inplace)
+        FA_CHECK(s.residual_out_row_stride == s.residual_row_stride && s.residual_out_dtype == s.residual_dtype,
+                 "%s: residual_out shares residual's base address but not its row stride and dtype (in place needs all equal)", op);
+    const int rsz = s.residual_dtype == FA_FP32 ? 4 : 2, rosz = s.residual_out_dtype == FA_FP32 ? 4 : 2;
+    const uint64_t wbytes = (uint64_t)s.n * (s.weight_dtype == FA_FP32 ? 4 : 2);
+    const AnView in[] = {
+        an_view("x", s.x, s.rows, s.x_row_stride, s.n, 2),
+        an_view("residual", s.residual, s.rows, s.residual_row_stride, s.n, rsz),
+        an_flat("weight", s.weight, wbytes),
+        an_flat("bias", s.bias, wbytes),
+    };
+    const AnView out[] = {
+        an_view("out", s.out, s.rows, s.out_row_stride, s.n, 2),
+        an_view("residual_out", s.residual_out, s.rows, s.residual_out_row_stride, s.n, rosz),
+    };
+    int ex_out[2], ex_in[2], n_ex = 0;
+    if (x_inplace) { ex_out[n_ex] = 0; ex_in[n_ex++] = 0; }
+    if (r_inplace) { ex_out[n_ex] = 1; ex_in[n_ex++] = 1; }
+    return an_overlaps(op, out, 2, in, 4, ex_out, ex_in, n_ex);
+}
+
+// fa_add_norm_bwd's argument rules.  query: the workspace itself and where the tensors lie are not looked at
+static int add_norm_bwd_check(const fa_add_norm_bwd_params& s, bool query) {
+    const char* op = "add_norm_bwd";
+    FA_CHECK(s.dy && s.z, "%s: dy and z must not be NULL", op);
+    FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    const int rc = add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset);
+    if (rc != FA_OK) return rc;
+    FA_CHECK(an_is_io_or_fp32(s.z_dtype, s.dtype), "%s: z_dtype must be the io dtype or fp32", op);
+    if (s.dres) FA_CHECK(an_is_io_or_fp32(s.dres_dtype, s.dtype), "%s: dres_dtype must be the io dtype or fp32", op);
+    FA_CHECK(an_stride_ok(s.dy_row_stride, s.rows, s.n) && an_stride_ok(s.z_row_stride, s.rows, s.n) &&
+             (!s.dres_out || an_stride_ok(s.dres_out_row_stride, s.rows, s.n)) && (!s.dx || an_stride_ok(s.dx_row_stride, s.rows, s.n)) &&
+             (!s.dres || an_stride_ok(s.dres_row_stride, s.rows, s.n)),
+             "%s: row strides must be non-negative multiples of 8 elements and (rows > 1) at least n", op);
+    FA_CHECK(((reinterpret_cast<uintptr_t>(s.dy) | reinterpret_cast<uintptr_t>(s.z) | reinterpret_cast<uintptr_t>(s.dres_out) |
+               reinterpret_cast<uintptr_t>(s.dx) | reinterpret_cast<uintptr_t>(s.dres) | reinterpret_cast<uintptr_t>(s.weight) |
+               reinterpret_cast<uintptr_t>(s.dweight) | reinterpret_cast<uintptr_t>(s.dbias)) & 15) == 0,
+             "%s: dy / z / dres_out / dx / dres / weight / dweight / dbias must be 16-byte aligned", op);
+    if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
+    const bool inplace = s.dx && s.dx == s.dy;
+    if (inplace) FA_CHECK(s.dx_row_stride == s.dy_row_stride, "%s: dx shares dy's base address but not its row stride (in place needs both equal)", op);
+    if (query) return FA_OK;
+    const size_t need = fa::add_norm_bwd_workspace_bytes(s);
+    if (need) {
+        FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_add_norm_bwd_workspace_bytes() reports %zu",
+                 op, s.workspace ? s.workspace_bytes : (size_t)0, need);
+        FA_CHECK(reinterpret_cast<uintptr_t>(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+    }
+    const int zsz = s.z_dtype == FA_FP32 ? 4 : 2, dsz = s.dres_dtype == FA_FP32 ? 4 : 2;
+    const uint64_t wbytes = (uint64_t)s.n * (s.weight_dtype == FA_FP32 ? 4 : 2);
+    const AnView in[] = {
+        an_view("dy", s.dy, s.rows, s.dy_row_stride, s.n, 2),
+        an_view("z", s.z, s.rows, s.z_row_stride, s.n, zsz),
+        an_view("dres_out", s.dres_out, s.rows, s.dres_out_row_stride, s.n, zsz),
+        an_flat("weight", s.weight, wbytes),
+    };
+    const AnView out[] = {
+        an_view("dx", s.dx, s.rows, s.dx_row_stride, s.n, 2),
+        an_view("dres", s.dres, s.rows, s.dres_row_stride, s.n, dsz),
+        an_flat("dweight", s.dweight, wbytes),
+        an_flat("dbias", s.dbias, wbytes),
+        an_flat("workspace", need ? s.workspace : nullptr, need),
+    };
+    const int ex_out[1] = {0}, ex_in[1] = {0};
+    return an_overlaps(op, out, 5, in, 4, ex_out, ex_in, inplace ? 1 : 0);
+}
+
+extern "C" {
+
+int fa_add_norm(const fa_add_norm_params* sp, void* stream) {
+    FA_CHECK(sp, "fa_add_norm_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_add_norm_params), "fa_add_norm_params::struct_size %zu is smaller than this library's %zu",
+             sp->struct_size, sizeof(fa_add_norm_params));
+    fa_add_norm_params s = *sp;
+    const int rc = add_norm_check(s);
+    if (rc != FA_OK) return rc;
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_add_norm(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_add_norm launch");
+}
+
+size_t fa_add_norm_bwd_workspace_bytes(const fa_add_norm_bwd_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_add_norm_bwd_params)) return 0;
+    if (add_norm_bwd_check(*sp, true) != FA_OK) return 0;
+    return fa::add_norm_bwd_workspace_bytes(*sp);
+}
+
+int fa_add_norm_bwd(const fa_add_norm_bwd_params* sp, void* stream) {
+    FA_CHECK(sp, "fa_add_norm_bwd_params must not be NULL");
+    FA_CHECK(sp->struct_size >= sizeof(fa_add_norm_bwd_params), "fa_add_norm_bwd_params::struct_size %zu is smaller than this library's %zu",
+             sp->struct_size, sizeof(fa_add_norm_bwd_params));
+    fa_add_norm_bwd_params s = *sp;
+    const int rc = add_norm_bwd_check(s, false);
+    if (rc != FA_OK) return rc;
+    if (!s.dx && !s.dres && !s.dweight && !s.dbias) return FA_OK;
+    if (s.rows == 0 && !s.dweight && !s.dbias) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_add_norm_bwd(s, static_cast<hipStream_t>(stream));          // (rows == 0: a wanted dweight / dbias is set to zeros, no kernel)
+    return check_hip("fa_add_norm_bwd launch");
 }
 
 }  // extern "C"

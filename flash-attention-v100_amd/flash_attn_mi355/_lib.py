@@ -259,6 +259,41 @@ class FaQkNormRopeBwdParams(ctypes.Structure):
     ]
 
 
+class FaAddNormParams(ctypes.Structure):
+    """Mirror of `struct fa_add_norm_params` (include/fa_mi355.h): fa_add_norm, residual add + RMSNorm / LayerNorm over the whole
+    hidden size.  struct_size must be set to sizeof(FaAddNormParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("x", _ptr), ("residual", _ptr),                      # residual NULL: none
+        ("out", _ptr), ("residual_out", _ptr),                # may equal x / residual (in place); residual_out NULL: not written
+        ("x_row_stride", _i64), ("residual_row_stride", _i64), ("out_row_stride", _i64), ("residual_out_row_stride", _i64),
+        ("weight", _ptr), ("bias", _ptr),                     # [n] of weight_dtype; bias NULL: none
+        ("rows", _i64),
+        ("n", _i32), ("dtype", _i32), ("residual_dtype", _i32), ("residual_out_dtype", _i32), ("weight_dtype", _i32),
+        ("is_rms_norm", _i32),
+        ("eps", _f32), ("weight_offset", _f32),
+        ("reserved", _i64 * 2),
+    ]
+
+
+class FaAddNormBwdParams(ctypes.Structure):
+    """Mirror of `struct fa_add_norm_bwd_params` (include/fa_mi355.h): fa_add_norm_bwd, the backward of fa_add_norm - dx / dres
+    from dy, the saved z and an optional dres_out, and dweight / dbias.  struct_size must be set to sizeof(FaAddNormBwdParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dy", _ptr), ("z", _ptr), ("dres_out", _ptr),        # dres_out NULL: none
+        ("dx", _ptr), ("dres", _ptr),                         # outputs; dx may equal dy (in place); NULL: skipped
+        ("dy_row_stride", _i64), ("z_row_stride", _i64), ("dres_out_row_stride", _i64), ("dx_row_stride", _i64),
+        ("dres_row_stride", _i64),
+        ("weight", _ptr), ("dweight", _ptr), ("dbias", _ptr),  # [n] of weight_dtype; dweight / dbias NULL: skipped
+        ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("rows", _i64),
+        ("n", _i32), ("dtype", _i32), ("z_dtype", _i32), ("dres_dtype", _i32), ("weight_dtype", _i32), ("is_rms_norm", _i32),
+        ("eps", _f32), ("weight_offset", _f32),
+        ("reserved", _i64 * 2),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -268,7 +303,9 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_merge_states", "fa_merge_params_size", "fa_rotary", "fa_rotary_params_size",
            "fa_kv_store", "fa_kv_store_params_size", "fa_kv_gather", "fa_kv_gather_params_size",
            "fa_rope_store", "fa_rope_store_params_size", "fa_qk_norm_rope_store", "fa_qk_norm_rope_store_params_size",
-           "fa_qk_norm_rope_bwd", "fa_qk_norm_rope_bwd_workspace_bytes", "fa_qk_norm_rope_bwd_params_size"] + EXT_OPS
+           "fa_qk_norm_rope_bwd", "fa_qk_norm_rope_bwd_workspace_bytes", "fa_qk_norm_rope_bwd_params_size",
+           "fa_add_norm", "fa_add_norm_params_size",
+           "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size"] + EXT_OPS
 
 
 def _load():
@@ -324,6 +361,14 @@ def _load():
     lib.fa_qk_norm_rope_bwd_workspace_bytes.restype = ctypes.c_size_t
     lib.fa_qk_norm_rope_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaQkNormRopeBwdParams)]
     lib.fa_qk_norm_rope_bwd_params_size.restype = ctypes.c_size_t
+    lib.fa_add_norm.restype = ctypes.c_int
+    lib.fa_add_norm.argtypes = [ctypes.POINTER(FaAddNormParams), ctypes.c_void_p]
+    lib.fa_add_norm_params_size.restype = ctypes.c_size_t
+    lib.fa_add_norm_bwd.restype = ctypes.c_int
+    lib.fa_add_norm_bwd.argtypes = [ctypes.POINTER(FaAddNormBwdParams), ctypes.c_void_p]
+    lib.fa_add_norm_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.fa_add_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaAddNormBwdParams)]
+    lib.fa_add_norm_bwd_params_size.restype = ctypes.c_size_t
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -358,6 +403,12 @@ def _load():
     if lib.fa_qk_norm_rope_bwd_params_size() != ctypes.sizeof(FaQkNormRopeBwdParams):
         raise ImportError(f"fa_qk_norm_rope_bwd_params size mismatch: library {lib.fa_qk_norm_rope_bwd_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaQkNormRopeBwdParams)}")
+    if lib.fa_add_norm_params_size() != ctypes.sizeof(FaAddNormParams):
+        raise ImportError(f"fa_add_norm_params size mismatch: library {lib.fa_add_norm_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaAddNormParams)}")
+    if lib.fa_add_norm_bwd_params_size() != ctypes.sizeof(FaAddNormBwdParams):
+        raise ImportError(f"fa_add_norm_bwd_params size mismatch: library {lib.fa_add_norm_bwd_params_size()} vs ctypes "
+                          f"{ctypes.sizeof(FaAddNormBwdParams)}")
     return lib
 
 
@@ -444,6 +495,25 @@ def call_qk_norm_rope_bwd(params, stream):
 def qk_norm_rope_bwd_workspace_bytes(params):
     """fa_qk_norm_rope_bwd_workspace_bytes: needs no device"""
     return int(lib.fa_qk_norm_rope_bwd_workspace_bytes(ctypes.byref(params)))
+
+
+def call_add_norm(params, stream):
+    """fa_add_norm"""
+    rc = lib.fa_add_norm(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_add_norm failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def call_add_norm_bwd(params, stream):
+    """fa_add_norm_bwd"""
+    rc = lib.fa_add_norm_bwd(ctypes.byref(params), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"fa_add_norm_bwd failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def add_norm_bwd_workspace_bytes(params):
+    """fa_add_norm_bwd_workspace_bytes: needs no device"""
+    return int(lib.fa_add_norm_bwd_workspace_bytes(ctypes.byref(params)))
 
 
 def call_rows(name, *args):

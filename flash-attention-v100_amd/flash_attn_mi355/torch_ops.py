@@ -5,7 +5,9 @@ fa_rotary; `kv_store`: a ragged packed batch of K / V rows into a KV cache, fa_k
 rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache; `rope_store_`: q / k rotated at per-token positions
 and K / V stored by slot in one launch, fa_rope_store; `qk_norm_rope_store_`: the same behind a per-head RMSNorm of q and k,
 fa_qk_norm_rope_store; `qk_norm_rope` / `qk_norm_rope_bwd`: that norm + rotation out of place with an autograd formula, and its
-backward, fa_qk_norm_rope_bwd - registered, but not listed in `__all__`).
+backward, fa_qk_norm_rope_bwd; `add_norm` / `add_norm_` / `add_norm_bwd`: residual add + RMSNorm / LayerNorm over the hidden size
+with an autograd formula, its in-place form and its backward, fa_add_norm / fa_add_norm_bwd - registered, but not listed in
+`__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -29,6 +31,7 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import add_norm as _add_norm
 from . import cascade as _cascade
 from . import flash_attn_interface as _fi
 from . import kv_gather as _kv_gather
@@ -594,6 +597,96 @@ def _qk_norm_rope_backward(ctx, dq_out, dk_out):
 
 
 qk_norm_rope.register_autograd(_qk_norm_rope_backward, setup_context=_qk_norm_rope_setup)
+
+
+# ------------------------------------------------------------------------------------------
+# residual add + RMSNorm / LayerNorm over the hidden size (flash_attn_mi355.add_norm; csrc/fa_add_norm.hip, fa_add_norm_bwd.hip).
+# Reached as torch.ops.flash_attn_mi355.add_norm / .add_norm_ / .add_norm_bwd; not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::add_norm", mutates_args=(), device_types="cuda")
+def add_norm(x: Tensor, weight: Tensor, bias: Optional[Tensor], residual: Optional[Tensor], eps: float, weight_offset: float,
+             is_rms_norm: bool, prenorm: bool, residual_in_fp32: bool) -> Tuple[Tensor, Tensor]:
+    """add_norm.add_norm_forward out of place: (out, residual_out), fresh contiguous tensors; without a residual and without
+    prenorm residual_out is an empty (0,) tensor.  Differentiable in x, weight, bias and residual (add_norm_bwd)."""
+    out, ro = _add_norm.add_norm_forward(x, weight, bias, residual, eps=eps, weight_offset=weight_offset, is_rms_norm=is_rms_norm,
+                                         prenorm=prenorm, residual_in_fp32=residual_in_fp32, inplace=False)
+    return out, (x.new_empty((0,)) if ro is None else ro)
+
+
+@add_norm.register_fake
+def _(x, weight, bias, residual, eps, weight_offset, is_rms_norm, prenorm, residual_in_fp32):
+    if residual is None and not prenorm:
+        return x.new_empty(x.shape), x.new_empty((0,))
+    ro_dtype = _add_norm.residual_out_dtype(x.dtype, None if residual is None else residual.dtype, residual_in_fp32)
+    return x.new_empty(x.shape), x.new_empty(x.shape, dtype=ro_dtype)
+
+
+@torch.library.custom_op(f"{_NS}::add_norm_", mutates_args=("x", "residual"), device_types="cuda")
+def add_norm_(x: Tensor, residual: Optional[Tensor], weight: Tensor, bias: Optional[Tensor], eps: float, weight_offset: float,
+              is_rms_norm: bool) -> None:
+    """in place: residual <- x + residual (one rounding to residual's dtype), x <- norm(residual); without a residual x <- norm(x)"""
+    _add_norm.add_norm_forward(x, weight, bias, residual, eps=eps, weight_offset=weight_offset, is_rms_norm=is_rms_norm,
+                               inplace=True)
+
+
+@add_norm_.register_fake
+def _(x, residual, weight, bias, eps, weight_offset, is_rms_norm):
+    return None
+
+
+@torch.library.custom_op(f"{_NS}::add_norm_bwd", mutates_args=(), device_types="cuda")
+def add_norm_bwd(dy: Tensor, z: Tensor, dres_out: Optional[Tensor], weight: Tensor, eps: float, weight_offset: float,
+                 is_rms_norm: bool, dres_fp32: bool, need_dx: bool, need_dres: bool, need_dweight: bool,
+                 need_dbias: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """add_norm.add_norm_backward out of place: (dx, dres, dweight, dbias), fresh tensors; an output that is not needed is an
+    empty (0,) tensor and is not computed.  dres has dy's dtype, or float32 with dres_fp32."""
+    dx, dres, dw, db = _add_norm.add_norm_backward(dy, z, weight, dres_out, eps=eps, weight_offset=weight_offset,
+                                                   is_rms_norm=is_rms_norm, dres_dtype=torch.float32 if dres_fp32 else dy.dtype,
+                                                   need_dx=need_dx, need_dres=need_dres, need_dw=need_dweight, need_db=need_dbias)
+    none = lambda: dy.new_empty((0,))                           # noqa: E731
+    return tuple(none() if t is None else t for t in (dx, dres, dw, db))
+
+
+@add_norm_bwd.register_fake
+def _(dy, z, dres_out, weight, eps, weight_offset, is_rms_norm, dres_fp32, need_dx, need_dres, need_dweight, need_dbias):
+    none = lambda: dy.new_empty((0,))                           # noqa: E731
+    return (dy.new_empty(dy.shape) if need_dx else none(),
+            dy.new_empty(dy.shape, dtype=torch.float32 if dres_fp32 else dy.dtype) if need_dres else none(),
+            weight.new_empty(weight.shape) if need_dweight else none(),
+            weight.new_empty(weight.shape) if need_dbias else none())
+
+
+def _add_norm_setup(ctx, inputs, output):
+    (x, weight, bias, residual, eps, weight_offset, is_rms_norm, prenorm, residual_in_fp32) = inputs
+    ctx.set_materialize_grads(False)
+    # z: what the norm read - residual_out where there is one (without a residual it is the prenorm copy of x), else x itself
+    has_ro = residual is not None or prenorm
+    ctx.save_for_backward(output[1] if has_ro else x, weight)
+    ctx.args = (eps, weight_offset, is_rms_norm)
+    ctx.res_dtype = None if residual is None else residual.dtype
+    ctx.io_dtype = x.dtype
+    ctx.has_bias = bias is not None
+    ctx.has_ro = has_ro
+
+
+def _add_norm_backward(ctx, dout, dres_out):
+    z, weight = ctx.saved_tensors
+    eps, weight_offset, is_rms_norm = ctx.args
+    need = ctx.needs_input_grad                 # (x, weight, bias, residual, ...)
+    need_x, need_w, need_b = need[0], need[1], need[2] and ctx.has_bias
+    need_r = need[3] and ctx.res_dtype is not None
+    if dout is None:                            # (only residual_out was used: the norm contributes nothing)
+        dout = torch.zeros(z.shape, dtype=ctx.io_dtype, device=z.device)
+    if not ctx.has_ro:
+        dres_out = None
+    same = need_x and need_r and ctx.res_dtype == dout.dtype    # dx and dres hold the same bits: one tensor for both
+    dx, dres, dw, db = add_norm_bwd(dout, z, dres_out, weight, eps, weight_offset, is_rms_norm, ctx.res_dtype == torch.float32,
+                                    need_x, need_r and not same, need_w, need_b)
+    pick = lambda g, on: g if on else None                      # noqa: E731
+    return (pick(dx, need_x), pick(dw, need_w), pick(db, need_b), pick(dx if same else dres, need_r), None, None, None, None, None)
+
+
+add_norm.register_autograd(_add_norm_backward, setup_context=_add_norm_setup)
 
 
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",

@@ -795,6 +795,123 @@ size_t fa_qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params* s);
 size_t fa_qk_norm_rope_bwd_params_size(void);
 
 /*
+ * fa_add_norm - residual add + RMSNorm / LayerNorm over the whole hidden size, one launch (additive: fa_params and FA_ABI_VERSION
+ * are unchanged).  x: [rows, n] of `dtype` (fp16 / bf16).  All arithmetic is fp32:
+ *     z            = x                                                (residual NULL)
+ *     z            = round_res(float(x) + float(residual))           ONE fp32 add, ONE rounding to residual_out_dtype
+ *     residual_out = z                                                (required with a residual; without one it is optional
+ *                                                                      and gets float(x) or x: the prenorm copy)
+ *     RMSNorm:   rstd = 1 / sqrt(sum(z^2) / n + eps);                     xhat = z * rstd
+ *     LayerNorm: mean = sum(z) / n;  rstd = 1 / sqrt(sum((z - mean)^2) / n + eps);  xhat = (z - mean) * rstd   (two passes)
+ *     out = round_to_dtype(xhat * g)           g = weight_offset + weight   (weight_offset 1.0: Gemma, zero-centred weights)
+ *     out = round_to_dtype(fma(xhat, g, b))    with a bias b (one fused multiply-add)
+ * The norm reads the STORED z - the value residual_out holds -, so fa_add_norm(x, residual) leaves in `out` exactly the bits of
+ * fa_add_norm(residual_out) when residual_out_dtype == dtype, as the HF modules and vLLM's fused_add_rms_norm do; a backward can
+ * recompute mean / rstd from residual_out and the forward saves nothing.
+ * The order of every row sum is fixed and depends on n alone (csrc/fa_rowsum.h): a row's bits do not depend on the number of rows,
+ * on the row's index or on the device.  n <= 256: the row is owned by G adjacent lanes of a wave as a head is in
+ * fa_qk_norm_rope_store (csrc/fa_rmsnorm.h), and an RMSNorm without bias has that op's bits for a head of n columns.
+ * x, residual, out, residual_out: each with its own row stride in elements (a multiple of 8), the last dimension contiguous,
+ * 16-byte aligned bases.  residual_dtype: `dtype` or FA_FP32.  residual_out_dtype: `dtype` or FA_FP32; FA_FP32 where
+ * residual_dtype is FA_FP32.  weight, bias: device [n] of `weight_dtype` (`dtype` or FA_FP32), 16-byte aligned; bias may be NULL.
+ * In place: out == x (the same base address AND row stride), and residual_out == residual (base, row stride and dtype) are
+ * legal - a lane loads everything it owns before its first store.  Every other overlap of an output with an input or with the
+ * other output is rejected.
+ * No workspace, no atomics, no host synchronisation, bitwise repeatable, capturable in a graph.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL x, out or weight; a residual without residual_out; a
+ * dtype other than FA_FP16 / FA_BF16; a residual_dtype / residual_out_dtype / weight_dtype other than `dtype` or FA_FP32, or a
+ * 16-bit residual_out_dtype with an fp32 residual; n not a multiple of 8 or outside [8, 16384]; negative rows or row strides; a
+ * row stride that is not a multiple of 8 elements or (rows > 1) smaller than n; bases, weight or bias not 16-byte aligned; a
+ * negative or non-finite eps; a non-finite weight_offset; an illegal overlap; non-zero reserved fields.  rows > 2^31 - 1:
+ * FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
+ */
+typedef struct fa_add_norm_params {
+    size_t         struct_size;      /* sizeof(fa_add_norm_params) as the caller compiled it */
+    const void*    x;                /* [rows, n] of `dtype` */
+    const void*    residual;         /* [rows, n] of `residual_dtype`, or NULL */
+    void*          out;              /* [rows, n] of `dtype`; may equal x */
+    void*          residual_out;     /* [rows, n] of `residual_out_dtype`; may equal residual; NULL without a residual: not written */
+    int64_t        x_row_stride, residual_row_stride, out_row_stride, residual_out_row_stride;     /* elements */
+    const void*    weight;           /* device [n] of `weight_dtype`, 16-byte aligned */
+    const void*    bias;             /* device [n] of `weight_dtype`, or NULL */
+    int64_t        rows;
+    int32_t        n;                /* a multiple of 8, 8 .. 16384 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        residual_dtype;   /* `dtype` or FA_FP32 (read where residual is given) */
+    int32_t        residual_out_dtype;   /* `dtype` or FA_FP32 (read where residual or residual_out is given) */
+    int32_t        weight_dtype;     /* `dtype` or FA_FP32 */
+    int32_t        is_rms_norm;      /* 0: LayerNorm */
+    float          eps;              /* >= 0, finite */
+    float          weight_offset;    /* finite */
+    int64_t        reserved[2];      /* 0 */
+} fa_add_norm_params;
+
+int    fa_add_norm(const fa_add_norm_params* s, void* stream);
+size_t fa_add_norm_params_size(void);
+
+/*
+ * fa_add_norm_bwd - the backward of fa_add_norm.  Both roundings of the forward (z to residual_out_dtype, out to `dtype`) are
+ * treated as the identity (straight-through), all arithmetic is fp32.  From dy [rows, n] of `dtype` (the gradient of out), the
+ * saved z [rows, n] of `z_dtype` (residual_out; x itself where the forward had no residual), an optional dres_out [rows, n] of
+ * `z_dtype` (the gradient of residual_out under prenorm) and the weight:
+ *     mean, rstd: recomputed from z with the forward's fixed-order sums (csrc/fa_rowsum.h) - the forward's bits
+ *     a = dy * g,  g = weight_offset + weight;   xhat = z * rstd   (LayerNorm: (z - mean) * rstd)
+ *     RMSNorm:   c  = (sum_d a xhat) / n;                       dz = rstd * fma(-xhat, c, a)
+ *     LayerNorm: c1 = (sum_d a) / n;  c2 = (sum_d a xhat) / n;  dz = rstd * fma(-xhat, c2, a - c1)
+ *     with dres_out:  dz = fma(rstd, that fma, float(dres_out))
+ *     dx   = round_to_dtype(dz)                [rows, n] of `dtype`; may equal dy (base AND row stride: in place)
+ *     dres = round(dz) to `dres_dtype`         [rows, n]: the gradient of the forward's residual
+ *     dweight[d] = sum over rows of dy[d] xhat[d];   dbias[d] = sum over rows of dy[d]       [n] of `weight_dtype`, one rounding
+ * The sums for c, c1, c2 have the forward's fixed order: a row's dx / dres bits do not depend on what else is in the batch.  For
+ * n <= 256 an RMSNorm's dx has the bits of fa_qk_norm_rope_bwd without rotation on a head of n columns.
+ * Each of dx, dres, dweight, dbias may be NULL and is then skipped (with all four NULL: FA_OK, nothing is read).
+ * dweight / dbias are deterministic, no atomics: a workgroup walks a run of consecutive rows with its partial sums in registers
+ * (fmaf in row order), writes ONE fp32 partial row [1 or 2][n] (2 with dbias) into `workspace`, and a second small kernel on the
+ * same stream adds the P partial rows - 16 contiguous runs of them in row order side by side, then the runs in order.  P <= 256
+ * and the run length depend on (rows, n, dbias given) alone, never on the device: fa_add_norm_bwd_workspace_bytes() needs no
+ * device, the bits are the same on every card, and the workspace is at most 256 x 2 x 16384 x 4 bytes = 32 MiB.  Without dweight
+ * and dbias: one launch, a workgroup (n > 256) or a group of lanes (n <= 256) per row, no workspace.
+ * No host synchronisation, bitwise repeatable, capturable in a graph.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL dy, z or weight; a dtype other than FA_FP16 / FA_BF16; a
+ * z_dtype / dres_dtype / weight_dtype other than `dtype` or FA_FP32; n not a multiple of 8 or outside [8, 16384]; negative rows
+ * or row strides; a row stride that is not a multiple of 8 elements or (rows > 1) smaller than n; bases, weight, dweight, dbias
+ * or the workspace not 16-byte aligned; a negative or non-finite eps; a non-finite weight_offset; a dx that shares dy's base but
+ * not its row stride; an output (dx, dres, dweight, dbias, the workspace) that overlaps an input other than by that aliasing, or
+ * another output; a workspace smaller than reported; non-zero reserved fields.  rows > 2^31 - 1: FA_ERR_UNSUPPORTED.
+ * rows == 0: FA_OK without a kernel launch; a dweight / dbias that was asked for is set to zeros on `stream`.
+ */
+typedef struct fa_add_norm_bwd_params {
+    size_t         struct_size;      /* sizeof(fa_add_norm_bwd_params) as the caller compiled it */
+    const void*    dy;               /* [rows, n] of `dtype`: the gradient of out */
+    const void*    z;                /* [rows, n] of `z_dtype`: the forward's residual_out (x without a residual) */
+    const void*    dres_out;         /* [rows, n] of `z_dtype`: the gradient of residual_out, or NULL */
+    void*          dx;               /* [rows, n] of `dtype`; may equal dy; NULL: skipped */
+    void*          dres;             /* [rows, n] of `dres_dtype`; NULL: skipped */
+    int64_t        dy_row_stride, z_row_stride, dres_out_row_stride, dx_row_stride, dres_row_stride;   /* elements */
+    const void*    weight;           /* device [n] of `weight_dtype`, 16-byte aligned */
+    void*          dweight;          /* device [n] of `weight_dtype`, 16-byte aligned; NULL: skipped */
+    void*          dbias;            /* device [n] of `weight_dtype`, 16-byte aligned; NULL: skipped */
+    void*          workspace;        /* fa_add_norm_bwd_workspace_bytes() bytes, 16-byte aligned; may be NULL where that is 0 */
+    size_t         workspace_bytes;
+    int64_t        rows;
+    int32_t        n;                /* a multiple of 8, 8 .. 16384 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        z_dtype;          /* `dtype` or FA_FP32 */
+    int32_t        dres_dtype;       /* `dtype` or FA_FP32 (read where dres is given) */
+    int32_t        weight_dtype;     /* `dtype` or FA_FP32 */
+    int32_t        is_rms_norm;      /* 0: LayerNorm */
+    float          eps;              /* the forward's */
+    float          weight_offset;    /* the forward's */
+    int64_t        reserved[2];      /* 0 */
+} fa_add_norm_bwd_params;
+
+int    fa_add_norm_bwd(const fa_add_norm_bwd_params* s, void* stream);
+/* the workspace of that call; `workspace`, `workspace_bytes` and where the tensors lie are not looked at; 0 for a block that the
+ * call rejects for any other reason */
+size_t fa_add_norm_bwd_workspace_bytes(const fa_add_norm_bwd_params* s);
+size_t fa_add_norm_bwd_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
