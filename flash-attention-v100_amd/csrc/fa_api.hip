@@ -645,214 +645,282 @@ int fa_merge_states(const fa_merge_params* m, void* stream) {
     return check_hip("fa_merge_states launch");
 }
 
-// bytes from the first to one past the last element of x / out as fa_rotary addresses it (strides >= 0, sizes > 0)
-static uint64_t rotary_span_bytes(const fa_rotary_params& r, int64_t bs, int64_t rs, int64_t hs) {
-    const int64_t rows = r.cu_seqlens ? r.total_rows : r.seqlen;
-    const int64_t last = (r.cu_seqlens ? 0 : (int64_t)(r.batch - 1) * bs) + (rows - 1) * rs + (int64_t)(r.nheads - 1) * hs + r.head_dim;
-    return (uint64_t)last * 2;
+}  // extern "C"
+
+// ---- The row ops around attention (fa_rotary .. fa_add_norm_bwd): one argument-checking layer, then the entry points. ----
+// Every helper takes `op`, the name its messages begin with, and is parameterised by data alone: pointers, sizes and which fields
+// a block has.  A rule that only one op has stays in that op's own function.
+
+#define FA_TRY(expr)                         \
+    do {                                     \
+        const int rc_ = (expr);              \
+        if (rc_ != FA_OK) return rc_;        \
+    } while (0)
+
+static uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// the head of every struct-taking entry point: the block is there and not smaller than this library's
+template <typename P>
+static int check_header(const P* p, const char* type) {
+    FA_CHECK(p, "%s must not be NULL", type);
+    FA_CHECK(p->struct_size >= sizeof(P), "%s::struct_size %zu is smaller than this library's %zu", type, p->struct_size, sizeof(P));
+    return FA_OK;
 }
 
-int fa_rotary(const fa_rotary_params* r, void* stream) {
-    FA_CHECK(r, "fa_rotary_params must not be NULL");
-    FA_CHECK(r->struct_size >= sizeof(fa_rotary_params), "fa_rotary_params::struct_size %zu is smaller than this library's %zu",
-             r->struct_size, sizeof(fa_rotary_params));
-    FA_CHECK(r->x && r->out && r->cos && r->sin, "rotary: x, out, cos and sin must not be NULL");
-    FA_CHECK(r->dtype == FA_FP16 || r->dtype == FA_BF16, "rotary dtype must be fp16 or bf16");
-    FA_CHECK(r->batch >= 0 && r->seqlen >= 0 && r->nheads >= 0 && r->head_dim >= 0 && r->seqlen_ro >= 0 && r->total_rows >= 0 &&
-             r->seqlen_offset >= 0, "rotary sizes and seqlen_offset must be non-negative");
-    FA_CHECK(r->rotary_dim > 0 && r->rotary_dim % 2 == 0, "rotary_dim must be positive and even, got %d", r->rotary_dim);
-    FA_CHECK(r->rotary_dim <= r->head_dim, "rotary_dim must be <= head_dim (%d > %d)", r->rotary_dim, r->head_dim);
-    FA_CHECK(r->x_batch_stride >= 0 && r->x_row_stride >= 0 && r->x_head_stride >= 0 && r->o_batch_stride >= 0 &&
-             r->o_row_stride >= 0 && r->o_head_stride >= 0, "rotary strides must be non-negative");
-    const uintptr_t xa = reinterpret_cast<uintptr_t>(r->x), oa = reinterpret_cast<uintptr_t>(r->out);
-    FA_CHECK(xa % 2 == 0 && oa % 2 == 0, "rotary: x and out must be 2-byte aligned");
-    const uintptr_t cs_al = r->cos_sin_fp32 ? 4 : 2;
-    FA_CHECK(reinterpret_cast<uintptr_t>(r->cos) % cs_al == 0 && reinterpret_cast<uintptr_t>(r->sin) % cs_al == 0,
-             "rotary: cos / sin must be aligned to their element size (%d bytes)", (int)cs_al);
-    FA_CHECK(reinterpret_cast<uintptr_t>(r->seqlen_offsets) % 4 == 0 && reinterpret_cast<uintptr_t>(r->cu_seqlens) % 4 == 0,
-             "rotary: seqlen_offsets and cu_seqlens must be 4-byte aligned int32 arrays");
-    if ((int64_t)r->nheads * r->head_dim > ((int64_t)1 << 24))
-        return fail(FA_ERR_UNSUPPORTED, "rotary: nheads x head_dim is too large for one launch");
-    const bool empty = r->batch == 0 || r->nheads == 0 || (r->cu_seqlens ? r->total_rows == 0 : r->seqlen == 0);
-    if (!empty) {
-        const bool same_strides = r->x_row_stride == r->o_row_stride && r->x_head_stride == r->o_head_stride &&
-                                  (r->cu_seqlens || r->x_batch_stride == r->o_batch_stride);
-        if (xa == oa) {
-            FA_CHECK(same_strides, "rotary: out shares x's base address but not its strides (in place needs both equal)");
-        } else {
-            const uint64_t xe = rotary_span_bytes(*r, r->x_batch_stride, r->x_row_stride, r->x_head_stride);
-            const uint64_t oe = rotary_span_bytes(*r, r->o_batch_stride, r->o_row_stride, r->o_head_stride);
-            FA_CHECK((uint64_t)oa >= (uint64_t)xa + xe || (uint64_t)xa >= (uint64_t)oa + oe,
-                     "rotary: out overlaps x without being x itself (in place: the same base address and strides)");
-        }
+// `what` names the tensors in the message: "k / v dtype", "dtype", ...
+static int check_io_dtype(const char* op, int dtype, const char* what) {
+    FA_CHECK(dtype == FA_FP16 || dtype == FA_BF16, "%s: %s must be fp16 or bf16", op, what);
+    return FA_OK;
+}
+
+static int check_cache_dtype(const char* op, int cache_dtype, int dtype) {
+    FA_CHECK(cache_dtype == dtype || cache_dtype == FA_FP8_E4M3, "%s: the cache dtype must be the k / v dtype or fp8-e4m3", op);
+    return FA_OK;
+}
+
+// P: a block with k_cache / v_cache and their kc_* / vc_* strides
+template <typename P>
+static int check_cache_align(const char* op, const P& s, bool kv8) {
+    const uintptr_t cal = kv8 ? 7 : 15;                   // bytes; strides are in elements of 1 / 2 bytes
+    const int64_t sal = 7;
+    FA_CHECK(((addr(s.k_cache) | addr(s.v_cache)) & cal) == 0 &&
+             ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
+             "%s: cache base addresses and strides must be multiples of %d bytes", op, kv8 ? 8 : 16);
+    return FA_OK;
+}
+
+// checked for every cache type, used by fp8 caches; normalises 0 to 1.0
+static int check_descales(const char* op, float& k_descale, float& v_descale) {
+    float* ds[2] = {&k_descale, &v_descale};
+    for (float* d : ds) {
+        FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "%s: k / v descales must be finite and >= 0 (0 = 1.0)", op);
+        if (*d == 0.f) *d = 1.0f;
     }
-    if (empty) return FA_OK;
-    fa::launch_rotary(*r, static_cast<hipStream_t>(stream));
-    return check_hip("fa_rotary launch");
+    return FA_OK;
 }
 
-int fa_kv_store(const fa_kv_store_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_kv_store_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_kv_store_params), "fa_kv_store_params::struct_size %zu is smaller than this library's %zu",
-             sp->struct_size, sizeof(fa_kv_store_params));
-    fa_kv_store_params s = *sp;
-    FA_CHECK(s.k && s.v && s.k_cache && s.v_cache, "kv_store: k, v, k_cache and v_cache must not be NULL");
-    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "kv_store: k / v dtype must be fp16 or bf16");
-    FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "kv_store: the cache dtype must be the k / v dtype or fp8-e4m3");
-    const bool slot_mode = s.slot_mapping != nullptr, seq_mode = s.cu_seqlens != nullptr;
-    FA_CHECK(slot_mode != seq_mode, "kv_store: exactly one addressing mode - slot_mapping, or cu_seqlens (%s given)",
-             slot_mode ? "both" : "neither");
-    FA_CHECK(!(s.block_table && s.cache_batch_idx), "kv_store: block_table and cache_batch_idx exclude each other (paged caches have no cache_batch_idx)");
+// The rotary-table group of a block with positions / rotary_cos / rotary_sin / rotary_dim / seqlen_ro / head_dim, in the three
+// places where the per-token ops look at it (between them come the op's own sizes, which the later rules rely on).
+// 1. which pointers are there.  no_rope_ok: seqlen_ro == 0 means "no rotation" - positions and the tables may be NULL then and
+//    rotary_dim is not read (the block is normalised: all four cleared); otherwise all three are required, and so is k.
+//    Returns *no_rope.
+template <typename P>
+static int check_rope_tables(const char* op, P& s, bool no_rope_ok, bool* no_rope) {
+    *no_rope = no_rope_ok && s.seqlen_ro == 0;
+    if (*no_rope) {
+        s.positions = nullptr; s.rotary_cos = s.rotary_sin = nullptr; s.rotary_dim = 0;
+    } else if (no_rope_ok) {
+        FA_CHECK(s.seqlen_ro < 0 || (s.positions && s.rotary_cos && s.rotary_sin),             // (< 0: rejected with the op's sizes)
+                 "%s: positions, rotary_cos and rotary_sin may be NULL only where seqlen_ro == 0", op);
+    } else {
+        FA_CHECK(s.k && s.positions && s.rotary_cos && s.rotary_sin, "%s: k, positions, rotary_cos and rotary_sin must not be NULL", op);
+    }
+    return FA_OK;
+}
+// 2. rotary_dim against the kernels' 16-column pieces and against head_dim
+template <typename P>
+static int check_rope_dims(const char* op, const P& s, bool no_rope) {
+    if (!no_rope) FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "%s: rotary_dim must be positive and divisible by 16, got %d", op, s.rotary_dim);
+    FA_CHECK(s.rotary_dim <= s.head_dim, "%s: rotary_dim must be <= head_dim (%d > %d)", op, s.rotary_dim, s.head_dim);
+    return FA_OK;
+}
+// 3. where the tables lie
+template <typename P>
+static int check_rope_align(const char* op, const P& s) {
+    FA_CHECK(((addr(s.rotary_cos) | addr(s.rotary_sin)) & 15) == 0, "%s: rotary_cos / rotary_sin must be 16-byte aligned", op);
+    return FA_OK;
+}
+
+// The norm scalars.  io: how the message names the 16-bit dtype ("q / k dtype", "io dtype")
+static int check_weight_dtype(const char* op, int weight_dtype, int dtype, const char* io) {
+    FA_CHECK(weight_dtype == FA_FP32 || (weight_dtype == dtype && (dtype == FA_FP16 || dtype == FA_BF16)),
+             "%s: weight_dtype must be the %s or fp32", op, io);
+    return FA_OK;
+}
+static int check_norm_scalars(const char* op, float eps, float weight_offset) {
+    FA_CHECK(eps >= 0.f && eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
+    FA_CHECK(weight_offset >= -3.402823466e38f && weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
+    return FA_OK;
+}
+
+// bytes from the first to one past the last element of a [blocks, rows, heads, d] tensor (sizes > 0, strides >= 0, in elements)
+static uint64_t span_bytes(int64_t blocks, int64_t bs, int64_t rows, int64_t rs, int64_t heads, int64_t hs, int64_t d, int esize) {
+    return (uint64_t)((blocks - 1) * bs + (rows - 1) * rs + (heads - 1) * hs + d) * (uint64_t)esize;
+}
+
+// What the overlap rules look at (bytes): `rows` rows of row_bytes each, row_stride apart; a NULL pointer or no element: empty.
+// note: the hint a message ends with where both the output and the input of a pair carry one (the input's is printed)
+struct View { const char* name; uint64_t at, row_stride, row_bytes, bytes; const char* note; };
+// rows of `row_elems` elements (a head-strided row: (heads - 1) * head_stride + head_dim), the row stride in elements
+static View view_rows(const char* name, const void* p, int64_t rows, int64_t rs, int64_t row_elems, int esize, const char* note = nullptr) {
+    View v = {name, (uint64_t)addr(p), (uint64_t)rs * esize, 0, 0, note};
+    if (p && rows > 0 && row_elems > 0) {
+        v.row_bytes = (uint64_t)row_elems * esize;
+        v.bytes = (uint64_t)(rows - 1) * v.row_stride + v.row_bytes;
+    }
+    return v;
+}
+// one address range: the rule for it is the plain range test
+static View view_flat(const char* name, const void* p, uint64_t bytes, const char* note = nullptr) {
+    return View{name, (uint64_t)addr(p), 0, p ? bytes : 0, p ? bytes : 0, note};
+}
+// no common element: disjoint address ranges, or the heads / column ranges of one packed buffer - the same row stride, and within
+// a row the one view ends before the other begins
+static bool views_disjoint(const View& a, const View& b) {
+    if (!a.bytes || !b.bytes || a.at >= b.at + b.bytes || b.at >= a.at + a.bytes) return true;
+    const View& lo = a.at <= b.at ? a : b;
+    const View& hi = a.at <= b.at ? b : a;
+    const uint64_t delta = hi.at - lo.at;
+    return a.row_stride == b.row_stride && delta < lo.row_stride && lo.row_bytes <= delta && delta + hi.row_bytes <= lo.row_stride;
+}
+// every output against every input and - among_outs - against the later outputs; exempt[k] = {output, input}, k < n_ex: the exact
+// in-place pairs, which the caller guarantees
+static int check_overlaps(const char* op, const View* out, int n_out, const View* in, int n_in, bool among_outs,
+                          const int (*exempt)[2] = nullptr, int n_ex = 0) {
+    for (int o = 0; o < n_out; ++o) {
+        for (int i = 0; i < n_in; ++i) {
+            bool ex = false;
+            for (int k = 0; k < n_ex; ++k) ex = ex || (exempt[k][0] == o && exempt[k][1] == i);
+            FA_CHECK(ex || views_disjoint(out[o], in[i]), "%s: %s overlaps %s%s", op, out[o].name, in[i].name,
+                     out[o].note && in[i].note ? in[i].note : "");
+        }
+        for (int p = o + 1; among_outs && p < n_out; ++p)
+            FA_CHECK(views_disjoint(out[o], out[p]), "%s: %s overlaps %s", op, out[o].name, out[p].name);
+    }
+    return FA_OK;
+}
+
+static int rotary_check(const fa_rotary_params& r, bool* empty) {
+    FA_CHECK(r.x && r.out && r.cos && r.sin, "rotary: x, out, cos and sin must not be NULL");
+    FA_CHECK(r.dtype == FA_FP16 || r.dtype == FA_BF16, "rotary dtype must be fp16 or bf16");
+    FA_CHECK(r.batch >= 0 && r.seqlen >= 0 && r.nheads >= 0 && r.head_dim >= 0 && r.seqlen_ro >= 0 && r.total_rows >= 0 &&
+             r.seqlen_offset >= 0, "rotary sizes and seqlen_offset must be non-negative");
+    FA_CHECK(r.rotary_dim > 0 && r.rotary_dim % 2 == 0, "rotary_dim must be positive and even, got %d", r.rotary_dim);
+    FA_CHECK(r.rotary_dim <= r.head_dim, "rotary_dim must be <= head_dim (%d > %d)", r.rotary_dim, r.head_dim);
+    FA_CHECK(r.x_batch_stride >= 0 && r.x_row_stride >= 0 && r.x_head_stride >= 0 && r.o_batch_stride >= 0 &&
+             r.o_row_stride >= 0 && r.o_head_stride >= 0, "rotary strides must be non-negative");
+    FA_CHECK(addr(r.x) % 2 == 0 && addr(r.out) % 2 == 0, "rotary: x and out must be 2-byte aligned");
+    const uintptr_t cs_al = r.cos_sin_fp32 ? 4 : 2;
+    FA_CHECK(addr(r.cos) % cs_al == 0 && addr(r.sin) % cs_al == 0,
+             "rotary: cos / sin must be aligned to their element size (%d bytes)", (int)cs_al);
+    FA_CHECK(addr(r.seqlen_offsets) % 4 == 0 && addr(r.cu_seqlens) % 4 == 0,
+             "rotary: seqlen_offsets and cu_seqlens must be 4-byte aligned int32 arrays");
+    if ((int64_t)r.nheads * r.head_dim > ((int64_t)1 << 24))
+        return fail(FA_ERR_UNSUPPORTED, "rotary: nheads x head_dim is too large for one launch");
+    *empty = r.batch == 0 || r.nheads == 0 || (r.cu_seqlens ? r.total_rows == 0 : r.seqlen == 0);
+    if (*empty) return FA_OK;
+    if (r.x == r.out) {
+        FA_CHECK(r.x_row_stride == r.o_row_stride && r.x_head_stride == r.o_head_stride &&
+                 (r.cu_seqlens || r.x_batch_stride == r.o_batch_stride),
+                 "rotary: out shares x's base address but not its strides (in place needs both equal)");
+        return FA_OK;
+    }
+    // x / out as fa_rotary addresses them: one address range each
+    const char* note = " without being x itself (in place: the same base address and strides)";
+    const int64_t blocks = r.cu_seqlens ? 1 : r.batch, rows = r.cu_seqlens ? r.total_rows : r.seqlen;
+    const View x = view_flat("x", r.x, span_bytes(blocks, r.x_batch_stride, rows, r.x_row_stride, r.nheads, r.x_head_stride, r.head_dim, 2), note);
+    const View out = view_flat("out", r.out, span_bytes(blocks, r.o_batch_stride, rows, r.o_row_stride, r.nheads, r.o_head_stride, r.head_dim, 2), note);
+    return check_overlaps("rotary", &out, 1, &x, 1, false);
+}
+
+// What fa_kv_store and fa_kv_gather share: a packed k / v pair, a cache pair and the two addressing modes.  P: either block.
+// seq_base / seq_base_name: the op's own per-sequence int32 array of sequence mode (cache_seqlens, seq_offsets); more_sizes_ok:
+// the op's further sizes are non-negative.  Normalises the descales; *seq_mode: cu_seqlens addressing.
+template <typename P>
+static int kv_rows_check(const char* op, P& s, const void* seq_base, const char* seq_base_name, bool more_sizes_ok, bool* seq_mode) {
+    FA_CHECK(s.k && s.v && s.k_cache && s.v_cache, "%s: k, v, k_cache and v_cache must not be NULL", op);
+    FA_TRY(check_io_dtype(op, s.dtype, "k / v dtype"));
+    FA_TRY(check_cache_dtype(op, s.cache_dtype, s.dtype));
+    const bool slot_mode = s.slot_mapping != nullptr;
+    *seq_mode = s.cu_seqlens != nullptr;
+    FA_CHECK(slot_mode != *seq_mode, "%s: exactly one addressing mode - slot_mapping, or cu_seqlens (%s given)", op, slot_mode ? "both" : "neither");
+    FA_CHECK(!(s.block_table && s.cache_batch_idx), "%s: block_table and cache_batch_idx exclude each other (paged caches have no cache_batch_idx)", op);
     FA_CHECK(s.total_rows >= 0 && s.nheads >= 0 && s.head_dim >= 0 && s.num_blocks >= 0 && s.batch >= 0 && s.max_blocks >= 0 &&
-             s.seqlen_ro >= 0 && s.rotary_dim >= 0, "kv_store sizes must be non-negative");
-    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "kv_store head_dim must be a multiple of 8 and <= 256, got %d", s.head_dim);
-    FA_CHECK(s.page_block_size > 0, "kv_store: page_block_size must be positive (a contiguous cache: S_max)");
+             more_sizes_ok, "%s sizes must be non-negative", op);
+    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "%s head_dim must be a multiple of 8 and <= 256, got %d", op, s.head_dim);
+    FA_CHECK(s.page_block_size > 0, "%s: page_block_size must be positive (a contiguous cache: S_max)", op);
     FA_CHECK(s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.v_row_stride >= 0 && s.v_head_stride >= 0 && s.kc_batch_stride >= 0 &&
              s.kc_row_stride >= 0 && s.kc_head_stride >= 0 && s.vc_batch_stride >= 0 && s.vc_row_stride >= 0 &&
-             s.vc_head_stride >= 0 && s.block_table_batch_stride >= 0, "kv_store strides must be non-negative");
+             s.vc_head_stride >= 0 && s.block_table_batch_stride >= 0, "%s strides must be non-negative", op);
     if (slot_mode) {
-        FA_CHECK(!s.cache_seqlens && !s.block_table && !s.cache_batch_idx,
-                 "kv_store: slot mode takes no cache_seqlens, block_table or cache_batch_idx (the slot is the whole address)");
+        FA_CHECK(!seq_base && !s.block_table && !s.cache_batch_idx,
+                 "%s: slot mode takes no %s, block_table or cache_batch_idx (the slot is the whole address)", op, seq_base_name);
+    } else {
+        if (s.paged) FA_CHECK(s.block_table, "%s: sequence mode on a paged cache needs a block_table", op);
+        else         FA_CHECK(!s.block_table, "%s: a block_table needs paged != 0", op);
+        FA_CHECK(s.paged || s.cache_batch_idx || s.batch <= s.num_blocks,
+                 "%s: the cache has %d batch slots for %d sequences (pass cache_batch_idx)", op, s.num_blocks, s.batch);
+        FA_CHECK(addr(s.cu_seqlens) % 4 == 0 && addr(seq_base) % 4 == 0 && addr(s.block_table) % 4 == 0 && addr(s.cache_batch_idx) % 4 == 0,
+                 "%s: cu_seqlens, %s, block_table and cache_batch_idx must be 4-byte aligned int32 arrays", op, seq_base_name);
+    }
+    return FA_OK;
+}
+// ... and, behind the op's own slot-mode rules, where the tensors lie and the descales
+template <typename P>
+static int kv_rows_check_layout(const char* op, P& s) {
+    if (s.slot_mapping) FA_CHECK(addr(s.slot_mapping) % 8 == 0, "%s: slot_mapping must be an 8-byte aligned int64 array", op);
+    FA_CHECK(((addr(s.k) | addr(s.v)) & 15) == 0 && ((s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride) & 7) == 0,
+             "%s: k / v base addresses and strides must be multiples of 16 bytes", op);
+    FA_TRY(check_cache_align(op, s, s.cache_dtype == FA_FP8_E4M3));
+    return check_descales(op, s.k_descale, s.v_descale);
+}
+
+// fa_kv_store's argument rules; normalises the block.  *empty: nothing to launch
+static int kv_store_check(fa_kv_store_params& s, bool* empty) {
+    const char* op = "kv_store";
+    bool seq_mode;
+    FA_TRY(kv_rows_check(op, s, s.cache_seqlens, "cache_seqlens", s.seqlen_ro >= 0 && s.rotary_dim >= 0, &seq_mode));
+    if (!seq_mode)
         FA_CHECK(s.rotary_dim == 0 && !s.rotary_cos && !s.rotary_sin,
                  "kv_store: rotary needs sequence mode (a slot carries no position); rotate with fa_rotary first");
-        FA_CHECK(reinterpret_cast<uintptr_t>(s.slot_mapping) % 8 == 0, "kv_store: slot_mapping must be an 8-byte aligned int64 array");
-    } else {
-        if (s.paged) FA_CHECK(s.block_table, "kv_store: sequence mode on a paged cache needs a block_table");
-        else         FA_CHECK(!s.block_table, "kv_store: a block_table needs paged != 0");
-        FA_CHECK(s.paged || s.cache_batch_idx || s.batch <= s.num_blocks,
-                 "kv_store: the cache has %d batch slots for %d sequences (pass cache_batch_idx)", s.num_blocks, s.batch);
-        FA_CHECK(reinterpret_cast<uintptr_t>(s.cu_seqlens) % 4 == 0 && reinterpret_cast<uintptr_t>(s.cache_seqlens) % 4 == 0 &&
-                 reinterpret_cast<uintptr_t>(s.block_table) % 4 == 0 && reinterpret_cast<uintptr_t>(s.cache_batch_idx) % 4 == 0,
-                 "kv_store: cu_seqlens, cache_seqlens, block_table and cache_batch_idx must be 4-byte aligned int32 arrays");
-    }
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.v)) & 15) == 0 &&
-             ((s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride) & 7) == 0,
-             "kv_store: k / v base addresses and strides must be multiples of 16 bytes");
-    const bool kv8 = s.cache_dtype == FA_FP8_E4M3;
-    {
-        const uintptr_t cal = kv8 ? 7 : 15;               // bytes; strides are in elements of 1 / 2 bytes
-        const int64_t sal = 7;
-        FA_CHECK(((reinterpret_cast<uintptr_t>(s.k_cache) | reinterpret_cast<uintptr_t>(s.v_cache)) & cal) == 0 &&
-                 ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
-                 "kv_store: cache base addresses and strides must be multiples of %d bytes", kv8 ? 8 : 16);
-    }
-    {
-        float* ds[2] = {&s.k_descale, &s.v_descale};      // (checked for every cache type, used by fp8 caches)
-        for (float* d : ds) {
-            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "kv_store: k / v descales must be finite and >= 0 (0 = 1.0)");
-            if (*d == 0.f) *d = 1.0f;
-        }
-    }
+    FA_TRY(kv_rows_check_layout(op, s));
     if (s.rotary_dim > 0 || s.rotary_cos || s.rotary_sin) {
         // fa_fwd_kvcache's constraints (the tables need not cover the capacity here: a position outside them is stored unrotated)
         FA_CHECK(s.rotary_cos && s.rotary_sin, "rotary_cos and rotary_sin must both be given");
         FA_CHECK(s.rotary_dim > 0, "kv_store: rotary_cos / rotary_sin need rotary_dim > 0");
         FA_CHECK(s.rotary_dim <= s.head_dim, "rotary_dim must be <= headdim");
         FA_CHECK(s.rotary_dim % 16 == 0, "rotary_dim must be divisible by 16");
-        FA_CHECK(((reinterpret_cast<uintptr_t>(s.rotary_cos) | reinterpret_cast<uintptr_t>(s.rotary_sin)) & 15) == 0,
-                 "kv_store: rotary_cos / rotary_sin must be 16-byte aligned");
+        FA_TRY(check_rope_align(op, s));
     }
     if ((int64_t)s.nheads * s.head_dim > ((int64_t)1 << 24))
         return fail(FA_ERR_UNSUPPORTED, "kv_store: nheads x head_dim is too large for one launch");
-    if (s.total_rows == 0 || s.nheads == 0 || s.head_dim == 0 || (seq_mode && s.batch == 0)) return FA_OK;
-    fa::launch_kv_store(s, static_cast<hipStream_t>(stream));
-    return check_hip("fa_kv_store launch");
+    *empty = s.total_rows == 0 || s.nheads == 0 || s.head_dim == 0 || (seq_mode && s.batch == 0);
+    return FA_OK;
 }
 
-// bytes from the first to one past the last element of a [rows, nheads, head_dim] tensor (sizes > 0, strides >= 0, in elements)
-static uint64_t kv_span_bytes(int64_t blocks, int64_t bs, int64_t rows, int64_t rs, int64_t heads, int64_t hs, int64_t d, int esize) {
-    return (uint64_t)((blocks - 1) * bs + (rows - 1) * rs + (heads - 1) * hs + d) * (uint64_t)esize;
-}
-
-int fa_kv_gather(const fa_kv_gather_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_kv_gather_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_kv_gather_params), "fa_kv_gather_params::struct_size %zu is smaller than this library's %zu",
-             sp->struct_size, sizeof(fa_kv_gather_params));
-    fa_kv_gather_params s = *sp;
-    FA_CHECK(s.k && s.v && s.k_cache && s.v_cache, "kv_gather: k, v, k_cache and v_cache must not be NULL");
-    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "kv_gather: k / v dtype must be fp16 or bf16");
-    FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "kv_gather: the cache dtype must be the k / v dtype or fp8-e4m3");
-    const bool slot_mode = s.slot_mapping != nullptr, seq_mode = s.cu_seqlens != nullptr;
-    FA_CHECK(slot_mode != seq_mode, "kv_gather: exactly one addressing mode - slot_mapping, or cu_seqlens (%s given)",
-             slot_mode ? "both" : "neither");
-    FA_CHECK(!(s.block_table && s.cache_batch_idx), "kv_gather: block_table and cache_batch_idx exclude each other (paged caches have no cache_batch_idx)");
-    FA_CHECK(s.total_rows >= 0 && s.nheads >= 0 && s.head_dim >= 0 && s.num_blocks >= 0 && s.batch >= 0 && s.max_blocks >= 0,
-             "kv_gather sizes must be non-negative");
-    FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "kv_gather head_dim must be a multiple of 8 and <= 256, got %d", s.head_dim);
-    FA_CHECK(s.page_block_size > 0, "kv_gather: page_block_size must be positive (a contiguous cache: S_max)");
-    FA_CHECK(s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.v_row_stride >= 0 && s.v_head_stride >= 0 && s.kc_batch_stride >= 0 &&
-             s.kc_row_stride >= 0 && s.kc_head_stride >= 0 && s.vc_batch_stride >= 0 && s.vc_row_stride >= 0 &&
-             s.vc_head_stride >= 0 && s.block_table_batch_stride >= 0, "kv_gather strides must be non-negative");
-    if (slot_mode) {
-        FA_CHECK(!s.seq_offsets && !s.block_table && !s.cache_batch_idx,
-                 "kv_gather: slot mode takes no seq_offsets, block_table or cache_batch_idx (the slot is the whole address)");
-        FA_CHECK(reinterpret_cast<uintptr_t>(s.slot_mapping) % 8 == 0, "kv_gather: slot_mapping must be an 8-byte aligned int64 array");
-    } else {
-        if (s.paged) FA_CHECK(s.block_table, "kv_gather: sequence mode on a paged cache needs a block_table");
-        else         FA_CHECK(!s.block_table, "kv_gather: a block_table needs paged != 0");
-        FA_CHECK(s.paged || s.cache_batch_idx || s.batch <= s.num_blocks,
-                 "kv_gather: the cache has %d batch slots for %d sequences (pass cache_batch_idx)", s.num_blocks, s.batch);
-        FA_CHECK(reinterpret_cast<uintptr_t>(s.cu_seqlens) % 4 == 0 && reinterpret_cast<uintptr_t>(s.seq_offsets) % 4 == 0 &&
-                 reinterpret_cast<uintptr_t>(s.block_table) % 4 == 0 && reinterpret_cast<uintptr_t>(s.cache_batch_idx) % 4 == 0,
-                 "kv_gather: cu_seqlens, seq_offsets, block_table and cache_batch_idx must be 4-byte aligned int32 arrays");
-    }
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.v)) & 15) == 0 &&
-             ((s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride) & 7) == 0,
-             "kv_gather: k / v base addresses and strides must be multiples of 16 bytes");
-    const bool kv8 = s.cache_dtype == FA_FP8_E4M3;
-    {
-        const uintptr_t cal = kv8 ? 7 : 15;               // bytes; strides are in elements of 1 / 2 bytes
-        const int64_t sal = 7;
-        FA_CHECK(((reinterpret_cast<uintptr_t>(s.k_cache) | reinterpret_cast<uintptr_t>(s.v_cache)) & cal) == 0 &&
-                 ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
-                 "kv_gather: cache base addresses and strides must be multiples of %d bytes", kv8 ? 8 : 16);
-    }
-    {
-        float* ds[2] = {&s.k_descale, &s.v_descale};      // (checked for every cache type, used by fp8 caches)
-        for (float* d : ds) {
-            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "kv_gather: k / v descales must be finite and >= 0 (0 = 1.0)");
-            if (*d == 0.f) *d = 1.0f;
-        }
-    }
+// fa_kv_gather's argument rules; normalises the block.  *empty: nothing to launch
+static int kv_gather_check(fa_kv_gather_params& s, bool* empty) {
+    const char* op = "kv_gather";
+    bool seq_mode;
+    FA_TRY(kv_rows_check(op, s, s.seq_offsets, "seq_offsets", true, &seq_mode));
+    FA_TRY(kv_rows_check_layout(op, s));
     if ((int64_t)s.nheads * s.head_dim > ((int64_t)1 << 24))
         return fail(FA_ERR_UNSUPPORTED, "kv_gather: nheads x head_dim is too large for one launch");
-    if (s.total_rows == 0 || s.nheads == 0 || s.head_dim == 0) return FA_OK;
-    if (s.num_blocks > 0) {
-        // the output must not lie inside what is read: the rows are written while other workgroups still read the cache
-        const uint64_t ce[2] = {kv_span_bytes(s.num_blocks, s.kc_batch_stride, s.page_block_size, s.kc_row_stride, s.nheads, s.kc_head_stride, s.head_dim, kv8 ? 1 : 2),
-                                kv_span_bytes(s.num_blocks, s.vc_batch_stride, s.page_block_size, s.vc_row_stride, s.nheads, s.vc_head_stride, s.head_dim, kv8 ? 1 : 2)};
-        const uint64_t oe[2] = {kv_span_bytes(1, 0, s.total_rows, s.k_row_stride, s.nheads, s.k_head_stride, s.head_dim, 2),
-                                kv_span_bytes(1, 0, s.total_rows, s.v_row_stride, s.nheads, s.v_head_stride, s.head_dim, 2)};
-        const uint64_t ca[2] = {(uint64_t)reinterpret_cast<uintptr_t>(s.k_cache), (uint64_t)reinterpret_cast<uintptr_t>(s.v_cache)};
-        const uint64_t oa[2] = {(uint64_t)reinterpret_cast<uintptr_t>(s.k), (uint64_t)reinterpret_cast<uintptr_t>(s.v)};
-        for (int o = 0; o < 2; ++o)
-            for (int c = 0; c < 2; ++c)
-                FA_CHECK(oa[o] >= ca[c] + ce[c] || ca[c] >= oa[o] + oe[o], "kv_gather: %s overlaps %s (gather into a separate buffer)",
-                         o ? "v" : "k", c ? "v_cache" : "k_cache");
-    }
-    fa::launch_kv_gather(s, static_cast<hipStream_t>(stream));
-    return check_hip("fa_kv_gather launch");
+    *empty = s.total_rows == 0 || s.nheads == 0 || s.head_dim == 0;
+    if (*empty || s.num_blocks == 0) return FA_OK;
+    // the output must not lie inside what is read: the rows are written while other workgroups still read the cache
+    const int csize = s.cache_dtype == FA_FP8_E4M3 ? 1 : 2;
+    const char* note = " (gather into a separate buffer)";
+    const View in[] = {
+        view_flat("k_cache", s.k_cache, span_bytes(s.num_blocks, s.kc_batch_stride, s.page_block_size, s.kc_row_stride, s.nheads, s.kc_head_stride, s.head_dim, csize), note),
+        view_flat("v_cache", s.v_cache, span_bytes(s.num_blocks, s.vc_batch_stride, s.page_block_size, s.vc_row_stride, s.nheads, s.vc_head_stride, s.head_dim, csize), note),
+    };
+    const View out[] = {
+        view_flat("k", s.k, span_bytes(1, 0, s.total_rows, s.k_row_stride, s.nheads, s.k_head_stride, s.head_dim, 2), note),
+        view_flat("v", s.v, span_bytes(1, 0, s.total_rows, s.v_row_stride, s.nheads, s.v_head_stride, s.head_dim, 2), note),
+    };
+    return check_overlaps(op, out, 2, in, 2, false);
 }
 
-
-// The argument rules that fa_rope_store and fa_qk_norm_rope_store share (the second block begins with the fields of the first).
-// `op` names the entry point in the messages.  no_rope_ok: seqlen_ro == 0 means "no rotation" - positions and the tables may be
-// NULL then and rotary_dim is not read (set to 0).  extra: further read-only spans that an out-of-place output must not overlap.
+// The argument rules that fa_rope_store and fa_qk_norm_rope_store share.  P: either block (the second begins with the fields of
+// the first).  no_rope_ok: see check_rope_tables.  extra: further read-only views that an out-of-place output must not overlap.
 // Normalises the block (descales of 0 -> 1.0, nheads_q = 0 without q); *empty: nothing to launch.
-struct RsSpan { const char* name; uint64_t at, bytes; };
-static int rope_store_check(fa_rope_store_params& s, const char* op, bool no_rope_ok, const RsSpan* extra, int n_extra, bool* empty) {
+template <typename P>
+static int rope_store_check(P& s, const char* op, bool no_rope_ok, const View* extra, int n_extra, bool* empty) {
     *empty = false;
-    const bool no_rope = no_rope_ok && s.seqlen_ro == 0;
-    if (no_rope) {
-        FA_CHECK(s.k, "%s: k must not be NULL", op);
-        s.positions = nullptr; s.rotary_cos = s.rotary_sin = nullptr; s.rotary_dim = 0;
-    } else if (no_rope_ok) {
-        FA_CHECK(s.k, "%s: k must not be NULL", op);
-        FA_CHECK(s.seqlen_ro < 0 || (s.positions && s.rotary_cos && s.rotary_sin),         // (< 0: rejected with the sizes below)
-                 "%s: positions, rotary_cos and rotary_sin may be NULL only where seqlen_ro == 0", op);
-    } else {
-        FA_CHECK(s.k && s.positions && s.rotary_cos && s.rotary_sin, "%s: k, positions, rotary_cos and rotary_sin must not be NULL", op);
-    }
+    if (no_rope_ok) FA_CHECK(s.k, "%s: k must not be NULL", op);
+    bool no_rope;
+    FA_TRY(check_rope_tables(op, s, no_rope_ok, &no_rope));
     FA_CHECK((s.q != nullptr) == (s.q_out != nullptr), "%s: q and q_out go together (%s given)", op, s.q ? "q without q_out" : "q_out without q");
     FA_CHECK((s.k_cache != nullptr) == (s.v_cache != nullptr), "%s: k_cache and v_cache go together (both, or neither: rotate only)", op);
     const bool cached = s.k_cache != nullptr;
@@ -862,43 +930,26 @@ static int rope_store_check(fa_rope_store_params& s, const char* op, bool no_rop
         FA_CHECK(!s.v && !s.slot_mapping, "%s: v and slot_mapping need caches (the rotate-only form takes neither)", op);
         FA_CHECK(s.q || s.k_out, "%s: the rotate-only form needs q or k_out (nothing would be written)", op);
     }
-    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "%s: q / k / v dtype must be fp16 or bf16", op);
-    if (cached)
-        FA_CHECK(s.cache_dtype == s.dtype || s.cache_dtype == FA_FP8_E4M3, "%s: the cache dtype must be the k / v dtype or fp8-e4m3", op);
+    FA_TRY(check_io_dtype(op, s.dtype, "q / k / v dtype"));
+    if (cached) FA_TRY(check_cache_dtype(op, s.cache_dtype, s.dtype));
     FA_CHECK(s.total_rows >= 0 && s.nheads_q >= 0 && s.nheads_k >= 0 && s.head_dim >= 0 && s.seqlen_ro >= 0 && s.num_blocks >= 0,
              "%s sizes must be non-negative", op);
     FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "%s head_dim must be a multiple of 8 and <= 256, got %d", op, s.head_dim);
-    if (!no_rope) FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "%s: rotary_dim must be positive and divisible by 16, got %d", op, s.rotary_dim);
-    FA_CHECK(s.rotary_dim <= s.head_dim, "%s: rotary_dim must be <= head_dim (%d > %d)", op, s.rotary_dim, s.head_dim);
+    FA_TRY(check_rope_dims(op, s, no_rope));
     FA_CHECK(s.q_row_stride >= 0 && s.q_head_stride >= 0 && s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.v_row_stride >= 0 &&
              s.v_head_stride >= 0 && s.qo_row_stride >= 0 && s.qo_head_stride >= 0 && s.ko_row_stride >= 0 && s.ko_head_stride >= 0 &&
              s.kc_batch_stride >= 0 && s.kc_row_stride >= 0 && s.kc_head_stride >= 0 && s.vc_batch_stride >= 0 &&
              s.vc_row_stride >= 0 && s.vc_head_stride >= 0, "%s strides must be non-negative", op);
     if (cached) FA_CHECK(s.page_block_size > 0, "%s: page_block_size must be positive (a contiguous cache: S_max)", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.q) | reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.v) |
-               reinterpret_cast<uintptr_t>(s.q_out) | reinterpret_cast<uintptr_t>(s.k_out)) & 15) == 0 &&
+    FA_CHECK(((addr(s.q) | addr(s.k) | addr(s.v) | addr(s.q_out) | addr(s.k_out)) & 15) == 0 &&
              ((s.q_row_stride | s.q_head_stride | s.k_row_stride | s.k_head_stride | s.v_row_stride | s.v_head_stride |
                s.qo_row_stride | s.qo_head_stride | s.ko_row_stride | s.ko_head_stride) & 7) == 0,
              "%s: q / k / v / q_out / k_out base addresses and strides must be multiples of 16 bytes", op);
     const bool kv8 = cached && s.cache_dtype == FA_FP8_E4M3;
-    if (cached) {
-        const uintptr_t cal = kv8 ? 7 : 15;               // bytes; strides are in elements of 1 / 2 bytes
-        const int64_t sal = 7;
-        FA_CHECK(((reinterpret_cast<uintptr_t>(s.k_cache) | reinterpret_cast<uintptr_t>(s.v_cache)) & cal) == 0 &&
-                 ((s.kc_batch_stride | s.kc_row_stride | s.kc_head_stride | s.vc_batch_stride | s.vc_row_stride | s.vc_head_stride) & sal) == 0,
-                 "%s: cache base addresses and strides must be multiples of %d bytes", op, kv8 ? 8 : 16);
-    }
-    FA_CHECK(reinterpret_cast<uintptr_t>(s.positions) % 8 == 0 && reinterpret_cast<uintptr_t>(s.slot_mapping) % 8 == 0,
-             "%s: positions and slot_mapping must be 8-byte aligned int64 arrays", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.rotary_cos) | reinterpret_cast<uintptr_t>(s.rotary_sin)) & 15) == 0,
-             "%s: rotary_cos / rotary_sin must be 16-byte aligned", op);
-    {
-        float* ds[2] = {&s.k_descale, &s.v_descale};      // (checked for every cache type, used by fp8 caches)
-        for (float* d : ds) {
-            FA_CHECK(*d >= 0.f && *d <= 3.402823466e38f, "%s: k / v descales must be finite and >= 0 (0 = 1.0)", op);
-            if (*d == 0.f) *d = 1.0f;
-        }
-    }
+    if (cached) FA_TRY(check_cache_align(op, s, kv8));
+    FA_CHECK(addr(s.positions) % 8 == 0 && addr(s.slot_mapping) % 8 == 0, "%s: positions and slot_mapping must be 8-byte aligned int64 arrays", op);
+    FA_TRY(check_rope_align(op, s));
+    FA_TRY(check_descales(op, s.k_descale, s.v_descale));
     if ((int64_t)(s.nheads_q + 2 * (int64_t)s.nheads_k) * s.head_dim > ((int64_t)1 << 24))
         return fail(FA_ERR_UNSUPPORTED, "%s: (nheads_q + 2 nheads_k) x head_dim is too large for one launch", op);
     if (!s.q) s.nheads_q = 0;
@@ -910,112 +961,48 @@ static int rope_store_check(fa_rope_store_params& s, const char* op, bool no_rop
         FA_CHECK(s.k_row_stride == s.ko_row_stride && s.k_head_stride == s.ko_head_stride,
                  "%s: k_out shares k's base address but not its strides (in place needs both equal)", op);
     if (s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0)) { *empty = true; return FA_OK; }
-    {
-        // an out-of-place output must not lie inside anything that is read or inside a cache: other workgroups still read and write them
-        typedef RsSpan Span;
-        const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
-        const Span in[] = {
-            {"q", (uint64_t)reinterpret_cast<uintptr_t>(s.q), (s.q && Hq) ? kv_span_bytes(1, 0, T, s.q_row_stride, Hq, s.q_head_stride, D, 2) : 0},
-            {"k", (uint64_t)reinterpret_cast<uintptr_t>(s.k), Hk ? kv_span_bytes(1, 0, T, s.k_row_stride, Hk, s.k_head_stride, D, 2) : 0},
-            {"v", (uint64_t)reinterpret_cast<uintptr_t>(s.v), (s.v && Hk) ? kv_span_bytes(1, 0, T, s.v_row_stride, Hk, s.v_head_stride, D, 2) : 0},
-            {"positions", (uint64_t)reinterpret_cast<uintptr_t>(s.positions), s.positions ? (uint64_t)T * 8 : 0},
-            {"slot_mapping", (uint64_t)reinterpret_cast<uintptr_t>(s.slot_mapping), s.slot_mapping ? (uint64_t)T * 8 : 0},
-            {"rotary_cos", (uint64_t)reinterpret_cast<uintptr_t>(s.rotary_cos), (uint64_t)s.seqlen_ro * half * 2},
-            {"rotary_sin", (uint64_t)reinterpret_cast<uintptr_t>(s.rotary_sin), (uint64_t)s.seqlen_ro * half * 2},
-            {"k_cache", (uint64_t)reinterpret_cast<uintptr_t>(s.k_cache), (cached && Hk && s.num_blocks)
-                ? kv_span_bytes(s.num_blocks, s.kc_batch_stride, s.page_block_size, s.kc_row_stride, Hk, s.kc_head_stride, D, kv8 ? 1 : 2) : 0},
-            {"v_cache", (uint64_t)reinterpret_cast<uintptr_t>(s.v_cache), (cached && Hk && s.num_blocks)
-                ? kv_span_bytes(s.num_blocks, s.vc_batch_stride, s.page_block_size, s.vc_row_stride, Hk, s.vc_head_stride, D, kv8 ? 1 : 2) : 0},
-        };
-        const Span out[2] = {
-            {"q_out", (uint64_t)reinterpret_cast<uintptr_t>(s.q_out),
-             (s.q && Hq && !q_inplace) ? kv_span_bytes(1, 0, T, s.qo_row_stride, Hq, s.qo_head_stride, D, 2) : 0},
-            {"k_out", (uint64_t)reinterpret_cast<uintptr_t>(s.k_out),
-             (s.k_out && Hk && !k_inplace) ? kv_span_bytes(1, 0, T, s.ko_row_stride, Hk, s.ko_head_stride, D, 2) : 0},
-        };
-        for (const Span& o : out) {
-            for (const Span& i : in)
-                if (o.bytes && i.bytes)
-                    FA_CHECK(o.at >= i.at + i.bytes || i.at >= o.at + o.bytes,
-                             "%s: %s overlaps %s without being in place (in place: the same base address and strides)", op, o.name, i.name);
-            for (int e = 0; e < n_extra; ++e)
-                if (o.bytes && extra[e].bytes)
-                    FA_CHECK(o.at >= extra[e].at + extra[e].bytes || extra[e].at >= o.at + o.bytes, "%s: %s overlaps %s", op, o.name, extra[e].name);
-        }
+    // an out-of-place output must not lie inside anything that is read or inside a cache: other workgroups still read and write
+    // them.  One address range per tensor (an in-place output: empty, it is exempt)
+    const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
+    const int csize = kv8 ? 1 : 2;
+    const char* note = " without being in place (in place: the same base address and strides)";
+    const View in[] = {
+        view_flat("q", s.q, Hq ? span_bytes(1, 0, T, s.q_row_stride, Hq, s.q_head_stride, D, 2) : 0, note),
+        view_flat("k", s.k, Hk ? span_bytes(1, 0, T, s.k_row_stride, Hk, s.k_head_stride, D, 2) : 0, note),
+        view_flat("v", s.v, Hk ? span_bytes(1, 0, T, s.v_row_stride, Hk, s.v_head_stride, D, 2) : 0, note),
+        view_flat("positions", s.positions, (uint64_t)T * 8, note),
+        view_flat("slot_mapping", s.slot_mapping, (uint64_t)T * 8, note),
+        view_flat("rotary_cos", s.rotary_cos, (uint64_t)s.seqlen_ro * half * 2, note),
+        view_flat("rotary_sin", s.rotary_sin, (uint64_t)s.seqlen_ro * half * 2, note),
+        view_flat("k_cache", s.k_cache, (Hk && s.num_blocks)
+            ? span_bytes(s.num_blocks, s.kc_batch_stride, s.page_block_size, s.kc_row_stride, Hk, s.kc_head_stride, D, csize) : 0, note),
+        view_flat("v_cache", s.v_cache, (Hk && s.num_blocks)
+            ? span_bytes(s.num_blocks, s.vc_batch_stride, s.page_block_size, s.vc_row_stride, Hk, s.vc_head_stride, D, csize) : 0, note),
+    };
+    const View out[2] = {
+        view_flat("q_out", s.q_out, (s.q && Hq && !q_inplace) ? span_bytes(1, 0, T, s.qo_row_stride, Hq, s.qo_head_stride, D, 2) : 0, note),
+        view_flat("k_out", s.k_out, (Hk && !k_inplace) ? span_bytes(1, 0, T, s.ko_row_stride, Hk, s.ko_head_stride, D, 2) : 0, note),
+    };
+    for (const View& o : out) {                           // (q_out against everything, then k_out)
+        FA_TRY(check_overlaps(op, &o, 1, in, (int)(sizeof(in) / sizeof(in[0])), false));
+        FA_TRY(check_overlaps(op, &o, 1, extra, n_extra, false));
     }
     return FA_OK;
 }
 
-int fa_rope_store(const fa_rope_store_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_rope_store_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_rope_store_params), "fa_rope_store_params::struct_size %zu is smaller than this library's %zu",
-             sp->struct_size, sizeof(fa_rope_store_params));
-    fa_rope_store_params s = *sp;
-    bool empty;
-    const int rc = rope_store_check(s, "rope_store", false, nullptr, 0, &empty);
-    if (rc != FA_OK || empty) return rc;
-    fa::launch_rope_store(s, static_cast<hipStream_t>(stream));
-    return check_hip("fa_rope_store launch");
-}
-
-int fa_qk_norm_rope_store(const fa_qk_norm_rope_store_params* sp, void* stream) {
-    // the block begins with fa_rope_store_params, field for field: the shared rules read (and normalise) that part
-    static_assert(offsetof(fa_qk_norm_rope_store_params, q_weight) == sizeof(fa_rope_store_params) &&
-                  offsetof(fa_qk_norm_rope_store_params, v_descale) == offsetof(fa_rope_store_params, v_descale) &&
-                  offsetof(fa_qk_norm_rope_store_params, k_cache) == offsetof(fa_rope_store_params, k_cache) &&
-                  offsetof(fa_qk_norm_rope_store_params, positions) == offsetof(fa_rope_store_params, positions),
-                  "fa_qk_norm_rope_store_params must begin with the fields of fa_rope_store_params");
-    FA_CHECK(sp, "fa_qk_norm_rope_store_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_qk_norm_rope_store_params),
-             "fa_qk_norm_rope_store_params::struct_size %zu is smaller than this library's %zu", sp->struct_size, sizeof(fa_qk_norm_rope_store_params));
-    fa_qk_norm_rope_store_params s = *sp;
+// fa_qk_norm_rope_store's argument rules: the norm's, then fa_rope_store's on the same block
+static int qk_norm_rope_store_check(fa_qk_norm_rope_store_params& s, bool* empty) {
     const char* op = "qk_norm_rope_store";
-    const bool weights = s.q_weight || s.k_weight;
-    if (weights)
-        FA_CHECK(s.weight_dtype == FA_FP32 || (s.weight_dtype == s.dtype && (s.dtype == FA_FP16 || s.dtype == FA_BF16)),
-                 "%s: weight_dtype must be the q / k dtype or fp32", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.q_weight) | reinterpret_cast<uintptr_t>(s.k_weight)) & 15) == 0,
-             "%s: q_weight / k_weight must be 16-byte aligned", op);
-    FA_CHECK(s.eps >= 0.f && s.eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
-    FA_CHECK(s.weight_offset >= -3.402823466e38f && s.weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
+    if (s.q_weight || s.k_weight) FA_TRY(check_weight_dtype(op, s.weight_dtype, s.dtype, "q / k dtype"));
+    FA_CHECK(((addr(s.q_weight) | addr(s.k_weight)) & 15) == 0, "%s: q_weight / k_weight must be 16-byte aligned", op);
+    FA_TRY(check_norm_scalars(op, s.eps, s.weight_offset));
     const uint64_t wbytes = (uint64_t)(s.head_dim > 0 ? s.head_dim : 0) * (s.weight_dtype == FA_FP32 ? 4 : 2);
-    const RsSpan extra[2] = {{"q_weight", (uint64_t)reinterpret_cast<uintptr_t>(s.q_weight), s.q_weight ? wbytes : 0},
-                             {"k_weight", (uint64_t)reinterpret_cast<uintptr_t>(s.k_weight), s.k_weight ? wbytes : 0}};
-    fa_rope_store_params base;
-    memcpy(&base, &s, sizeof(base));
-    bool empty;
-    const int rc = rope_store_check(base, op, true, extra, 2, &empty);
-    if (rc != FA_OK || empty) return rc;
-    memcpy(&s, &base, sizeof(base));
-    s.struct_size = sizeof(s);
-    fa::launch_qk_norm_rope_store(s, static_cast<hipStream_t>(stream));
-    return check_hip("fa_qk_norm_rope_store launch");
+    const View extra[2] = {view_flat("q_weight", s.q_weight, wbytes), view_flat("k_weight", s.k_weight, wbytes)};
+    return rope_store_check(s, op, true, extra, 2, empty);
 }
 
-}  // extern "C"
-
-// A [rows, heads, head_dim] view for fa_qk_norm_rope_bwd's overlap rules (bytes; rows, heads, head_dim > 0, strides >= 0)
-struct QnbView { const char* name; uint64_t at, row_stride, row_bytes, bytes; };
-static QnbView qnb_view(const char* name, const void* p, int64_t rows, int64_t rs, int64_t heads, int64_t hs, int64_t d) {
-    QnbView v = {name, (uint64_t)reinterpret_cast<uintptr_t>(p), (uint64_t)rs * 2, 0, 0};
-    if (p && rows > 0 && heads > 0 && d > 0) {
-        v.row_bytes = (uint64_t)((heads - 1) * hs + d) * 2;
-        v.bytes = (uint64_t)(rows - 1) * v.row_stride + v.row_bytes;
-    }
-    return v;
-}
-// no common element: disjoint address ranges, or the heads of one packed buffer - the same row stride, and within a row the
-// one view ends before the other begins
-static bool qnb_disjoint(const QnbView& a, const QnbView& b) {
-    if (!a.bytes || !b.bytes || a.at >= b.at + b.bytes || b.at >= a.at + a.bytes) return true;
-    const QnbView& lo = a.at <= b.at ? a : b;
-    const QnbView& hi = a.at <= b.at ? b : a;
-    const uint64_t delta = hi.at - lo.at;
-    return a.row_stride == b.row_stride && delta < lo.row_stride && lo.row_bytes <= delta && delta + hi.row_bytes <= lo.row_stride;
-}
-
-// fa_qk_norm_rope_bwd's argument rules (the forward's, rope_store_check above, where the two ops share a field); normalises the
-// block (no rotation: the pointers and rotary_dim cleared; no q: nheads_q = 0).  query: the workspace itself is not looked at
+// fa_qk_norm_rope_bwd's argument rules (the forward's where the two ops share a field); normalises the block (no rotation: the
+// pointers and rotary_dim cleared; no q: nheads_q = 0).  query: the workspace itself is not looked at
 static int qk_norm_rope_bwd_check(fa_qk_norm_rope_bwd_params& s, bool query) {
     const char* op = "qk_norm_rope_bwd";
     FA_CHECK(s.k && s.dk_out, "%s: k and dk_out must not be NULL", op);
@@ -1024,34 +1011,25 @@ static int qk_norm_rope_bwd_check(fa_qk_norm_rope_bwd_params& s, bool query) {
     FA_CHECK(!s.dq_weight || s.q_weight, "%s: dq_weight needs q_weight", op);
     FA_CHECK(!s.dk_weight || s.k_weight, "%s: dk_weight needs k_weight", op);
     FA_CHECK(s.reserved == 0 && s.reserved1[0] == 0 && s.reserved1[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
-    if (s.seqlen_ro == 0) {
-        s.positions = nullptr; s.rotary_cos = s.rotary_sin = nullptr; s.rotary_dim = 0;
-    } else {
-        FA_CHECK(s.seqlen_ro < 0 || (s.positions && s.rotary_cos && s.rotary_sin),                 // (< 0: rejected with the sizes below)
-                 "%s: positions, rotary_cos and rotary_sin may be NULL only where seqlen_ro == 0", op);
-    }
-    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16, "%s: q / k dtype must be fp16 or bf16", op);
-    if (s.q_weight || s.k_weight)
-        FA_CHECK(s.weight_dtype == FA_FP32 || s.weight_dtype == s.dtype, "%s: weight_dtype must be the q / k dtype or fp32", op);
+    bool no_rope;
+    FA_TRY(check_rope_tables(op, s, true, &no_rope));
+    FA_TRY(check_io_dtype(op, s.dtype, "q / k dtype"));
+    if (s.q_weight || s.k_weight) FA_TRY(check_weight_dtype(op, s.weight_dtype, s.dtype, "q / k dtype"));
     FA_CHECK(s.total_rows >= 0 && s.nheads_q >= 0 && s.nheads_k >= 0 && s.head_dim >= 0 && s.seqlen_ro >= 0, "%s sizes must be non-negative", op);
     FA_CHECK(s.head_dim % 8 == 0 && s.head_dim <= 256, "%s head_dim must be a multiple of 8 and <= 256, got %d", op, s.head_dim);
-    if (s.seqlen_ro > 0) FA_CHECK(s.rotary_dim > 0 && s.rotary_dim % 16 == 0, "%s: rotary_dim must be positive and divisible by 16, got %d", op, s.rotary_dim);
-    FA_CHECK(s.rotary_dim <= s.head_dim, "%s: rotary_dim must be <= head_dim (%d > %d)", op, s.rotary_dim, s.head_dim);
+    FA_TRY(check_rope_dims(op, s, no_rope));
     FA_CHECK(s.dqo_row_stride >= 0 && s.dqo_head_stride >= 0 && s.dko_row_stride >= 0 && s.dko_head_stride >= 0 && s.q_row_stride >= 0 &&
              s.q_head_stride >= 0 && s.k_row_stride >= 0 && s.k_head_stride >= 0 && s.dq_row_stride >= 0 && s.dq_head_stride >= 0 &&
              s.dk_row_stride >= 0 && s.dk_head_stride >= 0, "%s strides must be non-negative", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.dq_out) | reinterpret_cast<uintptr_t>(s.dk_out) | reinterpret_cast<uintptr_t>(s.q) |
-               reinterpret_cast<uintptr_t>(s.k) | reinterpret_cast<uintptr_t>(s.dq) | reinterpret_cast<uintptr_t>(s.dk)) & 15) == 0 &&
+    FA_CHECK(((addr(s.dq_out) | addr(s.dk_out) | addr(s.q) | addr(s.k) | addr(s.dq) | addr(s.dk)) & 15) == 0 &&
              ((s.dqo_row_stride | s.dqo_head_stride | s.dko_row_stride | s.dko_head_stride | s.q_row_stride | s.q_head_stride |
                s.k_row_stride | s.k_head_stride | s.dq_row_stride | s.dq_head_stride | s.dk_row_stride | s.dk_head_stride) & 7) == 0,
              "%s: dq_out / dk_out / q / k / dq / dk base addresses and strides must be multiples of 16 bytes", op);
-    FA_CHECK(reinterpret_cast<uintptr_t>(s.positions) % 8 == 0, "%s: positions must be an 8-byte aligned int64 array", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.rotary_cos) | reinterpret_cast<uintptr_t>(s.rotary_sin)) & 15) == 0,
-             "%s: rotary_cos / rotary_sin must be 16-byte aligned", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.q_weight) | reinterpret_cast<uintptr_t>(s.k_weight) | reinterpret_cast<uintptr_t>(s.dq_weight) |
-               reinterpret_cast<uintptr_t>(s.dk_weight)) & 15) == 0, "%s: q_weight / k_weight / dq_weight / dk_weight must be 16-byte aligned", op);
-    FA_CHECK(s.eps >= 0.f && s.eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
-    FA_CHECK(s.weight_offset >= -3.402823466e38f && s.weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
+    FA_CHECK(addr(s.positions) % 8 == 0, "%s: positions must be an 8-byte aligned int64 array", op);
+    FA_TRY(check_rope_align(op, s));
+    FA_CHECK(((addr(s.q_weight) | addr(s.k_weight) | addr(s.dq_weight) | addr(s.dk_weight)) & 15) == 0,
+             "%s: q_weight / k_weight / dq_weight / dk_weight must be 16-byte aligned", op);
+    FA_TRY(check_norm_scalars(op, s.eps, s.weight_offset));
     if ((int64_t)(s.nheads_q + (int64_t)s.nheads_k) * s.head_dim > ((int64_t)1 << 24))
         return fail(FA_ERR_UNSUPPORTED, "%s: (nheads_q + nheads_k) x head_dim is too large for one launch", op);
     if (!s.q) { s.nheads_q = 0; s.dq_out = nullptr; }
@@ -1063,124 +1041,54 @@ static int qk_norm_rope_bwd_check(fa_qk_norm_rope_bwd_params& s, bool query) {
         FA_CHECK(s.dk_row_stride == s.dko_row_stride && s.dk_head_stride == s.dko_head_stride,
                  "%s: dk shares dk_out's base address but not its strides (in place needs both equal)", op);
     const size_t need = fa::qk_norm_rope_bwd_workspace_bytes(s);
-    if (!query && need) {
+    if (query) return FA_OK;                              // (the query is about sizes: it does not look at where the tensors lie)
+    if (need) {
         FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_qk_norm_rope_bwd_workspace_bytes() reports %zu",
                  op, s.workspace ? s.workspace_bytes : (size_t)0, need);
-        FA_CHECK(reinterpret_cast<uintptr_t>(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+        FA_CHECK(addr(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
     }
-    if (!query) {                                         // (the query is about sizes: it does not look at where the tensors lie)
-        // an output must share no element with anything that is read (the exact in-place aliasing apart: that output is exempt, the
-        // caller guarantees that its view shares no element with the others), with another output or with the workspace
-        const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
-        const uint64_t wbytes = (uint64_t)D * (s.weight_dtype == FA_FP32 ? 4 : 2);
-        auto flat = [](const char* name, const void* p, uint64_t bytes) {
-            return QnbView{name, (uint64_t)reinterpret_cast<uintptr_t>(p), 0, p ? bytes : 0, p ? bytes : 0};
-        };
-        const QnbView in[] = {
-            qnb_view("dq_out", s.dq_out, T, s.dqo_row_stride, Hq, s.dqo_head_stride, D),
-            qnb_view("dk_out", s.dk_out, T, s.dko_row_stride, Hk, s.dko_head_stride, D),
-            qnb_view("q", s.q, T, s.q_row_stride, Hq, s.q_head_stride, D),
-            qnb_view("k", s.k, T, s.k_row_stride, Hk, s.k_head_stride, D),
-            flat("positions", s.positions, (uint64_t)T * 8),
-            flat("rotary_cos", s.rotary_cos, (uint64_t)s.seqlen_ro * half * 2),
-            flat("rotary_sin", s.rotary_sin, (uint64_t)s.seqlen_ro * half * 2),
-            flat("q_weight", s.q_weight, wbytes),
-            flat("k_weight", s.k_weight, wbytes),
-        };
-        const QnbView out[] = {
-            qnb_view("dq", q_inplace ? nullptr : s.dq, T, s.dq_row_stride, Hq, s.dq_head_stride, D),
-            qnb_view("dk", k_inplace ? nullptr : s.dk, T, s.dk_row_stride, Hk, s.dk_head_stride, D),
-            flat("dq_weight", s.dq_weight, wbytes),
-            flat("dk_weight", s.dk_weight, wbytes),
-            flat("workspace", need ? s.workspace : nullptr, need),
-        };
-        const int n_out = (int)(sizeof(out) / sizeof(out[0]));
-        for (int o = 0; o < n_out; ++o) {
-            for (int i = 0; i < (int)(sizeof(in) / sizeof(in[0])); ++i)
-                FA_CHECK(qnb_disjoint(out[o], in[i]), "%s: %s overlaps %s%s", op, out[o].name, in[i].name,
-                         o < 2 && i < 2 ? " without being in place (in place: the gradient's base address and strides)" : "");
-            for (int p = o + 1; p < n_out; ++p)
-                FA_CHECK(qnb_disjoint(out[o], out[p]), "%s: %s overlaps %s", op, out[o].name, out[p].name);
-        }
-    }
-    return FA_OK;
+    // an output must share no element with anything that is read (the exact in-place aliasing apart: that output is exempt, the
+    // caller guarantees that its view shares no element with the others), with another output or with the workspace.  The q / k
+    // tensors are [rows, heads, head_dim] views: the heads of one packed buffer are disjoint
+    const int64_t T = s.total_rows, D = s.head_dim, Hq = s.nheads_q, Hk = s.nheads_k, half = s.rotary_dim / 2;
+    const uint64_t wbytes = (uint64_t)D * (s.weight_dtype == FA_FP32 ? 4 : 2);
+    const char* note = " without being in place (in place: the gradient's base address and strides)";
+    auto heads = [D](const char* name, const void* p, int64_t rows, int64_t rs, int64_t h, int64_t hs, const char* nt = nullptr) {
+        return view_rows(name, h > 0 && D > 0 ? p : nullptr, rows, rs, (h - 1) * hs + D, 2, nt);
+    };
+    const View in[] = {
+        heads("dq_out", s.dq_out, T, s.dqo_row_stride, Hq, s.dqo_head_stride, note),
+        heads("dk_out", s.dk_out, T, s.dko_row_stride, Hk, s.dko_head_stride, note),
+        heads("q", s.q, T, s.q_row_stride, Hq, s.q_head_stride),
+        heads("k", s.k, T, s.k_row_stride, Hk, s.k_head_stride),
+        view_flat("positions", s.positions, (uint64_t)T * 8),
+        view_flat("rotary_cos", s.rotary_cos, (uint64_t)s.seqlen_ro * half * 2),
+        view_flat("rotary_sin", s.rotary_sin, (uint64_t)s.seqlen_ro * half * 2),
+        view_flat("q_weight", s.q_weight, wbytes),
+        view_flat("k_weight", s.k_weight, wbytes),
+    };
+    const View out[] = {
+        heads("dq", q_inplace ? nullptr : s.dq, T, s.dq_row_stride, Hq, s.dq_head_stride, note),
+        heads("dk", k_inplace ? nullptr : s.dk, T, s.dk_row_stride, Hk, s.dk_head_stride, note),
+        view_flat("dq_weight", s.dq_weight, wbytes),
+        view_flat("dk_weight", s.dk_weight, wbytes),
+        view_flat("workspace", need ? s.workspace : nullptr, need),
+    };
+    return check_overlaps(op, out, (int)(sizeof(out) / sizeof(out[0])), in, (int)(sizeof(in) / sizeof(in[0])), true);
 }
 
-extern "C" {
-
-size_t fa_qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params* sp) {
-    if (!sp || sp->struct_size < sizeof(fa_qk_norm_rope_bwd_params)) return 0;
-    fa_qk_norm_rope_bwd_params s = *sp;
-    if (qk_norm_rope_bwd_check(s, true) != FA_OK) return 0;
-    return fa::qk_norm_rope_bwd_workspace_bytes(s);
-}
-
-int fa_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_qk_norm_rope_bwd_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_qk_norm_rope_bwd_params),
-             "fa_qk_norm_rope_bwd_params::struct_size %zu is smaller than this library's %zu", sp->struct_size, sizeof(fa_qk_norm_rope_bwd_params));
-    fa_qk_norm_rope_bwd_params s = *sp;
-    const int rc = qk_norm_rope_bwd_check(s, false);
-    if (rc != FA_OK) return rc;
-    const bool empty = s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0);
-    if (empty && !s.dq_weight && !s.dk_weight) return FA_OK;
-    s.struct_size = sizeof(s);
-    fa::launch_qk_norm_rope_bwd(s, static_cast<hipStream_t>(stream));      // (an empty problem: a wanted dw is set to zeros, no kernel)
-    return check_hip("fa_qk_norm_rope_bwd launch");
-}
-
-}  // extern "C"
-
-// A [rows, n] view for the overlap rules of fa_add_norm / fa_add_norm_bwd (bytes; a NULL pointer or no rows: empty)
-struct AnView { const char* name; uint64_t at, row_stride, row_bytes, bytes; };
-static AnView an_view(const char* name, const void* p, int64_t rows, int64_t rs, int64_t n, int esize) {
-    AnView v = {name, (uint64_t)reinterpret_cast<uintptr_t>(p), (uint64_t)rs * esize, 0, 0};
-    if (p && rows > 0 && n > 0) {
-        v.row_bytes = (uint64_t)n * esize;
-        v.bytes = (uint64_t)(rows - 1) * v.row_stride + v.row_bytes;
-    }
-    return v;
-}
-static AnView an_flat(const char* name, const void* p, uint64_t bytes) {
-    return AnView{name, (uint64_t)reinterpret_cast<uintptr_t>(p), 0, p ? bytes : 0, p ? bytes : 0};
-}
-// no common element: disjoint address ranges, or column ranges of one wider buffer - the same row stride, and within a row the one
-// view ends before the other begins
-static bool an_disjoint(const AnView& a, const AnView& b) {
-    if (!a.bytes || !b.bytes || a.at >= b.at + b.bytes || b.at >= a.at + a.bytes) return true;
-    const AnView& lo = a.at <= b.at ? a : b;
-    const AnView& hi = a.at <= b.at ? b : a;
-    const uint64_t delta = hi.at - lo.at;
-    return a.row_stride == b.row_stride && delta < lo.row_stride && lo.row_bytes <= delta && delta + hi.row_bytes <= lo.row_stride;
-}
-// every output against every input and against the later outputs; (ex_out[k], ex_in[k]), k < n_ex: the exact in-place pairs, exempt
-static int an_overlaps(const char* op, const AnView* out, int n_out, const AnView* in, int n_in, const int* ex_out, const int* ex_in,
-                       int n_ex) {
-    for (int o = 0; o < n_out; ++o) {
-        for (int i = 0; i < n_in; ++i) {
-            bool exempt = false;
-            for (int k = 0; k < n_ex; ++k) exempt = exempt || (ex_out[k] == o && ex_in[k] == i);
-            FA_CHECK(exempt || an_disjoint(out[o], in[i]), "%s: %s overlaps %s (in place needs the same base address, row stride and dtype)",
-                     op, out[o].name, in[i].name);
-        }
-        for (int p = o + 1; p < n_out; ++p) FA_CHECK(an_disjoint(out[o], out[p]), "%s: %s overlaps %s", op, out[o].name, out[p].name);
-    }
-    return FA_OK;
-}
 static bool an_is_io_or_fp32(int t, int dtype) { return t == dtype || t == FA_FP32; }
 static bool an_stride_ok(int64_t rs, int64_t rows, int n) { return rs >= 0 && rs % 8 == 0 && (rows <= 1 || rs >= n); }
 
 // what fa_add_norm and fa_add_norm_bwd share: dtype, n, rows, the weight, eps, weight_offset
 static int add_norm_common_check(const char* op, int dtype, int weight_dtype, int64_t rows, int n, const void* weight, float eps,
                                  float weight_offset) {
-    FA_CHECK(dtype == FA_FP16 || dtype == FA_BF16, "%s: dtype must be fp16 or bf16", op);
-    FA_CHECK(an_is_io_or_fp32(weight_dtype, dtype), "%s: weight_dtype must be the io dtype or fp32", op);
+    FA_TRY(check_io_dtype(op, dtype, "dtype"));
+    FA_TRY(check_weight_dtype(op, weight_dtype, dtype, "io dtype"));
     FA_CHECK(weight, "%s: weight must not be NULL", op);
     FA_CHECK(rows >= 0, "%s: rows must be non-negative", op);
     FA_CHECK(n >= 8 && n <= 16384 && n % 8 == 0, "%s: n must be a multiple of 8 in [8, 16384], got %d", op, n);
-    FA_CHECK(eps >= 0.f && eps <= 3.402823466e38f, "%s: eps must be finite and >= 0", op);
-    FA_CHECK(weight_offset >= -3.402823466e38f && weight_offset <= 3.402823466e38f, "%s: weight_offset must be finite", op);
-    return FA_OK;
+    return check_norm_scalars(op, eps, weight_offset);
 }
 
 // fa_add_norm's argument rules
@@ -1189,8 +1097,7 @@ static int add_norm_check(const fa_add_norm_params& s) {
     FA_CHECK(s.x && s.out, "%s: x and out must not be NULL", op);
     FA_CHECK(!s.residual || s.residual_out, "%s: a residual needs residual_out", op);
     FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
-    const int rc = add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset);
-    if (rc != FA_OK) return rc;
+    FA_TRY(add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset));
     if (s.residual) FA_CHECK(an_is_io_or_fp32(s.residual_dtype, s.dtype), "%s: residual_dtype must be the io dtype or fp32", op);
     if (s.residual_out) {
         FA_CHECK(an_is_io_or_fp32(s.residual_out_dtype, s.dtype), "%s: residual_out_dtype must be the io dtype or fp32", op);
@@ -1201,8 +1108,7 @@ static int add_norm_check(const fa_add_norm_params& s) {
              (!s.residual || an_stride_ok(s.residual_row_stride, s.rows, s.n)) &&
              (!s.residual_out || an_stride_ok(s.residual_out_row_stride, s.rows, s.n)),
              "%s: row strides must be non-negative multiples of 8 elements and (rows > 1) at least n", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.x) | reinterpret_cast<uintptr_t>(s.out) | reinterpret_cast<uintptr_t>(s.residual) |
-               reinterpret_cast<uintptr_t>(s.residual_out) | reinterpret_cast<uintptr_t>(s.weight) | reinterpret_cast<uintptr_t>(s.bias)) & 15) == 0,
+    FA_CHECK(((addr(s.x) | addr(s.out) | addr(s.residual) | addr(s.residual_out) | addr(s.weight) | addr(s.bias)) & 15) == 0,
              "%s: x / residual / out / residual_out / weight / bias must be 16-byte aligned", op);
     if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
     const bool x_inplace = s.out == s.x, r_inplace = s.residual_out && s.residual_out == s.residual;
@@ -1210,22 +1116,24 @@ static int add_norm_check(const fa_add_norm_params& s) {
     if (r_inplace)
         FA_CHECK(s.residual_out_row_stride == s.residual_row_stride && s.residual_out_dtype == s.residual_dtype,
                  "%s: residual_out shares residual's base address but not its row stride and dtype (in place needs all equal)", op);
+    // [rows, n] views: column ranges of one wider buffer are disjoint
     const int rsz = s.residual_dtype == FA_FP32 ? 4 : 2, rosz = s.residual_out_dtype == FA_FP32 ? 4 : 2;
     const uint64_t wbytes = (uint64_t)s.n * (s.weight_dtype == FA_FP32 ? 4 : 2);
-    const AnView in[] = {
-        an_view("x", s.x, s.rows, s.x_row_stride, s.n, 2),
-        an_view("residual", s.residual, s.rows, s.residual_row_stride, s.n, rsz),
-        an_flat("weight", s.weight, wbytes),
-        an_flat("bias", s.bias, wbytes),
+    const char* note = " (in place needs the same base address, row stride and dtype)";
+    const View in[] = {
+        view_rows("x", s.x, s.rows, s.x_row_stride, s.n, 2, note),
+        view_rows("residual", s.residual, s.rows, s.residual_row_stride, s.n, rsz, note),
+        view_flat("weight", s.weight, wbytes, note),
+        view_flat("bias", s.bias, wbytes, note),
     };
-    const AnView out[] = {
-        an_view("out", s.out, s.rows, s.out_row_stride, s.n, 2),
-        an_view("residual_out", s.residual_out, s.rows, s.residual_out_row_stride, s.n, rosz),
+    const View out[] = {
+        view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2, note),
+        view_rows("residual_out", s.residual_out, s.rows, s.residual_out_row_stride, s.n, rosz, note),
     };
-    int ex_out[2], ex_in[2], n_ex = 0;
-    if (x_inplace) { ex_out[n_ex] = 0; ex_in[n_ex++] = 0; }
-    if (r_inplace) { ex_out[n_ex] = 1; ex_in[n_ex++] = 1; }
-    return an_overlaps(op, out, 2, in, 4, ex_out, ex_in, n_ex);
+    int exempt[2][2], n_ex = 0;
+    if (x_inplace) { exempt[n_ex][0] = 0; exempt[n_ex++][1] = 0; }
+    if (r_inplace) { exempt[n_ex][0] = 1; exempt[n_ex++][1] = 1; }
+    return check_overlaps(op, out, 2, in, 4, true, exempt, n_ex);
 }
 
 // fa_add_norm_bwd's argument rules.  query: the workspace itself and where the tensors lie are not looked at
@@ -1233,17 +1141,14 @@ static int add_norm_bwd_check(const fa_add_norm_bwd_params& s, bool query) {
     const char* op = "add_norm_bwd";
     FA_CHECK(s.dy && s.z, "%s: dy and z must not be NULL", op);
     FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
-    const int rc = add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset);
-    if (rc != FA_OK) return rc;
+    FA_TRY(add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset));
     FA_CHECK(an_is_io_or_fp32(s.z_dtype, s.dtype), "%s: z_dtype must be the io dtype or fp32", op);
     if (s.dres) FA_CHECK(an_is_io_or_fp32(s.dres_dtype, s.dtype), "%s: dres_dtype must be the io dtype or fp32", op);
     FA_CHECK(an_stride_ok(s.dy_row_stride, s.rows, s.n) && an_stride_ok(s.z_row_stride, s.rows, s.n) &&
              (!s.dres_out || an_stride_ok(s.dres_out_row_stride, s.rows, s.n)) && (!s.dx || an_stride_ok(s.dx_row_stride, s.rows, s.n)) &&
              (!s.dres || an_stride_ok(s.dres_row_stride, s.rows, s.n)),
              "%s: row strides must be non-negative multiples of 8 elements and (rows > 1) at least n", op);
-    FA_CHECK(((reinterpret_cast<uintptr_t>(s.dy) | reinterpret_cast<uintptr_t>(s.z) | reinterpret_cast<uintptr_t>(s.dres_out) |
-               reinterpret_cast<uintptr_t>(s.dx) | reinterpret_cast<uintptr_t>(s.dres) | reinterpret_cast<uintptr_t>(s.weight) |
-               reinterpret_cast<uintptr_t>(s.dweight) | reinterpret_cast<uintptr_t>(s.dbias)) & 15) == 0,
+    FA_CHECK(((addr(s.dy) | addr(s.z) | addr(s.dres_out) | addr(s.dx) | addr(s.dres) | addr(s.weight) | addr(s.dweight) | addr(s.dbias)) & 15) == 0,
              "%s: dy / z / dres_out / dx / dres / weight / dweight / dbias must be 16-byte aligned", op);
     if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
     const bool inplace = s.dx && s.dx == s.dy;
@@ -1253,36 +1158,102 @@ static int add_norm_bwd_check(const fa_add_norm_bwd_params& s, bool query) {
     if (need) {
         FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_add_norm_bwd_workspace_bytes() reports %zu",
                  op, s.workspace ? s.workspace_bytes : (size_t)0, need);
-        FA_CHECK(reinterpret_cast<uintptr_t>(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+        FA_CHECK(addr(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
     }
     const int zsz = s.z_dtype == FA_FP32 ? 4 : 2, dsz = s.dres_dtype == FA_FP32 ? 4 : 2;
     const uint64_t wbytes = (uint64_t)s.n * (s.weight_dtype == FA_FP32 ? 4 : 2);
-    const AnView in[] = {
-        an_view("dy", s.dy, s.rows, s.dy_row_stride, s.n, 2),
-        an_view("z", s.z, s.rows, s.z_row_stride, s.n, zsz),
-        an_view("dres_out", s.dres_out, s.rows, s.dres_out_row_stride, s.n, zsz),
-        an_flat("weight", s.weight, wbytes),
+    const char* note = " (in place needs the same base address, row stride and dtype)";
+    const View in[] = {
+        view_rows("dy", s.dy, s.rows, s.dy_row_stride, s.n, 2, note),
+        view_rows("z", s.z, s.rows, s.z_row_stride, s.n, zsz, note),
+        view_rows("dres_out", s.dres_out, s.rows, s.dres_out_row_stride, s.n, zsz, note),
+        view_flat("weight", s.weight, wbytes, note),
     };
-    const AnView out[] = {
-        an_view("dx", s.dx, s.rows, s.dx_row_stride, s.n, 2),
-        an_view("dres", s.dres, s.rows, s.dres_row_stride, s.n, dsz),
-        an_flat("dweight", s.dweight, wbytes),
-        an_flat("dbias", s.dbias, wbytes),
-        an_flat("workspace", need ? s.workspace : nullptr, need),
+    const View out[] = {
+        view_rows("dx", s.dx, s.rows, s.dx_row_stride, s.n, 2, note),
+        view_rows("dres", s.dres, s.rows, s.dres_row_stride, s.n, dsz, note),
+        view_flat("dweight", s.dweight, wbytes, note),
+        view_flat("dbias", s.dbias, wbytes, note),
+        view_flat("workspace", need ? s.workspace : nullptr, need, note),
     };
-    const int ex_out[1] = {0}, ex_in[1] = {0};
-    return an_overlaps(op, out, 5, in, 4, ex_out, ex_in, inplace ? 1 : 0);
+    const int exempt[1][2] = {{0, 0}};
+    return check_overlaps(op, out, 5, in, 4, true, exempt, inplace ? 1 : 0);
 }
 
 extern "C" {
 
+int fa_rotary(const fa_rotary_params* r, void* stream) {
+    FA_TRY(check_header(r, "fa_rotary_params"));
+    bool empty;
+    FA_TRY(rotary_check(*r, &empty));
+    if (empty) return FA_OK;
+    fa::launch_rotary(*r, static_cast<hipStream_t>(stream));
+    return check_hip("fa_rotary launch");
+}
+
+int fa_kv_store(const fa_kv_store_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_kv_store_params"));
+    fa_kv_store_params s = *sp;
+    bool empty;
+    FA_TRY(kv_store_check(s, &empty));
+    if (empty) return FA_OK;
+    fa::launch_kv_store(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_kv_store launch");
+}
+
+int fa_kv_gather(const fa_kv_gather_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_kv_gather_params"));
+    fa_kv_gather_params s = *sp;
+    bool empty;
+    FA_TRY(kv_gather_check(s, &empty));
+    if (empty) return FA_OK;
+    fa::launch_kv_gather(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_kv_gather launch");
+}
+
+int fa_rope_store(const fa_rope_store_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_rope_store_params"));
+    fa_rope_store_params s = *sp;
+    bool empty;
+    FA_TRY(rope_store_check(s, "rope_store", false, nullptr, 0, &empty));
+    if (empty) return FA_OK;
+    fa::launch_rope_store(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_rope_store launch");
+}
+
+int fa_qk_norm_rope_store(const fa_qk_norm_rope_store_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_qk_norm_rope_store_params"));
+    fa_qk_norm_rope_store_params s = *sp;
+    bool empty;
+    FA_TRY(qk_norm_rope_store_check(s, &empty));
+    if (empty) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_qk_norm_rope_store(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_qk_norm_rope_store launch");
+}
+
+size_t fa_qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_qk_norm_rope_bwd_params)) return 0;
+    fa_qk_norm_rope_bwd_params s = *sp;
+    if (qk_norm_rope_bwd_check(s, true) != FA_OK) return 0;
+    return fa::qk_norm_rope_bwd_workspace_bytes(s);
+}
+
+int fa_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_qk_norm_rope_bwd_params"));
+    fa_qk_norm_rope_bwd_params s = *sp;
+    FA_TRY(qk_norm_rope_bwd_check(s, false));
+    const bool empty = s.total_rows == 0 || s.head_dim == 0 || (s.nheads_q == 0 && s.nheads_k == 0);
+    if (empty && !s.dq_weight && !s.dk_weight) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_qk_norm_rope_bwd(s, static_cast<hipStream_t>(stream));      // (an empty problem: a wanted dw is set to zeros, no kernel)
+    return check_hip("fa_qk_norm_rope_bwd launch");
+}
+
 int fa_add_norm(const fa_add_norm_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_add_norm_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_add_norm_params), "fa_add_norm_params::struct_size %zu is smaller than this library's %zu",
-             sp->struct_size, sizeof(fa_add_norm_params));
+    FA_TRY(check_header(sp, "fa_add_norm_params"));
     fa_add_norm_params s = *sp;
-    const int rc = add_norm_check(s);
-    if (rc != FA_OK) return rc;
+    FA_TRY(add_norm_check(s));
     if (s.rows == 0) return FA_OK;
     s.struct_size = sizeof(s);
     fa::launch_add_norm(s, static_cast<hipStream_t>(stream));
@@ -1296,12 +1267,9 @@ size_t fa_add_norm_bwd_workspace_bytes(const fa_add_norm_bwd_params* sp) {
 }
 
 int fa_add_norm_bwd(const fa_add_norm_bwd_params* sp, void* stream) {
-    FA_CHECK(sp, "fa_add_norm_bwd_params must not be NULL");
-    FA_CHECK(sp->struct_size >= sizeof(fa_add_norm_bwd_params), "fa_add_norm_bwd_params::struct_size %zu is smaller than this library's %zu",
-             sp->struct_size, sizeof(fa_add_norm_bwd_params));
+    FA_TRY(check_header(sp, "fa_add_norm_bwd_params"));
     fa_add_norm_bwd_params s = *sp;
-    const int rc = add_norm_bwd_check(s, false);
-    if (rc != FA_OK) return rc;
+    FA_TRY(add_norm_bwd_check(s, false));
     if (!s.dx && !s.dres && !s.dweight && !s.dbias) return FA_OK;
     if (s.rows == 0 && !s.dweight && !s.dbias) return FA_OK;
     s.struct_size = sizeof(s);

@@ -23,6 +23,7 @@
 //     85.3 us from an fp8 one; 2 - 3 us slower at 8192 rows, where the cache sits in the last-level cache between the sweep's calls).
 //     FA_KV_GATHER_NT_LOADS=0 builds the ordinary-load variant.
 #include <cstdint>
+#include "fa_rowops.h"
 #include "fa_fp8_cvt.h"
 
 #ifndef FA_KV_GATHER_NT_LOADS
@@ -220,14 +221,12 @@ void launch_kv_gather(const fa_kv_gather_params& s, hipStream_t stream) {
     const bool kv8 = s.cache_dtype == FA_FP8_E4M3;
     const int w = kvg_wide_ok(s) ? 2 : 1;
     const int64_t ipr = (int64_t)s.nheads * (s.head_dim / (8 * w));
-    const int64_t rows = (KVG_STEP_ITEMS + ipr - 1) / ipr;
-    a.group_rows = (int)(rows < 1 ? 1 : (rows > KVG_MAX_GROUP_ROWS ? KVG_MAX_GROUP_ROWS : rows));
-    const int64_t groups = (a.n_rows + a.group_rows - 1) / a.group_rows;
-    const int grid = (int)(groups < KVG_GRID_CAP ? groups : KVG_GRID_CAP);
+    const RowPlan pl = row_plan(a.n_rows, ipr, KVG_STEP_ITEMS, KVG_MAX_GROUP_ROWS, KVG_GRID_CAP);
+    a.group_rows = pl.group_rows;
     // (a 16-bit cache is copied bit for bit: one kernel serves fp16 and bf16)
-    if (!kv8)                    hipLaunchKernelGGL((kv_gather_kernel<bf16_tag, false, 1>), dim3(grid), dim3(KVG_THREADS), 0, stream, a);
-    else if (s.dtype == FA_BF16) launch_kv_gather_fp8<bf16_tag>(a, w, grid, stream);
-    else                         launch_kv_gather_fp8<fp16_tag>(a, w, grid, stream);
+    if (!kv8)                    hipLaunchKernelGGL((kv_gather_kernel<bf16_tag, false, 1>), dim3(pl.grid), dim3(KVG_THREADS), 0, stream, a);
+    else if (s.dtype == FA_BF16) launch_kv_gather_fp8<bf16_tag>(a, w, pl.grid, stream);
+    else                         launch_kv_gather_fp8<fp16_tag>(a, w, pl.grid, stream);
 }
 
 }  // namespace fa

@@ -20,7 +20,7 @@
 //   - k / v are read once: nontemporal loads.  The cache lines are re-read by the attention call that follows: ordinary stores
 //     (FA_KV_STORE_NT_STORES=1 builds the nontemporal-store variant; profiles/kv_store.txt has both).
 #include <cstdint>
-#include "fa_rope.h"
+#include "fa_rowops.h"
 #include "fa_fp8_cvt.h"
 
 #ifndef FA_KV_STORE_NT_STORES
@@ -99,8 +99,6 @@ __device__ __forceinline__ KvsRow kvs_row(const KvStoreArgs& a, int64_t r0, int 
     return w;
 }
 
-__device__ __forceinline__ u32x4 kvs_ld(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-
 template <typename V>
 __device__ __forceinline__ void kvs_st(V* p, V v) {
 #if FA_KV_STORE_NT_STORES
@@ -110,15 +108,10 @@ __device__ __forceinline__ void kvs_st(V* p, V v) {
 #endif
 }
 
-enum { KVS_ROPE_NONE = 0, KVS_ROPE_INTERLEAVED = 1, KVS_ROPE_NEOX = 2 };
-
-template <int ROPE> struct KvsTable { typedef u32x2 type; };          // the cos / sin values of one piece: 4 pairs (interleaved)
-template <> struct KvsTable<KVS_ROPE_NEOX> { typedef u32x4 type; };   // 8 pairs
-
 // T: the 16-bit input type; KV8: fp8-e4m3 cache; W: 16-byte source pieces per item; ROPE: rotation of K
 template <typename T, bool KV8, int W, int ROPE>
 __global__ void __launch_bounds__(KVS_THREADS) kv_store_kernel(const KvStoreArgs a) {
-    typedef typename KvsTable<ROPE>::type CS;
+    typedef typename RopeTable<ROPE>::type CS;
     constexpr int U = 2;                                  // items in flight per lane: loads first, then stores
     const int lane = threadIdx.x & 63;
     const int half = a.rotary_dim >> 1;
@@ -163,17 +156,17 @@ __global__ void __launch_bounds__(KVS_THREADS) kv_store_kernel(const KvStoreArgs
 #pragma unroll
                 for (int q = 0; q < W; ++q) {
                     const int dq = d + 8 * q;
-                    const bool inside = ROPE != KVS_ROPE_NONE && dq < a.rotary_dim;
+                    const bool inside = ROPE != ROPE_NONE && dq < a.rotary_dim;
                     rot[u][q] = inside && ok[u] && pos >= 0;
                     first[u][q] = dq < half;
-                    kx[u][q] = kvs_ld(khead + dq);
-                    vx[u][q] = kvs_ld(vhead + dq);
-                    if (ROPE != KVS_ROPE_NONE) {
+                    kx[u][q] = ld_nt16(khead + dq);
+                    vx[u][q] = ld_nt16(vhead + dq);
+                    if (ROPE != ROPE_NONE) {
                         const int ds = inside ? dq : 0;
                         int t = ds >> 1;                  // interleaved: pairs ds / 2 .. ds / 2 + 3
-                        if (ROPE == KVS_ROPE_NEOX) {
+                        if (ROPE == ROPE_NEOX) {
                             const bool f = ds < half;
-                            kp[u][q] = kvs_ld(khead + ds + (f ? half : -half));
+                            kp[u][q] = ld_nt16(khead + ds + (f ? half : -half));
                             t = f ? ds : ds - half;
                         }
                         cw[u][q] = *reinterpret_cast<const CS*>(a.cos + trow + t);
@@ -184,7 +177,7 @@ __global__ void __launch_bounds__(KVS_THREADS) kv_store_kernel(const KvStoreArgs
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (!ok[u]) continue;
-                if (ROPE != KVS_ROPE_NONE) {
+                if (ROPE != ROPE_NONE) {
 #pragma unroll
                     for (int q = 0; q < W; ++q) {
                         // rope_chunk reads its cos / sin through pointers: hand it the piece's values (registers after inlining:
@@ -195,7 +188,7 @@ __global__ void __launch_bounds__(KVS_THREADS) kv_store_kernel(const KvStoreArgs
                         const uint16_t* cp = reinterpret_cast<const uint16_t*>(&cl);
                         const uint16_t* sp = reinterpret_cast<const uint16_t*>(&sl);
                         u32x4 y = kx[u][q];
-                        if (ROPE == KVS_ROPE_INTERLEAVED) {
+                        if (ROPE == ROPE_INTERLEAVED) {
                             rope_chunk<T>(y, y, cp, sp, 0, a.rotary_dim, true);
                         } else {
                             u32x4 y2 = y;
@@ -239,9 +232,9 @@ static bool kvs_wide_ok(const fa_kv_store_params& s) {
 template <typename T, bool KV8, int W>
 static void launch_kv_store_w(const KvStoreArgs& a, int rope, int grid, hipStream_t stream) {
     const dim3 g(grid), b(KVS_THREADS);
-    if (rope == KVS_ROPE_NONE)             hipLaunchKernelGGL((kv_store_kernel<T, KV8, W, KVS_ROPE_NONE>), g, b, 0, stream, a);
-    else if (rope == KVS_ROPE_INTERLEAVED) hipLaunchKernelGGL((kv_store_kernel<T, KV8, W, KVS_ROPE_INTERLEAVED>), g, b, 0, stream, a);
-    else                                   hipLaunchKernelGGL((kv_store_kernel<T, KV8, W, KVS_ROPE_NEOX>), g, b, 0, stream, a);
+    if (rope == ROPE_NONE)             hipLaunchKernelGGL((kv_store_kernel<T, KV8, W, ROPE_NONE>), g, b, 0, stream, a);
+    else if (rope == ROPE_INTERLEAVED) hipLaunchKernelGGL((kv_store_kernel<T, KV8, W, ROPE_INTERLEAVED>), g, b, 0, stream, a);
+    else                                   hipLaunchKernelGGL((kv_store_kernel<T, KV8, W, ROPE_NEOX>), g, b, 0, stream, a);
 }
 
 template <typename T>
@@ -276,14 +269,12 @@ void launch_kv_store(const fa_kv_store_params& s, hipStream_t stream) {
     a.k_descale = s.k_descale; a.v_descale = s.v_descale;
     const bool kv8 = s.cache_dtype == FA_FP8_E4M3;
     const int w = kvs_wide_ok(s) ? 2 : 1;
-    const int rope = (s.rotary_dim <= 0 || s.seqlen_ro <= 0) ? KVS_ROPE_NONE : (s.rotary_interleaved ? KVS_ROPE_INTERLEAVED : KVS_ROPE_NEOX);
+    const int rope = (s.rotary_dim <= 0 || s.seqlen_ro <= 0) ? ROPE_NONE : (s.rotary_interleaved ? ROPE_INTERLEAVED : ROPE_NEOX);
     const int64_t ipr = (int64_t)s.nheads * (s.head_dim / (8 * w));
-    const int64_t rows = (KVS_STEP_ITEMS + ipr - 1) / ipr;
-    a.group_rows = (int)(rows < 1 ? 1 : (rows > KVS_MAX_GROUP_ROWS ? KVS_MAX_GROUP_ROWS : rows));
-    const int64_t groups = (a.n_rows + a.group_rows - 1) / a.group_rows;
-    const int grid = (int)(groups < KVS_GRID_CAP ? groups : KVS_GRID_CAP);
-    if (s.dtype == FA_BF16) launch_kv_store_t<bf16_tag>(a, kv8, w, rope, grid, stream);
-    else                    launch_kv_store_t<fp16_tag>(a, kv8, w, rope, grid, stream);
+    const RowPlan pl = row_plan(a.n_rows, ipr, KVS_STEP_ITEMS, KVS_MAX_GROUP_ROWS, KVS_GRID_CAP);
+    a.group_rows = pl.group_rows;
+    if (s.dtype == FA_BF16) launch_kv_store_t<bf16_tag>(a, kv8, w, rope, pl.grid, stream);
+    else                    launch_kv_store_t<fp16_tag>(a, kv8, w, rope, pl.grid, stream);
 }
 
 }  // namespace fa

@@ -22,7 +22,7 @@
 // The grid, the rows per step and the cap depend on the parameter block alone (qnb_plan: the workspace query and the launch share
 // it), so the bits are the same on every card.  Without a wanted dw: no accumulation, no LDS, no second launch, no workspace.
 #include <cstdint>
-#include "fa_rope.h"
+#include "fa_rowops.h"
 #include "fa_rmsnorm.h"
 
 namespace fa {
@@ -66,20 +66,12 @@ struct QnbFinArgs {
     int n_parts, head_dim, w_fp32;
 };
 
-enum { QNB_ROPE_NONE = 0, QNB_ROPE_INTERLEAVED = 1, QNB_ROPE_NEOX = 2 };
-enum { QNB_Q = 0, QNB_K = 1 };
-
-template <int ROPE> struct QnbTable { typedef u32x2 type; };          // the cos / sin values of one piece: 4 pairs (interleaved)
-template <> struct QnbTable<QNB_ROPE_NEOX> { typedef u32x4 type; };   // 8 pairs
-
-__device__ __forceinline__ u32x4 qnb_ld(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-
 // T: the 16-bit io type; ROPE: the pair rule; DW: a weight gradient is wanted
 template <typename T, int ROPE, bool DW>
 __global__ void __launch_bounds__(QNB_THREADS) qk_norm_rope_bwd_kernel(const QnbArgs a) {
-    typedef typename QnbTable<ROPE>::type CS;
+    typedef typename RopeTable<ROPE>::type CS;
     using E = Elem<T>;
-    constexpr bool NEOX = ROPE == QNB_ROPE_NEOX;
+    constexpr bool NEOX = ROPE == ROPE_NEOX;
     const int lanes = 1 << a.group_log2;                  // G
     const int lane = threadIdx.x & 63;
     const int j = (int)threadIdx.x & (lanes - 1);         // the lane's piece of its head ...
@@ -87,7 +79,7 @@ __global__ void __launch_bounds__(QNB_THREADS) qk_norm_rope_bwd_kernel(const Qnb
     const int d = piece ? 8 * j : 0;                      // its first column (clamped: the loads stay inside the head)
     const int slot0 = (int)threadIdx.x >> a.group_log2;   // the lane's head slot within a pass
     const int spp = QNB_THREADS >> a.group_log2;          // head slots per pass of the workgroup
-    const int rd = ROPE == QNB_ROPE_NONE ? 0 : a.rotary_dim;
+    const int rd = ROPE == ROPE_NONE ? 0 : a.rotary_dim;
     const int half = rd >> 1;
     const bool inside = piece && d < rd;                  // the piece is rotated (where its row is)
     const bool first = d < half;                          // NeoX: a piece of the first half
@@ -116,21 +108,21 @@ __global__ void __launch_bounds__(QNB_THREADS) qk_norm_rope_bwd_kernel(const Qnb
                 const bool in = s < n;
                 const uint32_t sc = in ? (uint32_t)s : 0u;                        // (a slot past the step's last: its first one)
                 const uint32_t kr = sc / (uint32_t)hpr, c = sc - kr * (uint32_t)hpr;
-                kind[u] = (int)c < nq ? QNB_Q : QNB_K;
-                const bool isq = kind[u] == QNB_Q;
+                kind[u] = (int)c < nq ? ROW_Q : ROW_K;
+                const bool isq = kind[u] == ROW_Q;
                 const int64_t h = (int64_t)c - (isq ? 0 : nq);
                 const int64_t r = r0 + kr;
                 act[u] = in && piece;
-                dz[u] = qnb_ld((isq ? a.dzq + r * a.dzq_row_stride + h * a.dzq_head_stride
+                dz[u] = ld_nt16((isq ? a.dzq + r * a.dzq_row_stride + h * a.dzq_head_stride
                                     : a.dzk + r * a.dzk_row_stride + h * a.dzk_head_stride) + d);
                 x[u] = u32x4{0, 0, 0, 0};
                 if (isq ? norm_q : norm_k)
-                    x[u] = qnb_ld((isq ? a.xq + r * a.xq_row_stride + h * a.xq_head_stride
+                    x[u] = ld_nt16((isq ? a.xq + r * a.xq_row_stride + h * a.xq_head_stride
                                        : a.xk + r * a.xk_row_stride + h * a.xk_head_stride) + d);
                 op[u] = (isq ? a.dxq + r * a.dxq_row_stride + h * a.dxq_head_stride
                              : a.dxk + r * a.dxk_row_stride + h * a.dxk_head_stride) + d;
                 rot[u] = false;
-                if constexpr (ROPE != QNB_ROPE_NONE) {
+                if constexpr (ROPE != ROPE_NONE) {
                     const int64_t p = a.positions[r];
                     const bool at = p >= 0 && p < a.seqlen_ro;
                     rot[u] = act[u] && inside && at;
@@ -141,7 +133,7 @@ __global__ void __launch_bounds__(QNB_THREADS) qk_norm_rope_bwd_kernel(const Qnb
             }
 #pragma unroll
             for (int u = 0; u < QNB_U; ++u) {
-                const bool isq = kind[u] == QNB_Q;
+                const bool isq = kind[u] == ROW_Q;
                 const bool norm = isq ? norm_q : norm_k;
                 const u32x4 zero = {0, 0, 0, 0};
                 const float ss = rms_group_sum(rms_piece_ss<T>(act[u] ? x[u] : zero), lanes);
@@ -149,7 +141,7 @@ __global__ void __launch_bounds__(QNB_THREADS) qk_norm_rope_bwd_kernel(const Qnb
                 float dy[8];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { dy[2 * i] = E::lo(dz[u][i]); dy[2 * i + 1] = E::hi(dz[u][i]); }
-                if constexpr (ROPE != QNB_ROPE_NONE) {
+                if constexpr (ROPE != ROPE_NONE) {
                     // the conjugate rotation: sin -> -sin exactly, as fa_rotary.hip does, then fa_rope.h's pair rule in fp32.  Both
                     // halves' formulas are evaluated and one is kept (NeoX), so that the table values stay in registers
                     u32x4 dp = dz[u];                     // the partner's piece of dz (NeoX)
@@ -290,11 +282,8 @@ static QnbPlan qnb_plan(const fa_qk_norm_rope_bwd_params& s) {
     const int64_t hpr = (int64_t)pl.nheads_q + pl.nheads_k;
     if (hpr == 0 || s.total_rows <= 0 || s.head_dim <= 0) return pl;
     while ((8 << pl.group_log2) < s.head_dim) ++pl.group_log2;
-    const int64_t lanes_per_row = hpr << pl.group_log2;
-    const int64_t rows = (QNB_STEP_LANES + lanes_per_row - 1) / lanes_per_row;
-    pl.group_rows = (int)(rows < 1 ? 1 : (rows > QNB_MAX_GROUP_ROWS ? QNB_MAX_GROUP_ROWS : rows));
-    const int64_t groups = ((int64_t)s.total_rows + pl.group_rows - 1) / pl.group_rows;
-    pl.grid = (int)(groups < QNB_GRID_CAP ? groups : QNB_GRID_CAP);
+    const RowPlan rp = row_plan(s.total_rows, hpr << pl.group_log2, QNB_STEP_LANES, QNB_MAX_GROUP_ROWS, QNB_GRID_CAP);
+    pl.group_rows = rp.group_rows; pl.grid = rp.grid;
     // (a dw whose tensor is not worked on - a NULL q - still goes through the partial rows: they hold zeros for it)
     if (s.dq_weight || s.dk_weight) pl.bytes = (size_t)pl.grid * 2 * (size_t)s.head_dim * sizeof(float);
     return pl;
@@ -305,9 +294,9 @@ size_t qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params& s) { r
 template <typename T, bool DW>
 static void launch_qnb_w(const QnbArgs& a, int rope, int grid, hipStream_t stream) {
     const dim3 g(grid), b(QNB_THREADS);
-    if (rope == QNB_ROPE_NONE)             hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, QNB_ROPE_NONE, DW>), g, b, 0, stream, a);
-    else if (rope == QNB_ROPE_INTERLEAVED) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, QNB_ROPE_INTERLEAVED, DW>), g, b, 0, stream, a);
-    else                                   hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, QNB_ROPE_NEOX, DW>), g, b, 0, stream, a);
+    if (rope == ROPE_NONE)             hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, ROPE_NONE, DW>), g, b, 0, stream, a);
+    else if (rope == ROPE_INTERLEAVED) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, ROPE_INTERLEAVED, DW>), g, b, 0, stream, a);
+    else                                   hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<T, ROPE_NEOX, DW>), g, b, 0, stream, a);
 }
 
 // one launch, two with a wanted dw; where no head is worked on (no rows, no heads, no output that needs them) none, and a wanted
@@ -347,7 +336,7 @@ void launch_qk_norm_rope_bwd(const fa_qk_norm_rope_bwd_params& s, hipStream_t st
     a.w_fp32 = s.weight_dtype == FA_FP32;
     a.dw_q = pl.dw_q; a.dw_k = pl.dw_k;
     a.eps = s.eps; a.w_offset = s.weight_offset;
-    const int rope = s.seqlen_ro <= 0 ? QNB_ROPE_NONE : (s.rotary_interleaved ? QNB_ROPE_INTERLEAVED : QNB_ROPE_NEOX);
+    const int rope = s.seqlen_ro <= 0 ? ROPE_NONE : (s.rotary_interleaved ? ROPE_INTERLEAVED : ROPE_NEOX);
     const bool dw = pl.bytes != 0;
     if (s.dtype == FA_BF16) {
         if (dw) launch_qnb_w<bf16_tag, true>(a, rope, pl.grid, stream);

@@ -20,7 +20,7 @@
 //   - q / k / v are read once: nontemporal loads.  q_out / k_out and the cache lines are read by the attention call that follows:
 //     ordinary stores (the choices profiles/rope_store.txt measured).  Vector stores only; fp8 caches get 8-byte stores.
 #include <cstdint>
-#include "fa_rope.h"
+#include "fa_rowops.h"
 #include "fa_rmsnorm.h"
 #include "fa_fp8_cvt.h"
 
@@ -57,14 +57,6 @@ struct QkNormArgs {
     float k_descale, v_descale, eps, w_offset;
 };
 
-enum { QN_ROPE_NONE = 0, QN_ROPE_INTERLEAVED = 1, QN_ROPE_NEOX = 2 };     // NONE: no table, no row is rotated
-enum { QN_Q = 0, QN_K = 1, QN_V = 2 };
-
-template <int ROPE> struct QnTable { typedef u32x2 type; };           // the cos / sin values of one piece: 4 pairs (interleaved)
-template <> struct QnTable<QN_ROPE_NEOX> { typedef u32x4 type; };     // 8 pairs
-
-__device__ __forceinline__ u32x4 qn_ld(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-
 // where slot `s` lies in a cache with the given strides (the caller knows 0 <= s < n_slots)
 __device__ __forceinline__ int64_t qn_cache_row(int64_t s, int64_t n_slots, int page, int64_t batch_stride, int64_t row_stride) {
     int64_t blk, row;
@@ -80,8 +72,8 @@ __device__ __forceinline__ int64_t qn_cache_row(int64_t s, int64_t n_slots, int 
 // T: the 16-bit io type; KV8: fp8-e4m3 cache; ROPE: the pair rule
 template <typename T, bool KV8, int ROPE>
 __global__ void __launch_bounds__(QN_THREADS) qk_norm_rope_store_kernel(const QkNormArgs a) {
-    typedef typename QnTable<ROPE>::type CS;
-    constexpr bool NEOX = ROPE == QN_ROPE_NEOX;
+    typedef typename RopeTable<ROPE>::type CS;
+    constexpr bool NEOX = ROPE == ROPE_NEOX;
     const int lanes = 1 << a.group_log2;                  // G
     const int lane = threadIdx.x & 63;
     const int j = (int)threadIdx.x & (lanes - 1);         // the lane's piece of its head ...
@@ -89,7 +81,7 @@ __global__ void __launch_bounds__(QN_THREADS) qk_norm_rope_store_kernel(const Qk
     const int d = piece ? 8 * j : 0;                      // its first column (clamped: the loads stay inside the head)
     const int slot0 = (int)threadIdx.x >> a.group_log2;   // the lane's head slot within a pass
     const int spp = QN_THREADS >> a.group_log2;           // head slots per pass of the workgroup
-    const int rd = ROPE == QN_ROPE_NONE ? 0 : a.rotary_dim;
+    const int rd = ROPE == ROPE_NONE ? 0 : a.rotary_dim;
     const int half = rd >> 1;
     const bool inside = piece && d < rd;                  // the piece is rotated (where its row is)
     const bool first = d < half;                          // NeoX: a piece of the first half
@@ -126,31 +118,31 @@ __global__ void __launch_bounds__(QN_THREADS) qk_norm_rope_store_kernel(const Qk
                 const bool in = s < n;
                 const uint32_t sc = in ? (uint32_t)s : 0u;                        // (a slot past the step's last: its first one)
                 const uint32_t kr = sc / (uint32_t)hpr, c = sc - kr * (uint32_t)hpr;
-                kind[u] = (int)c < nq ? QN_Q : ((int)c < nqk ? QN_K : QN_V);
-                const int64_t h = (int64_t)c - (kind[u] == QN_Q ? 0 : (kind[u] == QN_K ? nq : nqk));
+                kind[u] = (int)c < nq ? ROW_Q : ((int)c < nqk ? ROW_K : ROW_V);
+                const int64_t h = (int64_t)c - (kind[u] == ROW_Q ? 0 : (kind[u] == ROW_K ? nq : nqk));
                 const int64_t r = r0 + kr;
                 act[u] = in && piece;
-                const uint16_t* src = kind[u] == QN_Q ? a.q + r * a.q_row_stride + h * a.q_head_stride
-                                    : kind[u] == QN_K ? a.k + r * a.k_row_stride + h * a.k_head_stride
-                                                      : a.v + r * a.v_row_stride + h * a.v_head_stride;
-                x[u] = qn_ld(src + d);
-                op[u] = (kind[u] == QN_Q ? a.qo + r * a.qo_row_stride + h * a.qo_head_stride
-                                         : a.ko + r * a.ko_row_stride + h * a.ko_head_stride) + d;
+                const uint16_t* src = kind[u] == ROW_Q ? a.q + r * a.q_row_stride + h * a.q_head_stride
+                                    : kind[u] == ROW_K ? a.k + r * a.k_row_stride + h * a.k_head_stride
+                                                       : a.v + r * a.v_row_stride + h * a.v_head_stride;
+                x[u] = ld_nt16(src + d);
+                op[u] = (kind[u] == ROW_Q ? a.qo + r * a.qo_row_stride + h * a.qo_head_stride
+                                          : a.ko + r * a.ko_row_stride + h * a.ko_head_stride) + d;
                 co[u] = -1;
                 if (cached) {
                     const int64_t slot = a.slot_mapping[r];
-                    if (kind[u] != QN_Q && slot >= 0 && slot < a.n_slots) {
-                        const bool isv = kind[u] == QN_V;
+                    if (kind[u] != ROW_Q && slot >= 0 && slot < a.n_slots) {
+                        const bool isv = kind[u] == ROW_V;
                         co[u] = qn_cache_row(slot, a.n_slots, a.page, isv ? a.vc_batch_stride : a.kc_batch_stride,
                                              isv ? a.vc_row_stride : a.kc_row_stride) +
                                 h * (isv ? a.vc_head_stride : a.kc_head_stride) + d;
                     }
                 }
                 rot[u] = false;
-                if constexpr (ROPE != QN_ROPE_NONE) {
+                if constexpr (ROPE != ROPE_NONE) {
                     const int64_t p = a.positions[r];
                     const bool at = p >= 0 && p < a.seqlen_ro;
-                    rot[u] = act[u] && inside && at && kind[u] != QN_V;
+                    rot[u] = act[u] && inside && at && kind[u] != ROW_V;
                     const int64_t trow = (at ? p : 0) * half;                     // (a row that is not rotated: the table's row 0)
                     cw[u] = *reinterpret_cast<const CS*>(a.cos + trow + tcol);
                     sw[u] = *reinterpret_cast<const CS*>(a.sin + trow + tcol);
@@ -158,15 +150,15 @@ __global__ void __launch_bounds__(QN_THREADS) qk_norm_rope_store_kernel(const Qk
             }
 #pragma unroll
             for (int u = 0; u < QN_U; ++u) {
-                const bool norm = kind[u] == QN_Q ? norm_q : (kind[u] == QN_K && norm_k);
+                const bool norm = kind[u] == ROW_Q ? norm_q : (kind[u] == ROW_K && norm_k);
                 const u32x4 zero = {0, 0, 0, 0};
                 const float ss = rms_group_sum(rms_piece_ss<T>(act[u] ? x[u] : zero), lanes);
                 const float rstd = rms_rstd(ss, a.head_dim, a.eps);
                 float g[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) g[i] = kind[u] == QN_Q ? gq[i] : gk[i];
+                for (int i = 0; i < 8; ++i) g[i] = kind[u] == ROW_Q ? gq[i] : gk[i];
                 u32x4 y = norm ? rms_scale<T>(x[u], rstd, g) : x[u];
-                if constexpr (ROPE != QN_ROPE_NONE) {
+                if constexpr (ROPE != ROPE_NONE) {
                     u32x4 yp = y;                         // the partner's normalised, rounded piece (NeoX)
                     if constexpr (NEOX) {
 #pragma unroll
@@ -188,17 +180,17 @@ __global__ void __launch_bounds__(QN_THREADS) qk_norm_rope_store_kernel(const Qk
                     }
                     y = rot[u] ? z : y;
                 }
-                if (act[u] && kind[u] != QN_V) {
-                    const bool inplace = kind[u] == QN_Q ? a.q_inplace != 0 : a.k_inplace != 0;
-                    const bool wanted = kind[u] == QN_Q || a.ko != nullptr;
+                if (act[u] && kind[u] != ROW_V) {
+                    const bool inplace = kind[u] == ROW_Q ? a.q_inplace != 0 : a.k_inplace != 0;
+                    const bool wanted = kind[u] == ROW_Q || a.ko != nullptr;
                     if (wanted && (!inplace || norm || rot[u])) *reinterpret_cast<u32x4*>(op[u]) = y;
                 }
                 if (act[u] && co[u] >= 0) {
                     if (KV8) {
-                        uint8_t* p = static_cast<uint8_t*>(kind[u] == QN_V ? a.vc : a.kc) + co[u];
-                        *reinterpret_cast<u32x2*>(p) = to_fp8x8<T>(y, kind[u] == QN_V ? vinv : kinv);
+                        uint8_t* p = static_cast<uint8_t*>(kind[u] == ROW_V ? a.vc : a.kc) + co[u];
+                        *reinterpret_cast<u32x2*>(p) = to_fp8x8<T>(y, kind[u] == ROW_V ? vinv : kinv);
                     } else {
-                        *reinterpret_cast<u32x4*>(static_cast<uint16_t*>(kind[u] == QN_V ? a.vc : a.kc) + co[u]) = y;
+                        *reinterpret_cast<u32x4*>(static_cast<uint16_t*>(kind[u] == ROW_V ? a.vc : a.kc) + co[u]) = y;
                     }
                 }
             }
@@ -209,61 +201,35 @@ __global__ void __launch_bounds__(QN_THREADS) qk_norm_rope_store_kernel(const Qk
 template <typename T, bool KV8>
 static void launch_qk_norm_w(const QkNormArgs& a, int rope, int grid, hipStream_t stream) {
     const dim3 g(grid), b(QN_THREADS);
-    if (rope == QN_ROPE_NONE)             hipLaunchKernelGGL((qk_norm_rope_store_kernel<T, KV8, QN_ROPE_NONE>), g, b, 0, stream, a);
-    else if (rope == QN_ROPE_INTERLEAVED) hipLaunchKernelGGL((qk_norm_rope_store_kernel<T, KV8, QN_ROPE_INTERLEAVED>), g, b, 0, stream, a);
-    else                                  hipLaunchKernelGGL((qk_norm_rope_store_kernel<T, KV8, QN_ROPE_NEOX>), g, b, 0, stream, a);
+    if (rope == ROPE_NONE)             hipLaunchKernelGGL((qk_norm_rope_store_kernel<T, KV8, ROPE_NONE>), g, b, 0, stream, a);
+    else if (rope == ROPE_INTERLEAVED) hipLaunchKernelGGL((qk_norm_rope_store_kernel<T, KV8, ROPE_INTERLEAVED>), g, b, 0, stream, a);
+    else                                  hipLaunchKernelGGL((qk_norm_rope_store_kernel<T, KV8, ROPE_NEOX>), g, b, 0, stream, a);
 }
 
 // one launch (none where a row has no head); the caller (fa_api.hip) has validated the block, replaced descales of 0 by 1.0, set
 // nheads_q to 0 where q is NULL and knows that total_rows and head_dim are positive
 void launch_qk_norm_rope_store(const fa_qk_norm_rope_store_params& s, hipStream_t stream) {
     QkNormArgs a;
-    a.q = static_cast<const uint16_t*>(s.q);
-    a.k = static_cast<const uint16_t*>(s.k);
-    a.v = static_cast<const uint16_t*>(s.v);
-    a.qo = static_cast<uint16_t*>(s.q_out);
-    a.ko = static_cast<uint16_t*>(s.k_out);
-    a.q_row_stride = s.q_row_stride; a.q_head_stride = s.q_head_stride;
-    a.k_row_stride = s.k_row_stride; a.k_head_stride = s.k_head_stride;
-    a.v_row_stride = s.v_row_stride; a.v_head_stride = s.v_head_stride;
-    a.qo_row_stride = s.qo_row_stride; a.qo_head_stride = s.qo_head_stride;
-    a.ko_row_stride = s.ko_row_stride; a.ko_head_stride = s.ko_head_stride;
-    a.kc = s.k_cache; a.vc = s.v_cache;
-    a.kc_batch_stride = s.kc_batch_stride; a.kc_row_stride = s.kc_row_stride; a.kc_head_stride = s.kc_head_stride;
-    a.vc_batch_stride = s.vc_batch_stride; a.vc_row_stride = s.vc_row_stride; a.vc_head_stride = s.vc_head_stride;
-    a.positions = s.positions;
-    a.slot_mapping = s.k_cache ? s.slot_mapping : nullptr;
-    a.n_rows = s.total_rows;
-    a.n_slots = s.k_cache ? (int64_t)s.num_blocks * s.page_block_size : 0;
-    a.cos = static_cast<const uint16_t*>(s.rotary_cos);
-    a.sin = static_cast<const uint16_t*>(s.rotary_sin);
+    fill_rope_store_args(a, s);
     a.wq = s.q ? s.q_weight : nullptr;
     a.wk = s.k_weight;
-    a.nheads_q = s.q ? s.nheads_q : 0; a.nheads_k = s.nheads_k; a.head_dim = s.head_dim;
-    a.page = s.k_cache ? s.page_block_size : 1;
-    a.rotary_dim = s.rotary_dim; a.seqlen_ro = s.seqlen_ro;
-    a.q_inplace = s.q_out == s.q; a.k_inplace = s.k_out == s.k;
     a.w_fp32 = s.weight_dtype == FA_FP32;
-    a.k_descale = s.k_descale; a.v_descale = s.v_descale;
     a.eps = s.eps; a.w_offset = s.weight_offset;
     const bool cached = s.k_cache != nullptr;
     const bool kv8 = cached && s.cache_dtype == FA_FP8_E4M3;
-    const int rope = s.seqlen_ro <= 0 ? QN_ROPE_NONE : (s.rotary_interleaved ? QN_ROPE_INTERLEAVED : QN_ROPE_NEOX);
+    const int rope = s.seqlen_ro <= 0 ? ROPE_NONE : (s.rotary_interleaved ? ROPE_INTERLEAVED : ROPE_NEOX);
     a.group_log2 = 0;
     while ((8 << a.group_log2) < s.head_dim) ++a.group_log2;
     const int64_t hpr = a.nheads_q + a.nheads_k * (cached ? 2 : 1);
     if (hpr == 0) return;
-    const int64_t lanes_per_row = hpr << a.group_log2;
-    const int64_t rows = (QN_STEP_LANES + lanes_per_row - 1) / lanes_per_row;
-    a.group_rows = (int)(rows < 1 ? 1 : (rows > QN_MAX_GROUP_ROWS ? QN_MAX_GROUP_ROWS : rows));
-    const int64_t groups = (a.n_rows + a.group_rows - 1) / a.group_rows;
-    const int grid = (int)(groups < QN_GRID_CAP ? groups : QN_GRID_CAP);
+    const RowPlan pl = row_plan(a.n_rows, hpr << a.group_log2, QN_STEP_LANES, QN_MAX_GROUP_ROWS, QN_GRID_CAP);
+    a.group_rows = pl.group_rows;
     if (s.dtype == FA_BF16) {
-        if (kv8) launch_qk_norm_w<bf16_tag, true>(a, rope, grid, stream);
-        else     launch_qk_norm_w<bf16_tag, false>(a, rope, grid, stream);
+        if (kv8) launch_qk_norm_w<bf16_tag, true>(a, rope, pl.grid, stream);
+        else     launch_qk_norm_w<bf16_tag, false>(a, rope, pl.grid, stream);
     } else {
-        if (kv8) launch_qk_norm_w<fp16_tag, true>(a, rope, grid, stream);
-        else     launch_qk_norm_w<fp16_tag, false>(a, rope, grid, stream);
+        if (kv8) launch_qk_norm_w<fp16_tag, true>(a, rope, pl.grid, stream);
+        else     launch_qk_norm_w<fp16_tag, false>(a, rope, pl.grid, stream);
     }
 }
 

@@ -22,7 +22,7 @@
 //   - two items are in flight per lane, also in the W = 2 form (FA_ROPE_STORE_WIDE_U=1 builds that form with one: fewer registers,
 //     no faster - the same profile).
 #include <cstdint>
-#include "fa_rope.h"
+#include "fa_rowops.h"
 #include "fa_fp8_cvt.h"
 
 #ifndef FA_ROPE_STORE_NT_OUT
@@ -85,8 +85,6 @@ __device__ __forceinline__ RsRow rs_row(const RopeStoreArgs& a, int64_t r0, int 
     return w;
 }
 
-__device__ __forceinline__ u32x4 rs_ld(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
-
 __device__ __forceinline__ void rs_st_out(uint16_t* p, u32x4 v) {
 #if FA_ROPE_STORE_NT_OUT
     __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
@@ -94,12 +92,6 @@ __device__ __forceinline__ void rs_st_out(uint16_t* p, u32x4 v) {
     *reinterpret_cast<u32x4*>(p) = v;
 #endif
 }
-
-enum { RS_ROPE_NONE = 0, RS_ROPE_INTERLEAVED = 1, RS_ROPE_NEOX = 2 };     // NONE: an empty table, every row is copied
-enum { RS_Q = 0, RS_K = 1, RS_V = 2 };
-
-template <int ROPE> struct RsTable { typedef u32x2 type; };           // the cos / sin values of one piece: 4 pairs (interleaved)
-template <> struct RsTable<RS_ROPE_NEOX> { typedef u32x4 type; };     // 8 pairs
 
 // one run of an item into the cache: W pieces at `off` (elements of the cache type)
 template <typename T, bool KV8, int W>
@@ -120,12 +112,12 @@ __device__ __forceinline__ void rs_st_cache(void* cache, int64_t off, const u32x
 // T: the 16-bit io type; KV8: fp8-e4m3 cache; W: 16-byte pieces per run (2: fp8 caches with 16-byte stores); ROPE: the pair rule
 template <typename T, bool KV8, int W, int ROPE>
 __global__ void __launch_bounds__(RS_THREADS) rope_store_kernel(const RopeStoreArgs a) {
-    typedef typename RsTable<ROPE>::type CS;
-    constexpr bool NEOX = ROPE == RS_ROPE_NEOX;
+    typedef typename RopeTable<ROPE>::type CS;
+    constexpr bool NEOX = ROPE == ROPE_NEOX;
     constexpr int U = W == 2 ? FA_ROPE_STORE_WIDE_U : 2;  // items in flight per lane: loads first, then stores
     constexpr int RUN = 8 * W;                            // columns of a run
     const int lane = threadIdx.x & 63;
-    const int rd = ROPE == RS_ROPE_NONE ? 0 : a.rotary_dim;
+    const int rd = ROPE == ROPE_NONE ? 0 : a.rotary_dim;
     const int half = rd >> 1;
     const int n_rot = rd / (NEOX ? 2 * RUN : RUN);        // items of a head inside rotary_dim
     const int n_tail = (a.head_dim - rd) / RUN;           // and behind it
@@ -160,28 +152,28 @@ __global__ void __launch_bounds__(RS_THREADS) rope_store_kernel(const RopeStoreA
                 const bool in = w < n;
                 const uint32_t wc = in ? (uint32_t)w : 0u;
                 const uint32_t kr = wc / (uint32_t)ipr, c = wc - kr * (uint32_t)ipr;
-                const int kind = (int)c < nq ? RS_Q : ((int)c < nq + nk ? RS_K : RS_V);
-                const uint32_t ck = c - (uint32_t)(kind == RS_Q ? 0 : (kind == RS_K ? nq : nq + nk));
-                const uint32_t iph = (uint32_t)(kind == RS_Q ? iph_q : (kind == RS_K ? iph_k : iph_v));
+                const int kind = (int)c < nq ? ROW_Q : ((int)c < nq + nk ? ROW_K : ROW_V);
+                const uint32_t ck = c - (uint32_t)(kind == ROW_Q ? 0 : (kind == ROW_K ? nq : nq + nk));
+                const uint32_t iph = (uint32_t)(kind == ROW_Q ? iph_q : (kind == ROW_K ? iph_k : iph_v));
                 const uint32_t h = ck / iph, j = ck - h * iph;
                 const int64_t rko = __shfl(mine.ko, (int)kr), rvo = __shfl(mine.vo, (int)kr);
                 const int pos = __shfl(mine.pos, (int)kr);
-                const int k_rot = kind == RS_V ? 0 : n_rot, k_rd = kind == RS_V ? 0 : rd;
+                const int k_rot = kind == ROW_V ? 0 : n_rot, k_rd = kind == ROW_V ? 0 : rd;
                 const bool inside = (int)j < k_rot;
                 const int d = inside ? (int)j * RUN : k_rd + ((int)j - k_rot) * RUN;      // first column of the item
                 const int64_t r = r0 + kr;
-                const uint16_t* src = kind == RS_Q ? a.q + r * a.q_row_stride + (int64_t)h * a.q_head_stride
-                                    : kind == RS_K ? a.k + r * a.k_row_stride + (int64_t)h * a.k_head_stride
-                                                   : a.v + r * a.v_row_stride + (int64_t)h * a.v_head_stride;
-                op[u] = (kind == RS_Q ? a.qo + r * a.qo_row_stride + (int64_t)h * a.qo_head_stride
-                                      : a.ko + r * a.ko_row_stride + (int64_t)h * a.ko_head_stride) + d;
-                cp[u] = kind == RS_V ? a.vc : a.kc;
-                co[u] = (kind == RS_V ? rvo + (int64_t)h * a.vc_head_stride : rko + (int64_t)h * a.kc_head_stride) + d;
-                inv[u] = kind == RS_V ? vinv : kinv;
-                rot[u] = ROPE != RS_ROPE_NONE && in && inside && pos >= 0;
+                const uint16_t* src = kind == ROW_Q ? a.q + r * a.q_row_stride + (int64_t)h * a.q_head_stride
+                                    : kind == ROW_K ? a.k + r * a.k_row_stride + (int64_t)h * a.k_head_stride
+                                                    : a.v + r * a.v_row_stride + (int64_t)h * a.v_head_stride;
+                op[u] = (kind == ROW_Q ? a.qo + r * a.qo_row_stride + (int64_t)h * a.qo_head_stride
+                                       : a.ko + r * a.ko_row_stride + (int64_t)h * a.ko_head_stride) + d;
+                cp[u] = kind == ROW_V ? a.vc : a.kc;
+                co[u] = (kind == ROW_V ? rvo + (int64_t)h * a.vc_head_stride : rko + (int64_t)h * a.kc_head_stride) + d;
+                inv[u] = kind == ROW_V ? vinv : kinv;
+                rot[u] = ROPE != ROPE_NONE && in && inside && pos >= 0;
                 two[u] = NEOX && inside;
-                st[u] = in && (kind == RS_Q ? (rot[u] || !a.q_inplace) : (kind == RS_K && a.ko && (rot[u] || !a.k_inplace)));
-                cst[u] = in && kind != RS_Q && cached && rko >= 0;
+                st[u] = in && (kind == ROW_Q ? (rot[u] || !a.q_inplace) : (kind == ROW_K && a.ko && (rot[u] || !a.k_inplace)));
+                cst[u] = in && kind != ROW_Q && cached && rko >= 0;
                 const int64_t trow = (int64_t)(pos >= 0 ? pos : 0) * half;
                 // every load is unconditional, from an address that is valid whatever the lane's item is (an item past the step's
                 // last one reads the step's first run, a run without a partner itself, a run that is not rotated the first table
@@ -189,9 +181,9 @@ __global__ void __launch_bounds__(RS_THREADS) rope_store_kernel(const RopeStoreA
                 // use.  What is stored, and whether, is decided afterwards.
 #pragma unroll
                 for (int q = 0; q < W; ++q) {
-                    xa[u][q] = rs_ld(src + d + 8 * q);
-                    if constexpr (NEOX) xb[u][q] = rs_ld(src + d + (inside ? half : 0) + 8 * q);
-                    if constexpr (ROPE != RS_ROPE_NONE) {
+                    xa[u][q] = ld_nt16(src + d + 8 * q);
+                    if constexpr (NEOX) xb[u][q] = ld_nt16(src + d + (inside ? half : 0) + 8 * q);
+                    if constexpr (ROPE != ROPE_NONE) {
                         const int ds = inside ? d + 8 * q : 0;
                         const int t = NEOX ? ds : ds >> 1;                        // interleaved: pairs ds / 2 .. ds / 2 + 3
                         cw[u][q] = *reinterpret_cast<const CS*>(a.cos + trow + t);
@@ -207,7 +199,7 @@ __global__ void __launch_bounds__(RS_THREADS) rope_store_kernel(const RopeStoreA
                 for (int q = 0; q < W; ++q) {
                     ya[q] = xa[u][q];
                     yb[q] = xa[u][q];
-                    if constexpr (ROPE != RS_ROPE_NONE) {
+                    if constexpr (ROPE != ROPE_NONE) {
                         // rope_chunk reads its cos / sin through pointers: hand it the piece's values (registers after inlining;
                         // d_base 0 / half = "a piece of the first / second half", table index 0).  Every piece is rotated and the
                         // result kept where the row is to be rotated: a branch around the arithmetic would let hipcc sink the
@@ -256,9 +248,9 @@ static bool rs_wide_ok(const fa_rope_store_params& s) {
 template <typename T, bool KV8, int W>
 static void launch_rope_store_w(const RopeStoreArgs& a, int rope, int grid, hipStream_t stream) {
     const dim3 g(grid), b(RS_THREADS);
-    if (rope == RS_ROPE_NONE)             hipLaunchKernelGGL((rope_store_kernel<T, KV8, W, RS_ROPE_NONE>), g, b, 0, stream, a);
-    else if (rope == RS_ROPE_INTERLEAVED) hipLaunchKernelGGL((rope_store_kernel<T, KV8, W, RS_ROPE_INTERLEAVED>), g, b, 0, stream, a);
-    else                                  hipLaunchKernelGGL((rope_store_kernel<T, KV8, W, RS_ROPE_NEOX>), g, b, 0, stream, a);
+    if (rope == ROPE_NONE)             hipLaunchKernelGGL((rope_store_kernel<T, KV8, W, ROPE_NONE>), g, b, 0, stream, a);
+    else if (rope == ROPE_INTERLEAVED) hipLaunchKernelGGL((rope_store_kernel<T, KV8, W, ROPE_INTERLEAVED>), g, b, 0, stream, a);
+    else                                  hipLaunchKernelGGL((rope_store_kernel<T, KV8, W, ROPE_NEOX>), g, b, 0, stream, a);
 }
 
 template <typename T>
@@ -272,48 +264,23 @@ static void launch_rope_store_t(const RopeStoreArgs& a, bool kv8, int w, int rop
 // replaced descales of 0 by 1.0 and knows that total_rows, head_dim and nheads_q + nheads_k are positive
 void launch_rope_store(const fa_rope_store_params& s, hipStream_t stream) {
     RopeStoreArgs a;
-    a.q = static_cast<const uint16_t*>(s.q);
-    a.k = static_cast<const uint16_t*>(s.k);
-    a.v = static_cast<const uint16_t*>(s.v);
-    a.qo = static_cast<uint16_t*>(s.q_out);
-    a.ko = static_cast<uint16_t*>(s.k_out);
-    a.q_row_stride = s.q_row_stride; a.q_head_stride = s.q_head_stride;
-    a.k_row_stride = s.k_row_stride; a.k_head_stride = s.k_head_stride;
-    a.v_row_stride = s.v_row_stride; a.v_head_stride = s.v_head_stride;
-    a.qo_row_stride = s.qo_row_stride; a.qo_head_stride = s.qo_head_stride;
-    a.ko_row_stride = s.ko_row_stride; a.ko_head_stride = s.ko_head_stride;
-    a.kc = s.k_cache; a.vc = s.v_cache;
-    a.kc_batch_stride = s.kc_batch_stride; a.kc_row_stride = s.kc_row_stride; a.kc_head_stride = s.kc_head_stride;
-    a.vc_batch_stride = s.vc_batch_stride; a.vc_row_stride = s.vc_row_stride; a.vc_head_stride = s.vc_head_stride;
-    a.positions = s.positions;
-    a.slot_mapping = s.k_cache ? s.slot_mapping : nullptr;
-    a.n_rows = s.total_rows;
-    a.n_slots = s.k_cache ? (int64_t)s.num_blocks * s.page_block_size : 0;
-    a.cos = static_cast<const uint16_t*>(s.rotary_cos);
-    a.sin = static_cast<const uint16_t*>(s.rotary_sin);
-    a.nheads_q = s.q ? s.nheads_q : 0; a.nheads_k = s.nheads_k; a.head_dim = s.head_dim;
-    a.page = s.k_cache ? s.page_block_size : 1;
-    a.rotary_dim = s.rotary_dim; a.seqlen_ro = s.seqlen_ro;
-    a.q_inplace = s.q_out == s.q; a.k_inplace = s.k_out == s.k;
-    a.k_descale = s.k_descale; a.v_descale = s.v_descale;
+    fill_rope_store_args(a, s);
     const bool cached = s.k_cache != nullptr;
     const bool kv8 = cached && s.cache_dtype == FA_FP8_E4M3;
     const int w = rs_wide_ok(s) ? 2 : 1;
-    const int rope = s.seqlen_ro <= 0 ? RS_ROPE_NONE : (s.rotary_interleaved ? RS_ROPE_INTERLEAVED : RS_ROPE_NEOX);
+    const int rope = s.seqlen_ro <= 0 ? ROPE_NONE : (s.rotary_interleaved ? ROPE_INTERLEAVED : ROPE_NEOX);
     // the kernel's own item count of a row
-    const int run = 8 * w, rd = rope == RS_ROPE_NONE ? 0 : s.rotary_dim;
-    const int n_rot = rd / (rope == RS_ROPE_NEOX ? 2 * run : run), n_tail = (s.head_dim - rd) / run;
+    const int run = 8 * w, rd = rope == ROPE_NONE ? 0 : s.rotary_dim;
+    const int n_rot = rd / (rope == ROPE_NEOX ? 2 * run : run), n_tail = (s.head_dim - rd) / run;
     const int64_t iph_q = n_rot + (a.q_inplace ? 0 : n_tail);
     const int64_t iph_k = n_rot + (cached || (a.ko && !a.k_inplace) ? n_tail : 0);
     const int64_t iph_v = cached ? s.head_dim / run : 0;
     const int64_t ipr = a.nheads_q * iph_q + a.nheads_k * (iph_k + iph_v);
     if (ipr == 0) return;
-    const int64_t rows = (RS_STEP_ITEMS + ipr - 1) / ipr;
-    a.group_rows = (int)(rows < 1 ? 1 : (rows > RS_MAX_GROUP_ROWS ? RS_MAX_GROUP_ROWS : rows));
-    const int64_t groups = (a.n_rows + a.group_rows - 1) / a.group_rows;
-    const int grid = (int)(groups < RS_GRID_CAP ? groups : RS_GRID_CAP);
-    if (s.dtype == FA_BF16) launch_rope_store_t<bf16_tag>(a, kv8, w, rope, grid, stream);
-    else                    launch_rope_store_t<fp16_tag>(a, kv8, w, rope, grid, stream);
+    const RowPlan pl = row_plan(a.n_rows, ipr, RS_STEP_ITEMS, RS_MAX_GROUP_ROWS, RS_GRID_CAP);
+    a.group_rows = pl.group_rows;
+    if (s.dtype == FA_BF16) launch_rope_store_t<bf16_tag>(a, kv8, w, rope, pl.grid, stream);
+    else                    launch_rope_store_t<fp16_tag>(a, kv8, w, rope, pl.grid, stream);
 }
 
 }  // namespace fa

@@ -17,7 +17,7 @@
 //   - x streams (nontemporal loads and stores: every byte crosses once), cos / sin use ordinary loads (reused across heads and
 //     batch entries, they stay in L2).
 #include <cstdint>
-#include "fa_rope.h"
+#include "fa_rowops.h"
 
 namespace fa {
 
@@ -76,7 +76,6 @@ __device__ __forceinline__ RotRow rot_row(const RotaryArgs& a, int64_t r0, int l
     return w;
 }
 
-__device__ __forceinline__ u32x4 rot_ld(const uint16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)); }
 __device__ __forceinline__ void rot_st(uint16_t* p, u32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p)); }
 
 template <bool INTERLEAVED> struct RotTable;                          // the cos / sin values of one item
@@ -129,8 +128,8 @@ __global__ void __launch_bounds__(ROT_THREADS) rotary_fast_kernel(const RotaryAr
                 va[u] = vb[u] = u32x4{0, 0, 0, 0};
                 cw[u] = sw[u] = CS{};
                 if (kind[u] != ROT_NONE) {
-                    va[u] = rot_ld(xp);
-                    if (two[u]) vb[u] = rot_ld(xp + half);
+                    va[u] = ld_nt16(xp);
+                    if (two[u]) vb[u] = ld_nt16(xp + half);
                 }
                 if (kind[u] == ROT_ROTATE) {
                     const int64_t t = (int64_t)pos * half + (INTERLEAVED ? d >> 1 : d);
@@ -271,12 +270,10 @@ void launch_rotary(const fa_rotary_params& r, hipStream_t stream) {
     const int half = r.rotary_dim / 2, tail = a.inplace ? 0 : r.head_dim - r.rotary_dim;
     const int64_t iph = fast ? (r.interleaved ? r.rotary_dim / 8 : r.rotary_dim / 16) + tail / 8 : half + tail;
     const int64_t ipr = iph * r.nheads;
-    int64_t rows = (ROT_STEP_ITEMS + ipr - 1) / ipr;
-    a.group_rows = (int)(rows < 1 ? 1 : (rows > ROT_MAX_GROUP_ROWS ? ROT_MAX_GROUP_ROWS : rows));
-    const int64_t groups = (a.n_rows + a.group_rows - 1) / a.group_rows;
-    const int grid = (int)(groups < ROT_GRID_CAP ? groups : ROT_GRID_CAP);
-    if (r.dtype == FA_BF16) launch_rotary_t<bf16_tag>(a, fast, r.interleaved != 0, r.cos_sin_fp32 != 0, grid, stream);
-    else                    launch_rotary_t<fp16_tag>(a, fast, r.interleaved != 0, r.cos_sin_fp32 != 0, grid, stream);
+    const RowPlan pl = row_plan(a.n_rows, ipr, ROT_STEP_ITEMS, ROT_MAX_GROUP_ROWS, ROT_GRID_CAP);
+    a.group_rows = pl.group_rows;
+    if (r.dtype == FA_BF16) launch_rotary_t<bf16_tag>(a, fast, r.interleaved != 0, r.cos_sin_fp32 != 0, pl.grid, stream);
+    else                    launch_rotary_t<fp16_tag>(a, fast, r.interleaved != 0, r.cos_sin_fp32 != 0, pl.grid, stream);
 }
 
 }  // namespace fa

@@ -308,6 +308,21 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size"] + EXT_OPS
 
 
+# The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
+# export is `<entry point>_params_size`.  _load() sets restype / argtypes and checks the sizes from this table; the call_* and
+# *_workspace_bytes functions below are bound from it.
+ROW_OPS = [
+    ("fa_rotary", FaRotaryParams, None),
+    ("fa_kv_store", FaKvStoreParams, None),
+    ("fa_kv_gather", FaKvGatherParams, None),
+    ("fa_rope_store", FaRopeStoreParams, None),
+    ("fa_qk_norm_rope_store", FaQkNormRopeStoreParams, None),
+    ("fa_qk_norm_rope_bwd", FaQkNormRopeBwdParams, "fa_qk_norm_rope_bwd_workspace_bytes"),
+    ("fa_add_norm", FaAddNormParams, None),
+    ("fa_add_norm_bwd", FaAddNormBwdParams, "fa_add_norm_bwd_workspace_bytes"),
+]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -341,34 +356,14 @@ def _load():
     lib.fa_merge_states.restype = ctypes.c_int
     lib.fa_merge_states.argtypes = [ctypes.POINTER(FaMergeParams), ctypes.c_void_p]
     lib.fa_merge_params_size.restype = ctypes.c_size_t
-    lib.fa_rotary.restype = ctypes.c_int
-    lib.fa_rotary.argtypes = [ctypes.POINTER(FaRotaryParams), ctypes.c_void_p]
-    lib.fa_rotary_params_size.restype = ctypes.c_size_t
-    lib.fa_kv_store.restype = ctypes.c_int
-    lib.fa_kv_store.argtypes = [ctypes.POINTER(FaKvStoreParams), ctypes.c_void_p]
-    lib.fa_kv_store_params_size.restype = ctypes.c_size_t
-    lib.fa_kv_gather.restype = ctypes.c_int
-    lib.fa_kv_gather.argtypes = [ctypes.POINTER(FaKvGatherParams), ctypes.c_void_p]
-    lib.fa_kv_gather_params_size.restype = ctypes.c_size_t
-    lib.fa_rope_store.restype = ctypes.c_int
-    lib.fa_rope_store.argtypes = [ctypes.POINTER(FaRopeStoreParams), ctypes.c_void_p]
-    lib.fa_rope_store_params_size.restype = ctypes.c_size_t
-    lib.fa_qk_norm_rope_store.restype = ctypes.c_int
-    lib.fa_qk_norm_rope_store.argtypes = [ctypes.POINTER(FaQkNormRopeStoreParams), ctypes.c_void_p]
-    lib.fa_qk_norm_rope_store_params_size.restype = ctypes.c_size_t
-    lib.fa_qk_norm_rope_bwd.restype = ctypes.c_int
-    lib.fa_qk_norm_rope_bwd.argtypes = [ctypes.POINTER(FaQkNormRopeBwdParams), ctypes.c_void_p]
-    lib.fa_qk_norm_rope_bwd_workspace_bytes.restype = ctypes.c_size_t
-    lib.fa_qk_norm_rope_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaQkNormRopeBwdParams)]
-    lib.fa_qk_norm_rope_bwd_params_size.restype = ctypes.c_size_t
-    lib.fa_add_norm.restype = ctypes.c_int
-    lib.fa_add_norm.argtypes = [ctypes.POINTER(FaAddNormParams), ctypes.c_void_p]
-    lib.fa_add_norm_params_size.restype = ctypes.c_size_t
-    lib.fa_add_norm_bwd.restype = ctypes.c_int
-    lib.fa_add_norm_bwd.argtypes = [ctypes.POINTER(FaAddNormBwdParams), ctypes.c_void_p]
-    lib.fa_add_norm_bwd_workspace_bytes.restype = ctypes.c_size_t
-    lib.fa_add_norm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(FaAddNormBwdParams)]
-    lib.fa_add_norm_bwd_params_size.restype = ctypes.c_size_t
+    for entry, struct, query in ROW_OPS:
+        fn = getattr(lib, entry)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        getattr(lib, entry + "_params_size").restype = ctypes.c_size_t
+        if query:
+            getattr(lib, query).restype = ctypes.c_size_t
+            getattr(lib, query).argtypes = [ctypes.POINTER(struct)]
     i64 = ctypes.c_int64
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
@@ -385,30 +380,10 @@ def _load():
     if lib.fa_merge_params_size() != ctypes.sizeof(FaMergeParams):
         raise ImportError(f"fa_merge_params size mismatch: library {lib.fa_merge_params_size()} vs ctypes "
                           f"{ctypes.sizeof(FaMergeParams)}")
-    if lib.fa_rotary_params_size() != ctypes.sizeof(FaRotaryParams):
-        raise ImportError(f"fa_rotary_params size mismatch: library {lib.fa_rotary_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaRotaryParams)}")
-    if lib.fa_kv_store_params_size() != ctypes.sizeof(FaKvStoreParams):
-        raise ImportError(f"fa_kv_store_params size mismatch: library {lib.fa_kv_store_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaKvStoreParams)}")
-    if lib.fa_kv_gather_params_size() != ctypes.sizeof(FaKvGatherParams):
-        raise ImportError(f"fa_kv_gather_params size mismatch: library {lib.fa_kv_gather_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaKvGatherParams)}")
-    if lib.fa_rope_store_params_size() != ctypes.sizeof(FaRopeStoreParams):
-        raise ImportError(f"fa_rope_store_params size mismatch: library {lib.fa_rope_store_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaRopeStoreParams)}")
-    if lib.fa_qk_norm_rope_store_params_size() != ctypes.sizeof(FaQkNormRopeStoreParams):
-        raise ImportError(f"fa_qk_norm_rope_store_params size mismatch: library {lib.fa_qk_norm_rope_store_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaQkNormRopeStoreParams)}")
-    if lib.fa_qk_norm_rope_bwd_params_size() != ctypes.sizeof(FaQkNormRopeBwdParams):
-        raise ImportError(f"fa_qk_norm_rope_bwd_params size mismatch: library {lib.fa_qk_norm_rope_bwd_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaQkNormRopeBwdParams)}")
-    if lib.fa_add_norm_params_size() != ctypes.sizeof(FaAddNormParams):
-        raise ImportError(f"fa_add_norm_params size mismatch: library {lib.fa_add_norm_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaAddNormParams)}")
-    if lib.fa_add_norm_bwd_params_size() != ctypes.sizeof(FaAddNormBwdParams):
-        raise ImportError(f"fa_add_norm_bwd_params size mismatch: library {lib.fa_add_norm_bwd_params_size()} vs ctypes "
-                          f"{ctypes.sizeof(FaAddNormBwdParams)}")
+    for entry, struct, _ in ROW_OPS:
+        size = getattr(lib, entry + "_params_size")()
+        if size != ctypes.sizeof(struct):
+            raise ImportError(f"{entry}_params size mismatch: library {size} vs ctypes {ctypes.sizeof(struct)}")
     return lib
 
 
@@ -443,77 +418,38 @@ def call_tree(params, ext, tree, stream):
         raise RuntimeError(f"fa_fwd_kvcache_tree failed ({rc}): {msg}")
 
 
-def call_merge(params, stream):
-    """fa_merge_states"""
-    rc = lib.fa_merge_states(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_merge_states failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+def _struct_call(entry):
+    """the call_* function of a (params, stream) entry point: raises RuntimeError with the library's message on failure"""
+    fn = getattr(lib, entry)
+
+    def call_op(params, stream):
+        rc = fn(ctypes.byref(params), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"{entry} failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+    call_op.__name__ = call_op.__qualname__ = "call_" + entry[len("fa_"):]
+    call_op.__doc__ = entry
+    return call_op
 
 
-def call_rotary(params, stream):
-    """fa_rotary"""
-    rc = lib.fa_rotary(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_rotary failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+def _workspace_query(query):
+    """the *_workspace_bytes function of a workspace query: needs no device"""
+    fn = getattr(lib, query)
+
+    def workspace_bytes(params):
+        return int(fn(ctypes.byref(params)))
+    workspace_bytes.__name__ = workspace_bytes.__qualname__ = query[len("fa_"):]
+    workspace_bytes.__doc__ = query + ": needs no device"
+    return workspace_bytes
 
 
-def call_kv_store(params, stream):
-    """fa_kv_store"""
-    rc = lib.fa_kv_store(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_kv_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def call_kv_gather(params, stream):
-    """fa_kv_gather"""
-    rc = lib.fa_kv_gather(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_kv_gather failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def call_rope_store(params, stream):
-    """fa_rope_store"""
-    rc = lib.fa_rope_store(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_rope_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def call_qk_norm_rope_store(params, stream):
-    """fa_qk_norm_rope_store"""
-    rc = lib.fa_qk_norm_rope_store(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_qk_norm_rope_store failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def call_qk_norm_rope_bwd(params, stream):
-    """fa_qk_norm_rope_bwd"""
-    rc = lib.fa_qk_norm_rope_bwd(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_qk_norm_rope_bwd failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def qk_norm_rope_bwd_workspace_bytes(params):
-    """fa_qk_norm_rope_bwd_workspace_bytes: needs no device"""
-    return int(lib.fa_qk_norm_rope_bwd_workspace_bytes(ctypes.byref(params)))
-
-
-def call_add_norm(params, stream):
-    """fa_add_norm"""
-    rc = lib.fa_add_norm(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_add_norm failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def call_add_norm_bwd(params, stream):
-    """fa_add_norm_bwd"""
-    rc = lib.fa_add_norm_bwd(ctypes.byref(params), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"fa_add_norm_bwd failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
-
-
-def add_norm_bwd_workspace_bytes(params):
-    """fa_add_norm_bwd_workspace_bytes: needs no device"""
-    return int(lib.fa_add_norm_bwd_workspace_bytes(ctypes.byref(params)))
+call_merge = _struct_call("fa_merge_states")
+# call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
+# call_add_norm_bwd; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes
+for _entry, _struct, _query in ROW_OPS:
+    globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
+    if _query:
+        globals()[_query[len("fa_"):]] = _workspace_query(_query)
+del _entry, _struct, _query
 
 
 def call_rows(name, *args):

@@ -27,6 +27,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from . import _rowargs as _ra
 from . import flash_attn_interface as _fi
 
 MAX_N = 16384
@@ -51,12 +52,7 @@ def _rows(t, N, inplace, name):
 
 
 def _param(w, N, dtype, name):
-    if w.dtype not in (dtype, torch.float32):
-        raise RuntimeError(f"add_norm: {name} must have x's dtype ({dtype}) or float32, got {w.dtype}")
-    if tuple(w.shape) != (N,):
-        raise RuntimeError(f"add_norm: {name} must have shape (N,) = ({N},), got {tuple(w.shape)}")
-    w = w.contiguous()
-    return w if w.data_ptr() % 16 == 0 else w.clone()
+    return _ra.weight("add_norm", w, N, dtype, name, of="x", dim="N")
 
 
 def _check_x(x, name="x"):
@@ -68,15 +64,6 @@ def _check_x(x, name="x"):
     if N % 8 != 0 or not (8 <= N <= MAX_N):
         raise RuntimeError(f"add_norm: the hidden size must be a multiple of 8 in [8, {MAX_N}], got {N}")
     return N
-
-
-def _scalars(eps, weight_offset):
-    eps, weight_offset = float(eps), float(weight_offset)
-    if not (0.0 <= eps < float("inf")):
-        raise RuntimeError(f"add_norm: eps must be finite and >= 0, got {eps}")
-    if not (abs(weight_offset) < float("inf")):
-        raise RuntimeError(f"add_norm: weight_offset must be finite, got {weight_offset}")
-    return eps, weight_offset
 
 
 def _code(dtype, io):
@@ -106,11 +93,8 @@ def add_norm_forward(x, weight, bias=None, residual=None, *, eps: float = 1e-6, 
             raise RuntimeError(f"add_norm: residual must have x's dtype ({x.dtype}) or float32, got {residual.dtype}")
         if tuple(residual.shape) != tuple(x.shape):
             raise RuntimeError(f"add_norm: residual must have x's shape {tuple(x.shape)}, got {tuple(residual.shape)}")
-    eps, weight_offset = _scalars(eps, weight_offset)
-    tensors = [x, w, b, residual]
-    _fi._check_device(*tensors)
-    if any(t is not None and t.device != x.device for t in tensors):
-        raise RuntimeError("add_norm: every tensor must be on x's device")
+    eps, weight_offset = _ra.scalars("add_norm", eps, weight_offset)
+    _ra.same_device("add_norm", [x, w, b, residual], x, "x's")
 
     ro_dtype = residual_out_dtype(x.dtype, None if residual is None else residual.dtype, residual_in_fp32)
     want_ro = residual is not None or prenorm
@@ -178,11 +162,8 @@ def add_norm_backward(dy, z, weight, dres_out=None, *, eps: float = 1e-6, weight
     if weight is None:
         raise RuntimeError("add_norm: weight must not be None")
     w = _param(weight, N, dy.dtype, "weight")
-    eps, weight_offset = _scalars(eps, weight_offset)
-    tensors = [dy, z, dres_out, w]
-    _fi._check_device(*tensors)
-    if any(t is not None and t.device != dy.device for t in tensors):
-        raise RuntimeError("add_norm: every tensor must be on dy's device")
+    eps, weight_offset = _ra.scalars("add_norm", eps, weight_offset)
+    _ra.same_device("add_norm", [dy, z, dres_out, w], dy, "dy's")
 
     dev = dy.device
     dyi = _rows(dy, N, inplace and need_dx, "dy")

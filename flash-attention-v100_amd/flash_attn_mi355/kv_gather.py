@@ -18,14 +18,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from . import _rowargs as _ra
 from . import flash_attn_interface as _fi
 from . import kv_store as _kv_store
-
-
-def _i32(t, shape, name):
-    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"kv_gather: {name} must be an int32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    return t.contiguous()
 
 
 def _viewable(t):
@@ -57,14 +52,13 @@ def gather_kv_cache(k_cache, v_cache, *, slot_mapping: Optional[torch.Tensor] = 
     any other `out` is an error, never a copy.  Without `out` fresh contiguous tensors are returned; cu_seqlens mode then needs
     total_rows (a host number: the call does not read cu_seqlens[-1] back), slot mode takes it from slot_mapping.
     No host synchronisation; capturable in a HIP graph."""
+    op = "kv_gather"
     fp8 = k_cache.dtype == _fi._FP8
     if v_cache.dtype != k_cache.dtype or not (fp8 or k_cache.dtype in _fi._DTYPES):
         raise RuntimeError(f"kv_gather: k_cache / v_cache must both be fp16, bf16 or float8_e4m3fn, got {k_cache.dtype} / {v_cache.dtype}")
-    if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape):
-        raise RuntimeError(f"kv_gather: k_cache and v_cache must have the same 4-D shape, got {tuple(k_cache.shape)} / {tuple(v_cache.shape)}")
+    _ra.cache_shape(op, k_cache, v_cache)
     H, D = k_cache.shape[2:]
-    if D % 8 != 0 or D > 256:
-        raise RuntimeError(f"kv_gather: head dimension must be a multiple of 8 and <= 256, got {D}")
+    _ra.head_dim(op, D)
     if fp8:
         if dtype is None:
             raise RuntimeError("kv_gather: a float8_e4m3fn cache needs dtype= (torch.float16 or torch.bfloat16)")
@@ -74,52 +68,31 @@ def gather_kv_cache(k_cache, v_cache, *, slot_mapping: Optional[torch.Tensor] = 
         if dtype is not None and dtype != k_cache.dtype:
             raise RuntimeError(f"kv_gather: a 16-bit cache is copied bit for bit: dtype must be None or the cache's ({k_cache.dtype}), got {dtype}")
         dtype = k_cache.dtype
-        if k_descale is not None or v_descale is not None:
-            raise RuntimeError("kv_gather: k_descale / v_descale go with a float8_e4m3fn cache")
-    if (slot_mapping is None) == (cu_seqlens is None):
-        raise RuntimeError("kv_gather: exactly one addressing mode - slot_mapping, or cu_seqlens (with seq_offsets and block_table "
-                           f"/ cache_batch_idx); {'both' if slot_mapping is not None else 'neither'} given")
-    if k_cache.stride(-1) != 1 or v_cache.stride(-1) != 1:
-        raise RuntimeError("kv_gather: k_cache / v_cache must have a contiguous last dimension (a cache is never copied)")
+        _ra.descales_need_fp8(op, fp8, k_descale, v_descale)
+    _ra.one_mode(op, slot_mapping, cu_seqlens, "seq_offsets")
+    _ra.cache_last_dim(op, k_cache, v_cache)
 
     s = _lib.FaKvGatherParams()
     s.struct_size = ctypes.sizeof(_lib.FaKvGatherParams)
-    keep = []                                             # tensors made here stay referenced until the launch is queued
+    B = 0
     if slot_mapping is not None:
-        if seq_offsets is not None or block_table is not None or cache_batch_idx is not None:
-            raise RuntimeError("kv_gather: slot_mapping takes no seq_offsets, block_table or cache_batch_idx")
+        _ra.slot_mode(op, seq_offsets, "seq_offsets", block_table, cache_batch_idx)
         if slot_mapping.dtype not in (torch.int64, torch.int32) or slot_mapping.dim() != 1:
             raise RuntimeError("kv_gather: slot_mapping must be an int64 (or int32) tensor of shape (total_rows,)")
         if total_rows is not None and int(total_rows) != slot_mapping.numel():
             raise RuntimeError(f"kv_gather: total_rows {total_rows} is not slot_mapping's length {slot_mapping.numel()}")
         T = slot_mapping.numel()
         slot_mapping = slot_mapping.to(torch.int64).contiguous()
-        keep.append(slot_mapping)
     else:
-        if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 1:
-            raise RuntimeError("kv_gather: cu_seqlens must be an int32 tensor of shape (batch + 1,)")
-        B = cu_seqlens.numel() - 1
-        cu_seqlens = cu_seqlens.contiguous()
-        if seq_offsets is not None:
-            seq_offsets = _i32(seq_offsets, (B,), "seq_offsets")
-        if block_table is not None:
-            if cache_batch_idx is not None:
-                raise RuntimeError("kv_gather: a paged cache (block_table) does not take cache_batch_idx")
-            if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-                raise RuntimeError(f"kv_gather: block_table must be an int32 tensor of shape ({B}, max_num_blocks_per_seq)")
-            if block_table.stride(1) != 1:
-                block_table = block_table.contiguous()
-        elif cache_batch_idx is not None:
-            cache_batch_idx = _i32(cache_batch_idx, (B,), "cache_batch_idx")
-        elif k_cache.shape[0] < B:
-            raise RuntimeError(f"kv_gather: the cache has {k_cache.shape[0]} batch slots for {B} sequences (pass cache_batch_idx)")
+        B, cu_seqlens, seq_offsets, block_table, cache_batch_idx = _ra.sequence_mode(
+            op, k_cache, cu_seqlens, seq_offsets, "seq_offsets", block_table, cache_batch_idx)
         if total_rows is None and out is None:
             raise RuntimeError("kv_gather: cu_seqlens mode needs total_rows= (or out=): the number of rows is a host quantity, "
                                "the call does not read cu_seqlens[-1] back from the device")
         T = int(total_rows) if total_rows is not None else int(out[0].shape[0])
         if T < 0:
             raise RuntimeError(f"kv_gather: total_rows must be >= 0, got {T}")
-        keep += [cu_seqlens, seq_offsets, block_table, cache_batch_idx]
+    # (the tensors made above stay referenced by these names until the launch is queued)
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 2:
             raise RuntimeError("kv_gather: out must be a pair (k_out, v_out)")
@@ -132,44 +105,24 @@ def gather_kv_cache(k_cache, v_cache, *, slot_mapping: Optional[torch.Tensor] = 
                                    "that are multiples of 16 bytes (an output is never copied behind the caller's back)")
     else:
         k = v = None
-    tensors = [k_cache, v_cache, slot_mapping, cu_seqlens, seq_offsets, block_table, cache_batch_idx, k, v]
-    _fi._check_device(*tensors)
-    if any(t is not None and t.device != k_cache.device for t in tensors):
-        raise RuntimeError("kv_gather: every tensor must be on the cache's device")
+    _ra.same_device(op, [k_cache, v_cache, slot_mapping, cu_seqlens, seq_offsets, block_table, cache_batch_idx, k, v], k_cache,
+                    "the cache's")
     if out is None:
         k = torch.empty((T, H, D), dtype=dtype, device=k_cache.device)
         v = torch.empty((T, H, D), dtype=dtype, device=k_cache.device)
     if T == 0 or H == 0:
         return k, v
 
-    s.k_cache, s.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
-    s.kc_batch_stride, s.kc_row_stride, s.kc_head_stride = k_cache.stride(0), k_cache.stride(1), k_cache.stride(2)
-    s.vc_batch_stride, s.vc_row_stride, s.vc_head_stride = v_cache.stride(0), v_cache.stride(1), v_cache.stride(2)
     s.k, s.v = k.data_ptr(), v.data_ptr()
     s.k_row_stride, s.k_head_stride = k.stride(0), k.stride(1)
     s.v_row_stride, s.v_head_stride = v.stride(0), v.stride(1)
     s.total_rows, s.nheads, s.head_dim = T, H, D
     s.dtype = _fi._DTYPES[dtype]
-    s.cache_dtype = _lib.FA_FP8_E4M3 if fp8 else s.dtype
-    s.num_blocks, s.page_block_size = k_cache.shape[0], k_cache.shape[1]
-    if fp8:
-        s.k_descale = 1.0 if k_descale is None else float(k_descale)
-        s.v_descale = 1.0 if v_descale is None else float(v_descale)
-    if slot_mapping is not None:
-        s.slot_mapping = slot_mapping.data_ptr()
-    else:
-        s.cu_seqlens, s.batch = cu_seqlens.data_ptr(), B
-        if seq_offsets is not None:
-            s.seq_offsets = seq_offsets.data_ptr()
-        if block_table is not None:
-            s.paged = 1
-            s.block_table, s.block_table_batch_stride = block_table.data_ptr(), block_table.stride(0)
-            s.max_blocks = block_table.shape[1]
-        elif cache_batch_idx is not None:
-            s.cache_batch_idx = cache_batch_idx.data_ptr()
+    _ra.fill_cache(s, k_cache, v_cache, fp8, k_descale, v_descale)
+    _ra.fill_mode(s, slot_mapping, cu_seqlens, B, seq_offsets, "seq_offsets", block_table, cache_batch_idx)
     with _fi._on_device(k_cache.device):
-        _lib.call_kv_gather(s, _fi._stream(k_cache.device))   # (queued: `keep` stays referenced until here)
-    del keep
+        _lib.call_kv_gather(s, _fi._stream(k_cache.device))   # (queued: the prepared tensors stay referenced until here)
+    del slot_mapping, cu_seqlens, seq_offsets, block_table, cache_batch_idx
     return k, v
 
 
