@@ -17,6 +17,14 @@ deliberate (DESIGN.md "divergences"):
     `flash_attn_sinks_func` for the dense layout, keyword `sinks` of `flash_attn_varlen_func` and
     `flash_attn_with_kvcache` (the C ABI's *_ext entry points).
 There is no CPU fallback: tensors must live on an AMD GPU and the HIP library must load.
+
+Structure of the host code: each op checks its arguments and allocates its outputs itself; the ~60 fields of `fa_params`
+are filled in ONE place, `_fill_params` (layouts "bshd", "thd", paged K / V; fp8 q / k / v and fp8 caches; the optional
+gradient block), for the dense and varlen forwards and backwards and for the slow path of `flash_attn_with_kvcache`
+(whose cached fast path copies a filled struct and rewrites the pointers).  `_attach_workspace` (query, allocate, attach
+- on q's device) and `_finish_out` (the caller's `out`, or the slice off the head-dim padding) are shared by those
+paths; the two backwards are one body, `_backward`; the five autograd classes share `_save_ctx`,
+`_grad_buffers`, `_autograd_backward` and `_cut_grads`.
 """
 import collections
 import ctypes
@@ -152,8 +160,6 @@ def _check_qkv(q, k, v):
         raise RuntimeError("q, k, v must have the same number of dimensions")
     if q.shape[-1] != k.shape[-1] or q.shape[-1] != v.shape[-1]:
         raise RuntimeError("q, k, v must have the same head dimension")
-    if q.stride(-1) != 1 or k.stride(-1) != 1 or v.stride(-1) != 1:
-        pass                                             # _prep() makes a contiguous copy
 
 
 def _check_out(out, q):
@@ -224,9 +230,7 @@ def _set3(p, name, t, layout):
         setattr(p, name + "_head_stride", t.stride(1))
 
 
-def _alibi(p, alibi_slopes, batch, nheads, device):
-    if alibi_slopes is None:
-        return None
+def _alibi(p, alibi_slopes, batch, nheads):
     if alibi_slopes.dtype != torch.float32 or not alibi_slopes.is_cuda:
         raise RuntimeError("alibi_slopes must be fp32 on the GPU")
     if alibi_slopes.stride(-1) != 1:
@@ -235,15 +239,12 @@ def _alibi(p, alibi_slopes, batch, nheads, device):
         raise RuntimeError("alibi_slopes must be [H_Q] or [B, H_Q]")
     p.alibi_slopes = _ptr(alibi_slopes)
     p.alibi_batch_stride = alibi_slopes.stride(0) if alibi_slopes.dim() == 2 else 0
-    return alibi_slopes
 
 
 def _philox(p, dropout_p, batch, nheads, device, rng=None):
-    """Seed/offset from the default GPU generator; the offset advances by B*H*32 per call
+    """dropout_p > 0: seed/offset from the default GPU generator; the offset advances by B*H*32 per call
     (kernel/fused_mha_forward.cu:377-386)."""
     p.p_dropout = float(dropout_p)
-    if dropout_p <= 0.0:
-        return (0, 0)
     if rng is None:
         gen = torch.cuda.default_generators[device.index if device.index is not None
                                             else torch.cuda.current_device()]
@@ -260,7 +261,18 @@ def _workspace(nbytes, device):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def _base_params(q, dtype, scale, causal, window_size, softcap):
+def _attach_workspace(p, query, device):
+    """Ask `query` (a *_workspace_bytes export) what the launch of `p` needs, allocate it and attach it: (workspace or None,
+    bytes asked for).  Call it inside `_on_device(device)`: the query reads the CURRENT device's CU count, which must be
+    the device of the launch.  The caller keeps the tensor until the launch is enqueued."""
+    nbytes = int(query(ctypes.byref(p)))
+    ws = _workspace(nbytes, device)
+    if ws is not None:
+        p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
+    return ws, nbytes
+
+
+def _base_params(_q, dtype, scale, causal, window_size, softcap):
     p = FaParams()
     p.dtype = p.kv_dtype = _DTYPES[dtype]
     p.softmax_scale = float(scale)
@@ -271,6 +283,78 @@ def _base_params(q, dtype, scale, causal, window_size, softcap):
     return p
 
 
+def _fill_params(layout, q, k, v, o, lse, dims, seqlen_q, seqlen_k, softmax_scale, causal, window_size, softcap, alibi_slopes,
+                 flags=0, dropout_p=0.0, rng=None, descales=(None, None, None), cu_seqlens=None, seqused_k=None,
+                 block_table=None, grads=None):
+    """The one place fa_params is filled: (p, rng) for every attention launch but the cached decode fast path.
+
+    layout: 'bshd' - q / k / v / o [B, S, H, D], lse [B, H, S] - or 'thd' - [T, H, D], lse [H, T], with cu_seqlens =
+    (cu_seqlens_q, cu_seqlens_k) as contiguous int32 tensors; with a block_table (contiguous int32 [B, max_blocks]) k / v are
+    paged [num_blocks, page, Hk, D].  The tensors are the ones the kernels see (_prep / _prep8 done); dims = (batch, H_Q, H_K,
+    their head dim), which every caller has at hand (reading them off the tensors again costs 0.4 us a call); seqlen_q /
+    seqlen_k are the dense lengths or the varlen maxima.  float8_e4m3fn q (then k and v too) selects the fp8 forward and its bf16
+    out, float8_e4m3fn k with a 16-bit q an fp8 cache; descales = (q, k, v) scalars, None = 1, read for fp8 tensors only.
+    grads = (dout, dq, dk, dv, softmax_d) for a backward: a None gradient stays NULL with zero strides, so its kernel does
+    not run.  rng: the forward's (seed, offset) for a backward, None to draw from the default generator (dropout_p > 0)."""
+    if k.dtype == _FP8:                                  # an fp8 cache or, with an fp8 q, the fp8 forward (bf16 out)
+        fp8_q = q.dtype == _FP8
+        p = _base_params(q, torch.bfloat16 if fp8_q else q.dtype, softmax_scale, causal, window_size, softcap)
+        p.kv_dtype = _lib.FA_FP8_E4M3
+        if fp8_q:
+            p.dtype = _lib.FA_FP8_E4M3
+            p.o_dtype = _lib.FA_BF16
+            p.q_descale = 1.0 if descales[0] is None else float(descales[0])
+        p.k_descale = 1.0 if descales[1] is None else float(descales[1])
+        p.v_descale = 1.0 if descales[2] is None else float(descales[2])
+    else:
+        p = _base_params(q, q.dtype, softmax_scale, causal, window_size, softcap)
+    p.q, p.k, p.v, p.o, p.lse = _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse)
+    kv_layout = layout if block_table is None else "pshd"
+    _set3(p, "q", q, layout); _set3(p, "k", k, kv_layout); _set3(p, "v", v, kv_layout)
+    _set3(p, "o", o, layout)
+    B, H_Q, H_K, D = dims
+    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
+    _set_head_dim(p, D)
+    if layout == "thd":
+        p.seqlen_q, p.seqlen_k = int(seqlen_q), int(seqlen_k)
+        p.lse_batch_stride, p.lse_head_stride = 0, lse.stride(0)
+        p.cu_seqlens_q, p.cu_seqlens_k = _ptr(cu_seqlens[0]), _ptr(cu_seqlens[1])
+        p.total_q = q.shape[0]
+        p.total_k = k.shape[0] if block_table is None else 0
+        p.seqused_k = _ptr(seqused_k)
+    else:
+        p.seqlen_q, p.seqlen_k = seqlen_q, seqlen_k
+        p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
+    if block_table is not None:
+        p.block_table = _ptr(block_table)
+        p.block_table_batch_stride = block_table.stride(0)
+        p.page_block_size = k.shape[1]
+    if grads is not None:
+        dout, dq, dk, dv, softmax_d = grads
+        p.dout, p.dq, p.dk, p.dv, p.softmax_d = _ptr(dout), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(softmax_d)
+        for name, t in (("do", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+            if t is not None:
+                _set3(p, name, t, layout)
+    if flags:
+        p.flags = flags
+    if alibi_slopes is not None:
+        _alibi(p, alibi_slopes, B, H_Q)
+    if dropout_p > 0.0:
+        return p, _philox(p, dropout_p, B, H_Q, q.device, rng=rng)
+    p.p_dropout = float(dropout_p)
+    return p, (0, 0)
+
+
+def _finish_out(out, out_, dpad, head_size_og):
+    """what a forward returns for the tensor the kernel wrote: the caller's `out` (copied into when the kernel could not write
+    it directly), else out_ (head dim dpad) without the head-dim padding.  The forwards return out_ themselves in the usual case
+    (no caller's out, no padding) and come here for the rest."""
+    if out is not None and out_ is not out:
+        out.copy_(out_[..., :head_size_og])
+        return out
+    return out_ if dpad == head_size_og else out_[..., :head_size_og].contiguous()
+
+
 # ======================================================================================
 # DENSE ATTENTION (B, M, H, D)
 # ======================================================================================
@@ -279,107 +363,89 @@ def _base_params(q, dtype, scale, causal, window_size, softcap):
 FWD_SPLIT = os.environ.get("FA_FWD_SPLIT", "0") == "1"
 
 
-def _dense_forward_fp8(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax):
-    """fa_fwd on float8_e4m3fn [B, S, H, D] q, k, v (descales 1): bf16 out, fp32 LSE; the return tuple of _dense_forward."""
-    if q.dim() != 4:
-        raise RuntimeError("q, k, v must be (batch, seqlen, nheads, headdim)")
-    B, M, H_Q, head_size_og = q.shape
-    N, H_K = k.shape[1], k.shape[2]
-    _check_shape(k, (B, N, H_K, head_size_og), "k")
-    _check_shape(v, (B, N, H_K, head_size_og), "v")
-    _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes)
-    d16 = (head_size_og + 15) // 16 * 16
-    q_, k_, v_ = _prep8(q, d16), _prep8(k, d16), _prep8(v, d16)
-    if softmax_scale is None:
-        softmax_scale = head_size_og ** -0.5
-    out_ = torch.empty((B, M, H_Q, d16), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, H_Q, M), dtype=torch.float32, device=q.device)
-    p = _base_params(q_, torch.bfloat16, softmax_scale, causal, window_size, softcap)
-    p.dtype = p.kv_dtype = _lib.FA_FP8_E4M3
-    p.o_dtype = _lib.FA_BF16
-    p.q_descale = 1.0
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
-    _set3(p, "q", q_, "bshd"); _set3(p, "k", k_, "bshd"); _set3(p, "v", v_, "bshd")
-    _set3(p, "o", out_, "bshd")
-    p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
-    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
-    p.seqlen_q, p.seqlen_k = M, N
-    _set_head_dim(p, d16)
-    if q_.numel() > 0:
-        with _on_device(q.device):
-            _lib.call("fa_fwd", p, _stream(q.device))
-    res = out_ if d16 == head_size_og else out_[..., :head_size_og].contiguous()
-    dmask = torch.empty((0,), dtype=torch.bfloat16, device=q.device)
-    return res, lse, dmask, (q_, k_, v_, out_), (0, 0), softmax_scale
-
-
 def _dense_forward(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                    return_softmax, out=None, keep_window=False, sinks=None):
-    """One fa_fwd call on [B, S, H, D] views (any strides with a contiguous last dim).  keep_window (sharding.py only):
+    """One fa_fwd call on [B, S, H, D] views (any strides with a contiguous last dim).  float8_e4m3fn q, k, v (descales 1)
+    run the fp8 forward: bf16 out, fp32 LSE.  keep_window (sharding.py only):
     FA_FLAG_KEEP_WINDOW - a right window of >= seqlen_k keys stays a window where it still hides keys (seqlen_q >
     seqlen_k); the public functions keep the reference's normalisation, which drops it.  sinks: contiguous fp32 [H_Q]
     attention sinks (_check_sinks) or None - with sinks the call goes through fa_fwd_ext."""
     _check_device(q, k, v)
-    if _is_fp8_qkv(q, k, v):
+    fp8 = _is_fp8_qkv(q, k, v)
+    if fp8:
         if sinks is not None:
             raise RuntimeError("fp8 forward: attention sinks are not supported")
         if out is not None or keep_window:
             raise RuntimeError("fp8 forward: no caller-allocated out / sharding window")
-        return _dense_forward_fp8(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                                  return_softmax)
-    _check_qkv(q, k, v)
+    else:
+        _check_qkv(q, k, v)
     if q.dim() != 4:
         raise RuntimeError("q, k, v must be (batch, seqlen, nheads, headdim)")
     B, M, H_Q, head_size_og = q.shape
     N, H_K = k.shape[1], k.shape[2]
     _check_shape(k, (B, N, H_K, head_size_og), "k")
     _check_shape(v, (B, N, H_K, head_size_og), "v")
-    if out is not None:
-        _check_out(out, q)
-    dpad = (head_size_og + 7) // 8 * 8
-    _padded_head_dim(dpad)                                   # raises above 256
-    q_, k_, v_ = _prep(q, dpad), _prep(k, dpad), _prep(v, dpad)
+    if fp8:
+        _check_fp8_options(head_size_og, dropout_p, softcap, alibi_slopes)
+        dpad, prep, o_dtype = (head_size_og + 15) // 16 * 16, _prep8, torch.bfloat16
+    else:
+        if out is not None:
+            _check_out(out, q)
+        dpad, prep, o_dtype = (head_size_og + 7) // 8 * 8, _prep, q.dtype
+        _padded_head_dim(dpad)                               # raises above 256
+    q_, k_, v_ = prep(q, dpad), prep(k, dpad), prep(v, dpad)
     if softmax_scale is None:
         softmax_scale = head_size_og ** -0.5
 
-    out_ = out if _usable_out(out, dpad, head_size_og) else torch.empty((B, M, H_Q, dpad), dtype=q.dtype, device=q.device)
+    out_ = out if _usable_out(out, dpad, head_size_og) else torch.empty((B, M, H_Q, dpad), dtype=o_dtype, device=q.device)
     lse = torch.empty((B, H_Q, M), dtype=torch.float32, device=q.device)
-    p = _base_params(q_, q.dtype, softmax_scale, causal, window_size, softcap)
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
-    _set3(p, "q", q_, "bshd"); _set3(p, "k", k_, "bshd"); _set3(p, "v", v_, "bshd")
-    _set3(p, "o", out_, "bshd")
-    p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
-    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
-    p.seqlen_q, p.seqlen_k = M, N
-    if keep_window:
-        p.flags = _lib.FA_FLAG_KEEP_WINDOW
-    if FWD_SPLIT:
-        p.flags |= _lib.FA_FLAG_FWD_KEY_SPLIT
-    _set_head_dim(p, dpad)
-    _alibi(p, alibi_slopes, B, H_Q, q.device)
-    rng = _philox(p, dropout_p, B, H_Q, q.device)
-    dmask = torch.empty((0,), dtype=q.dtype, device=q.device)
+    split = FWD_SPLIT and not fp8
+    flags = (_lib.FA_FLAG_KEEP_WINDOW if keep_window else 0) | (_lib.FA_FLAG_FWD_KEY_SPLIT if split else 0)
+    p, rng = _fill_params("bshd", q_, k_, v_, out_, lse, (B, H_Q, H_K, dpad), M, N, softmax_scale, causal, window_size,
+                          softcap, alibi_slopes, flags, dropout_p)
+    dmask = torch.empty((0,), dtype=o_dtype, device=q.device)
     if return_softmax and dropout_p > 0.0:
-        dmask = torch.zeros((B, H_Q, M, N), dtype=q.dtype, device=q.device)
+        dmask = torch.zeros((B, H_Q, M, N), dtype=o_dtype, device=q.device)
         p.dmask = _ptr(dmask)
     if q_.numel() > 0:                                   # (an empty query block is a no-op)
         with _on_device(q.device):
             # (non-zero only with the opt-in key split of one-wave causal launches, include/fa_mi355.h: FA_FLAG_FWD_KEY_SPLIT)
-            ws = _workspace(_lib.lib.fa_fwd_workspace_bytes(ctypes.byref(p)), q.device) if (FWD_SPLIT and N > 0) else None
-            if ws is not None:
-                p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
+            ws = _attach_workspace(p, _lib.lib.fa_fwd_workspace_bytes, q.device) if (split and N > 0) else None
             _lib.call_ext("fa_fwd", p, None if sinks is None else _lib.ext_params(sinks), _stream(q.device))
-    if out is not None and out_ is not out:              # caller-allocated out the kernel could not write directly
-        out.copy_(out_[..., :head_size_og])
-        res = out
-    else:
-        res = out_ if dpad == head_size_og else out_[..., :head_size_og].contiguous()
+    res = out_ if (out is None and dpad == head_size_og) else _finish_out(out, out_, dpad, head_size_og)
     return res, lse, dmask, (q_, k_, v_, out_), rng, softmax_scale
 
 
 # Opt-in experiment (include/fa_mi355.h: FA_FLAG_DS_HANDOFF; break-even on BASELINE config 2, profiles/r06_ds_handoff.txt): the dense
 # D = 128 backward hands dS from the dK/dV kernel to a one-GEMM dQ kernel instead of recomputing S and dP.  FA_BWD_DS=1 at import.
 DS_HANDOFF = os.environ.get("FA_BWD_DS", "0") == "1"
+
+
+def _backward(layout, dout, q_, k_, v_, out_, lse, cu_seqlens, seqlen_q, seqlen_k, alibi_slopes, dropout_p, softmax_scale,
+              causal, window_size, softcap, rng, dq_, dk_, dv_, flags, sinks, dsinks):
+    """One fa_bwd ('bshd') / fa_varlen_bwd ('thd') call: the body of _dense_backward and _varlen_backward.  Returns
+    softmax_d, which is allocated on the empty-query path too (where nothing is launched)."""
+    H_Q, dpad = q_.shape[-2], q_.shape[-1]
+    batch = q_.shape[0] if layout == "bshd" else cu_seqlens[0].numel() - 1
+    dout_ = _prep(dout, dpad)
+    softmax_d = torch.empty((batch, H_Q, q_.shape[1]) if layout == "bshd" else (H_Q, q_.shape[0]),
+                            dtype=torch.float32, device=q_.device)
+    if (dk_ is None) != (dv_ is None):
+        raise RuntimeError("dk and dv are computed together: pass both or neither")
+    if q_.numel() == 0:                                  # no queries: nothing flows into K / V
+        if dk_ is not None:
+            dk_.zero_(); dv_.zero_()
+        if dsinks is not None:
+            dsinks.zero_()
+        return softmax_d
+    p, _ = _fill_params(layout, q_, k_, v_, out_, lse, (batch, H_Q, k_.shape[-2], dpad), seqlen_q, seqlen_k, softmax_scale,
+                        causal, window_size, softcap, alibi_slopes, flags, dropout_p, rng, cu_seqlens=cu_seqlens,
+                        grads=(dout_, dq_, dk_, dv_, softmax_d))
+    with _on_device(q_.device):
+        ws = _attach_workspace(p, _lib.lib.fa_bwd_workspace_bytes, q_.device)
+        ext = None if sinks is None else _lib.ext_params(sinks, dsinks)
+        _lib.call_ext("fa_bwd" if layout == "bshd" else "fa_varlen_bwd", p, ext, _stream(q_.device))
+    return softmax_d
 
 
 def _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, dropout_p, softmax_scale, causal,
@@ -395,49 +461,20 @@ def _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, dropout_p, softma
 
     sinks / dsinks: the forward's fp32 [H_Q] attention sinks and a caller-allocated fp32 [H_Q] for their gradient (or
     None): fa_bwd_ext.  dq_ = dk_ = dv_ = None with dsinks given computes the sinks' gradient only."""
-    B, M, H_Q, dpad = q_.shape
-    N, H_K = k_.shape[1], k_.shape[2]
-    dout_ = _prep(dout, dpad)
-    softmax_d = torch.empty((B, H_Q, M), dtype=torch.float32, device=q_.device)
-    if (dk_ is None) != (dv_ is None):
-        raise RuntimeError("dk and dv are computed together: pass both or neither")
-    if q_.numel() == 0:                                  # no queries: nothing flows into K / V
-        if dk_ is not None:
-            dk_.zero_(); dv_.zero_()
-        if dsinks is not None:
-            dsinks.zero_()
-        return softmax_d
-    p = _base_params(q_, q_.dtype, softmax_scale, causal, window_size, softcap)
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
-    p.dout, p.dq, p.dk, p.dv, p.softmax_d = _ptr(dout_), _ptr(dq_), _ptr(dk_), _ptr(dv_), _ptr(softmax_d)
-    for name, t in (("q", q_), ("k", k_), ("v", v_), ("o", out_), ("do", dout_),
-                    ("dq", dq_), ("dk", dk_), ("dv", dv_)):
-        if t is not None:                               # a gradient nobody needs: NULL -> its kernel does not run
-            _set3(p, name, t, "bshd")
-    p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
-    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
-    p.seqlen_q, p.seqlen_k = M, N
-    if keep_window:
-        p.flags = _lib.FA_FLAG_KEEP_WINDOW
-    if deterministic:
-        p.flags |= _lib.FA_FLAG_NO_DKV_SPLIT
-    if DS_HANDOFF:
-        p.flags |= _lib.FA_FLAG_DS_HANDOFF
-    _set_head_dim(p, dpad)
-    _alibi(p, alibi_slopes, B, H_Q, q_.device)
-    _philox(p, dropout_p, B, H_Q, q_.device, rng=rng)
-    with _on_device(q_.device):                          # (the query reads the CURRENT device's CU count: same device as the launch)
-        ws = _workspace(_lib.lib.fa_bwd_workspace_bytes(ctypes.byref(p)), q_.device)
-        if ws is not None:
-            p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
-        ext = None if sinks is None else _lib.ext_params(sinks, dsinks)
-        _lib.call_ext("fa_bwd", p, ext, _stream(q_.device))
-    return softmax_d
+    flags = ((_lib.FA_FLAG_KEEP_WINDOW if keep_window else 0) | (_lib.FA_FLAG_NO_DKV_SPLIT if deterministic else 0) |
+             (_lib.FA_FLAG_DS_HANDOFF if DS_HANDOFF else 0))
+    return _backward("bshd", dout, q_, k_, v_, out_, lse, None, q_.shape[1], k_.shape[1], alibi_slopes, dropout_p,
+                     softmax_scale, causal, window_size, softcap, rng, dq_, dk_, dv_, flags, sinks, dsinks)
 
 
-def _save_dense(ctx, saved, lse, alibi_slopes, dropout_p, softmax_scale, causal, window_size, softcap,
-                deterministic, head_size_og, rng):
-    ctx.save_for_backward(*saved, lse, alibi_slopes)
+# ---- what the autograd classes share (and the backward ops of torch_ops.py / sharding.py: _grad_buffers) ----
+def _save_ctx(ctx, res, alibi_slopes, sinks, dropout_p, causal, window_size, softcap, deterministic, head_size_og,
+              max_seqlens=(None, None)):
+    """what every autograd backward needs, from `res`, _dense_forward's / _varlen_forward's return tuple.  One form for the
+    five classes: the saved tensors end in (lse, alibi_slopes, sinks) - sinks None where the class has none - and the dense
+    classes keep max_seqlen_q / max_seqlen_k = None."""
+    _, lse, _, saved, rng, softmax_scale = res
+    ctx.save_for_backward(*saved, lse, alibi_slopes, sinks)
     ctx.dropout_p = dropout_p
     ctx.softmax_scale = softmax_scale
     ctx.causal = causal
@@ -445,7 +482,42 @@ def _save_dense(ctx, saved, lse, alibi_slopes, dropout_p, softmax_scale, causal,
     ctx.softcap = softcap
     ctx.deterministic = deterministic
     ctx.head_size_og = head_size_og
+    ctx.max_seqlen_q, ctx.max_seqlen_k = max_seqlens
     ctx.rng = rng
+
+
+def _autograd_result(ctx, res):
+    """what an autograd forward returns with return_attn_probs: (out, lse, dmask), the last two non-differentiable"""
+    ctx.mark_non_differentiable(res[1], res[2])
+    return res[:3]
+
+
+def _grad_buffers(q_, k_, v_, need_q=True, need_kv=True):
+    """(dq_, dk_, dv_) padded like the prepared q_ / k_ / v_; a gradient nobody needs is None"""
+    dpad = q_.shape[-1]
+    dq_ = _prep(torch.empty_like(q_), dpad) if need_q else None
+    if not need_kv:
+        return dq_, None, None
+    return dq_, _prep(torch.empty_like(k_), dpad), _prep(torch.empty_like(v_), dpad)
+
+
+def _autograd_backward(ctx, saved_tensors, dout, dq_, dk_, dv_, dsinks=None):
+    """the backward launch from what _save_ctx kept (saved_tensors = ctx.saved_tensors, unpacked once by the caller):
+    dense, or varlen when _save_ctx was given max_seqlens"""
+    *saved, lse, alibi_slopes, sinks = saved_tensors
+    if ctx.max_seqlen_q is None:                         # a dense class: saved = (q_, k_, v_, out_)
+        _dense_backward(dout, *saved, lse, alibi_slopes, ctx.dropout_p, ctx.softmax_scale, ctx.causal, ctx.window_size,
+                        ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic, sinks=sinks, dsinks=dsinks)
+    else:                                                # FlashAttnVarlenFunc: saved = (q_, k_, v_, out_, cu_seqlens_q, cu_seqlens_k)
+        _varlen_backward(dout, *saved[:4], lse, saved[4], saved[5], alibi_slopes, ctx.max_seqlen_q, ctx.max_seqlen_k,
+                         ctx.dropout_p, ctx.softmax_scale, ctx.causal, ctx.window_size, ctx.softcap, ctx.rng,
+                         dq_, dk_, dv_, deterministic=ctx.deterministic, sinks=sinks, dsinks=dsinks)
+
+
+def _cut_grads(ctx, dq_, dk_, dv_):
+    """(dq, dk, dv) without the head-dim padding, None where inputs 0 / 1 / 2 of the Function need no gradient"""
+    d, need = ctx.head_size_og, ctx.needs_input_grad
+    return (dq_[..., :d] if need[0] else None, dk_[..., :d] if need[1] else None, dv_[..., :d] if need[2] else None)
 
 
 class FlashAttnFunc(torch.autograd.Function):
@@ -453,28 +525,17 @@ class FlashAttnFunc(torch.autograd.Function):
     def forward(ctx, q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
                 alibi_slopes, deterministic, return_softmax, is_grad_enabled):
         is_grad = is_grad_enabled and any(x.requires_grad for x in [q, k, v])
-        out, lse, dmask, saved, rng, softmax_scale = _dense_forward(
-            q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax)
+        res = _dense_forward(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax)
         if is_grad:
-            _save_dense(ctx, saved, lse, alibi_slopes, dropout_p, softmax_scale, causal, window_size,
-                        softcap, deterministic, q.shape[-1], rng)
-        if return_softmax:
-            ctx.mark_non_differentiable(lse, dmask)
-            return out, lse, dmask
-        return out
+            _save_ctx(ctx, res, alibi_slopes, None, dropout_p, causal, window_size, softcap, deterministic, q.shape[-1])
+        return _autograd_result(ctx, res) if return_softmax else res[0]
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q_, k_, v_, out_, lse, alibi_slopes = ctx.saved_tensors
-        d = ctx.head_size_og
-        need_q, need_kv = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        new = lambda t: _prep(torch.empty_like(t), q_.shape[-1])
-        dq_ = new(q_) if need_q else None
-        dk_, dv_ = (new(k_), new(v_)) if need_kv else (None, None)
-        _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, ctx.dropout_p, ctx.softmax_scale,
-                        ctx.causal, ctx.window_size, ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic)
-        cut = lambda t, need: t[..., :d] if (t is not None and need) else None
-        return (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2])) + (None,) * 10
+        saved, need = ctx.saved_tensors, ctx.needs_input_grad
+        dq_, dk_, dv_ = _grad_buffers(saved[0], saved[1], saved[2], need[0], need[1] or need[2])
+        _autograd_backward(ctx, saved, dout, dq_, dk_, dv_)
+        return _cut_grads(ctx, dq_, dk_, dv_) + (None,) * 10
 
 
 class FlashAttnSinksFunc(torch.autograd.Function):
@@ -485,30 +546,19 @@ class FlashAttnSinksFunc(torch.autograd.Function):
     def forward(ctx, q, k, v, sinks, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                 return_softmax, is_grad_enabled):
         is_grad = is_grad_enabled and any(x.requires_grad for x in [q, k, v, sinks])
-        out, lse, dmask, saved, rng, softmax_scale = _dense_forward(
-            q, k, v, 0.0, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax, sinks=sinks)
+        res = _dense_forward(q, k, v, 0.0, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax,
+                             sinks=sinks)
         if is_grad:
-            _save_dense(ctx, saved + (sinks,), lse, alibi_slopes, 0.0, softmax_scale, causal, window_size,
-                        softcap, deterministic, q.shape[-1], rng)
-        if return_softmax:
-            ctx.mark_non_differentiable(lse, dmask)
-            return out, lse, dmask
-        return out
+            _save_ctx(ctx, res, alibi_slopes, sinks, 0.0, causal, window_size, softcap, deterministic, q.shape[-1])
+        return _autograd_result(ctx, res) if return_softmax else res[0]
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q_, k_, v_, out_, sinks, lse, alibi_slopes = ctx.saved_tensors
-        d = ctx.head_size_og
-        need_q, need_kv = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        need_s = ctx.needs_input_grad[3]
-        new = lambda t: _prep(torch.empty_like(t), q_.shape[-1])
-        dq_ = new(q_) if need_q else None
-        dk_, dv_ = (new(k_), new(v_)) if need_kv else (None, None)
-        dsinks = torch.empty_like(sinks) if need_s else None
-        _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, 0.0, ctx.softmax_scale, ctx.causal, ctx.window_size,
-                        ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic, sinks=sinks, dsinks=dsinks)
-        cut = lambda t, need: t[..., :d] if (t is not None and need) else None
-        return (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2]), dsinks) + (None,) * 8
+        saved, need = ctx.saved_tensors, ctx.needs_input_grad
+        dq_, dk_, dv_ = _grad_buffers(saved[0], saved[1], saved[2], need[0], need[1] or need[2])
+        dsinks = torch.empty_like(saved[-1]) if need[3] else None
+        _autograd_backward(ctx, saved, dout, dq_, dk_, dv_, dsinks)
+        return _cut_grads(ctx, dq_, dk_, dv_) + (dsinks,) + (None,) * 8
 
 
 class FlashAttnQKVPackedFunc(torch.autograd.Function):
@@ -521,27 +571,20 @@ class FlashAttnQKVPackedFunc(torch.autograd.Function):
         if qkv.dtype == _FP8:
             _check_fp8_no_grad(qkv, grad_enabled=is_grad_enabled)
         is_grad = is_grad_enabled and qkv.requires_grad
-        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
-        out, lse, dmask, saved, rng, softmax_scale = _dense_forward(
-            q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax)
+        res = _dense_forward(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size,
+                             softcap, alibi_slopes, return_softmax)
         if is_grad:
-            _save_dense(ctx, saved, lse, alibi_slopes, dropout_p, softmax_scale, causal, window_size,
-                        softcap, deterministic, qkv.shape[-1], rng)
-        if return_softmax:
-            ctx.mark_non_differentiable(lse, dmask)
-            return out, lse, dmask
-        return out
+            _save_ctx(ctx, res, alibi_slopes, None, dropout_p, causal, window_size, softcap, deterministic, qkv.shape[-1])
+        return _autograd_result(ctx, res) if return_softmax else res[0]
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q_, k_, v_, out_, lse, alibi_slopes = ctx.saved_tensors
-        d = ctx.head_size_og
+        saved = ctx.saved_tensors
+        q_ = saved[0]
         B, S, H, dpad = q_.shape
         dqkv = torch.empty((B, S, 3, H, dpad), dtype=q_.dtype, device=q_.device)
-        _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, ctx.dropout_p, ctx.softmax_scale,
-                        ctx.causal, ctx.window_size, ctx.softcap, ctx.rng,
-                        dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], deterministic=ctx.deterministic)
-        return (dqkv[..., :d],) + (None,) * 9
+        _autograd_backward(ctx, saved, dout, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2])
+        return (dqkv[..., :ctx.head_size_og],) + (None,) * 9
 
 
 class FlashAttnKVPackedFunc(torch.autograd.Function):
@@ -553,28 +596,21 @@ class FlashAttnKVPackedFunc(torch.autograd.Function):
         if _is_fp8_qkv(q, kv, kv):
             _check_fp8_no_grad(q, kv, grad_enabled=is_grad_enabled)
         is_grad = is_grad_enabled and any(x.requires_grad for x in [q, kv])
-        k, v = kv[:, :, 0], kv[:, :, 1]
-        out, lse, dmask, saved, rng, softmax_scale = _dense_forward(
-            q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, return_softmax)
+        res = _dense_forward(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap,
+                             alibi_slopes, return_softmax)
         if is_grad:
-            _save_dense(ctx, saved, lse, alibi_slopes, dropout_p, softmax_scale, causal, window_size,
-                        softcap, deterministic, q.shape[-1], rng)
-        if return_softmax:
-            ctx.mark_non_differentiable(lse, dmask)
-            return out, lse, dmask
-        return out
+            _save_ctx(ctx, res, alibi_slopes, None, dropout_p, causal, window_size, softcap, deterministic, q.shape[-1])
+        return _autograd_result(ctx, res) if return_softmax else res[0]
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q_, k_, v_, out_, lse, alibi_slopes = ctx.saved_tensors
-        d = ctx.head_size_og
+        saved = ctx.saved_tensors
+        q_, k_ = saved[0], saved[1]
         B, Sk, Hk, dpad = k_.shape
-        dq_ = torch.empty_like(q_)
-        dq_ = _prep(dq_, dpad)
+        dq_ = _prep(torch.empty_like(q_), dpad)
         dkv = torch.empty((B, Sk, 2, Hk, dpad), dtype=q_.dtype, device=q_.device)
-        _dense_backward(dout, q_, k_, v_, out_, lse, alibi_slopes, ctx.dropout_p, ctx.softmax_scale,
-                        ctx.causal, ctx.window_size, ctx.softcap, ctx.rng, dq_, dkv[:, :, 0], dkv[:, :, 1],
-                        deterministic=ctx.deterministic)
+        _autograd_backward(ctx, saved, dout, dq_, dkv[:, :, 0], dkv[:, :, 1])
+        d = ctx.head_size_og
         return (dq_[..., :d], dkv[..., :d]) + (None,) * 9
 
 
@@ -709,9 +745,7 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     if softmax_scale is None:
         softmax_scale = head_size_og ** -0.5
     T_Q, H_Q = q_.shape[0], q_.shape[1]
-    H_K = k_.shape[-2]
-    B = cu_seqlens_q.numel() - 1
-    paged = block_table is not None
+    dims = (cu_seqlens_q.numel() - 1, H_Q, k_.shape[-2], dpad)
 
     o_dtype = torch.bfloat16 if fp8_q else q.dtype           # (the fp8 forward writes bf16)
     if out is not None:
@@ -721,52 +755,22 @@ def _varlen_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqle
     if zero_tensors:
         out_.zero_()
         lse.fill_(float("-inf"))
-    p = _base_params(q_, o_dtype, softmax_scale, causal, window_size, softcap)
-    if fp8_q:
-        p.dtype = p.kv_dtype = _lib.FA_FP8_E4M3
-        p.o_dtype = _lib.FA_BF16
-        p.q_descale = 1.0 if q_descale is None else float(q_descale)
-        p.k_descale = 1.0 if k_descale is None else float(k_descale)
-        p.v_descale = 1.0 if v_descale is None else float(v_descale)
-    if fp8:
-        p.kv_dtype = _lib.FA_FP8_E4M3
-        p.k_descale = 1.0 if k_descale is None else float(k_descale)
-        p.v_descale = 1.0 if v_descale is None else float(v_descale)
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
-    p.seqused_k = _ptr(seqused_k)
-    _set3(p, "q", q_, "thd"); _set3(p, "o", out_, "thd")
-    _set3(p, "k", k_, "pshd" if paged else "thd"); _set3(p, "v", v_, "pshd" if paged else "thd")
-    p.lse_batch_stride, p.lse_head_stride = 0, lse.stride(0)
-    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
-    p.seqlen_q, p.seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
-    _set_head_dim(p, dpad)
-    p.cu_seqlens_q, p.cu_seqlens_k = _ptr(cu_seqlens_q), _ptr(cu_seqlens_k)
-    p.total_q = T_Q
-    p.total_k = 0 if paged else k_.shape[0]
-    if paged:
+    if block_table is not None:
         block_table = block_table.to(torch.int32).contiguous()
-        p.block_table = _ptr(block_table)
-        p.block_table_batch_stride = block_table.stride(0)
-        p.page_block_size = k_.shape[1]
-    _alibi(p, alibi_slopes, B, H_Q, q.device)
-    rng = _philox(p, dropout_p, B, H_Q, q.device)
+    p, rng = _fill_params("thd", q_, k_, v_, out_, lse, dims, max_seqlen_q, max_seqlen_k, softmax_scale, causal, window_size,
+                          softcap, alibi_slopes, 0, dropout_p, None, (q_descale, k_descale, v_descale),
+                          (cu_seqlens_q, cu_seqlens_k), seqused_k, block_table)
     dmask = torch.empty((0,), dtype=o_dtype, device=q.device)
     if return_attn_probs and dropout_p > 0.0:
-        dmask = torch.zeros((T_Q, H_Q, max_seqlen_k), dtype=q.dtype, device=q.device)
+        dmask = torch.zeros((T_Q, H_Q, max_seqlen_k), dtype=o_dtype, device=q.device)
         p.dmask = _ptr(dmask)
-    # (decode issued through this op - the same few query tokens per sequence over paged K / V - runs the decode kernels
-    #  when their split-KV workspace is there: fa_api.hip varlen_decode_route)
-    ws = _workspace(_lib.lib.fa_fwd_workspace_bytes(ctypes.byref(p)), q.device)
-    if ws is not None:
-        p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
-    if q_.numel() > 0:
-        with _on_device(q.device):
+    with _on_device(q.device):
+        # (decode issued through this op - the same few query tokens per sequence over paged K / V - runs the decode kernels
+        #  when their split-KV workspace is there: fa_api.hip varlen_decode_route)
+        ws = _attach_workspace(p, _lib.lib.fa_fwd_workspace_bytes, q.device)
+        if q_.numel() > 0:
             _lib.call_ext("fa_varlen_fwd", p, None if sinks is None else _lib.ext_params(sinks), _stream(q.device))
-    if out is not None and out_ is not out:
-        out.copy_(out_[..., :head_size_og])
-        res = out
-    else:
-        res = out_ if dpad == head_size_og else out_[..., :head_size_og].contiguous()
+    res = out_ if (out is None and dpad == head_size_og) else _finish_out(out, out_, dpad, head_size_og)
     return res, lse, dmask, (q_, k_, v_, out_, cu_seqlens_q, cu_seqlens_k), rng, softmax_scale
 
 
@@ -774,43 +778,9 @@ def _varlen_backward(dout, q_, k_, v_, out_, lse, cu_seqlens_q, cu_seqlens_k, al
                      max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal, window_size,
                      softcap, rng, dq_, dk_, dv_, deterministic=False, sinks=None, dsinks=None):
     """One fa_varlen_bwd call (fa_varlen_bwd_ext with attention sinks; see _dense_backward for sinks / dsinks)."""
-    T_Q, H_Q, dpad = q_.shape
-    H_K = k_.shape[1]
-    B = cu_seqlens_q.numel() - 1
-    dout_ = _prep(dout, dpad)
-    softmax_d = torch.empty((H_Q, T_Q), dtype=torch.float32, device=q_.device)
-    if (dk_ is None) != (dv_ is None):
-        raise RuntimeError("dk and dv are computed together: pass both or neither")
-    if q_.numel() == 0:
-        if dk_ is not None:
-            dk_.zero_(); dv_.zero_()
-        if dsinks is not None:
-            dsinks.zero_()
-        return softmax_d
-    p = _base_params(q_, q_.dtype, softmax_scale, causal, window_size, softcap)
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q_), _ptr(k_), _ptr(v_), _ptr(out_), _ptr(lse)
-    p.dout, p.dq, p.dk, p.dv, p.softmax_d = _ptr(dout_), _ptr(dq_), _ptr(dk_), _ptr(dv_), _ptr(softmax_d)
-    for name, t in (("q", q_), ("k", k_), ("v", v_), ("o", out_), ("do", dout_),
-                    ("dq", dq_), ("dk", dk_), ("dv", dv_)):
-        if t is not None:                               # a gradient nobody needs: NULL -> its kernel does not run
-            _set3(p, name, t, "thd")
-    p.lse_batch_stride, p.lse_head_stride = 0, lse.stride(0)
-    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
-    p.seqlen_q, p.seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
-    _set_head_dim(p, dpad)
-    p.cu_seqlens_q, p.cu_seqlens_k = _ptr(cu_seqlens_q), _ptr(cu_seqlens_k)
-    p.total_q, p.total_k = T_Q, k_.shape[0]
-    if deterministic:
-        p.flags |= _lib.FA_FLAG_NO_DKV_SPLIT
-    _alibi(p, alibi_slopes, B, H_Q, q_.device)
-    _philox(p, dropout_p, B, H_Q, q_.device, rng=rng)
-    with _on_device(q_.device):
-        ws = _workspace(_lib.lib.fa_bwd_workspace_bytes(ctypes.byref(p)), q_.device)
-        if ws is not None:
-            p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
-        ext = None if sinks is None else _lib.ext_params(sinks, dsinks)
-        _lib.call_ext("fa_varlen_bwd", p, ext, _stream(q_.device))
-    return softmax_d
+    return _backward("thd", dout, q_, k_, v_, out_, lse, (cu_seqlens_q, cu_seqlens_k), max_seqlen_q, max_seqlen_k,
+                     alibi_slopes, dropout_p, softmax_scale, causal, window_size, softcap, rng, dq_, dk_, dv_,
+                     _lib.FA_FLAG_NO_DKV_SPLIT if deterministic else 0, sinks, dsinks)
 
 
 class FlashAttnVarlenFunc(torch.autograd.Function):
@@ -819,45 +789,25 @@ class FlashAttnVarlenFunc(torch.autograd.Function):
                 softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                 return_attn_probs, block_table, is_grad_enabled, sinks=None):
         is_grad = is_grad_enabled and any(x is not None and x.requires_grad for x in [q, k, v, sinks])
-        out, lse, dmask, saved, rng, softmax_scale = _varlen_forward(
+        res = _varlen_forward(
             q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
             causal, window_size, softcap, alibi_slopes, return_attn_probs, block_table, sinks=sinks)
         if is_grad:
             if block_table is not None:
                 raise RuntimeError("backward through paged K/V (block_table) is not supported")
-            ctx.save_for_backward(*saved, lse, alibi_slopes, sinks)
-            ctx.dropout_p = dropout_p
-            ctx.softmax_scale = softmax_scale
-            ctx.causal = causal
-            ctx.window_size = window_size
-            ctx.softcap = softcap
-            ctx.deterministic = deterministic
-            ctx.head_size_og = q.size(-1)
-            ctx.max_seqlen_q = max_seqlen_q
-            ctx.max_seqlen_k = max_seqlen_k
-            ctx.rng = rng
-        if return_attn_probs:
-            ctx.mark_non_differentiable(lse, dmask)
-            return out, lse, dmask
-        return out
+            _save_ctx(ctx, res, alibi_slopes, sinks, dropout_p, causal, window_size, softcap, deterministic,
+                      q.size(-1), (max_seqlen_q, max_seqlen_k))
+        return _autograd_result(ctx, res) if return_attn_probs else res[0]
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q_, k_, v_, out_, cu_seqlens_q, cu_seqlens_k, lse, alibi_slopes, sinks = ctx.saved_tensors
-        d = ctx.head_size_og
-        need_q, need_kv = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        need_s = len(ctx.needs_input_grad) > 17 and ctx.needs_input_grad[17]
-        new = lambda t: _prep(torch.empty_like(t), q_.shape[-1])
-        dq_ = new(q_) if need_q else None
-        dk_, dv_ = (new(k_), new(v_)) if need_kv else (None, None)
-        dsinks = torch.empty_like(sinks) if need_s else None
-        _varlen_backward(dout, q_, k_, v_, out_, lse, cu_seqlens_q, cu_seqlens_k, alibi_slopes,
-                         ctx.max_seqlen_q, ctx.max_seqlen_k, ctx.dropout_p, ctx.softmax_scale,
-                         ctx.causal, ctx.window_size, ctx.softcap, ctx.rng, dq_, dk_, dv_, deterministic=ctx.deterministic,
-                         sinks=sinks, dsinks=dsinks)
-        cut = lambda t, need: t[..., :d] if (t is not None and need) else None
-        grads = (cut(dq_, need_q), cut(dk_, ctx.needs_input_grad[1]), cut(dv_, ctx.needs_input_grad[2])) + (None,) * 14
-        return grads + (dsinks,) if len(ctx.needs_input_grad) > 17 else grads
+        saved, need = ctx.saved_tensors, ctx.needs_input_grad
+        with_sinks = len(need) > 17                         # (apply() was given the optional 18th argument)
+        dq_, dk_, dv_ = _grad_buffers(saved[0], saved[1], saved[2], need[0], need[1] or need[2])
+        dsinks = torch.empty_like(saved[-1]) if (with_sinks and need[17]) else None
+        _autograd_backward(ctx, saved, dout, dq_, dk_, dv_, dsinks)
+        grads = _cut_grads(ctx, dq_, dk_, dv_) + (None,) * 14
+        return grads + (dsinks,) if with_sinks else grads
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int,
@@ -1028,34 +978,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
 
     out = torch.empty_like(q)
     lse = torch.empty((B, H_Q, T_Q), dtype=torch.float32, device=q.device)
-    p = _base_params(q, q.dtype, softmax_scale, causal, window_size, softcap)
-    if fp8:
-        p.kv_dtype = _lib.FA_FP8_E4M3
-        p.k_descale = 1.0 if k_descale is None else float(k_descale)
-        p.v_descale = 1.0 if v_descale is None else float(v_descale)
-    p.q, p.k, p.v, p.o, p.lse = _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(lse)
-    _set3(p, "q", q, "bshd"); _set3(p, "o", out, "bshd")
-    _set3(p, "k", k_cache, "bshd"); _set3(p, "v", v_cache, "bshd")
-    p.lse_batch_stride, p.lse_head_stride = lse.stride(0), lse.stride(1)
-    p.batch, p.nheads_q, p.nheads_k = B, H_Q, H_K
-    p.seqlen_q = T_Q
-    _set_head_dim(p, D)                                  # width 64 / 128 / 256; narrower rows read as zeros past D
-    if paged:
-        p.block_table = _ptr(block_table)
-        p.block_table_batch_stride = block_table.stride(0)
-        p.page_block_size = k_cache.shape[1]
-        p.seqlen_k = block_table.shape[1] * k_cache.shape[1]
-    else:
-        p.seqlen_k = k_cache.shape[1]
-    p.cache_seqlens = _ptr(cache_seqlens)
-    p.cache_batch_idx = _ptr(cache_batch_idx)
-    p.cache_leftpad = _ptr(cache_leftpad)
-    if k is not None:
-        if v is None:
-            raise RuntimeError("If key is supplied, value must also be passed in")
-        p.k_new, p.v_new = _ptr(k), _ptr(v)
-        _set3(p, "knew", k, "bshd"); _set3(p, "vnew", v, "bshd")
-        p.seqlen_new = k.shape[1]
+    if k is not None and v is None:
+        raise RuntimeError("If key is supplied, value must also be passed in")
     if rotary_cos is not None:
         if rotary_sin is None:
             raise RuntimeError("rotary_sin must be given with rotary_cos")
@@ -1063,26 +987,35 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
             raise RuntimeError("rotary_cos must have the same dtype as query")
         if rotary_cos.dim() != 2 or not rotary_cos.is_contiguous() or not rotary_sin.is_contiguous():
             raise RuntimeError("rotary_cos/rotary_sin must be contiguous 2D tensors")
+        if rotary_cos.shape[1] * 2 > q.shape[-1]:
+            raise RuntimeError("rotary_dim must be <= headdim")
+    # (head dim: width 64 / 128 / 256; narrower rows read as zeros past D.  The tree flag is set before the workspace
+    #  query, which answers for the route a tree call takes)
+    p, _ = _fill_params("bshd", q, k_cache, v_cache, out, lse, (B, H_Q, H_K, D), T_Q,
+                        block_table.shape[1] * k_cache.shape[1] if paged else k_cache.shape[1], softmax_scale, causal,
+                        window_size, softcap, alibi_slopes, _lib.FA_FLAG_TREE_MASK if tree_words is not None else 0,
+                        descales=(None, k_descale, v_descale), block_table=block_table)
+    # what only this op has: the cache index tensors, the new tokens, the in-kernel rotation, the split count
+    p.cache_seqlens = _ptr(cache_seqlens)
+    p.cache_batch_idx = _ptr(cache_batch_idx)
+    p.cache_leftpad = _ptr(cache_leftpad)
+    if k is not None:
+        p.k_new, p.v_new = _ptr(k), _ptr(v)
+        _set3(p, "knew", k, "bshd"); _set3(p, "vnew", v, "bshd")
+        p.seqlen_new = k.shape[1]
+    if rotary_cos is not None:
         p.rotary_cos, p.rotary_sin = _ptr(rotary_cos), _ptr(rotary_sin)
         p.rotary_dim = rotary_cos.shape[1] * 2
-        if p.rotary_dim > q.shape[-1]:
-            raise RuntimeError("rotary_dim must be <= headdim")
         p.seqlen_ro = rotary_cos.shape[0]
         p.rotary_interleaved = int(bool(rotary_interleaved))
-    _alibi(p, alibi_slopes, B, H_Q, q.device)
     p.num_splits = int(num_splits)
-    if tree_words is not None:
-        p.flags |= _lib.FA_FLAG_TREE_MASK               # (the workspace query answers for the route a tree call takes)
-    ws_bytes = int(_lib.lib.fa_fwd_kvcache_workspace_bytes(ctypes.byref(p)))
-    ws = _workspace(ws_bytes, q.device)
-    if ws is not None:
-        p.workspace, p.workspace_bytes = _ptr(ws), ws.numel()
+    ext = None if s32 is None else _lib.ext_params(s32)
     with _on_device(q.device):
+        ws, ws_bytes = _attach_workspace(p, _lib.lib.fa_fwd_kvcache_workspace_bytes, q.device)
         if tree_words is not None:
-            _lib.call_tree(p, None if s32 is None else _lib.ext_params(s32), _lib.tree_params(tree_words, tree_depths),
-                           _stream(q.device))
+            _lib.call_tree(p, ext, _lib.tree_params(tree_words, tree_depths), _stream(q.device))
         else:
-            _lib.call_ext("fa_fwd_kvcache", p, None if s32 is None else _lib.ext_params(s32), _stream(q.device))
+            _lib.call_ext("fa_fwd_kvcache", p, ext, _stream(q.device))
     if key is not None:                                  # (the call went through: this geometry passes every check)
         while len(_KV_PLANS) >= _KV_PLANS_MAX:           # least recently used geometry out (a workload whose geometry keeps
             _KV_PLANS.popitem(last=False)                # changing must not wipe the plans of the steady ones)

@@ -72,12 +72,11 @@ def _local_bwd(dout, q, k, v, out, lse, window, scale):
     """fa_bwd of the LOCAL problem (q over this rank's key shard) with the GLOBAL out / lse: P = exp(s - LSE_global) and
     D = rowsum(dO o O_global) are then the true probabilities / row-dots of the full problem, so dk, dv of the shard are
     complete and dq is this shard's share of the sum over keys."""
-    import torch
     from . import flash_attn_interface as fi
     d = q.shape[-1]
     dpad = (d + 7) // 8 * 8
     q_, k_, v_, o_ = (fi._prep(t, dpad) for t in (q, k, v, out))
-    dq_, dk_, dv_ = (fi._prep(torch.empty_like(t), dpad) for t in (q_, k_, v_))
+    dq_, dk_, dv_ = fi._grad_buffers(q_, k_, v_)
     fi._dense_backward(dout, q_, k_, v_, o_, lse.contiguous(), None, 0.0, d ** -0.5 if scale is None else scale, False,
                        window, 0.0, None, dq_, dk_, dv_, keep_window=True)
     return dq_[..., :d], dk_[..., :d], dv_[..., :d]

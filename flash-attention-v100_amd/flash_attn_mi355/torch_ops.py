@@ -51,7 +51,7 @@ def _rng_tensor(rng, device):
 
 
 def _out_dtype(q: Tensor):
-    """float8_e4m3fn q, k, v: the fp8 forward writes bf16 out (flash_attn_interface._dense_forward_fp8)"""
+    """float8_e4m3fn q, k, v: the fp8 forward writes bf16 out (flash_attn_interface._dense_forward)"""
     return torch.bfloat16 if q.dtype == torch.float8_e4m3fn else q.dtype
 
 
@@ -100,8 +100,7 @@ def bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, softmax_lse:
     d = q.shape[-1]
     dpad = (d + 7) // 8 * 8
     q_, k_, v_, out_ = (_fi._prep(t, dpad) for t in (q, k, v, out))
-    dq_, dk_, dv_ = torch.empty_like(q_), torch.empty_like(k_), torch.empty_like(v_)
-    dq_, dk_, dv_ = (_fi._prep(t, dpad) for t in (dq_, dk_, dv_))
+    dq_, dk_, dv_ = _fi._grad_buffers(q_, k_, v_)
     softmax_d = _fi._dense_backward(dout, q_, k_, v_, out_, softmax_lse, alibi_slopes, p_dropout,
                                     softmax_scale, is_causal, (window_size_left, window_size_right),
                                     softcap, _rng_tuple(rng_state) if p_dropout > 0.0 else (0, 0),
@@ -177,8 +176,7 @@ def varlen_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, softm
     d = q.shape[-1]
     dpad = (d + 7) // 8 * 8
     q_, k_, v_, out_ = (_fi._prep(t, dpad) for t in (q, k, v, out))
-    dq_, dk_, dv_ = torch.empty_like(q_), torch.empty_like(k_), torch.empty_like(v_)
-    dq_, dk_, dv_ = (_fi._prep(t, dpad) for t in (dq_, dk_, dv_))
+    dq_, dk_, dv_ = _fi._grad_buffers(q_, k_, v_)
     cu_q = cu_seqlens_q.to(torch.int32).contiguous()
     cu_k = cu_seqlens_k.to(torch.int32).contiguous()
     softmax_d = _fi._varlen_backward(dout, q_, k_, v_, out_, softmax_lse, cu_q, cu_k, alibi_slopes,
@@ -282,10 +280,7 @@ def bwd_out(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, softmax_
             raise RuntimeError(f"{name} must have the dtype and shape of its input and a contiguous last dimension")
     q_, k_, v_, out_ = (_fi._prep(t, dpad) for t in (q, k, v, out))
     direct = dpad == d and all(t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:-1]) for t in (dq, dk, dv))
-    if direct:
-        dq_, dk_, dv_ = dq, dk, dv
-    else:
-        dq_, dk_, dv_ = (_fi._prep(torch.empty_like(t), dpad) for t in (q_, k_, v_))
+    dq_, dk_, dv_ = (dq, dk, dv) if direct else _fi._grad_buffers(q_, k_, v_)
     softmax_d = _fi._dense_backward(dout, q_, k_, v_, out_, softmax_lse, alibi_slopes, p_dropout,
                                     softmax_scale, is_causal, (window_size_left, window_size_right),
                                     softcap, _rng_tuple(rng_state) if p_dropout > 0.0 else (0, 0),
