@@ -42,6 +42,11 @@ size_t qk_norm_rope_bwd_workspace_bytes(const fa_qk_norm_rope_bwd_params& s);   
 void launch_add_norm(const fa_add_norm_params& s, hipStream_t stream);                       // fa_add_norm.hip: residual add + RMSNorm / LayerNorm
 void launch_add_norm_bwd(const fa_add_norm_bwd_params& s, hipStream_t stream);               // fa_add_norm_bwd.hip: its backward (dx, dres, dweight, dbias)
 size_t add_norm_bwd_workspace_bytes(const fa_add_norm_bwd_params& s);                        // the partial rows of its launch plan
+void launch_cross_entropy(const fa_cross_entropy_params& s, hipStream_t stream);             // fa_cross_entropy.hip: softmax cross-entropy over the vocabulary
+void launch_cross_entropy_bwd(const fa_cross_entropy_bwd_params& s, hipStream_t stream);     // its backward (dlogits)
+size_t cross_entropy_workspace_bytes(int64_t rows, int vocab, int dtype);                    // the chunk partials of its launch plan
+int64_t ce_nchunks(int vocab, int dtype);                                                    // forward / backward workgroups per row
+int64_t ce_bwd_nchunks(int vocab);
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -214,6 +219,8 @@ size_t fa_qk_norm_rope_store_params_size(void) { return sizeof(fa_qk_norm_rope_s
 size_t fa_qk_norm_rope_bwd_params_size(void) { return sizeof(fa_qk_norm_rope_bwd_params); }
 size_t fa_add_norm_params_size(void) { return sizeof(fa_add_norm_params); }
 size_t fa_add_norm_bwd_params_size(void) { return sizeof(fa_add_norm_bwd_params); }
+size_t fa_cross_entropy_params_size(void) { return sizeof(fa_cross_entropy_params); }
+size_t fa_cross_entropy_bwd_params_size(void) { return sizeof(fa_cross_entropy_bwd_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -647,7 +654,7 @@ int fa_merge_states(const fa_merge_params* m, void* stream) {
 
 }  // extern "C"
 
-// ---- The row ops around attention (fa_rotary .. fa_add_norm_bwd): one argument-checking layer, then the entry points. ----
+// ---- The row ops around attention (fa_rotary .. fa_cross_entropy_bwd): one argument-checking layer, then the entry points. ----
 // Every helper takes `op`, the name its messages begin with, and is parameterised by data alone: pointers, sizes and which fields
 // a block has.  A rule that only one op has stays in that op's own function.
 
@@ -1180,6 +1187,85 @@ static int add_norm_bwd_check(const fa_add_norm_bwd_params& s, bool query) {
     return check_overlaps(op, out, 5, in, 4, true, exempt, inplace ? 1 : 0);
 }
 
+// what fa_cross_entropy and fa_cross_entropy_bwd share: dtype, vocab, rows, the scalars.  Returns the logits' element size
+static int cross_entropy_common_check(const char* op, int dtype, int vocab, int64_t rows, float label_smoothing, float logit_scale,
+                                      float lse_square_scale, int* esize) {
+    FA_CHECK(dtype == FA_FP16 || dtype == FA_BF16 || dtype == FA_FP32, "%s: dtype must be fp16, bf16 or fp32", op);
+    *esize = dtype == FA_FP32 ? 4 : 2;
+    FA_CHECK(vocab >= 1, "%s: vocab must be at least 1, got %d", op, vocab);
+    FA_CHECK(rows >= 0, "%s: rows must be non-negative", op);
+    FA_CHECK(label_smoothing >= 0.f && label_smoothing < 1.f, "%s: label_smoothing must be in [0, 1)", op);
+    FA_CHECK(logit_scale >= -3.402823466e38f && logit_scale <= 3.402823466e38f, "%s: logit_scale must be finite", op);
+    FA_CHECK(lse_square_scale >= 0.f && lse_square_scale <= 3.402823466e38f, "%s: lse_square_scale must be finite and >= 0", op);
+    return FA_OK;
+}
+static bool ce_stride_ok(int64_t rs, int64_t rows, int vocab) { return rs >= 0 && (rows <= 1 || rs >= vocab); }
+
+// fa_cross_entropy's argument rules.  query: the workspace itself and where the tensors lie are not looked at
+static int cross_entropy_check(const fa_cross_entropy_params& s, bool query) {
+    const char* op = "cross_entropy";
+    FA_CHECK(s.logits && s.labels && s.losses && s.z_losses && s.lse, "%s: logits, labels, losses, z_losses and lse must not be NULL", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    int esize;
+    FA_TRY(cross_entropy_common_check(op, s.dtype, s.vocab, s.rows, s.label_smoothing, s.logit_scale, s.lse_square_scale, &esize));
+    FA_CHECK(ce_stride_ok(s.logits_row_stride, s.rows, s.vocab), "%s: the row stride must be non-negative and (rows > 1) at least vocab", op);
+    FA_CHECK(addr(s.logits) % esize == 0 && addr(s.labels) % 8 == 0 && ((addr(s.losses) | addr(s.z_losses) | addr(s.lse)) & 3) == 0,
+             "%s: logits must be aligned to their element, labels to 8 bytes, losses / z_losses / lse to 4 bytes", op);
+    const int64_t nc = fa::ce_nchunks(s.vocab, s.dtype);
+    if (s.rows > 0x7fffffffLL / nc) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (rows x chunks) in one launch", op);
+    if (query) return FA_OK;
+    const size_t need = fa::cross_entropy_workspace_bytes(s.rows, s.vocab, s.dtype);
+    if (need) {
+        FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_cross_entropy_workspace_bytes() reports %zu",
+                 op, s.workspace ? s.workspace_bytes : (size_t)0, need);
+        FA_CHECK(addr(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+    }
+    const uint64_t vbytes = s.rows > 0 ? (uint64_t)s.rows * 4 : 0;
+    const View in[] = {
+        view_rows("logits", s.logits, s.rows, s.logits_row_stride, s.vocab, esize),
+        view_flat("labels", s.labels, 2 * vbytes),
+    };
+    const View out[] = {
+        view_flat("losses", s.losses, vbytes),
+        view_flat("z_losses", s.z_losses, vbytes),
+        view_flat("lse", s.lse, vbytes),
+        view_flat("workspace", need ? s.workspace : nullptr, need),
+    };
+    return check_overlaps(op, out, 4, in, 2, true);
+}
+
+// fa_cross_entropy_bwd's argument rules
+static int cross_entropy_bwd_check(const fa_cross_entropy_bwd_params& s) {
+    const char* op = "cross_entropy_bwd";
+    FA_CHECK(s.dlosses && s.logits && s.labels && s.lse && s.dlogits, "%s: dlosses, logits, labels, lse and dlogits must not be NULL", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    int esize;
+    FA_TRY(cross_entropy_common_check(op, s.dtype, s.vocab, s.rows, s.label_smoothing, s.logit_scale, s.lse_square_scale, &esize));
+    FA_CHECK(ce_stride_ok(s.logits_row_stride, s.rows, s.vocab) && ce_stride_ok(s.dlogits_row_stride, s.rows, s.vocab),
+             "%s: row strides must be non-negative and (rows > 1) at least vocab", op);
+    FA_CHECK(s.dlosses_stride >= 0, "%s: dlosses_stride must be non-negative", op);
+    FA_CHECK(addr(s.logits) % esize == 0 && addr(s.dlogits) % esize == 0 && addr(s.labels) % 8 == 0 && ((addr(s.dlosses) | addr(s.lse)) & 3) == 0,
+             "%s: logits / dlogits must be aligned to their element, labels to 8 bytes, dlosses / lse to 4 bytes", op);
+    if (s.rows > 0x7fffffffLL / fa::ce_bwd_nchunks(s.vocab))
+        return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (rows x chunks) in one launch", op);
+    const bool inplace = s.dlogits == s.logits;
+    if (inplace) FA_CHECK(s.dlogits_row_stride == s.logits_row_stride,
+                          "%s: dlogits shares logits' base address but not its row stride (in place needs both equal)", op);
+    const uint64_t vbytes = s.rows > 0 ? (uint64_t)s.rows * 4 : 0;
+    const char* note = " (in place needs the same base address and row stride)";
+    const View in[] = {
+        view_rows("logits", s.logits, s.rows, s.logits_row_stride, s.vocab, esize, note),
+        view_rows("dlosses", s.dlosses, s.rows, s.dlosses_stride, 1, 4),
+        view_flat("labels", s.labels, 2 * vbytes),
+        view_flat("lse", s.lse, vbytes),
+    };
+    const View out = view_rows("dlogits", s.dlogits, s.rows, s.dlogits_row_stride, s.vocab, esize, note);
+    const int exempt[1][2] = {{0, 0}};
+    return check_overlaps(op, &out, 1, in, 4, false, exempt, inplace ? 1 : 0);
+}
+
 extern "C" {
 
 int fa_rotary(const fa_rotary_params* r, void* stream) {
@@ -1275,6 +1361,32 @@ int fa_add_norm_bwd(const fa_add_norm_bwd_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_add_norm_bwd(s, static_cast<hipStream_t>(stream));          // (rows == 0: a wanted dweight / dbias is set to zeros, no kernel)
     return check_hip("fa_add_norm_bwd launch");
+}
+
+size_t fa_cross_entropy_workspace_bytes(const fa_cross_entropy_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_cross_entropy_params)) return 0;
+    if (cross_entropy_check(*sp, true) != FA_OK) return 0;
+    return fa::cross_entropy_workspace_bytes(sp->rows, sp->vocab, sp->dtype);
+}
+
+int fa_cross_entropy(const fa_cross_entropy_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_cross_entropy_params"));
+    fa_cross_entropy_params s = *sp;
+    FA_TRY(cross_entropy_check(s, false));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_cross_entropy(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_cross_entropy launch");
+}
+
+int fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_cross_entropy_bwd_params"));
+    fa_cross_entropy_bwd_params s = *sp;
+    FA_TRY(cross_entropy_bwd_check(s));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_cross_entropy_bwd(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_cross_entropy_bwd launch");
 }
 
 }  // extern "C"

@@ -294,6 +294,39 @@ class FaAddNormBwdParams(ctypes.Structure):
     ]
 
 
+class FaCrossEntropyParams(ctypes.Structure):
+    """Mirror of `struct fa_cross_entropy_params` (include/fa_mi355.h): fa_cross_entropy, the softmax cross-entropy loss over the
+    vocabulary - losses, z_losses and lse of [rows, vocab] logits.  struct_size must be set to sizeof(FaCrossEntropyParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("logits", _ptr), ("labels", _ptr),                   # [rows, vocab] of dtype; int64 [rows]
+        ("losses", _ptr), ("z_losses", _ptr), ("lse", _ptr),  # fp32 [rows], written
+        ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("logits_row_stride", _i64),
+        ("rows", _i64), ("ignore_index", _i64),
+        ("vocab", _i32), ("dtype", _i32),
+        ("label_smoothing", _f32), ("logit_scale", _f32), ("lse_square_scale", _f32),
+        ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaCrossEntropyBwdParams(ctypes.Structure):
+    """Mirror of `struct fa_cross_entropy_bwd_params` (include/fa_mi355.h): fa_cross_entropy_bwd, dlogits from dlosses, the logits,
+    the labels and the forward's lse.  struct_size must be set to sizeof(FaCrossEntropyBwdParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dlosses", _ptr), ("logits", _ptr), ("labels", _ptr), ("lse", _ptr),
+        ("dlogits", _ptr),                                    # may equal logits (in place)
+        ("dlosses_stride", _i64), ("logits_row_stride", _i64), ("dlogits_row_stride", _i64),
+        ("rows", _i64), ("ignore_index", _i64),
+        ("vocab", _i32), ("dtype", _i32),
+        ("label_smoothing", _f32), ("logit_scale", _f32), ("lse_square_scale", _f32),
+        ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -305,7 +338,9 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_rope_store", "fa_rope_store_params_size", "fa_qk_norm_rope_store", "fa_qk_norm_rope_store_params_size",
            "fa_qk_norm_rope_bwd", "fa_qk_norm_rope_bwd_workspace_bytes", "fa_qk_norm_rope_bwd_params_size",
            "fa_add_norm", "fa_add_norm_params_size",
-           "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size"] + EXT_OPS
+           "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size",
+           "fa_cross_entropy", "fa_cross_entropy_workspace_bytes", "fa_cross_entropy_params_size",
+           "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -320,6 +355,8 @@ ROW_OPS = [
     ("fa_qk_norm_rope_bwd", FaQkNormRopeBwdParams, "fa_qk_norm_rope_bwd_workspace_bytes"),
     ("fa_add_norm", FaAddNormParams, None),
     ("fa_add_norm_bwd", FaAddNormBwdParams, "fa_add_norm_bwd_workspace_bytes"),
+    ("fa_cross_entropy", FaCrossEntropyParams, "fa_cross_entropy_workspace_bytes"),
+    ("fa_cross_entropy_bwd", FaCrossEntropyBwdParams, None),
 ]
 
 
@@ -444,7 +481,8 @@ def _workspace_query(query):
 
 call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
-# call_add_norm_bwd; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes
+# call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
+# cross_entropy_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
     if _query:

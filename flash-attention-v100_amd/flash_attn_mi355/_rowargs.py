@@ -1,6 +1,6 @@
-"""What the wrappers of the row ops share (rope_store, qk_norm, kv_store, kv_gather, add_norm): the validators of their common
-arguments and the fillers of the parameter-block fields that go with them.  Every validator takes `op`, the prefix of the
-wrapper's messages ("rope_store", "qk_norm", "kv_store", "kv_gather", "add_norm"), and raises RuntimeError; a filler writes
+"""What the wrappers of the row ops share (rope_store, qk_norm, kv_store, kv_gather, add_norm, cross_entropy): the validators of
+their common arguments and the fillers of the parameter-block fields that go with them.  Every validator takes `op`, the prefix of
+the wrapper's messages ("rope_store", "qk_norm", "kv_store", "kv_gather", "add_norm", "cross_entropy"), and raises RuntimeError; a filler writes
 into any block that has the fields (the blocks share their names, include/fa_mi355.h).  Private: nothing here is API."""
 import ctypes
 
@@ -54,6 +54,22 @@ def scalars(op, eps, weight_offset):
     if not (abs(weight_offset) < float("inf")):
         raise RuntimeError(f"{op}: weight_offset must be finite, got {weight_offset}")
     return eps, weight_offset
+
+
+def loss_scalars(op, label_smoothing, logit_scale, lse_square_scale, ignore_index):
+    """(label_smoothing, logit_scale, lse_square_scale, ignore_index): label_smoothing in [0, 1), logit_scale finite,
+    lse_square_scale finite and >= 0, ignore_index an int64"""
+    label_smoothing, logit_scale, lse_square_scale = float(label_smoothing), float(logit_scale), float(lse_square_scale)
+    if not (0.0 <= label_smoothing < 1.0):
+        raise RuntimeError(f"{op}: label_smoothing must be in [0, 1), got {label_smoothing}")
+    if not (abs(logit_scale) < float("inf")):
+        raise RuntimeError(f"{op}: logit_scale must be finite, got {logit_scale}")
+    if not (0.0 <= lse_square_scale < float("inf")):
+        raise RuntimeError(f"{op}: lse_square_scale must be finite and >= 0, got {lse_square_scale}")
+    ignore_index = int(ignore_index)
+    if not (-2 ** 63 <= ignore_index < 2 ** 63):
+        raise RuntimeError(f"{op}: ignore_index must fit an int64, got {ignore_index}")
+    return label_smoothing, logit_scale, lse_square_scale, ignore_index
 
 
 def same_device(op, tensors, ref, whose):

@@ -6,8 +6,9 @@ rows out of a KV cache, fa_kv_gather, and gather -> store inside one cache; `rop
 and K / V stored by slot in one launch, fa_rope_store; `qk_norm_rope_store_`: the same behind a per-head RMSNorm of q and k,
 fa_qk_norm_rope_store; `qk_norm_rope` / `qk_norm_rope_bwd`: that norm + rotation out of place with an autograd formula, and its
 backward, fa_qk_norm_rope_bwd; `add_norm` / `add_norm_` / `add_norm_bwd`: residual add + RMSNorm / LayerNorm over the hidden size
-with an autograd formula, its in-place form and its backward, fa_add_norm / fa_add_norm_bwd - registered, but not listed in
-`__all__`).
+with an autograd formula, its in-place form and its backward, fa_add_norm / fa_add_norm_bwd; `cross_entropy` / `cross_entropy_bwd`
+/ `cross_entropy_bwd_`: the softmax cross-entropy loss over the vocabulary with an autograd formula, its backward and the backward
+in place, fa_cross_entropy / fa_cross_entropy_bwd - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -33,6 +34,7 @@ from torch import Tensor
 
 from . import add_norm as _add_norm
 from . import cascade as _cascade
+from . import cross_entropy as _ce
 from . import flash_attn_interface as _fi
 from . import kv_gather as _kv_gather
 from . import kv_store as _kv_store
@@ -682,6 +684,78 @@ def _add_norm_backward(ctx, dout, dres_out):
 
 
 add_norm.register_autograd(_add_norm_backward, setup_context=_add_norm_setup)
+
+
+# ------------------------------------------------------------------------------------------
+# softmax cross-entropy over the vocabulary (flash_attn_mi355.cross_entropy; csrc/fa_cross_entropy.hip).
+# Reached as torch.ops.flash_attn_mi355.cross_entropy / .cross_entropy_bwd / .cross_entropy_bwd_; not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::cross_entropy", mutates_args=(), device_types="cuda")
+def cross_entropy(logits: Tensor, labels: Tensor, label_smoothing: float, logit_scale: float, lse_square_scale: float,
+                  ignore_index: int, inplace_backward: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """cross_entropy.cross_entropy_forward: (losses, z_losses, lse), fp32 of labels' shape.  Differentiable in logits through
+    losses (cross_entropy_bwd; with inplace_backward cross_entropy_bwd_, which overwrites the logits with their gradient)."""
+    losses, z_losses, lse = _ce.cross_entropy_forward(logits, labels, label_smoothing=label_smoothing, logit_scale=logit_scale,
+                                                      lse_square_scale=lse_square_scale, ignore_index=ignore_index)
+    return losses, z_losses, lse
+
+
+@cross_entropy.register_fake
+def _(logits, labels, label_smoothing, logit_scale, lse_square_scale, ignore_index, inplace_backward):
+    new = lambda: logits.new_empty(labels.shape, dtype=torch.float32)   # noqa: E731
+    return new(), new(), new()
+
+
+@torch.library.custom_op(f"{_NS}::cross_entropy_bwd", mutates_args=(), device_types="cuda")
+def cross_entropy_bwd(dlosses: Tensor, logits: Tensor, labels: Tensor, lse: Tensor, label_smoothing: float, logit_scale: float,
+                      lse_square_scale: float, ignore_index: int) -> Tensor:
+    """cross_entropy.cross_entropy_backward out of place: dlogits, a fresh contiguous tensor of logits' dtype and shape"""
+    return _ce.cross_entropy_backward(dlosses, logits, labels, lse, label_smoothing=label_smoothing, logit_scale=logit_scale,
+                                      lse_square_scale=lse_square_scale, ignore_index=ignore_index, inplace=False)
+
+
+@cross_entropy_bwd.register_fake
+def _(dlosses, logits, labels, lse, label_smoothing, logit_scale, lse_square_scale, ignore_index):
+    return logits.new_empty(logits.shape)
+
+
+@torch.library.custom_op(f"{_NS}::cross_entropy_bwd_", mutates_args=("logits",), device_types="cuda")
+def cross_entropy_bwd_(dlosses: Tensor, logits: Tensor, labels: Tensor, lse: Tensor, label_smoothing: float, logit_scale: float,
+                       lse_square_scale: float, ignore_index: int) -> None:
+    """in place: logits <- dlogits; nothing is allocated"""
+    _ce.cross_entropy_backward(dlosses, logits, labels, lse, label_smoothing=label_smoothing, logit_scale=logit_scale,
+                               lse_square_scale=lse_square_scale, ignore_index=ignore_index, inplace=True)
+
+
+@cross_entropy_bwd_.register_fake
+def _(dlosses, logits, labels, lse, label_smoothing, logit_scale, lse_square_scale, ignore_index):
+    return None
+
+
+def _cross_entropy_setup(ctx, inputs, output):
+    logits, labels, label_smoothing, logit_scale, lse_square_scale, ignore_index, inplace_backward = inputs
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(output[1], output[2])          # z_losses, lse
+    ctx.save_for_backward(logits, labels, output[2])
+    ctx.args = (label_smoothing, logit_scale, lse_square_scale, ignore_index)
+    ctx.inplace = inplace_backward
+
+
+def _cross_entropy_backward(ctx, dlosses, dz_losses, dlse):
+    # (z_losses and lse are not differentiable: what arrives for them is dropped, as upstream marks them)
+    none = (None,) * 6
+    if dlosses is None or not ctx.needs_input_grad[0]:
+        return (None,) + none
+    logits, labels, lse = ctx.saved_tensors
+    if dlosses.dtype != torch.float32:
+        dlosses = dlosses.float()
+    if ctx.inplace:
+        cross_entropy_bwd_(dlosses, logits, labels, lse, *ctx.args)
+        return (logits,) + none
+    return (cross_entropy_bwd(dlosses, logits, labels, lse, *ctx.args),) + none
+
+
+cross_entropy.register_autograd(_cross_entropy_backward, setup_context=_cross_entropy_setup)
 
 
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",

@@ -65,7 +65,7 @@ typedef enum fa_dtype {
     FA_BF16 = 1,      /* bfloat16 */
     FA_FP8_E4M3 = 2,  /* OCP e4m3fn: k/v of fa_fwd_kvcache and of paged fa_varlen_fwd; q, k and v together in fa_fwd /
                          fa_varlen_fwd (forward only, 16-bit o of fa_params::o_dtype) */
-    FA_FP32 = 3       /* IEEE single: fa_qk_norm_rope_store_params::weight_dtype only */
+    FA_FP32 = 3       /* IEEE single: weights / residuals of the norm ops, logits of fa_cross_entropy */
 } fa_dtype;
 
 typedef enum fa_status {
@@ -910,6 +910,96 @@ int    fa_add_norm_bwd(const fa_add_norm_bwd_params* s, void* stream);
  * call rejects for any other reason */
 size_t fa_add_norm_bwd_workspace_bytes(const fa_add_norm_bwd_params* s);
 size_t fa_add_norm_bwd_params_size(void);
+
+/*
+ * fa_cross_entropy - softmax cross-entropy loss over the vocabulary, forward (additive: fa_params and FA_ABI_VERSION are
+ * unchanged).  logits: [rows, vocab] of `dtype` (FA_FP16, FA_BF16 or FA_FP32), last dimension contiguous, any row stride >= vocab
+ * (elements); labels: int64 [rows].  All arithmetic is fp32, in this order:
+ *     l_j  = logit_scale * float(logits_j)                          ONE rounding
+ *     lse  = m + log(s),  m = max_j l_j,  s = sum_j exp(l_j - m)    (a running maximum and sum in a fixed order, below)
+ *     loss = fma(-(1 - label_smoothing), l_label, lse)              label_smoothing == 0: lse - l_label
+ *     loss = fma(-(label_smoothing / vocab), sum_j l_j, loss)       label_smoothing > 0 only; sum_j l_j is not formed otherwise
+ *     z    = (lse_square_scale * lse) * lse;   loss = loss + z
+ * 1 - label_smoothing and label_smoothing / vocab are fp32 operations on the host.  losses, z_losses, lse: fp32 [rows], written.
+ * label == ignore_index: loss = z = +0 (lse is still written).  A label outside [0, vocab) that is not ignore_index: loss = z =
+ * NaN - no address is formed from it.  A logit of -inf (a masked vocabulary entry) contributes exactly 0 to s and to sum_j l_j.
+ * A row without a finite maximum - all -inf, or one that holds +inf - and a row with a NaN have lse = NaN.
+ * Order: pieces are 8 columns counted from column 0 of the row; a row is cut into nchunks = ceil(vocab / CHUNK) chunks, CHUNK a
+ * function of `dtype` alone; 256 lanes own the pieces of a chunk round robin and fold them in ascending order, then the lanes, the
+ * waves and the chunks are merged in index order (csrc/fa_lse.h).  A row's bits depend on (vocab, dtype) and its values alone -
+ * never on rows, the row's index, its alignment (a row that does not start on a 16-byte boundary is read element by element: the
+ * same values) or the device.  No column >= vocab is read.
+ * nchunks > 1: rows x nchunks workgroups write one 16-byte partial each into `workspace` and a second kernel on the same stream
+ * merges them; fa_cross_entropy_workspace_bytes() = rows x nchunks x 16 needs no device.  nchunks == 1: one launch, no workspace.
+ * No atomics, no host synchronisation, bitwise repeatable, capturable in a graph.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL logits, labels, losses, z_losses or lse; a dtype other
+ * than FA_FP16 / FA_BF16 / FA_FP32; vocab < 1; negative rows or row stride, or (rows > 1) a row stride below vocab; logits not
+ * aligned to their element, labels not 8-byte and the outputs not 4-byte aligned; label_smoothing outside [0, 1); a non-finite
+ * logit_scale; a negative or non-finite lse_square_scale; a workspace smaller than reported or not 16-byte aligned; an output or
+ * the workspace that overlaps an input or another output; non-zero reserved fields.  rows x nchunks > 2^31 - 1:
+ * FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
+ */
+typedef struct fa_cross_entropy_params {
+    size_t         struct_size;      /* sizeof(fa_cross_entropy_params) as the caller compiled it */
+    const void*    logits;           /* [rows, vocab] of `dtype` */
+    const int64_t* labels;           /* device [rows] */
+    float*         losses;           /* device [rows] */
+    float*         z_losses;         /* device [rows] */
+    float*         lse;              /* device [rows]: what the backward needs, and nothing else */
+    void*          workspace;        /* fa_cross_entropy_workspace_bytes() bytes, 16-byte aligned; may be NULL where that is 0 */
+    size_t         workspace_bytes;
+    int64_t        logits_row_stride;    /* elements */
+    int64_t        rows;
+    int64_t        ignore_index;     /* upstream's default: -100 */
+    int32_t        vocab;            /* >= 1 */
+    int32_t        dtype;            /* FA_FP16, FA_BF16 or FA_FP32 */
+    float          label_smoothing;  /* [0, 1) */
+    float          logit_scale;      /* finite */
+    float          lse_square_scale; /* >= 0, finite: the z-loss weight */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 (room for a vocabulary-parallel form: class_start, total_classes, a precomputed lse) */
+} fa_cross_entropy_params;
+
+int    fa_cross_entropy(const fa_cross_entropy_params* s, void* stream);
+/* the workspace of that call: a function of (rows, vocab, dtype); `workspace`, `workspace_bytes` and where the tensors lie are not
+ * looked at; 0 for a block that the call rejects for any other reason */
+size_t fa_cross_entropy_workspace_bytes(const fa_cross_entropy_params* s);
+size_t fa_cross_entropy_params_size(void);
+
+/*
+ * fa_cross_entropy_bwd - the backward of fa_cross_entropy: one element-wise launch, no workspace.  From dlosses (fp32 [rows], any
+ * element stride >= 0: a broadcast scalar is stride 0), the logits, the labels and the forward's lse, with the forward's scalars:
+ *     g = dloss * logit_scale;   F = fma(2 * lse_square_scale, lse, 1);   p_j = exp(l_j - lse)
+ *     dlogits_j = round_to_dtype(g * (((p_j * F) - (1 - label_smoothing) [j == label]) - label_smoothing / vocab))
+ * Nothing but p_j is recomputed.  label == ignore_index: a row of +0; a label outside [0, vocab): a row of NaN.
+ * dlogits: [rows, vocab] of `dtype` with its own row stride; it may be the logits tensor itself (the same base AND row stride: a
+ * lane loads everything it owns before its first store); every other overlap of dlogits with an input is rejected.
+ * No atomics, no host synchronisation, bitwise repeatable, capturable in a graph.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL dlosses, logits, labels, lse or dlogits; the dtype, vocab,
+ * rows, row stride, alignment and scalar rules of fa_cross_entropy (for logits and dlogits alike); a negative dlosses_stride; a
+ * dlogits that shares the logits' base but not their row stride; an illegal overlap; non-zero reserved fields.
+ * rows x ceil(vocab / 8192) > 2^31 - 1: FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
+ */
+typedef struct fa_cross_entropy_bwd_params {
+    size_t         struct_size;      /* sizeof(fa_cross_entropy_bwd_params) as the caller compiled it */
+    const float*   dlosses;          /* device fp32: the gradient of losses; row r at dlosses[r * dlosses_stride] */
+    const void*    logits;           /* [rows, vocab] of `dtype` */
+    const int64_t* labels;           /* device [rows] */
+    const float*   lse;              /* device [rows]: the forward's */
+    void*          dlogits;          /* [rows, vocab] of `dtype`; may equal logits */
+    int64_t        dlosses_stride;   /* elements, >= 0 */
+    int64_t        logits_row_stride, dlogits_row_stride;   /* elements */
+    int64_t        rows;
+    int64_t        ignore_index;
+    int32_t        vocab;
+    int32_t        dtype;            /* FA_FP16, FA_BF16 or FA_FP32 */
+    float          label_smoothing, logit_scale, lse_square_scale;   /* the forward's */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_cross_entropy_bwd_params;
+
+int    fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* s, void* stream);
+size_t fa_cross_entropy_bwd_params_size(void);
 
 /*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
