@@ -47,6 +47,10 @@ void launch_cross_entropy_bwd(const fa_cross_entropy_bwd_params& s, hipStream_t 
 size_t cross_entropy_workspace_bytes(int64_t rows, int vocab, int dtype);                    // the chunk partials of its launch plan
 int64_t ce_nchunks(int vocab, int dtype);                                                    // forward / backward workgroups per row
 int64_t ce_bwd_nchunks(int vocab);
+void launch_act_mul(const fa_act_mul_params& s, hipStream_t stream);                         // fa_act_mul.hip: act(gate) * up, element-wise
+void launch_act_mul_bwd(const fa_act_mul_bwd_params& s, hipStream_t stream);                 // its backward (dgate, dup)
+struct ActPlan { int chunk_pieces; int64_t nchunks, items; int grid; };                      // its launch plan: runs per row, items, grid
+ActPlan act_plan(int64_t rows, int n);
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -221,6 +225,8 @@ size_t fa_add_norm_params_size(void) { return sizeof(fa_add_norm_params); }
 size_t fa_add_norm_bwd_params_size(void) { return sizeof(fa_add_norm_bwd_params); }
 size_t fa_cross_entropy_params_size(void) { return sizeof(fa_cross_entropy_params); }
 size_t fa_cross_entropy_bwd_params_size(void) { return sizeof(fa_cross_entropy_bwd_params); }
+size_t fa_act_mul_params_size(void) { return sizeof(fa_act_mul_params); }
+size_t fa_act_mul_bwd_params_size(void) { return sizeof(fa_act_mul_bwd_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -654,7 +660,7 @@ int fa_merge_states(const fa_merge_params* m, void* stream) {
 
 }  // extern "C"
 
-// ---- The row ops around attention (fa_rotary .. fa_cross_entropy_bwd): one argument-checking layer, then the entry points. ----
+// ---- The row ops around attention (fa_rotary .. fa_act_mul_bwd): one argument-checking layer, then the entry points. ----
 // Every helper takes `op`, the name its messages begin with, and is parameterised by data alone: pointers, sizes and which fields
 // a block has.  A rule that only one op has stays in that op's own function.
 
@@ -1266,6 +1272,84 @@ static int cross_entropy_bwd_check(const fa_cross_entropy_bwd_params& s) {
     return check_overlaps(op, &out, 1, in, 4, false, exempt, inplace ? 1 : 0);
 }
 
+// what fa_act_mul and fa_act_mul_bwd share: dtype, activation, n, rows, and that rows x runs fits a grid index
+static int act_mul_common_check(const char* op, int dtype, int activation, int n, int64_t rows) {
+    FA_TRY(check_io_dtype(op, dtype, "dtype"));
+    FA_CHECK(activation >= FA_ACT_SILU && activation <= FA_ACT_RELU2, "%s: unknown activation %d", op, activation);
+    FA_CHECK(n >= 1, "%s: n must be at least 1, got %d", op, n);
+    FA_CHECK(rows >= 0, "%s: rows must be non-negative", op);
+    if (rows > 0x7fffffffLL / fa::act_plan(0, n).nchunks)
+        return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 items (rows x runs per row) in one launch", op);
+    return FA_OK;
+}
+static bool act_stride_ok(const void* p, int64_t rs, int64_t rows, int n) { return !p || (rs >= 0 && (rows <= 1 || rs >= n)); }
+
+// the exact in-place pair (out, in): the same base address needs the same row stride
+static int act_inplace(const char* op, const char* out_name, const void* out, int64_t out_rs, const char* in_name, const void* in,
+                       int64_t in_rs, bool* inplace) {
+    *inplace = out && out == in;
+    if (*inplace) FA_CHECK(out_rs == in_rs, "%s: %s shares %s's base address but not its row stride (in place needs both equal)", op,
+                           out_name, in_name);
+    return FA_OK;
+}
+
+static const char* const kActNote = " (in place needs the same base address and row stride)";
+
+// fa_act_mul's argument rules
+static int act_mul_check(const fa_act_mul_params& s) {
+    const char* op = "act_mul";
+    FA_CHECK(s.gate && s.out, "%s: gate and out must not be NULL", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(act_mul_common_check(op, s.dtype, s.activation, s.n, s.rows));
+    FA_CHECK(act_stride_ok(s.gate, s.gate_row_stride, s.rows, s.n) && act_stride_ok(s.up, s.up_row_stride, s.rows, s.n) &&
+             act_stride_ok(s.out, s.out_row_stride, s.rows, s.n), "%s: row strides must be non-negative and (rows > 1) at least n", op);
+    FA_CHECK(((addr(s.gate) | addr(s.up) | addr(s.out)) & 1) == 0, "%s: gate / up / out must be aligned to their element", op);
+    bool on_gate, on_up;
+    FA_TRY(act_inplace(op, "out", s.out, s.out_row_stride, "gate", s.gate, s.gate_row_stride, &on_gate));
+    FA_TRY(act_inplace(op, "out", s.out, s.out_row_stride, "up", s.up, s.up_row_stride, &on_up));
+    const View in[] = {
+        view_rows("gate", s.gate, s.rows, s.gate_row_stride, s.n, 2, kActNote),
+        view_rows("up", s.up, s.rows, s.up_row_stride, s.n, 2, kActNote),
+    };
+    const View out = view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2, kActNote);
+    int exempt[2][2], n_ex = 0;                             // {output, input}
+    if (on_gate) { exempt[n_ex][0] = 0; exempt[n_ex++][1] = 0; }
+    if (on_up) { exempt[n_ex][0] = 0; exempt[n_ex++][1] = 1; }
+    return check_overlaps(op, &out, 1, in, 2, false, exempt, n_ex);
+}
+
+// fa_act_mul_bwd's argument rules
+static int act_mul_bwd_check(const fa_act_mul_bwd_params& s) {
+    const char* op = "act_mul_bwd";
+    FA_CHECK(s.dout && s.gate && s.dgate, "%s: dout, gate and dgate must not be NULL", op);
+    FA_CHECK((s.up == nullptr) == (s.dup == nullptr), "%s: up and dup go together (both, or both NULL: the ungated form)", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(act_mul_common_check(op, s.dtype, s.activation, s.n, s.rows));
+    FA_CHECK(act_stride_ok(s.dout, s.dout_row_stride, s.rows, s.n) && act_stride_ok(s.gate, s.gate_row_stride, s.rows, s.n) &&
+             act_stride_ok(s.up, s.up_row_stride, s.rows, s.n) && act_stride_ok(s.dgate, s.dgate_row_stride, s.rows, s.n) &&
+             act_stride_ok(s.dup, s.dup_row_stride, s.rows, s.n), "%s: row strides must be non-negative and (rows > 1) at least n", op);
+    FA_CHECK(((addr(s.dout) | addr(s.gate) | addr(s.up) | addr(s.dgate) | addr(s.dup)) & 1) == 0,
+             "%s: dout / gate / up / dgate / dup must be aligned to their element", op);
+    bool on_gate, on_up;
+    FA_TRY(act_inplace(op, "dgate", s.dgate, s.dgate_row_stride, "gate", s.gate, s.gate_row_stride, &on_gate));
+    FA_TRY(act_inplace(op, "dup", s.dup, s.dup_row_stride, "up", s.up, s.up_row_stride, &on_up));
+    const View in[] = {
+        view_rows("gate", s.gate, s.rows, s.gate_row_stride, s.n, 2, kActNote),
+        view_rows("up", s.up, s.rows, s.up_row_stride, s.n, 2, kActNote),
+        view_rows("dout", s.dout, s.rows, s.dout_row_stride, s.n, 2),
+    };
+    const View out[] = {
+        view_rows("dgate", s.dgate, s.rows, s.dgate_row_stride, s.n, 2, kActNote),
+        view_rows("dup", s.dup, s.rows, s.dup_row_stride, s.n, 2, kActNote),
+    };
+    int exempt[2][2], n_ex = 0;                             // {output, input}
+    if (on_gate) { exempt[n_ex][0] = 0; exempt[n_ex++][1] = 0; }
+    if (on_up) { exempt[n_ex][0] = 1; exempt[n_ex++][1] = 1; }
+    return check_overlaps(op, out, 2, in, 3, true, exempt, n_ex);
+}
+
 extern "C" {
 
 int fa_rotary(const fa_rotary_params* r, void* stream) {
@@ -1387,6 +1471,35 @@ int fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_cross_entropy_bwd(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_cross_entropy_bwd launch");
+}
+
+int fa_act_mul_plan(int64_t rows, int32_t n, int64_t* run_columns, int64_t* items, int64_t* grid) {
+    FA_TRY(act_mul_common_check("act_mul_plan", FA_BF16, FA_ACT_SILU, n, rows));
+    const fa::ActPlan pl = fa::act_plan(rows, n);
+    if (run_columns) *run_columns = 8 * (int64_t)pl.chunk_pieces;
+    if (items) *items = pl.items;
+    if (grid) *grid = pl.grid;
+    return FA_OK;
+}
+
+int fa_act_mul(const fa_act_mul_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_act_mul_params"));
+    fa_act_mul_params s = *sp;
+    FA_TRY(act_mul_check(s));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_act_mul(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_act_mul launch");
+}
+
+int fa_act_mul_bwd(const fa_act_mul_bwd_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_act_mul_bwd_params"));
+    fa_act_mul_bwd_params s = *sp;
+    FA_TRY(act_mul_bwd_check(s));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_act_mul_bwd(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_act_mul_bwd launch");
 }
 
 }  // extern "C"

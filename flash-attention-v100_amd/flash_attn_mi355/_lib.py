@@ -15,6 +15,7 @@ FA_FLAG_NO_DKV_SPLIT = 2
 FA_FLAG_DS_HANDOFF = 4
 FA_FLAG_FWD_KEY_SPLIT = 8
 FA_FLAG_TREE_MASK = 16
+FA_ACT_SILU, FA_ACT_GELU, FA_ACT_GELU_TANH, FA_ACT_RELU, FA_ACT_RELU2 = 0, 1, 2, 3, 4    # enum fa_act
 
 _i64, _i32, _f32, _u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
 _ptr = ctypes.c_void_p
@@ -327,6 +328,37 @@ class FaCrossEntropyBwdParams(ctypes.Structure):
     ]
 
 
+class FaActMulParams(ctypes.Structure):
+    """Mirror of `struct fa_act_mul_params` (include/fa_mi355.h): fa_act_mul, the gated activation act(gate) * up of the MLP
+    (up NULL: act(gate)).  struct_size must be set to sizeof(FaActMulParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("gate", _ptr), ("up", _ptr),                         # [rows, n] of dtype; up NULL: ungated
+        ("out", _ptr),                                        # may equal gate or up (in place)
+        ("gate_row_stride", _i64), ("up_row_stride", _i64), ("out_row_stride", _i64),
+        ("rows", _i64),
+        ("n", _i32), ("dtype", _i32), ("activation", _i32),
+        ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaActMulBwdParams(ctypes.Structure):
+    """Mirror of `struct fa_act_mul_bwd_params` (include/fa_mi355.h): fa_act_mul_bwd, dgate and dup from dout, gate and up.
+    struct_size must be set to sizeof(FaActMulBwdParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dout", _ptr), ("gate", _ptr), ("up", _ptr),
+        ("dgate", _ptr), ("dup", _ptr),                       # may equal gate / up (in place); dup NULL exactly where up is
+        ("dout_row_stride", _i64), ("gate_row_stride", _i64), ("up_row_stride", _i64), ("dgate_row_stride", _i64),
+        ("dup_row_stride", _i64),
+        ("rows", _i64),
+        ("n", _i32), ("dtype", _i32), ("activation", _i32),
+        ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -340,7 +372,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_add_norm", "fa_add_norm_params_size",
            "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size",
            "fa_cross_entropy", "fa_cross_entropy_workspace_bytes", "fa_cross_entropy_params_size",
-           "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size"] + EXT_OPS
+           "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size",
+           "fa_act_mul", "fa_act_mul_params_size", "fa_act_mul_plan", "fa_act_mul_bwd", "fa_act_mul_bwd_params_size"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -357,6 +390,8 @@ ROW_OPS = [
     ("fa_add_norm_bwd", FaAddNormBwdParams, "fa_add_norm_bwd_workspace_bytes"),
     ("fa_cross_entropy", FaCrossEntropyParams, "fa_cross_entropy_workspace_bytes"),
     ("fa_cross_entropy_bwd", FaCrossEntropyBwdParams, None),
+    ("fa_act_mul", FaActMulParams, None),
+    ("fa_act_mul_bwd", FaActMulBwdParams, None),
 ]
 
 
@@ -402,6 +437,8 @@ def _load():
             getattr(lib, query).restype = ctypes.c_size_t
             getattr(lib, query).argtypes = [ctypes.POINTER(struct)]
     i64 = ctypes.c_int64
+    lib.fa_act_mul_plan.restype = ctypes.c_int
+    lib.fa_act_mul_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
     lib.fa_scatter_rows.restype = ctypes.c_int
@@ -481,7 +518,7 @@ def _workspace_query(query):
 
 call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
-# call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
+# call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
@@ -495,3 +532,12 @@ def call_rows(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+
+
+def act_mul_plan(rows, n):
+    """fa_act_mul_plan: (run_columns, items, grid) of fa_act_mul / fa_act_mul_bwd, a function of (rows, n) alone; needs no device"""
+    out = [ctypes.c_int64() for _ in range(3)]
+    rc = lib.fa_act_mul_plan(rows, n, *(ctypes.byref(o) for o in out))
+    if rc != 0:
+        raise RuntimeError(f"fa_act_mul_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+    return tuple(o.value for o in out)

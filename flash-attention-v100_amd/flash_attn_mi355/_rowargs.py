@@ -1,6 +1,7 @@
-"""What the wrappers of the row ops share (rope_store, qk_norm, kv_store, kv_gather, add_norm, cross_entropy): the validators of
-their common arguments and the fillers of the parameter-block fields that go with them.  Every validator takes `op`, the prefix of
-the wrapper's messages ("rope_store", "qk_norm", "kv_store", "kv_gather", "add_norm", "cross_entropy"), and raises RuntimeError; a filler writes
+"""What the wrappers of the row ops share (rope_store, qk_norm, kv_store, kv_gather, add_norm, cross_entropy, act_mul): the
+validators of their common arguments and the fillers of the parameter-block fields that go with them.  Every validator takes `op`,
+the prefix of the wrapper's messages ("rope_store", "qk_norm", "kv_store", "kv_gather", "add_norm", "cross_entropy", "act_mul"), and
+raises RuntimeError; a filler writes
 into any block that has the fields (the blocks share their names, include/fa_mi355.h).  Private: nothing here is API."""
 import ctypes
 

@@ -8,7 +8,9 @@ fa_qk_norm_rope_store; `qk_norm_rope` / `qk_norm_rope_bwd`: that norm + rotation
 backward, fa_qk_norm_rope_bwd; `add_norm` / `add_norm_` / `add_norm_bwd`: residual add + RMSNorm / LayerNorm over the hidden size
 with an autograd formula, its in-place form and its backward, fa_add_norm / fa_add_norm_bwd; `cross_entropy` / `cross_entropy_bwd`
 / `cross_entropy_bwd_`: the softmax cross-entropy loss over the vocabulary with an autograd formula, its backward and the backward
-in place, fa_cross_entropy / fa_cross_entropy_bwd - registered, but not listed in `__all__`).
+in place, fa_cross_entropy / fa_cross_entropy_bwd; `act_mul` / `act_and_mul` / `act_mul_bwd` / `act_and_mul_bwd` / `act_mul_bwd_`:
+the gated activation act(gate) * up of the MLP on separate or packed tensors with autograd formulas, its backward and the backward
+in place, fa_act_mul / fa_act_mul_bwd - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -32,6 +34,7 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import act_mul as _act_mul
 from . import add_norm as _add_norm
 from . import cascade as _cascade
 from . import cross_entropy as _ce
@@ -756,6 +759,117 @@ def _cross_entropy_backward(ctx, dlosses, dz_losses, dlse):
 
 
 cross_entropy.register_autograd(_cross_entropy_backward, setup_context=_cross_entropy_setup)
+
+
+# ------------------------------------------------------------------------------------------
+# the gated activation of the MLP, act(gate) * up (flash_attn_mi355.act_mul; csrc/fa_act_mul.hip).
+# Reached as torch.ops.flash_attn_mi355.act_mul / .act_and_mul / .act_mul_bwd / .act_and_mul_bwd / .act_mul_bwd_; not in __all__.
+# `activation` is the name ("silu", "gelu", "gelu_tanh", "relu", "relu2").  A torch.library return cannot be optional: the
+# ungated form (up None) has no dup, and act_mul_bwd returns an EMPTY tensor of shape (0,) in its place.
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::act_mul", mutates_args=(), device_types="cuda")
+def act_mul(gate: Tensor, up: Optional[Tensor], activation: str, inplace_backward: bool) -> Tensor:
+    """act_mul.act_mul_forward: act(gate) * up (up None: act(gate)), a fresh contiguous tensor.  Differentiable in gate and up
+    (act_mul_bwd; with inplace_backward act_mul_bwd_, which overwrites gate and up with their gradients)."""
+    return _act_mul.act_mul_forward(gate, up, activation=activation)
+
+
+@act_mul.register_fake
+def _(gate, up, activation, inplace_backward):
+    return gate.new_empty(gate.shape)
+
+
+@torch.library.custom_op(f"{_NS}::act_and_mul", mutates_args=(), device_types="cuda")
+def act_and_mul(x: Tensor, activation: str, inplace_backward: bool) -> Tensor:
+    """act(x[..., :N]) * x[..., N:] of a packed [..., 2N]: a fresh contiguous [..., N].  Differentiable in x (act_and_mul_bwd: ONE
+    packed gradient; with inplace_backward act_mul_bwd_ on the halves of x)."""
+    gate, up = _act_mul._halves(x)
+    return _act_mul.act_mul_forward(gate, up, activation=activation)
+
+
+@act_and_mul.register_fake
+def _(x, activation, inplace_backward):
+    return x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] // 2,))
+
+
+@torch.library.custom_op(f"{_NS}::act_mul_bwd", mutates_args=(), device_types="cuda")
+def act_mul_bwd(dout: Tensor, gate: Tensor, up: Optional[Tensor], activation: str) -> Tuple[Tensor, Tensor]:
+    """act_mul.act_mul_backward out of place: (dgate, dup), fresh contiguous tensors of gate's shape; up None: dup is an empty
+    tensor of shape (0,)"""
+    dgate, dup = _act_mul.act_mul_backward(dout, gate, up, activation=activation)
+    return dgate, (gate.new_empty((0,)) if dup is None else dup)
+
+
+@act_mul_bwd.register_fake
+def _(dout, gate, up, activation):
+    return gate.new_empty(gate.shape), gate.new_empty((0,) if up is None else gate.shape)
+
+
+@torch.library.custom_op(f"{_NS}::act_and_mul_bwd", mutates_args=(), device_types="cuda")
+def act_and_mul_bwd(dout: Tensor, x: Tensor, activation: str) -> Tensor:
+    """the gradient of a packed [..., 2N] x: ONE fresh contiguous [..., 2N], both halves written by one launch"""
+    gate, up = _act_mul._halves(x)
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    _act_mul.act_mul_backward(dout, gate, up, activation=activation, out=_act_mul._halves(dx))
+    return dx
+
+
+@act_and_mul_bwd.register_fake
+def _(dout, x, activation):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op(f"{_NS}::act_mul_bwd_", mutates_args=("gate", "up"), device_types="cuda")
+def act_mul_bwd_(dout: Tensor, gate: Tensor, up: Optional[Tensor], activation: str) -> None:
+    """in place: gate <- dgate, up <- dup; nothing is allocated"""
+    _act_mul.act_mul_backward(dout, gate, up, activation=activation, inplace=True)
+
+
+@act_mul_bwd_.register_fake
+def _(dout, gate, up, activation):
+    return None
+
+
+def _act_mul_setup(ctx, inputs, output):
+    gate, up, activation, inplace_backward = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(gate, up)
+    ctx.activation, ctx.inplace = activation, inplace_backward
+
+
+def _act_mul_backward(ctx, dout):
+    if dout is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+        return None, None, None, None
+    gate, up = ctx.saved_tensors
+    if ctx.inplace:
+        act_mul_bwd_(dout, gate, up, ctx.activation)
+        return gate, up, None, None
+    dgate, dup = act_mul_bwd(dout, gate, up, ctx.activation)
+    return dgate, (None if up is None else dup), None, None
+
+
+act_mul.register_autograd(_act_mul_backward, setup_context=_act_mul_setup)
+
+
+def _act_and_mul_setup(ctx, inputs, output):
+    x, activation, inplace_backward = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(x)
+    ctx.activation, ctx.inplace = activation, inplace_backward
+
+
+def _act_and_mul_backward(ctx, dout):
+    if dout is None or not ctx.needs_input_grad[0]:
+        return None, None, None
+    (x,) = ctx.saved_tensors
+    if ctx.inplace:
+        gate, up = _act_mul._halves(x)
+        act_mul_bwd_(dout, gate, up, ctx.activation)
+        return x, None, None
+    return act_and_mul_bwd(dout, x, ctx.activation), None, None
+
+
+act_and_mul.register_autograd(_act_and_mul_backward, setup_context=_act_and_mul_setup)
 
 
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",

@@ -1002,6 +1002,95 @@ int    fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* s, void* stream);
 size_t fa_cross_entropy_bwd_params_size(void);
 
 /*
+ * fa_act_mul - the gated activation of the MLP, act(gate) * up: SwiGLU, GeGLU and their ungated forms, forward (additive:
+ * fa_params and FA_ABI_VERSION are unchanged).  gate, up, out: [rows, n] of `dtype` (FA_FP16 or FA_BF16), last dimension
+ * contiguous, each with a row stride of its own >= n (elements).  The packed [rows, 2 n] form needs nothing more: gate = base,
+ * up = base + n, both row strides 2 n.  All arithmetic is fp32 with ONE rounding to `dtype`:
+ *     g = float(gate_j), u = float(up_j);   out_j = round(act(g) * u);   up == NULL (ungated): out_j = round(act(g))
+ * act and its derivative, in exactly this fp32 order (every operation rounds once; fma is one rounding):
+ *     e(t) = exp2(t * log2e) on the hardware exp2, log2e rounded to fp32;   sig(t) = rcp(1 + e(-t)) on the hardware reciprocal
+ *     FA_ACT_SILU       s = sig(g);   act = g * s;   act' = s * fma(g, 1 - s, 1)
+ *     FA_ACT_GELU_TANH  q = g * g;   w = (K2 * g) * fma(C3, q, 1);   s = sig(w);   act = g * s
+ *                       act' = s * fma(g * (1 - s), K2 * fma(3 C3, q, 1), 1)
+ *                       K2 = 2 sqrt(2 / pi), C3 = 0.044715, 3 C3 = 0.134145 as fp32 (0.5 (1 + tanh z) = sig(2 z): no tanh, no 1 + t)
+ *     FA_ACT_GELU       ph = fma(0.5, erff(g * sqrt(1/2)), 0.5);   act = g * ph
+ *                       act' = fma(g, e((g * g) * -0.5) * sqrt(1 / (2 pi)), ph)
+ *     FA_ACT_RELU       act = g <= 0 ? +0 : g (a NaN stays a NaN);   act' = g <= 0 ? 0 : (g > 0 ? 1 : g)
+ *     FA_ACT_RELU2      r = relu(g);   act = r * r;   act' = r + r
+ * Special values are what these lines give literally: act(-100) = -0 for SILU and both GELUs (e overflows to +inf, rcp(+inf) = 0),
+ * never NaN; a gate of -inf gives NaN there (-inf * 0) and +0 for the ReLUs; a NaN gate gives NaN.
+ * A row is cut into runs of equal length (at most 8192 columns, whole waves of 8-column pieces); one workgroup of 256 lanes takes a
+ * run, and a lane loads a piece from every input before it stores to it; no other lane touches it.  So out may be EXACTLY gate or EXACTLY up
+ * (the same base address and row stride); every other overlap of out with an input is rejected.  The two halves of one packed
+ * tensor - the same row stride, disjoint column ranges - do not overlap.  A row that does not start on a 16-byte boundary, and
+ * the last n % 8 columns, are taken element by element: the same bits.  An element's bits depend on its own operands alone.
+ * One launch, no workspace, no LDS, no atomics, no host synchronisation, capturable in a graph.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL gate or out; a dtype other than FA_FP16 / FA_BF16; an
+ * unknown activation; n < 1; negative rows or row strides, or (rows > 1) a row stride below n; a pointer that is not 2-byte
+ * aligned; an illegal overlap; non-zero reserved fields.  rows x runs per row > 2^31 - 1: FA_ERR_UNSUPPORTED.  rows == 0: FA_OK
+ * without a launch.
+ */
+typedef enum fa_act {
+    FA_ACT_SILU = 0,
+    FA_ACT_GELU = 1,        /* the erf form */
+    FA_ACT_GELU_TANH = 2,
+    FA_ACT_RELU = 3,
+    FA_ACT_RELU2 = 4        /* squared ReLU */
+} fa_act;
+
+typedef struct fa_act_mul_params {
+    size_t         struct_size;      /* sizeof(fa_act_mul_params) as the caller compiled it */
+    const void*    gate;             /* [rows, n] of `dtype` */
+    const void*    up;               /* [rows, n] of `dtype`; NULL: the ungated form */
+    void*          out;              /* [rows, n] of `dtype`; may equal gate or up */
+    int64_t        gate_row_stride, up_row_stride, out_row_stride;   /* elements; up_row_stride is not read where up is NULL */
+    int64_t        rows;
+    int32_t        n;                /* >= 1 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        activation;       /* fa_act */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_act_mul_params;
+
+int    fa_act_mul(const fa_act_mul_params* s, void* stream);
+size_t fa_act_mul_params_size(void);
+/* the launch plan, a function of (rows, n) alone; needs no device.  run_columns: the columns of one run of a row (a multiple of
+ * 512), items = rows x ceil(n / run_columns), grid = min(items, the cap): a workgroup strides over items.  Each output pointer may
+ * be NULL.  FA_ERR_INVALID_ARGUMENT: rows < 0 or n < 1; FA_ERR_UNSUPPORTED: items > 2^31 - 1. */
+int    fa_act_mul_plan(int64_t rows, int32_t n, int64_t* run_columns, int64_t* items, int64_t* grid);
+
+/*
+ * fa_act_mul_bwd - the backward of fa_act_mul: one element-wise launch with fa_act_mul's plan, no workspace.  It reads dout, gate
+ * and up - the forward saves nothing but its inputs - and writes, with d = float(dout_j) and act / act' as above:
+ *     dgate_j = round((d * u) * act'(g))        up == NULL: round(d * act'(g))
+ *     dup_j   = round(d * act(g))               up == NULL: dup must be NULL too, and nothing is written for it
+ * Every tensor is [rows, n] of `dtype` with a row stride of its own.  dgate may be EXACTLY gate and dup EXACTLY up (the same base
+ * address and row stride: the backward in place, which needs no memory); dgate and dup may be the two halves of one packed
+ * [rows, 2 n] gradient.  Every other overlap of an output with an input or with the other output is rejected.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL dout, gate or dgate; dup NULL while up is not, or the
+ * reverse; the dtype, activation, n, rows, row stride and alignment rules of fa_act_mul; an illegal overlap; non-zero reserved
+ * fields.  rows x runs per row > 2^31 - 1: FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
+ */
+typedef struct fa_act_mul_bwd_params {
+    size_t         struct_size;      /* sizeof(fa_act_mul_bwd_params) as the caller compiled it */
+    const void*    dout;             /* [rows, n]: the gradient of out */
+    const void*    gate;             /* the forward's */
+    const void*    up;               /* the forward's; NULL: ungated */
+    void*          dgate;            /* [rows, n]; may equal gate */
+    void*          dup;              /* [rows, n]; may equal up; NULL exactly where up is */
+    int64_t        dout_row_stride, gate_row_stride, up_row_stride, dgate_row_stride, dup_row_stride;   /* elements */
+    int64_t        rows;
+    int32_t        n;
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        activation;       /* fa_act */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_act_mul_bwd_params;
+
+int    fa_act_mul_bwd(const fa_act_mul_bwd_params* s, void* stream);
+size_t fa_act_mul_bwd_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
