@@ -51,6 +51,9 @@ void launch_act_mul(const fa_act_mul_params& s, hipStream_t stream);            
 void launch_act_mul_bwd(const fa_act_mul_bwd_params& s, hipStream_t stream);                 // its backward (dgate, dup)
 struct ActPlan { int chunk_pieces; int64_t nchunks, items; int grid; };                      // its launch plan: runs per row, items, grid
 ActPlan act_plan(int64_t rows, int n);
+void launch_quant_fp8(const fa_quant_fp8_params& s, hipStream_t stream);                     // fa_quant.hip: dynamic fp8-e4m3 quantisation of [rows, n]
+void launch_add_norm_quant(const fa_add_norm_quant_params& s, hipStream_t stream);           // .. behind fa_add_norm's forward
+void launch_act_mul_quant(const fa_act_mul_quant_params& s, hipStream_t stream);             // .. behind fa_act_mul's forward
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -227,6 +230,9 @@ size_t fa_cross_entropy_params_size(void) { return sizeof(fa_cross_entropy_param
 size_t fa_cross_entropy_bwd_params_size(void) { return sizeof(fa_cross_entropy_bwd_params); }
 size_t fa_act_mul_params_size(void) { return sizeof(fa_act_mul_params); }
 size_t fa_act_mul_bwd_params_size(void) { return sizeof(fa_act_mul_bwd_params); }
+size_t fa_quant_fp8_params_size(void) { return sizeof(fa_quant_fp8_params); }
+size_t fa_add_norm_quant_params_size(void) { return sizeof(fa_add_norm_quant_params); }
+size_t fa_act_mul_quant_params_size(void) { return sizeof(fa_act_mul_quant_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -660,7 +666,7 @@ int fa_merge_states(const fa_merge_params* m, void* stream) {
 
 }  // extern "C"
 
-// ---- The row ops around attention (fa_rotary .. fa_act_mul_bwd): one argument-checking layer, then the entry points. ----
+// ---- The row ops around attention (fa_rotary .. fa_act_mul_quant): one argument-checking layer, then the entry points. ----
 // Every helper takes `op`, the name its messages begin with, and is parameterised by data alone: pointers, sizes and which fields
 // a block has.  A rule that only one op has stays in that op's own function.
 
@@ -1104,10 +1110,15 @@ static int add_norm_common_check(const char* op, int dtype, int weight_dtype, in
     return check_norm_scalars(op, eps, weight_offset);
 }
 
-// fa_add_norm's argument rules
-static int add_norm_check(const fa_add_norm_params& s) {
-    const char* op = "add_norm";
-    FA_CHECK(s.x && s.out, "%s: x and out must not be NULL", op);
+// fa_add_norm's argument rules.  quant_out (fa_add_norm_quant): the n_quant views - codes, scales - that take the place of `out`,
+// which must be NULL then
+static int add_norm_check(const fa_add_norm_params& s, const char* op = "add_norm", const View* quant_out = nullptr, int n_quant = 0) {
+    if (quant_out) {
+        FA_CHECK(s.x, "%s: x must not be NULL", op);
+        FA_CHECK(!s.out && s.out_row_stride == 0, "%s: norm.out must be NULL and norm.out_row_stride 0 (codes take its place)", op);
+    } else {
+        FA_CHECK(s.x && s.out, "%s: x and out must not be NULL", op);
+    }
     FA_CHECK(!s.residual || s.residual_out, "%s: a residual needs residual_out", op);
     FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0, "%s: reserved fields must be 0 (zero-initialise the struct)", op);
     FA_TRY(add_norm_common_check(op, s.dtype, s.weight_dtype, s.rows, s.n, s.weight, s.eps, s.weight_offset));
@@ -1117,14 +1128,14 @@ static int add_norm_check(const fa_add_norm_params& s) {
         FA_CHECK(!s.residual || s.residual_dtype != FA_FP32 || s.residual_out_dtype == FA_FP32,
                  "%s: an fp32 residual needs an fp32 residual_out", op);
     }
-    FA_CHECK(an_stride_ok(s.x_row_stride, s.rows, s.n) && an_stride_ok(s.out_row_stride, s.rows, s.n) &&
+    FA_CHECK(an_stride_ok(s.x_row_stride, s.rows, s.n) && (quant_out || an_stride_ok(s.out_row_stride, s.rows, s.n)) &&
              (!s.residual || an_stride_ok(s.residual_row_stride, s.rows, s.n)) &&
              (!s.residual_out || an_stride_ok(s.residual_out_row_stride, s.rows, s.n)),
              "%s: row strides must be non-negative multiples of 8 elements and (rows > 1) at least n", op);
     FA_CHECK(((addr(s.x) | addr(s.out) | addr(s.residual) | addr(s.residual_out) | addr(s.weight) | addr(s.bias)) & 15) == 0,
              "%s: x / residual / out / residual_out / weight / bias must be 16-byte aligned", op);
     if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
-    const bool x_inplace = s.out == s.x, r_inplace = s.residual_out && s.residual_out == s.residual;
+    const bool x_inplace = s.out && s.out == s.x, r_inplace = s.residual_out && s.residual_out == s.residual;
     if (x_inplace) FA_CHECK(s.out_row_stride == s.x_row_stride, "%s: out shares x's base address but not its row stride (in place needs both equal)", op);
     if (r_inplace)
         FA_CHECK(s.residual_out_row_stride == s.residual_row_stride && s.residual_out_dtype == s.residual_dtype,
@@ -1139,14 +1150,15 @@ static int add_norm_check(const fa_add_norm_params& s) {
         view_flat("weight", s.weight, wbytes, note),
         view_flat("bias", s.bias, wbytes, note),
     };
-    const View out[] = {
+    View out[4] = {
         view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2, note),
         view_rows("residual_out", s.residual_out, s.rows, s.residual_out_row_stride, s.n, rosz, note),
     };
+    for (int i = 0; i < n_quant && i < 2; ++i) out[2 + i] = quant_out[i];
     int exempt[2][2], n_ex = 0;
     if (x_inplace) { exempt[n_ex][0] = 0; exempt[n_ex++][1] = 0; }
     if (r_inplace) { exempt[n_ex][0] = 1; exempt[n_ex++][1] = 1; }
-    return check_overlaps(op, out, 2, in, 4, true, exempt, n_ex);
+    return check_overlaps(op, out, 2 + (n_quant < 2 ? n_quant : 2), in, 4, true, exempt, n_ex);
 }
 
 // fa_add_norm_bwd's argument rules.  query: the workspace itself and where the tensors lie are not looked at
@@ -1350,6 +1362,105 @@ static int act_mul_bwd_check(const fa_act_mul_bwd_params& s) {
     return check_overlaps(op, out, 2, in, 3, true, exempt, n_ex);
 }
 
+// ---- fa_quant_fp8, fa_add_norm_quant, fa_act_mul_quant
+// the quantisation fields the three blocks share: mode, scale, scale_ub, the scales pointer and n against the mode
+static int quant_rule_check(const char* op, int mode, int has_scale_ub, float scale, float scale_ub, const void* codes, const void* scales,
+                            int n) {
+    FA_CHECK(mode == FA_QUANT_ROW || mode == FA_QUANT_GROUP || mode == FA_QUANT_STATIC, "%s: unknown mode %d", op, mode);
+    FA_CHECK(codes, "%s: codes must not be NULL", op);
+    FA_CHECK(has_scale_ub == 0 || has_scale_ub == 1, "%s: has_scale_ub must be 0 or 1", op);
+    if (mode == FA_QUANT_STATIC) {
+        FA_CHECK(scale > 0.f && scale <= 3.402823466e38f, "%s: the static mode needs a scale that is finite and > 0", op);
+        FA_CHECK(!has_scale_ub && scale_ub == 0.f, "%s: scale_ub goes with the dynamic modes (the static mode takes none)", op);
+        FA_CHECK(!scales, "%s: scales must be NULL in the static mode (none is written)", op);
+    } else {
+        FA_CHECK(scale == 0.f, "%s: scale is given in the static mode only (the dynamic modes compute it; pass 0)", op);
+        if (has_scale_ub) FA_CHECK(scale_ub > 0.f && scale_ub <= 3.402823466e38f, "%s: scale_ub must be finite and > 0", op);
+        else              FA_CHECK(scale_ub == 0.f, "%s: scale_ub must be 0 where has_scale_ub is 0", op);
+        FA_CHECK(scales, "%s: scales must not be NULL in the row and group modes", op);
+        FA_CHECK((addr(scales) & 3) == 0, "%s: scales must be 4-byte aligned", op);
+    }
+    if (mode == FA_QUANT_GROUP) FA_CHECK(n % 128 == 0, "%s: the group mode needs n to be a multiple of 128, got %d", op, n);
+    return FA_OK;
+}
+static int quant_n_check(const char* op, int n) {
+    FA_CHECK(n >= 8 && n <= 65536 && n % 8 == 0, "%s: n must be a multiple of 8 in [8, 65536], got %d", op, n);
+    return FA_OK;
+}
+// the scales a mode writes, as the overlap rules see them
+static View quant_scales_view(const void* scales, int mode, int64_t rows, int n) {
+    const uint64_t count = mode == FA_QUANT_GROUP ? (uint64_t)rows * (uint64_t)(n / 128) : (uint64_t)rows;
+    return view_flat("scales", mode == FA_QUANT_STATIC ? nullptr : scales, count * 4);
+}
+
+// fa_quant_fp8's argument rules
+static int quant_fp8_check(const fa_quant_fp8_params& s) {
+    const char* op = "quant_fp8";
+    FA_CHECK(s.x, "%s: x must not be NULL", op);
+    FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(check_io_dtype(op, s.dtype, "dtype"));
+    FA_TRY(quant_n_check(op, s.n));
+    FA_TRY(quant_rule_check(op, s.mode, s.has_scale_ub, s.scale, s.scale_ub, s.codes, s.scales, s.n));
+    FA_CHECK(s.rows >= 0, "%s: rows must be non-negative", op);
+    FA_CHECK(act_stride_ok(s.x, s.x_row_stride, s.rows, s.n) && act_stride_ok(s.codes, s.codes_row_stride, s.rows, s.n),
+             "%s: row strides must be non-negative and (rows > 1) at least n", op);
+    FA_CHECK((addr(s.x) & 1) == 0, "%s: x must be aligned to its element", op);
+    if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
+    const View in = view_rows("x", s.x, s.rows, s.x_row_stride, s.n, 2);
+    const View out[] = {
+        view_rows("codes", s.codes, s.rows, s.codes_row_stride, s.n, 1),
+        quant_scales_view(s.scales, s.mode, s.rows, s.n),
+    };
+    return check_overlaps(op, out, 2, &in, 1, true);
+}
+
+// fa_add_norm_quant's argument rules: fa_add_norm's on `norm`, codes and scales in the place of out
+static int add_norm_quant_check(const fa_add_norm_quant_params& s) {
+    const char* op = "add_norm_quant";
+    FA_CHECK(s.norm.struct_size >= sizeof(fa_add_norm_params), "%s: norm.struct_size %zu is smaller than this library's %zu", op,
+             s.norm.struct_size, sizeof(fa_add_norm_params));
+    FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(add_norm_common_check(op, s.norm.dtype, s.norm.weight_dtype, s.norm.rows, s.norm.n, s.norm.weight, s.norm.eps,
+                                 s.norm.weight_offset));                       // (n and rows first: the rules below read them)
+    FA_TRY(quant_rule_check(op, s.mode, s.has_scale_ub, s.scale, s.scale_ub, s.codes, s.scales, s.norm.n));
+    FA_CHECK((addr(s.codes) & 7) == 0 && s.codes_row_stride >= 0 && s.codes_row_stride % 8 == 0 &&
+             (s.norm.rows <= 1 || s.codes_row_stride >= s.norm.n),
+             "%s: codes must be 8-byte aligned, with a row stride that is a non-negative multiple of 8 and (rows > 1) at least n", op);
+    const View out[] = {
+        view_rows("codes", s.codes, s.norm.rows, s.codes_row_stride, s.norm.n, 1),
+        quant_scales_view(s.scales, s.mode, s.norm.rows, s.norm.n),
+    };
+    return add_norm_check(s.norm, op, out, 2);
+}
+
+// fa_act_mul_quant's argument rules
+static int act_mul_quant_check(const fa_act_mul_quant_params& s) {
+    const char* op = "act_mul_quant";
+    FA_CHECK(s.gate, "%s: gate must not be NULL", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(check_io_dtype(op, s.dtype, "dtype"));
+    FA_CHECK(s.activation >= FA_ACT_SILU && s.activation <= FA_ACT_RELU2, "%s: unknown activation %d", op, s.activation);
+    FA_TRY(quant_n_check(op, s.n));
+    FA_TRY(quant_rule_check(op, s.mode, s.has_scale_ub, s.scale, s.scale_ub, s.codes, s.scales, s.n));
+    FA_CHECK(s.rows >= 0, "%s: rows must be non-negative", op);
+    FA_CHECK(act_stride_ok(s.gate, s.gate_row_stride, s.rows, s.n) && act_stride_ok(s.up, s.up_row_stride, s.rows, s.n) &&
+             act_stride_ok(s.codes, s.codes_row_stride, s.rows, s.n), "%s: row strides must be non-negative and (rows > 1) at least n", op);
+    FA_CHECK(((addr(s.gate) | addr(s.up)) & 1) == 0, "%s: gate / up must be aligned to their element", op);
+    if (s.rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 rows in one launch", op);
+    const View in[] = {
+        view_rows("gate", s.gate, s.rows, s.gate_row_stride, s.n, 2),
+        view_rows("up", s.up, s.rows, s.up_row_stride, s.n, 2),
+    };
+    const View out[] = {
+        view_rows("codes", s.codes, s.rows, s.codes_row_stride, s.n, 1),
+        quant_scales_view(s.scales, s.mode, s.rows, s.n),
+    };
+    return check_overlaps(op, out, 2, in, 2, true);
+}
+
 extern "C" {
 
 int fa_rotary(const fa_rotary_params* r, void* stream) {
@@ -1500,6 +1611,37 @@ int fa_act_mul_bwd(const fa_act_mul_bwd_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_act_mul_bwd(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_act_mul_bwd launch");
+}
+
+int fa_quant_fp8(const fa_quant_fp8_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_quant_fp8_params"));
+    fa_quant_fp8_params s = *sp;
+    FA_TRY(quant_fp8_check(s));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_quant_fp8(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_quant_fp8 launch");
+}
+
+int fa_add_norm_quant(const fa_add_norm_quant_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_add_norm_quant_params"));
+    fa_add_norm_quant_params s = *sp;
+    FA_TRY(add_norm_quant_check(s));
+    if (s.norm.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    s.norm.struct_size = sizeof(s.norm);
+    fa::launch_add_norm_quant(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_add_norm_quant launch");
+}
+
+int fa_act_mul_quant(const fa_act_mul_quant_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_act_mul_quant_params"));
+    fa_act_mul_quant_params s = *sp;
+    FA_TRY(act_mul_quant_check(s));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_act_mul_quant(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_act_mul_quant launch");
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ FA_FLAG_DS_HANDOFF = 4
 FA_FLAG_FWD_KEY_SPLIT = 8
 FA_FLAG_TREE_MASK = 16
 FA_ACT_SILU, FA_ACT_GELU, FA_ACT_GELU_TANH, FA_ACT_RELU, FA_ACT_RELU2 = 0, 1, 2, 3, 4    # enum fa_act
+FA_QUANT_ROW, FA_QUANT_GROUP, FA_QUANT_STATIC = 0, 1, 2                                  # enum fa_quant_mode
 
 _i64, _i32, _f32, _u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
 _ptr = ctypes.c_void_p
@@ -359,6 +360,51 @@ class FaActMulBwdParams(ctypes.Structure):
     ]
 
 
+class FaQuantFp8Params(ctypes.Structure):
+    """Mirror of `struct fa_quant_fp8_params` (include/fa_mi355.h): fa_quant_fp8, dynamic fp8-e4m3 quantisation of [rows, n]
+    fp16 / bf16 - codes and fp32 scales.  struct_size must be set to sizeof(FaQuantFp8Params)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("x", _ptr),
+        ("codes", _ptr), ("scales", _ptr),                    # [rows, n] bytes; fp32 [rows] / [rows, n / 128] / NULL (static)
+        ("x_row_stride", _i64), ("codes_row_stride", _i64),
+        ("rows", _i64),
+        ("n", _i32), ("dtype", _i32), ("mode", _i32), ("has_scale_ub", _i32),
+        ("scale", _f32), ("scale_ub", _f32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaAddNormQuantParams(ctypes.Structure):
+    """Mirror of `struct fa_add_norm_quant_params` (include/fa_mi355.h): fa_add_norm_quant, fa_add_norm's forward with fp8 codes
+    and scales in the place of `out` (norm.out NULL).  struct_size and norm.struct_size must both be set."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("norm", FaAddNormParams),
+        ("codes", _ptr), ("scales", _ptr),
+        ("codes_row_stride", _i64),
+        ("mode", _i32), ("has_scale_ub", _i32),
+        ("scale", _f32), ("scale_ub", _f32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaActMulQuantParams(ctypes.Structure):
+    """Mirror of `struct fa_act_mul_quant_params` (include/fa_mi355.h): fa_act_mul_quant, act(gate) * up (up NULL: act(gate))
+    as fp8 codes and scales.  struct_size must be set to sizeof(FaActMulQuantParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("gate", _ptr), ("up", _ptr),
+        ("codes", _ptr), ("scales", _ptr),
+        ("gate_row_stride", _i64), ("up_row_stride", _i64), ("codes_row_stride", _i64),
+        ("rows", _i64),
+        ("n", _i32), ("dtype", _i32), ("activation", _i32), ("mode", _i32), ("has_scale_ub", _i32),
+        ("scale", _f32), ("scale_ub", _f32),
+        ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -373,7 +419,9 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size",
            "fa_cross_entropy", "fa_cross_entropy_workspace_bytes", "fa_cross_entropy_params_size",
            "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size",
-           "fa_act_mul", "fa_act_mul_params_size", "fa_act_mul_plan", "fa_act_mul_bwd", "fa_act_mul_bwd_params_size"] + EXT_OPS
+           "fa_act_mul", "fa_act_mul_params_size", "fa_act_mul_plan", "fa_act_mul_bwd", "fa_act_mul_bwd_params_size",
+           "fa_quant_fp8", "fa_quant_fp8_params_size", "fa_add_norm_quant", "fa_add_norm_quant_params_size",
+           "fa_act_mul_quant", "fa_act_mul_quant_params_size"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -392,6 +440,9 @@ ROW_OPS = [
     ("fa_cross_entropy_bwd", FaCrossEntropyBwdParams, None),
     ("fa_act_mul", FaActMulParams, None),
     ("fa_act_mul_bwd", FaActMulBwdParams, None),
+    ("fa_quant_fp8", FaQuantFp8Params, None),
+    ("fa_add_norm_quant", FaAddNormQuantParams, None),
+    ("fa_act_mul_quant", FaActMulQuantParams, None),
 ]
 
 
@@ -518,7 +569,8 @@ def _workspace_query(query):
 
 call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
-# call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
+# call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
+# call_act_mul_quant; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)

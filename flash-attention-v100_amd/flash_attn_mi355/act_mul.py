@@ -43,8 +43,10 @@ Tensors are `[..., N]`.  A view with a contiguous last dimension whose rows flat
 halves of a packed `[..., 2N]` tensor, a `[:, :N]` view of padded rows.  Anything else is copied - which in place would change
 the copy, so there it is an error.  CPU tensors raise: there is no torch fallback.
 
-Not covered: a bias and its gradient (a column sum), an fp8-quantised output, fp32 io, `F.glu`'s sigmoid gate, fusing into the
-GEMMs on either side, an `Mlp` module, and a double backward.  Nothing here is exported through the packages' `__all__` lists."""
+An fp8-quantised output in the place of the 16-bit one is `quant.act_mul_quant` / `quant.act_and_mul_quant` (the forward only).
+
+Not covered: a bias and its gradient (a column sum), fp32 io, `F.glu`'s sigmoid gate, fusing into the GEMMs on either side, an
+`Mlp` module, and a double backward.  Nothing here is exported through the packages' `__all__` lists."""
 import ctypes
 
 import torch

@@ -18,9 +18,11 @@ N <= 256 an RMSNorm without bias has the bits of `qk_norm.qk_rms_norm` on a head
 The backward treats both roundings as the identity (straight-through) and sums dweight / dbias without atomics in an order that
 depends on (rows, N, bias) alone: bitwise repeatable.
 
-Not covered: dropout, rowscale / layerscale, the parallel-residual second branch (x1 / weight1 / bias1), fp32 or fp8 x, an
-fp8-quantised output, N > 16384 or N that is not a multiple of 8, and a double backward.  Nothing here is exported through the
-packages' `__all__` lists."""
+An fp8-quantised output in the place of the 16-bit one is `quant.add_norm_quant` (the forward only).
+
+Not covered: dropout, rowscale / layerscale, the parallel-residual second branch (x1 / weight1 / bias1), fp32 or fp8 x,
+N > 16384 or N that is not a multiple of 8, and a double backward.  Nothing here is exported through the packages' `__all__`
+lists."""
 import ctypes
 from typing import Optional
 

@@ -10,7 +10,9 @@ with an autograd formula, its in-place form and its backward, fa_add_norm / fa_a
 / `cross_entropy_bwd_`: the softmax cross-entropy loss over the vocabulary with an autograd formula, its backward and the backward
 in place, fa_cross_entropy / fa_cross_entropy_bwd; `act_mul` / `act_and_mul` / `act_mul_bwd` / `act_and_mul_bwd` / `act_mul_bwd_`:
 the gated activation act(gate) * up of the MLP on separate or packed tensors with autograd formulas, its backward and the backward
-in place, fa_act_mul / fa_act_mul_bwd - registered, but not listed in `__all__`).
+in place, fa_act_mul / fa_act_mul_bwd; `quant_fp8` / `add_norm_quant` / `act_mul_quant` / `act_and_mul_quant`: dynamic fp8-e4m3
+quantisation alone and fused behind the forwards of add_norm and act_mul, fa_quant_fp8 / fa_add_norm_quant / fa_act_mul_quant, not
+differentiable - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -42,6 +44,7 @@ from . import flash_attn_interface as _fi
 from . import kv_gather as _kv_gather
 from . import kv_store as _kv_store
 from . import qk_norm as _qk_norm
+from . import quant as _quant
 from . import rope_store as _rope_store
 from . import rotary as _rotary
 
@@ -874,3 +877,99 @@ act_and_mul.register_autograd(_act_and_mul_backward, setup_context=_act_and_mul_
 
 __all__ = ["fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache", "fwd_kvcache_tree", "fwd_out", "varlen_fwd_out", "bwd_out",
            "merge_states", "rotary", "rotary_", "kv_store"]
+
+
+# ------------------------------------------------------------------------------------------
+# dynamic fp8-e4m3 quantisation, alone and behind the forwards of add_norm and act_mul (flash_attn_mi355.quant; csrc/fa_quant.hip).
+# Reached as torch.ops.flash_attn_mi355.quant_fp8 / .add_norm_quant / .act_mul_quant / .act_and_mul_quant; not in __all__.
+# `mode` is the name ("row", "group", "static"); scale goes with "static", scale_ub with the other two.  Functional, not
+# differentiable: an input that requires grad raises by name.  A torch.library return cannot be optional: the static mode has no
+# scales and add_norm_quant without residual / prenorm no residual_out - an EMPTY tensor of shape (0,) stands in their place.
+# ------------------------------------------------------------------------------------------
+def _scales_shape(x, mode):
+    lead = tuple(x.shape[:-1])
+    return (0,) if mode == "static" else (lead + (x.shape[-1] // _quant.GROUP,) if mode == "group" else lead)
+
+
+def _fake_codes_scales(x, mode, last=None):
+    shape = tuple(x.shape[:-1]) + (x.shape[-1] if last is None else last,)
+    like = x.new_empty(shape, dtype=torch.float8_e4m3fn)
+    return like, x.new_empty(_scales_shape(like, mode), dtype=torch.float32)
+
+
+def _not_differentiable(op, names):
+    """(backward, setup_context) of an op without a gradient: an input that requires grad raises by name at the call"""
+    def setup(ctx, inputs, output):
+        bad = [n for n, need in zip(names, ctx.needs_input_grad) if need]
+        if bad:
+            raise RuntimeError(f"{op}: {', '.join(bad)} requires grad, and {op} is not differentiable (detach it)")
+
+    def backward(ctx, *grads):
+        raise RuntimeError(f"{op} is not differentiable")
+    return backward, setup
+
+
+@torch.library.custom_op(f"{_NS}::quant_fp8", mutates_args=(), device_types="cuda")
+def quant_fp8(x: Tensor, mode: str, scale: Optional[float], scale_ub: Optional[float]) -> Tuple[Tensor, Tensor]:
+    """quant.quant_fp8: (codes, scales), fresh contiguous tensors; mode 'static': scales is an empty tensor of shape (0,)"""
+    codes, scales = _quant.quant_fp8(x, mode=mode, scale=scale, scale_ub=scale_ub)
+    return codes, (x.new_empty((0,), dtype=torch.float32) if scales is None else scales)
+
+
+@quant_fp8.register_fake
+def _(x, mode, scale, scale_ub):
+    return _fake_codes_scales(x, mode)
+
+
+@torch.library.custom_op(f"{_NS}::add_norm_quant", mutates_args=(), device_types="cuda")
+def add_norm_quant(x: Tensor, residual: Optional[Tensor], weight: Tensor, bias: Optional[Tensor], eps: float, weight_offset: float,
+                   is_rms_norm: bool, prenorm: bool, residual_in_fp32: bool, mode: str, scale: Optional[float],
+                   scale_ub: Optional[float]) -> Tuple[Tensor, Tensor, Tensor]:
+    """quant.add_norm_quant out of place: (codes, scales, residual_out); scales (mode 'static') and residual_out (no residual, no
+    prenorm) are empty tensors of shape (0,) where there is none"""
+    codes, scales, ro = _quant.add_norm_quant(x, residual, weight, bias, eps=eps, weight_offset=weight_offset, is_rms_norm=is_rms_norm,
+                                              prenorm=prenorm, residual_in_fp32=residual_in_fp32, mode=mode, scale=scale,
+                                              scale_ub=scale_ub)
+    return (codes, x.new_empty((0,), dtype=torch.float32) if scales is None else scales,
+            x.new_empty((0,)) if ro is None else ro)
+
+
+@add_norm_quant.register_fake
+def _(x, residual, weight, bias, eps, weight_offset, is_rms_norm, prenorm, residual_in_fp32, mode, scale, scale_ub):
+    codes, scales = _fake_codes_scales(x, mode)
+    if residual is None and not prenorm:
+        return codes, scales, x.new_empty((0,))
+    ro_dtype = _add_norm.residual_out_dtype(x.dtype, None if residual is None else residual.dtype, residual_in_fp32)
+    return codes, scales, x.new_empty(x.shape, dtype=ro_dtype)
+
+
+@torch.library.custom_op(f"{_NS}::act_mul_quant", mutates_args=(), device_types="cuda")
+def act_mul_quant(gate: Tensor, up: Optional[Tensor], activation: str, mode: str, scale: Optional[float],
+                  scale_ub: Optional[float]) -> Tuple[Tensor, Tensor]:
+    """quant.act_mul_quant: (codes, scales) of act(gate) * up (up None: act(gate)); mode 'static': scales is empty, shape (0,)"""
+    codes, scales = _quant.act_mul_quant(gate, up, activation=activation, mode=mode, scale=scale, scale_ub=scale_ub)
+    return codes, (gate.new_empty((0,), dtype=torch.float32) if scales is None else scales)
+
+
+@act_mul_quant.register_fake
+def _(gate, up, activation, mode, scale, scale_ub):
+    return _fake_codes_scales(gate, mode)
+
+
+@torch.library.custom_op(f"{_NS}::act_and_mul_quant", mutates_args=(), device_types="cuda")
+def act_and_mul_quant(x: Tensor, activation: str, mode: str, scale: Optional[float], scale_ub: Optional[float]) -> Tuple[Tensor, Tensor]:
+    """quant.act_and_mul_quant on a packed [..., 2N]: (codes [..., N], scales)"""
+    codes, scales = _quant.act_and_mul_quant(x, activation=activation, mode=mode, scale=scale, scale_ub=scale_ub)
+    return codes, (x.new_empty((0,), dtype=torch.float32) if scales is None else scales)
+
+
+@act_and_mul_quant.register_fake
+def _(x, activation, mode, scale, scale_ub):
+    return _fake_codes_scales(x, mode, last=x.shape[-1] // 2)
+
+
+for _op, _names in ((quant_fp8, ("x",)), (add_norm_quant, ("x", "residual", "weight", "bias")), (act_mul_quant, ("gate", "up")),
+                    (act_and_mul_quant, ("x",))):
+    _bwd, _setup = _not_differentiable(_op._opoverload._schema.name.split("::")[-1], _names)
+    _op.register_autograd(_bwd, setup_context=_setup)
+del _op, _names, _bwd, _setup

@@ -1091,6 +1091,117 @@ int    fa_act_mul_bwd(const fa_act_mul_bwd_params* s, void* stream);
 size_t fa_act_mul_bwd_params_size(void);
 
 /*
+ * fa_quant_fp8, fa_add_norm_quant, fa_act_mul_quant - dynamic fp8-e4m3 (OCP, "e4m3fn") quantisation of 16-bit activations, alone
+ * and fused behind fa_add_norm's forward and fa_act_mul's forward (additive: fa_params and FA_ABI_VERSION are unchanged).  One
+ * rule in all three, fp32 throughout; y_j are the values to quantise AFTER their rounding to `dtype` (fa_quant_fp8: x itself):
+ *     a      = fmaxf(+0, |y_0|, |y_1|, ..)   over the row (FA_QUANT_ROW) or over each aligned group of 128 columns (FA_QUANT_GROUP);
+ *                                            exact and order-free; fmaxf skips a NaN, so a row of NaNs alone has a = +0
+ *     a'     = has_scale_ub ? fminf(a, scale_ub) : a
+ *     scale  = fmaxf(a' / 448.0f, 0x1p-64f)  one IEEE division; the floor keeps 1 / scale finite for an all-zero row
+ *     inv    = 1.0f / scale                  one IEEE division
+ *     code_j = e4m3(fminf(fmaxf(y_j * inv, -448), 448))      the hardware conversion: round to nearest even, saturating
+ * FA_QUANT_STATIC: `scale` is given by the caller (finite, > 0), only the last two lines run and no scale is written - the rule
+ * fa_kv_store and the kv-cache append write fp8 caches with (csrc/fa_fp8_cvt.h), and what the fp8 q / k / v forward reads.
+ * codes: [rows, n] bytes with a row stride of their own (>= n).  scales: fp32, contiguous - [rows] (ROW) or [rows, n / 128] (GROUP).
+ * Fused means bit-identical to unfused: fa_add_norm_quant leaves the codes and scales of fa_quant_fp8 on fa_add_norm's `out`
+ * (and fa_add_norm's residual_out), fa_act_mul_quant those of fa_quant_fp8 on fa_act_mul's `out` - the same arithmetic in the
+ * same order, rounded to `dtype`, then the rule above.  The 16-bit `out` itself is not written.
+ * Special values are what the lines above give literally; none is a fault, a device assert or a host synchronisation:
+ *     an all-zero row (group)      a = 0, scale = 2^-64 (the floor), every code +0 or -0 with y's sign
+ *     y_j = NaN                    skipped by a; its own code: NaN * inv = NaN, fmaxf(NaN, -448) = -448 -> the code of -448 (0xFE);
+ *                                  the other codes and the scale are those of the row without it
+ *     y_j = +-inf, no scale_ub     a = +inf, scale = +inf (stored), inv = 0: every finite y gives +-0, the infinite ones
+ *                                  inf * 0 = NaN -> 0xFE
+ *     y_j = +-inf, scale_ub        a' = scale_ub, the scale is finite: +-inf saturates to +-448 (0x7E / 0xFE)
+ *     FA_QUANT_STATIC              NaN -> 0xFE, +-inf -> +-448
+ * fa_quant_fp8: x [rows, n] of `dtype`, last dimension contiguous, any row stride >= n; n a multiple of 8 in [8, 65536] (GROUP: of
+ *   128).  x is read once: a row (n > 512: one workgroup per row; below, 256 / G rows per workgroup, G lanes a row) stays in
+ *   registers between the amax and the conversion.  A row of x that does not start on a 16-byte boundary, and a row of codes that
+ *   does not start on an 8-byte boundary, are taken element by element: the same bits.
+ * fa_add_norm_quant: fa_add_norm's forward - every field of `norm` as there, both of its forms (n <= 256 and wide) with its
+ *   ownership and the order of its sums - except that norm.out must be NULL (norm.out_row_stride 0): codes and scales take its
+ *   place.  residual_out is written as before; residual_out == residual stays legal.  codes: 8-byte aligned base and row stride.
+ * fa_act_mul_quant: act(gate) * up (up NULL: act(gate)) with fa_act_mul's activations and fp32 order; gate, up as there but n a
+ *   multiple of 8 in [8, 65536].  One workgroup owns a whole row in every mode (256 lanes up to 16384 columns, 1024 above, at
+ *   most 8 pieces of 8 columns per lane and input).
+ * One launch each, no workspace, no atomics, no host synchronisation, bitwise repeatable, capturable in a graph; a row's codes and
+ * scale depend on that row alone.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL input or codes; scales NULL in ROW / GROUP or given in
+ * STATIC; an unknown mode; a dtype other than FA_FP16 / FA_BF16; n not a multiple of 8 (GROUP: of 128) or outside the op's range;
+ * negative rows or row strides, or (rows > 1) a row stride below n; a misaligned pointer (inputs: their element; scales: 4 bytes;
+ * fa_add_norm_quant: fa_add_norm's rules); `scale` not finite and > 0 in STATIC, or not 0 elsewhere; has_scale_ub other than 0 / 1,
+ * with STATIC, or with a scale_ub that is not finite and > 0 (scale_ub must be 0 where has_scale_ub is 0); any overlap of an output
+ * with an input or another output (but residual_out == residual); fa_add_norm's and fa_act_mul's own rules; non-zero reserved
+ * fields.  rows > 2^31 - 1: FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
+ * Not covered: a backward or a straight-through estimator; device-resident static scales; per-tensor dynamic scales (a grid-wide
+ * reduction); E8M0 / MX power-of-two scales; e5m2 and the fnuz formats; column-major or transposed scales and codes; fp4; fusing
+ * into a GEMM; also writing the 16-bit out.
+ */
+typedef enum fa_quant_mode {
+    FA_QUANT_ROW = 0,       /* one dynamic scale per row */
+    FA_QUANT_GROUP = 1,     /* one dynamic scale per aligned group of 128 columns */
+    FA_QUANT_STATIC = 2     /* the caller's scale; none is written */
+} fa_quant_mode;
+
+/* (mode, has_scale_ub, scale, scale_ub mean the same in the three blocks) */
+typedef struct fa_quant_fp8_params {
+    size_t         struct_size;      /* sizeof(fa_quant_fp8_params) as the caller compiled it */
+    const void*    x;                /* [rows, n] of `dtype` */
+    void*          codes;            /* [rows, n] fp8-e4m3 bytes */
+    void*          scales;           /* fp32 [rows] (ROW), [rows, n / 128] (GROUP), NULL (STATIC) */
+    int64_t        x_row_stride, codes_row_stride;       /* elements */
+    int64_t        rows;
+    int32_t        n;                /* a multiple of 8, 8 .. 65536; GROUP: of 128 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        mode;             /* fa_quant_mode */
+    int32_t        has_scale_ub;     /* 0 / 1; 0 in STATIC */
+    float          scale;            /* STATIC: finite, > 0; otherwise 0 */
+    float          scale_ub;         /* has_scale_ub: finite, > 0; otherwise 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_quant_fp8_params;
+
+int    fa_quant_fp8(const fa_quant_fp8_params* s, void* stream);
+size_t fa_quant_fp8_params_size(void);
+
+typedef struct fa_add_norm_quant_params {
+    size_t         struct_size;      /* sizeof(fa_add_norm_quant_params) as the caller compiled it */
+    fa_add_norm_params norm;         /* fa_add_norm's block (its struct_size set); out NULL, out_row_stride 0 */
+    void*          codes;            /* [rows, n] fp8-e4m3 bytes; 8-byte aligned */
+    void*          scales;           /* fp32 [rows] (ROW), [rows, n / 128] (GROUP), NULL (STATIC) */
+    int64_t        codes_row_stride; /* elements; a multiple of 8 */
+    int32_t        mode;             /* fa_quant_mode */
+    int32_t        has_scale_ub;     /* 0 / 1; 0 in STATIC */
+    float          scale;            /* STATIC: finite, > 0; otherwise 0 */
+    float          scale_ub;         /* has_scale_ub: finite, > 0; otherwise 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_add_norm_quant_params;
+
+int    fa_add_norm_quant(const fa_add_norm_quant_params* s, void* stream);
+size_t fa_add_norm_quant_params_size(void);
+
+typedef struct fa_act_mul_quant_params {
+    size_t         struct_size;      /* sizeof(fa_act_mul_quant_params) as the caller compiled it */
+    const void*    gate;             /* [rows, n] of `dtype` */
+    const void*    up;               /* [rows, n] of `dtype`; NULL: the ungated form */
+    void*          codes;            /* [rows, n] fp8-e4m3 bytes */
+    void*          scales;           /* fp32 [rows] (ROW), [rows, n / 128] (GROUP), NULL (STATIC) */
+    int64_t        gate_row_stride, up_row_stride, codes_row_stride;   /* elements; up_row_stride is not read where up is NULL */
+    int64_t        rows;
+    int32_t        n;                /* a multiple of 8, 8 .. 65536; GROUP: of 128 */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        activation;       /* fa_act */
+    int32_t        mode;             /* fa_quant_mode */
+    int32_t        has_scale_ub;     /* 0 / 1; 0 in STATIC */
+    float          scale;            /* STATIC: finite, > 0; otherwise 0 */
+    float          scale_ub;         /* has_scale_ub: finite, > 0; otherwise 0 */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_act_mul_quant_params;
+
+int    fa_act_mul_quant(const fa_act_mul_quant_params* s, void* stream);
+size_t fa_act_mul_quant_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
