@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include "fa_common.h"
+#include "fa_moe.h"                                   // fa_moe.hip: the limits, the sort plan and the launchers of fa_moe_*
 
 namespace fa {
 int launch_fwd(const KArgs& a, hipStream_t stream);
@@ -233,6 +234,12 @@ size_t fa_act_mul_bwd_params_size(void) { return sizeof(fa_act_mul_bwd_params); 
 size_t fa_quant_fp8_params_size(void) { return sizeof(fa_quant_fp8_params); }
 size_t fa_add_norm_quant_params_size(void) { return sizeof(fa_add_norm_quant_params); }
 size_t fa_act_mul_quant_params_size(void) { return sizeof(fa_act_mul_quant_params); }
+size_t fa_moe_route_params_size(void) { return sizeof(fa_moe_route_params); }
+size_t fa_moe_route_bwd_params_size(void) { return sizeof(fa_moe_route_bwd_params); }
+size_t fa_moe_sort_params_size(void) { return sizeof(fa_moe_sort_params); }
+size_t fa_moe_permute_params_size(void) { return sizeof(fa_moe_permute_params); }
+size_t fa_moe_combine_params_size(void) { return sizeof(fa_moe_combine_params); }
+size_t fa_moe_combine_bwd_params_size(void) { return sizeof(fa_moe_combine_bwd_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1461,6 +1468,193 @@ static int act_mul_quant_check(const fa_act_mul_quant_params& s) {
     return check_overlaps(op, out, 2, in, 2, true);
 }
 
+// ---- fa_moe_*
+template <typename P>
+static bool moe_reserved_zero(const P& s) { return s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0; }
+
+// the sizes every fa_moe_* op shares; slots = tokens * top_k fits 31 bits afterwards
+static int moe_sizes_check(const char* op, int64_t tokens, int num_experts, int top_k) {
+    FA_CHECK(tokens >= 0, "%s: tokens must be non-negative", op);
+    if (num_experts < 2 || num_experts > fa::MOE_MAX_EXPERTS)
+        return fail(FA_ERR_UNSUPPORTED, "%s: num_experts must be in [2, %d], got %d", op, fa::MOE_MAX_EXPERTS, num_experts);
+    const int kmax = num_experts < fa::MOE_MAX_TOPK ? num_experts : fa::MOE_MAX_TOPK;
+    if (top_k < 1 || top_k > kmax)
+        return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, min(num_experts, %d)] = [1, %d], got %d", op, fa::MOE_MAX_TOPK, kmax, top_k);
+    if (tokens > 0x7fffffffLL / top_k)
+        return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k must stay below 2^31", op);
+    return FA_OK;
+}
+
+// the router's own fields: dtype, scoring, scale, the row strides
+static int moe_route_common_check(const char* op, int dtype, int scoring, int renormalize, float scale) {
+    FA_CHECK(dtype == FA_FP16 || dtype == FA_BF16 || dtype == FA_FP32, "%s: dtype must be fp16, bf16 or fp32", op);
+    FA_CHECK(scoring == FA_MOE_SOFTMAX || scoring == FA_MOE_SIGMOID, "%s: unknown scoring %d", op, scoring);
+    FA_CHECK(renormalize == 0 || renormalize == 1, "%s: renormalize must be 0 or 1", op);
+    FA_CHECK(scale >= -3.402823466e38f && scale <= 3.402823466e38f, "%s: scale must be finite", op);
+    return FA_OK;
+}
+static bool moe_stride_ok(int64_t rs, int64_t rows, int n) { return rs >= 0 && (rows <= 1 || rs >= n); }
+
+static int moe_route_check(const fa_moe_route_params& s) {
+    const char* op = "moe_route";
+    FA_CHECK(moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(moe_sizes_check(op, s.tokens, s.num_experts, s.top_k));
+    FA_TRY(moe_route_common_check(op, s.dtype, s.scoring, s.renormalize, s.scale));
+    FA_CHECK(s.scoring == FA_MOE_SIGMOID || !s.bias, "%s: bias goes with sigmoid scoring", op);
+    if (s.tokens == 0) return FA_OK;
+    FA_CHECK(s.logits && s.weights && s.ids, "%s: logits, weights and ids must not be NULL", op);
+    FA_CHECK(moe_stride_ok(s.logits_row_stride, s.tokens, s.num_experts), "%s: logits_row_stride must be non-negative and (tokens > 1) at least num_experts", op);
+    const int esize = s.dtype == FA_FP32 ? 4 : 2;
+    FA_CHECK((addr(s.logits) & (esize - 1)) == 0 && ((addr(s.bias) | addr(s.weights) | addr(s.ids)) & 3) == 0,
+             "%s: logits must be aligned to their element, bias / weights / ids to 4 bytes", op);
+    const View in[] = {
+        view_rows("logits", s.logits, s.tokens, s.logits_row_stride, s.num_experts, esize),
+        view_flat("bias", s.bias, (uint64_t)s.num_experts * 4),
+    };
+    const View out[] = {
+        view_flat("weights", s.weights, (uint64_t)s.tokens * s.top_k * 4),
+        view_flat("ids", s.ids, (uint64_t)s.tokens * s.top_k * 4),
+    };
+    return check_overlaps(op, out, 2, in, 2, true, nullptr, 0);
+}
+
+static int moe_route_bwd_check(const fa_moe_route_bwd_params& s) {
+    const char* op = "moe_route_bwd";
+    FA_CHECK(moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(moe_sizes_check(op, s.tokens, s.num_experts, s.top_k));
+    FA_TRY(moe_route_common_check(op, s.dtype, s.scoring, s.renormalize, s.scale));
+    if (s.tokens == 0) return FA_OK;
+    FA_CHECK(s.dweights && s.logits && s.ids && s.dlogits, "%s: dweights, logits, ids and dlogits must not be NULL", op);
+    FA_CHECK(moe_stride_ok(s.logits_row_stride, s.tokens, s.num_experts) && moe_stride_ok(s.dlogits_row_stride, s.tokens, s.num_experts),
+             "%s: row strides must be non-negative and (tokens > 1) at least num_experts", op);
+    FA_CHECK(s.tokens <= 1 || s.dlogits_row_stride >= s.num_experts, "%s: dlogits rows must not overlap", op);
+    const int esize = s.dtype == FA_FP32 ? 4 : 2;
+    FA_CHECK(((addr(s.logits) | addr(s.dlogits)) & (esize - 1)) == 0 && ((addr(s.dweights) | addr(s.ids)) & 3) == 0,
+             "%s: logits / dlogits must be aligned to their element, dweights / ids to 4 bytes", op);
+    const View in[] = {
+        view_rows("logits", s.logits, s.tokens, s.logits_row_stride, s.num_experts, esize),
+        view_flat("dweights", s.dweights, (uint64_t)s.tokens * s.top_k * 4),
+        view_flat("ids", s.ids, (uint64_t)s.tokens * s.top_k * 4),
+    };
+    const View out = view_rows("dlogits", s.dlogits, s.tokens, s.dlogits_row_stride, s.num_experts, esize);
+    return check_overlaps(op, &out, 1, in, 3, false, nullptr, 0);
+}
+
+// query: the workspace is not looked at
+static int moe_sort_check(const fa_moe_sort_params& s, bool query) {
+    const char* op = "moe_sort";
+    FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(moe_sizes_check(op, s.tokens, s.num_experts, s.top_k));
+    if (s.align < 1 || s.align > fa::MOE_MAX_ALIGN)
+        return fail(FA_ERR_UNSUPPORTED, "%s: align must be in [1, %d], got %d", op, fa::MOE_MAX_ALIGN, s.align);
+    const int64_t slots = s.tokens * s.top_k, mmax = slots + (int64_t)s.num_experts * (s.align - 1);
+    if (mmax > 0x7fffffffLL)
+        return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k + num_experts x (align - 1) must stay below 2^31", op);
+    if (query) return FA_OK;
+    FA_CHECK(s.expert_offsets && (slots == 0 || (s.ids && s.pos)) && (mmax == 0 || s.sorted_slot),
+             "%s: ids, sorted_slot, pos and expert_offsets must not be NULL", op);
+    FA_CHECK(((addr(s.ids) | addr(s.sorted_slot) | addr(s.pos) | addr(s.expert_offsets) | addr(s.workspace)) & 3) == 0,
+             "%s: ids, sorted_slot, pos, expert_offsets and workspace must be 4-byte aligned", op);
+    const size_t need = fa::moe_sort_plan(slots, s.num_experts).workspace_bytes;
+    FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: workspace too small (%zu bytes, need %zu)", op, s.workspace ? s.workspace_bytes : (size_t)0, need);
+    const View in[] = {view_flat("ids", s.ids, (uint64_t)slots * 4)};
+    const View out[] = {
+        view_flat("sorted_slot", s.sorted_slot, (uint64_t)mmax * 4),
+        view_flat("pos", s.pos, (uint64_t)slots * 4),
+        view_flat("expert_offsets", s.expert_offsets, (uint64_t)(s.num_experts + 1) * 4),
+        view_flat("workspace", s.workspace, need),
+    };
+    return check_overlaps(op, out, 4, in, 1, true, nullptr, 0);
+}
+
+// the [rows, n] 16-bit tensors of permute / combine: n, dtype, 16-byte pieces
+static int moe_hidden_check(const char* op, int n, int dtype) {
+    FA_TRY(check_io_dtype(op, dtype, "dtype"));
+    if (n < 8 || n > fa::MOE_MAX_N || n % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: n must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_MAX_N, n);
+    return FA_OK;
+}
+static bool moe_rows_ok(const void* p, int64_t rs, int64_t rows, int n) {
+    return !p || ((addr(p) & 15) == 0 && rs >= 0 && rs % 8 == 0 && (rows <= 1 || rs >= n));
+}
+static const char* const kMoeRowsRule = "16-byte aligned with row strides that are multiples of 8 and (rows > 1) at least n";
+
+static int moe_permute_check(const fa_moe_permute_params& s) {
+    const char* op = "moe_permute";
+    FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.tokens >= 0 && s.rows >= 0, "%s: tokens and rows must be non-negative", op);
+    if (s.top_k < 1 || s.top_k > fa::MOE_MAX_TOPK)
+        return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, %d], got %d", op, fa::MOE_MAX_TOPK, s.top_k);
+    if (s.tokens > 0x7fffffffLL / s.top_k || s.rows > 0x7fffffffLL)
+        return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k and rows must stay below 2^31", op);
+    FA_TRY(moe_hidden_check(op, s.n, s.dtype));
+    if (s.rows == 0) return FA_OK;
+    FA_CHECK(s.out && (s.tokens == 0 || s.x), "%s: x and out must not be NULL", op);
+    FA_CHECK(moe_rows_ok(s.x, s.x_row_stride, s.tokens, s.n) && moe_rows_ok(s.out, s.out_row_stride, s.rows, s.n), "%s: x and out must be %s", op, kMoeRowsRule);
+    FA_CHECK(s.rows <= 1 || s.out_row_stride >= s.n, "%s: out rows must not overlap", op);
+    FA_CHECK(((addr(s.sorted_slot) | addr(s.slot_scale)) & 3) == 0, "%s: sorted_slot and slot_scale must be 4-byte aligned", op);
+    const View in[] = {
+        view_rows("x", s.x, s.tokens, s.x_row_stride, s.n, 2),
+        view_flat("sorted_slot", s.sorted_slot, (uint64_t)s.rows * 4),
+        view_flat("slot_scale", s.slot_scale, (uint64_t)s.tokens * s.top_k * 4),
+    };
+    const View out = view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2);
+    return check_overlaps(op, &out, 1, in, 3, false, nullptr, 0);
+}
+
+static int moe_combine_check(const fa_moe_combine_params& s) {
+    const char* op = "moe_combine";
+    FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.tokens >= 0 && s.rows >= 0, "%s: tokens and rows must be non-negative", op);
+    if (s.top_k < 1 || s.top_k > fa::MOE_MAX_TOPK)
+        return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, %d], got %d", op, fa::MOE_MAX_TOPK, s.top_k);
+    if (s.tokens > 0x7fffffffLL / s.top_k || s.rows > 0x7fffffffLL)
+        return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k and rows must stay below 2^31", op);
+    FA_TRY(moe_hidden_check(op, s.n, s.dtype));
+    if (s.tokens == 0) return FA_OK;
+    FA_CHECK(s.out && s.pos && (s.rows == 0 || s.y), "%s: y, pos and out must not be NULL", op);
+    FA_CHECK(moe_rows_ok(s.y, s.y_row_stride, s.rows, s.n) && moe_rows_ok(s.out, s.out_row_stride, s.tokens, s.n), "%s: y and out must be %s", op, kMoeRowsRule);
+    FA_CHECK(((addr(s.pos) | addr(s.weights)) & 3) == 0, "%s: pos and weights must be 4-byte aligned", op);
+    const View in[] = {
+        view_rows("y", s.y, s.rows, s.y_row_stride, s.n, 2),
+        view_flat("pos", s.pos, (uint64_t)s.tokens * s.top_k * 4),
+        view_flat("weights", s.weights, (uint64_t)s.tokens * s.top_k * 4),
+    };
+    const View out = view_rows("out", s.out, s.tokens, s.out_row_stride, s.n, 2);
+    return check_overlaps(op, &out, 1, in, 3, false, nullptr, 0);
+}
+
+static int moe_combine_bwd_check(const fa_moe_combine_bwd_params& s) {
+    const char* op = "moe_combine_bwd";
+    FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.tokens >= 0 && s.rows >= 0, "%s: tokens and rows must be non-negative", op);
+    if (s.top_k < 1 || s.top_k > fa::MOE_MAX_TOPK)
+        return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, %d], got %d", op, fa::MOE_MAX_TOPK, s.top_k);
+    if (s.tokens > 0x7fffffffLL / s.top_k || s.rows > 0x7fffffffLL)
+        return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k and rows must stay below 2^31", op);
+    FA_TRY(moe_hidden_check(op, s.n, s.dtype));
+    if (!s.dy && !s.dw) return FA_OK;
+    const bool live = s.tokens > 0;
+    FA_CHECK(!live || (s.dout && s.pos), "%s: dout and pos must not be NULL", op);
+    FA_CHECK(!s.dy || !live || s.weights, "%s: dy needs weights", op);
+    FA_CHECK(!s.dw || !live || s.rows == 0 || s.y, "%s: dw needs y", op);
+    FA_CHECK(moe_rows_ok(s.dout, s.dout_row_stride, s.tokens, s.n) && moe_rows_ok(s.y, s.y_row_stride, s.rows, s.n) &&
+             moe_rows_ok(s.dy, s.dy_row_stride, s.rows, s.n), "%s: dout, y and dy must be %s", op, kMoeRowsRule);
+    FA_CHECK(((addr(s.pos) | addr(s.weights) | addr(s.dw)) & 3) == 0, "%s: pos, weights and dw must be 4-byte aligned", op);
+    const View in[] = {
+        view_rows("dout", s.dout, s.tokens, s.dout_row_stride, s.n, 2),
+        view_rows("y", s.dw ? s.y : nullptr, s.rows, s.y_row_stride, s.n, 2),
+        view_flat("pos", s.pos, (uint64_t)s.tokens * s.top_k * 4),
+        view_flat("weights", s.dy ? s.weights : nullptr, (uint64_t)s.tokens * s.top_k * 4),
+    };
+    const View out[] = {
+        view_rows("dy", s.dy, s.rows, s.dy_row_stride, s.n, 2),
+        view_flat("dw", s.dw, (uint64_t)s.tokens * s.top_k * 4),
+    };
+    return check_overlaps(op, out, 2, in, 4, true, nullptr, 0);
+}
+
+
 extern "C" {
 
 int fa_rotary(const fa_rotary_params* r, void* stream) {
@@ -1642,6 +1836,78 @@ int fa_act_mul_quant(const fa_act_mul_quant_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_act_mul_quant(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_act_mul_quant launch");
+}
+
+int fa_moe_route(const fa_moe_route_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_route_params"));
+    fa_moe_route_params s = *sp;
+    FA_TRY(moe_route_check(s));
+    if (s.tokens == 0) return FA_OK;
+    fa::launch_moe_route(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_route launch");
+}
+
+int fa_moe_route_bwd(const fa_moe_route_bwd_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_route_bwd_params"));
+    fa_moe_route_bwd_params s = *sp;
+    FA_TRY(moe_route_bwd_check(s));
+    if (s.tokens == 0) return FA_OK;
+    fa::launch_moe_route_bwd(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_route_bwd launch");
+}
+
+size_t fa_moe_sort_workspace_bytes(const fa_moe_sort_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_moe_sort_params)) return 0;
+    if (moe_sort_check(*sp, true) != FA_OK) return 0;
+    return fa::moe_sort_plan(sp->tokens * sp->top_k, sp->num_experts).workspace_bytes;
+}
+
+int fa_moe_sort_plan(int64_t slots, int32_t num_experts, int64_t* chunk_slots, int64_t* chunks, int64_t* workspace_bytes) {
+    FA_CHECK(slots >= 0, "moe_sort_plan: slots must be non-negative");
+    if (slots > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "moe_sort_plan: slots must stay below 2^31");
+    if (num_experts < 2 || num_experts > fa::MOE_MAX_EXPERTS)
+        return fail(FA_ERR_UNSUPPORTED, "moe_sort_plan: num_experts must be in [2, %d], got %d", fa::MOE_MAX_EXPERTS, num_experts);
+    const fa::MoeSortPlan pl = fa::moe_sort_plan(slots, num_experts);
+    if (chunk_slots) *chunk_slots = pl.chunk;
+    if (chunks) *chunks = pl.chunks;
+    if (workspace_bytes) *workspace_bytes = (int64_t)pl.workspace_bytes;
+    return FA_OK;
+}
+
+int fa_moe_sort(const fa_moe_sort_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_sort_params"));
+    fa_moe_sort_params s = *sp;
+    FA_TRY(moe_sort_check(s, false));
+    fa::launch_moe_sort(s, static_cast<hipStream_t>(stream));   // (tokens == 0: the offsets and the padding are still written)
+    return check_hip("fa_moe_sort launch");
+}
+
+int fa_moe_permute(const fa_moe_permute_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_permute_params"));
+    fa_moe_permute_params s = *sp;
+    FA_TRY(moe_permute_check(s));
+    if (s.rows == 0) return FA_OK;
+    fa::launch_moe_permute(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_permute launch");
+}
+
+int fa_moe_combine(const fa_moe_combine_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_combine_params"));
+    fa_moe_combine_params s = *sp;
+    FA_TRY(moe_combine_check(s));
+    if (s.tokens == 0) return FA_OK;
+    fa::launch_moe_combine(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_combine launch");
+}
+
+int fa_moe_combine_bwd(const fa_moe_combine_bwd_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_combine_bwd_params"));
+    fa_moe_combine_bwd_params s = *sp;
+    FA_TRY(moe_combine_bwd_check(s));
+    if ((!s.dy || s.rows == 0) && (!s.dw || s.tokens == 0)) return FA_OK;
+    if (s.rows == 0) s.dy = nullptr;
+    fa::launch_moe_combine_bwd(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_combine_bwd launch");
 }
 
 }  // extern "C"

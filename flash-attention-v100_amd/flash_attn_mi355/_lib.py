@@ -17,6 +17,7 @@ FA_FLAG_FWD_KEY_SPLIT = 8
 FA_FLAG_TREE_MASK = 16
 FA_ACT_SILU, FA_ACT_GELU, FA_ACT_GELU_TANH, FA_ACT_RELU, FA_ACT_RELU2 = 0, 1, 2, 3, 4    # enum fa_act
 FA_QUANT_ROW, FA_QUANT_GROUP, FA_QUANT_STATIC = 0, 1, 2                                  # enum fa_quant_mode
+FA_MOE_SOFTMAX, FA_MOE_SIGMOID = 0, 1                                                    # enum fa_moe_scoring
 
 _i64, _i32, _f32, _u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
 _ptr = ctypes.c_void_p
@@ -405,6 +406,92 @@ class FaActMulQuantParams(ctypes.Structure):
     ]
 
 
+class FaMoeRouteParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_route_params` (include/fa_mi355.h): fa_moe_route, top-k routing of [tokens, num_experts] logits -
+    fp32 weights and int32 ids.  struct_size must be set to sizeof(FaMoeRouteParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("logits", _ptr), ("bias", _ptr),                     # [tokens, num_experts] of dtype; fp32 [num_experts] or NULL
+        ("weights", _ptr), ("ids", _ptr),                     # fp32 / int32 [tokens, top_k], written
+        ("logits_row_stride", _i64),
+        ("tokens", _i64),
+        ("num_experts", _i32), ("top_k", _i32), ("dtype", _i32), ("scoring", _i32), ("renormalize", _i32),
+        ("scale", _f32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaMoeRouteBwdParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_route_bwd_params` (include/fa_mi355.h): fa_moe_route_bwd, dlogits from dweights, the logits and
+    the ids.  struct_size must be set to sizeof(FaMoeRouteBwdParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dweights", _ptr), ("logits", _ptr), ("ids", _ptr),
+        ("dlogits", _ptr),
+        ("logits_row_stride", _i64), ("dlogits_row_stride", _i64),
+        ("tokens", _i64),
+        ("num_experts", _i32), ("top_k", _i32), ("dtype", _i32), ("scoring", _i32), ("renormalize", _i32),
+        ("scale", _f32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaMoeSortParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_sort_params` (include/fa_mi355.h): fa_moe_sort, the stable counting sort of the (token, k) slots
+    by expert.  struct_size must be set to sizeof(FaMoeSortParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("ids", _ptr),
+        ("sorted_slot", _ptr), ("pos", _ptr), ("expert_offsets", _ptr),
+        ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("tokens", _i64),
+        ("num_experts", _i32), ("top_k", _i32), ("align", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaMoePermuteParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_permute_params` (include/fa_mi355.h): fa_moe_permute, the rows of x in sorted order, optionally
+    scaled per slot.  struct_size must be set to sizeof(FaMoePermuteParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("x", _ptr), ("sorted_slot", _ptr), ("slot_scale", _ptr),
+        ("out", _ptr),
+        ("x_row_stride", _i64), ("out_row_stride", _i64),
+        ("rows", _i64), ("tokens", _i64),
+        ("top_k", _i32), ("n", _i32), ("dtype", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaMoeCombineParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_combine_params` (include/fa_mi355.h): fa_moe_combine, the weighted sum of a token's expert rows.
+    struct_size must be set to sizeof(FaMoeCombineParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("y", _ptr), ("weights", _ptr), ("pos", _ptr),
+        ("out", _ptr),
+        ("y_row_stride", _i64), ("out_row_stride", _i64),
+        ("rows", _i64), ("tokens", _i64),
+        ("top_k", _i32), ("n", _i32), ("dtype", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaMoeCombineBwdParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_combine_bwd_params` (include/fa_mi355.h): fa_moe_combine_bwd, dy and dw of fa_moe_combine.
+    struct_size must be set to sizeof(FaMoeCombineBwdParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dout", _ptr), ("y", _ptr), ("weights", _ptr), ("pos", _ptr),
+        ("dy", _ptr), ("dw", _ptr),                            # NULL: skipped
+        ("dout_row_stride", _i64), ("y_row_stride", _i64), ("dy_row_stride", _i64),
+        ("rows", _i64), ("tokens", _i64),
+        ("top_k", _i32), ("n", _i32), ("dtype", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -421,7 +508,11 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size",
            "fa_act_mul", "fa_act_mul_params_size", "fa_act_mul_plan", "fa_act_mul_bwd", "fa_act_mul_bwd_params_size",
            "fa_quant_fp8", "fa_quant_fp8_params_size", "fa_add_norm_quant", "fa_add_norm_quant_params_size",
-           "fa_act_mul_quant", "fa_act_mul_quant_params_size"] + EXT_OPS
+           "fa_act_mul_quant", "fa_act_mul_quant_params_size",
+           "fa_moe_route", "fa_moe_route_params_size", "fa_moe_route_bwd", "fa_moe_route_bwd_params_size",
+           "fa_moe_sort", "fa_moe_sort_params_size", "fa_moe_sort_workspace_bytes", "fa_moe_sort_plan",
+           "fa_moe_permute", "fa_moe_permute_params_size", "fa_moe_combine", "fa_moe_combine_params_size",
+           "fa_moe_combine_bwd", "fa_moe_combine_bwd_params_size"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -443,6 +534,12 @@ ROW_OPS = [
     ("fa_quant_fp8", FaQuantFp8Params, None),
     ("fa_add_norm_quant", FaAddNormQuantParams, None),
     ("fa_act_mul_quant", FaActMulQuantParams, None),
+    ("fa_moe_route", FaMoeRouteParams, None),
+    ("fa_moe_route_bwd", FaMoeRouteBwdParams, None),
+    ("fa_moe_sort", FaMoeSortParams, "fa_moe_sort_workspace_bytes"),
+    ("fa_moe_permute", FaMoePermuteParams, None),
+    ("fa_moe_combine", FaMoeCombineParams, None),
+    ("fa_moe_combine_bwd", FaMoeCombineBwdParams, None),
 ]
 
 
@@ -490,6 +587,8 @@ def _load():
     i64 = ctypes.c_int64
     lib.fa_act_mul_plan.restype = ctypes.c_int
     lib.fa_act_mul_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
+    lib.fa_moe_sort_plan.restype = ctypes.c_int
+    lib.fa_moe_sort_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
     lib.fa_scatter_rows.restype = ctypes.c_int
@@ -570,8 +669,8 @@ def _workspace_query(query):
 call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
-# call_act_mul_quant; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
-# cross_entropy_workspace_bytes
+# call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd;
+# qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes, cross_entropy_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
     if _query:
@@ -592,4 +691,14 @@ def act_mul_plan(rows, n):
     rc = lib.fa_act_mul_plan(rows, n, *(ctypes.byref(o) for o in out))
     if rc != 0:
         raise RuntimeError(f"fa_act_mul_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+    return tuple(o.value for o in out)
+
+
+def moe_sort_plan(slots, num_experts):
+    """fa_moe_sort_plan: (chunk_slots, chunks, workspace_bytes) of fa_moe_sort, a function of (slots = tokens x top_k,
+    num_experts) alone; needs no device"""
+    out = [ctypes.c_int64() for _ in range(3)]
+    rc = lib.fa_moe_sort_plan(slots, num_experts, *(ctypes.byref(o) for o in out))
+    if rc != 0:
+        raise RuntimeError(f"fa_moe_sort_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
     return tuple(o.value for o in out)

@@ -12,7 +12,9 @@ in place, fa_cross_entropy / fa_cross_entropy_bwd; `act_mul` / `act_and_mul` / `
 the gated activation act(gate) * up of the MLP on separate or packed tensors with autograd formulas, its backward and the backward
 in place, fa_act_mul / fa_act_mul_bwd; `quant_fp8` / `add_norm_quant` / `act_mul_quant` / `act_and_mul_quant`: dynamic fp8-e4m3
 quantisation alone and fused behind the forwards of add_norm and act_mul, fa_quant_fp8 / fa_add_norm_quant / fa_act_mul_quant, not
-differentiable - registered, but not listed in `__all__`).
+differentiable; `moe_route` / `moe_route_bwd` / `moe_sort` / `moe_permute` / `moe_combine` / `moe_combine_bwd`: top-k routing, the
+stable sort of the (token, k) slots by expert, the permutation into per-expert segments and the weighted combine of a
+mixture-of-experts block with autograd formulas, fa_moe_* - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -973,3 +975,148 @@ for _op, _names in ((quant_fp8, ("x",)), (add_norm_quant, ("x", "residual", "wei
     _bwd, _setup = _not_differentiable(_op._opoverload._schema.name.split("::")[-1], _names)
     _op.register_autograd(_bwd, setup_context=_setup)
 del _op, _names, _bwd, _setup
+
+
+# ------------------------------------------------------------------------------------------
+# what surrounds the expert GEMMs of a mixture-of-experts block (flash_attn_mi355.moe; csrc/fa_moe.hip).
+# Reached as torch.ops.flash_attn_mi355.moe_route / .moe_route_bwd / .moe_sort / .moe_permute / .moe_combine / .moe_combine_bwd;
+# not in __all__.  All functional; every output shape is known on the host (M_max = T K + E (align - 1)), so every op has a fake
+# implementation and is capturable.  A torch.library return cannot be optional: moe_combine_bwd returns an EMPTY tensor of shape
+# (0,) in the place of a gradient that was not asked for.
+# ------------------------------------------------------------------------------------------
+from . import moe as _moe  # noqa: E402
+
+
+@torch.library.custom_op(f"{_NS}::moe_route", mutates_args=(), device_types="cuda")
+def moe_route(logits: Tensor, k: int, scoring: str, renormalize: bool, bias: Optional[Tensor], scale: float) -> Tuple[Tensor, Tensor]:
+    """moe.moe_route_forward: (weights fp32 [T, k], ids int32 [T, k]).  The weights are differentiable in the logits
+    (moe_route_bwd); ids is not differentiable."""
+    return _moe.moe_route_forward(logits, k, scoring=scoring, renormalize=renormalize, bias=bias, scale=scale)
+
+
+@moe_route.register_fake
+def _(logits, k, scoring, renormalize, bias, scale):
+    return (logits.new_empty((logits.shape[0], k), dtype=torch.float32), logits.new_empty((logits.shape[0], k), dtype=torch.int32))
+
+
+@torch.library.custom_op(f"{_NS}::moe_route_bwd", mutates_args=(), device_types="cuda")
+def moe_route_bwd(dweights: Tensor, logits: Tensor, ids: Tensor, scoring: str, renormalize: bool, bias: Optional[Tensor],
+                  scale: float) -> Tensor:
+    """moe.moe_route_backward: dlogits, a fresh contiguous tensor of the logits' dtype and shape, every element written"""
+    return _moe.moe_route_backward(dweights, logits, ids, scoring=scoring, renormalize=renormalize, bias=bias, scale=scale)
+
+
+@moe_route_bwd.register_fake
+def _(dweights, logits, ids, scoring, renormalize, bias, scale):
+    return logits.new_empty(logits.shape)
+
+
+def _moe_route_setup(ctx, inputs, output):
+    logits, k, scoring, renormalize, bias, scale = inputs
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(output[1])                      # ids
+    ctx.save_for_backward(logits, output[1], bias)
+    ctx.args = (scoring, renormalize, scale)
+
+
+def _moe_route_backward(ctx, dweights, dids):
+    none = (None,) * 5
+    if dweights is None or not ctx.needs_input_grad[0]:
+        return (None,) + none
+    logits, ids, bias = ctx.saved_tensors
+    scoring, renormalize, scale = ctx.args
+    return (moe_route_bwd(dweights.contiguous(), logits, ids, scoring, renormalize, bias, scale),) + none
+
+
+moe_route.register_autograd(_moe_route_backward, setup_context=_moe_route_setup)
+
+
+@torch.library.custom_op(f"{_NS}::moe_sort", mutates_args=(), device_types="cuda")
+def moe_sort(ids: Tensor, num_experts: int, align: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """moe.moe_sort: (sorted_slot int32 [T k + E (align - 1)], pos int32 [T, k], expert_offsets int32 [E + 1])"""
+    return _moe.moe_sort(ids, num_experts, align=align)
+
+
+@moe_sort.register_fake
+def _(ids, num_experts, align):
+    T, K = ids.shape
+    return (ids.new_empty((_moe.sort_max_rows(T, K, num_experts, align),)), ids.new_empty((T, K)), ids.new_empty((num_experts + 1,)))
+
+
+@torch.library.custom_op(f"{_NS}::moe_permute", mutates_args=(), device_types="cuda")
+def moe_permute(x: Tensor, sorted_slot: Tensor, k: int, scale: Optional[Tensor], pos: Optional[Tensor]) -> Tensor:
+    """moe.moe_permute_forward: xp [M_max, N], a fresh contiguous tensor.  Differentiable in x (moe_combine over pos, with the
+    scale - or ones - as weights); pos is only read by the backward."""
+    return _moe.moe_permute_forward(x, sorted_slot, k, scale=scale)
+
+
+@moe_permute.register_fake
+def _(x, sorted_slot, k, scale, pos):
+    return x.new_empty((sorted_slot.shape[0], x.shape[1]))
+
+
+def _moe_permute_setup(ctx, inputs, output):
+    x, sorted_slot, k, scale, pos = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(sorted_slot, scale, pos)
+    ctx.slots = (x.shape[0], k)
+
+
+def _moe_permute_backward(ctx, dxp):
+    if dxp is None or not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    sorted_slot, scale, pos = ctx.saved_tensors
+    T, k = ctx.slots
+    if pos is None:
+        # the inverse of sorted_slot, without a host synchronisation: padding rows (-1) are sent to a spare entry that is cut off
+        idx = torch.where(sorted_slot >= 0, sorted_slot, T * k).long()
+        rows = torch.arange(sorted_slot.shape[0], dtype=torch.int32, device=sorted_slot.device)
+        pos = torch.full((T * k + 1,), -1, dtype=torch.int32, device=sorted_slot.device).scatter_(0, idx, rows)[:T * k].view(T, k)
+    return moe_combine(dxp, scale, pos), None, None, None, None
+
+
+moe_permute.register_autograd(_moe_permute_backward, setup_context=_moe_permute_setup)
+
+
+@torch.library.custom_op(f"{_NS}::moe_combine", mutates_args=(), device_types="cuda")
+def moe_combine(y: Tensor, weights: Optional[Tensor], pos: Tensor) -> Tensor:
+    """moe.moe_combine_forward: out [T, N], a fresh contiguous tensor; weights None: ones.  Differentiable in y and weights
+    (moe_combine_bwd)."""
+    return _moe.moe_combine_forward(y, weights, pos)
+
+
+@moe_combine.register_fake
+def _(y, weights, pos):
+    return y.new_empty((pos.shape[0], y.shape[1]))
+
+
+@torch.library.custom_op(f"{_NS}::moe_combine_bwd", mutates_args=(), device_types="cuda")
+def moe_combine_bwd(dout: Tensor, y: Tensor, weights: Tensor, pos: Tensor, need_dy: bool, need_dw: bool) -> Tuple[Tensor, Tensor]:
+    """moe.moe_combine_backward: (dy [M_max, N], dw fp32 [T, k]); a gradient that is not needed is an empty tensor of shape (0,)"""
+    dy, dw = _moe.moe_combine_backward(dout, y, weights, pos, need_dy=need_dy, need_dw=need_dw)
+    return (y.new_empty((0,)) if dy is None else dy, y.new_empty((0,), dtype=torch.float32) if dw is None else dw)
+
+
+@moe_combine_bwd.register_fake
+def _(dout, y, weights, pos, need_dy, need_dw):
+    return (y.new_empty(y.shape if need_dy else (0,)), y.new_empty(tuple(pos.shape) if need_dw else (0,), dtype=torch.float32))
+
+
+def _moe_combine_setup(ctx, inputs, output):
+    y, weights, pos = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(y, weights, pos)
+
+
+def _moe_combine_backward(ctx, dout):
+    y, weights, pos = ctx.saved_tensors
+    need_dy, need_dw = ctx.needs_input_grad[0], weights is not None and ctx.needs_input_grad[1]
+    if dout is None or not (need_dy or need_dw):
+        return None, None, None
+    if weights is None:                                          # unit weights: dy is the plain permute's scatter form
+        weights = torch.ones(pos.shape, dtype=torch.float32, device=pos.device)
+    dy, dw = moe_combine_bwd(dout.contiguous(), y, weights, pos, need_dy, need_dw)
+    return (dy if need_dy else None), (dw if need_dw else None), None
+
+
+moe_combine.register_autograd(_moe_combine_backward, setup_context=_moe_combine_setup)

@@ -1202,6 +1202,187 @@ int    fa_act_mul_quant(const fa_act_mul_quant_params* s, void* stream);
 size_t fa_act_mul_quant_params_size(void);
 
 /*
+ * fa_moe_* - what surrounds the expert GEMMs of a mixture-of-experts block: top-k routing with its gradient, a stable counting
+ * sort of the (token, k) slots by expert, the permutation of the activations into per-expert segments and the weighted combine
+ * with its backward (additive: fa_params and FA_ABI_VERSION are unchanged).  The GEMMs themselves are not here: they see
+ * contiguous, `align`-padded per-expert segments of `xp` described by expert_offsets.  No entry point synchronises with the host,
+ * every result is a pure function of its inputs (no ordering depends on an atomic), all are capturable in a graph.
+ * Limits, checked before any device work: tokens T >= 0; 2 <= num_experts E <= 512; 1 <= top_k K <= min(E, 16); hidden size n a
+ * multiple of 8 in [8, 16384], fp16 / bf16; T * K + E * (align - 1) <= 2^31 - 1.  Outside them: FA_ERR_UNSUPPORTED.
+ * FA_ERR_INVALID_ARGUMENT: a short struct_size, a NULL required pointer, an unknown dtype / scoring, a negative size or stride,
+ * a row stride below the row's length (rows > 1), a misaligned pointer or stride (below), non-zero reserved fields, a workspace
+ * smaller than the query's answer.
+ *
+ * fa_moe_route: logits [T, E] of `dtype` (FA_FP16, FA_BF16 or FA_FP32), last dimension contiguous, any row stride >= E.  One
+ *   launch, no workspace, no atomics, no LDS.  A row lies 8 columns per lane in G adjacent lanes of a wave (G the smallest power
+ *   of two with 8 G >= E; 64 / G rows per wave).  In fp32, every operation rounding once:
+ *     FA_MOE_SOFTMAX  z_j = float(logit_j), a NaN read as -inf;  selection score c_j = z_j
+ *     FA_MOE_SIGMOID  s_j = rcp(1 + exp2(-float(logit_j) * log2e)) (fa_act_mul's sigmoid: hardware exp2 and reciprocal);
+ *                     c_j = s_j + bias_j (bias fp32 [E] or NULL: c_j = s_j), a NaN read as -inf
+ *     selection       K rounds; round k takes the largest c_j not yet taken, the LOWEST index among equals (-0 == +0).  Slot k
+ *                     holds the k-th winner: the ids of a row are distinct and inside [0, E) whatever the logits hold.
+ *     softmax, renormalize      m = c_{id_0};  e_k = exp2((c_{id_k} - m) * log2e);  S = e_0 + e_1 + .. (ascending k);  w_k = e_k / S
+ *     softmax, !renormalize     m = c_{id_0};  e_j = exp2((z_j - m) * log2e) for every column;  Z = the lane's columns added in
+ *                               column order (absent columns +0), then the xor butterfly over the G lanes (m = 1, 2, ..);  w_k = e_{id_k} / Z
+ *     sigmoid                   w_k = s_{id_k} (without the bias);  renormalize: S = w_0 + w_1 + .. (ascending k), w_k = w_k / S
+ *     last                      w_k = w_k * scale.  The divisions are IEEE divisions.
+ *   The order depends on (E, K, dtype) alone: a row's bits do not depend on T or on the row's index.  Special values follow
+ *   these lines literally: an all -inf (or all-NaN softmax) row has ids 0 .. K - 1 and NaN weights (-inf - -inf); a +inf logit
+ *   under softmax gives NaN weights for the row; a NaN logit under sigmoid loses the selection and, if it is selected all the
+ *   same, has a NaN weight (and a NaN S).  weights: fp32 [T, K], ids: int32 [T, K], both contiguous.
+ * fa_moe_route_bwd: dlogits [T, E] of `dtype` from dweights fp32 [T, K], the logits and the ids; nothing else is saved.  The
+ *   selected scores are recomputed in the forward's order (m, e_k, S / Z, w_k as above), g_k = dweights_k * scale, and
+ *     softmax, !renormalize     D = fma(g_k, p_k, D) ascending k from +0 (p = e / Z);  dl_j = p_j * (([j selected] ? g_j : 0) - D)
+ *     softmax, renormalize      D as above with w;  dl_{id_k} = w_k * (g_k - D);  every other column +0
+ *     sigmoid                   ds_k = g_k, or renormalize: D = fma(dweights_k, w_k, D), ds_k = ((dweights_k - D) * scale) / S;
+ *                               dl_{id_k} = (ds_k * s_k) * (1 - s_k);  every other column +0
+ *   with ONE rounding to `dtype`.  Every element of dlogits is written.  An id outside [0, E) is never used as an address: its
+ *   slot counts as a logit of -inf.  bias does not enter the gradient and is not read.
+ * fa_moe_sort: ids int32 [T * K] (slot s = t * K + k) -> sorted_slot int32 [M_max], pos int32 [T * K], expert_offsets int32
+ *   [E + 1], M_max = T * K + E * (align - 1), 1 <= align <= 256.  Segment e starts at expert_offsets[e], a multiple of align, holds
+ *   the slots with id e in ascending order and is padded with -1 to the next multiple of align; expert_offsets[E] is the padded
+ *   total and everything from there to M_max is -1.  pos[s] is the slot's row, -1 for an id outside [0, E) (dropped: only ever
+ *   compared).  Three launches over a workspace of fa_moe_sort_workspace_bytes (per-chunk expert counts): counts per chunk (LDS
+ *   integer adds of pure counts), an exclusive scan, the placement by rank inside a wave (ballots) - no position comes from an
+ *   atomic.  The plan is a function of (T * K, E) alone: fa_moe_sort_plan.
+ * fa_moe_permute: out[r] = x[sorted_slot[r] / K] for r < rows (= M_max), a bit-exact copy; a row whose sorted_slot is outside
+ *   [0, T * K) - the -1 padding - is +0.  With slot_scale (fp32 [T * K]): out[r] = round(slot_scale[s] * float(x[s / K])).
+ *   sorted_slot NULL: every row is +0.  x, out: 16-byte aligned, row strides multiples of 8.
+ * fa_moe_combine: out[t] = round(sum_k weights[t, k] * float(y[pos[t, k]])), acc = fma(w, y, acc) ascending k from +0, one
+ *   rounding.  A pos outside [0, rows) - the -1 of a dropped slot - is skipped; a token without a live slot is +0.  weights NULL:
+ *   every weight is 1 (the backward of fa_moe_permute).  A gather: no atomics.
+ * fa_moe_combine_bwd: dy[pos[t, k]] = round(weights[t, k] * float(dout[t])) - fa_moe_permute's scaled product, bit for bit - over
+ *   a dy set to +0 first (two launches; the pos of live slots are distinct, as fa_moe_sort leaves them), and
+ *   dw[t, k] = sum_n float(dout[t, n]) * float(y[pos[t, k], n]) in the fixed order of the row sums of fa_add_norm (n <= 256: 8
+ *   columns a lane, fma in column order, xor butterfly; above: 64 ceil(n / 512) <= 256 lanes, a lane's pieces added in ascending
+ *   order, butterfly over the wave, waves added in index order); a dropped slot gets +0.  dy or dw NULL: not computed.
+ */
+typedef enum fa_moe_scoring {
+    FA_MOE_SOFTMAX = 0,
+    FA_MOE_SIGMOID = 1
+} fa_moe_scoring;
+
+typedef struct fa_moe_route_params {
+    size_t         struct_size;      /* sizeof(fa_moe_route_params) as the caller compiled it */
+    const void*    logits;           /* [tokens, num_experts] of `dtype` */
+    const void*    bias;             /* fp32 [num_experts]; NULL: none.  FA_MOE_SIGMOID only */
+    void*          weights;          /* fp32 [tokens, top_k], written */
+    void*          ids;              /* int32 [tokens, top_k], written */
+    int64_t        logits_row_stride;/* elements */
+    int64_t        tokens;
+    int32_t        num_experts, top_k;
+    int32_t        dtype;            /* FA_FP16, FA_BF16 or FA_FP32 */
+    int32_t        scoring;          /* fa_moe_scoring */
+    int32_t        renormalize;      /* 0 / 1 */
+    float          scale;            /* finite */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_route_params;
+
+int    fa_moe_route(const fa_moe_route_params* s, void* stream);
+size_t fa_moe_route_params_size(void);
+
+typedef struct fa_moe_route_bwd_params {
+    size_t         struct_size;      /* sizeof(fa_moe_route_bwd_params) as the caller compiled it */
+    const void*    dweights;         /* fp32 [tokens, top_k] */
+    const void*    logits;           /* the forward's */
+    const void*    ids;              /* the forward's */
+    void*          dlogits;          /* [tokens, num_experts] of `dtype`, every element written */
+    int64_t        logits_row_stride, dlogits_row_stride;   /* elements */
+    int64_t        tokens;
+    int32_t        num_experts, top_k;
+    int32_t        dtype;
+    int32_t        scoring;
+    int32_t        renormalize;
+    float          scale;
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_route_bwd_params;
+
+int    fa_moe_route_bwd(const fa_moe_route_bwd_params* s, void* stream);
+size_t fa_moe_route_bwd_params_size(void);
+
+typedef struct fa_moe_sort_params {
+    size_t         struct_size;      /* sizeof(fa_moe_sort_params) as the caller compiled it */
+    const void*    ids;              /* int32 [tokens * top_k] */
+    void*          sorted_slot;      /* int32 [tokens * top_k + num_experts * (align - 1)] */
+    void*          pos;              /* int32 [tokens * top_k] */
+    void*          expert_offsets;   /* int32 [num_experts + 1] */
+    void*          workspace;        /* fa_moe_sort_workspace_bytes, 4-byte aligned */
+    size_t         workspace_bytes;
+    int64_t        tokens;
+    int32_t        num_experts, top_k;
+    int32_t        align;            /* 1 .. 256 */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_sort_params;
+
+int    fa_moe_sort(const fa_moe_sort_params* s, void* stream);
+size_t fa_moe_sort_params_size(void);
+size_t fa_moe_sort_workspace_bytes(const fa_moe_sort_params* s);   /* a function of (tokens * top_k, num_experts); no device */
+/* the launch plan, a function of (slots = T * K, num_experts) alone; needs no device.  chunk_slots: the slots one wave counts and
+ * places (a multiple of 64), chunks = max(1, ceil(slots / chunk_slots)) <= 1024, workspace_bytes = 4 * chunks * num_experts.
+ * Each output pointer may be NULL. */
+int    fa_moe_sort_plan(int64_t slots, int32_t num_experts, int64_t* chunk_slots, int64_t* chunks, int64_t* workspace_bytes);
+
+typedef struct fa_moe_permute_params {
+    size_t         struct_size;      /* sizeof(fa_moe_permute_params) as the caller compiled it */
+    const void*    x;                /* [tokens, n] of `dtype` */
+    const void*    sorted_slot;      /* int32 [rows]; NULL: every row +0 */
+    const void*    slot_scale;       /* fp32 [tokens * top_k]; NULL: a copy */
+    void*          out;              /* [rows, n] of `dtype` */
+    int64_t        x_row_stride, out_row_stride;   /* elements, multiples of 8 */
+    int64_t        rows;             /* M_max */
+    int64_t        tokens;
+    int32_t        top_k;
+    int32_t        n;
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_permute_params;
+
+int    fa_moe_permute(const fa_moe_permute_params* s, void* stream);
+size_t fa_moe_permute_params_size(void);
+
+typedef struct fa_moe_combine_params {
+    size_t         struct_size;      /* sizeof(fa_moe_combine_params) as the caller compiled it */
+    const void*    y;                /* [rows, n] of `dtype` */
+    const void*    weights;          /* fp32 [tokens, top_k]; NULL: ones */
+    const void*    pos;              /* int32 [tokens, top_k] */
+    void*          out;              /* [tokens, n] of `dtype` */
+    int64_t        y_row_stride, out_row_stride;   /* elements, multiples of 8 */
+    int64_t        rows;
+    int64_t        tokens;
+    int32_t        top_k;
+    int32_t        n;
+    int32_t        dtype;
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_combine_params;
+
+int    fa_moe_combine(const fa_moe_combine_params* s, void* stream);
+size_t fa_moe_combine_params_size(void);
+
+typedef struct fa_moe_combine_bwd_params {
+    size_t         struct_size;      /* sizeof(fa_moe_combine_bwd_params) as the caller compiled it */
+    const void*    dout;             /* [tokens, n] of `dtype` */
+    const void*    y;                /* [rows, n]; read for dw only (may be NULL where dw is) */
+    const void*    weights;          /* fp32 [tokens, top_k]; read for dy only (may be NULL where dy is) */
+    const void*    pos;              /* int32 [tokens, top_k] */
+    void*          dy;               /* [rows, n] of `dtype`; NULL: skipped */
+    void*          dw;               /* fp32 [tokens, top_k]; NULL: skipped */
+    int64_t        dout_row_stride, y_row_stride, dy_row_stride;   /* elements, multiples of 8 */
+    int64_t        rows;
+    int64_t        tokens;
+    int32_t        top_k;
+    int32_t        n;
+    int32_t        dtype;
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_combine_bwd_params;
+
+int    fa_moe_combine_bwd(const fa_moe_combine_bwd_params* s, void* stream);
+size_t fa_moe_combine_bwd_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
