@@ -10,18 +10,32 @@
     the wider (bf16) gates - which covers fp16's.  Pair mistakes go into the backward's P (the forward has its LSE),
     decoy and poison mistakes into the forward;
   * the gap: the same kind of mistake on N(0, 1) inputs at S 1300, D 128 stays below the bf16 gates in the backward;
+    so does a sink forgotten in the backward's P of 32 rows (0.01 - 0.38 x the gate in 6 draws), while a V row taken
+    from the neighbouring tree column does NOT hide on random data (2.5 - 8.2 x the bf16 out gate): see
+    test_random_inputs_hide_a_forgotten_sink_and_a_misplaced_v_row;
+  * sinks, tree masks, shared prefix and the further kv-cache routes (the second half of this file): the same design
+    checks on the exact score matrix (targets 3 U, any other key 2 U at most), and as mistakes the sink dropped or counted
+    twice (in the backward's P for the dense and varlen cases, in the forward elsewhere), a tree bit lost or gained - each
+    of columns 31, 32 and 63 on its own -, V of a tree column taken from the neighbouring slot with K right, one
+    sequence merged with the weights of its neighbour, and a poisoned row seen (stale, left pad, spare page, unreferenced
+    batch row: one poison); in all rows of a batch entry (a 32-row band for the backward) and in one single row;
   * oracle timing: measured here per call, forward / backward: dense 1300 x 1300 with 4 heads 0.20 / 0.28 s, the very
     first call of the run 0.48 / 0.60 s (the largest), varlen 0.05 / 0.06 s, kv-cache 0.08 s (64 heads).  The bound is 60
-    unit calls (one 650 x 650 head forward, 0.09 s here, timed in the same run) per oracle call.
+    unit calls (one 650 x 650 head forward, 0.09 s here, timed in the same run) per oracle call.  The new references:
+    sinks dense 520 x 520 with 4 heads 0.03 / 0.08 s, sinks varlen 0.05 / 0.07 s, the T_q 130 kv-cache call with 64 heads
+    0.38 s, shared prefix 0.08 s, tree_ref.ref_tree at most 1.2 s (12 unit calls: T 32, 16 heads, 1032 keys).
 """
 import time
 
 import numpy as np
 import pytest
+import torch
 
 import oracle
+import tree_ref
 import witness as w
-from util import LSE_ATOL, TOL_MAXREL, rand16
+from sink_ref import ref_dense, ref_varlen
+from util import LSE_ATOL, LSE_ATOL_FP8, TOL_MAXREL, rand16
 
 FACTOR = 10.0                                                 # a mistake must exceed the GPU test's gate this many times
 GATE = {"out": TOL_MAXREL["bf16"] * 1.0, "grad": TOL_MAXREL["bf16"] * 2.0}     # the wider of the two dtypes' gates
@@ -41,9 +55,16 @@ def unit():
 
 
 def _timed(fn, unit, what, budget=60):
+    """fn() within `budget` unit calls.  The unit is a best of three; a single sample of fn against it fails now and then
+    on a busy machine (seen: 3.0 s for a backward that takes 0.05 s, at a unit of 0.007 s).  The references are pure
+    functions, so a call over the budget is timed once more and the better of the two counts - same budget, same unit."""
     t = time.perf_counter()
     r = fn()
     dt = time.perf_counter() - t
+    if dt > max(budget * unit, 0.05):
+        t = time.perf_counter()
+        r = fn()
+        dt = min(dt, time.perf_counter() - t)
     assert dt <= max(budget * unit, 0.05), f"{what}: the oracle took {dt:.2f} s, {dt / unit:.0f} unit calls"
     return r
 
@@ -235,6 +256,342 @@ def test_random_inputs_hide_the_same_mistake_from_the_bf16_gates(capsys):
         print("\n" + "\n".join(lines))
     assert hidden > draws // 2, f"the bf16 gates caught the mistake in {draws - hidden} of {draws} draws: no gap"
     assert seen16 > draws // 2
+
+
+# ------------------------------------------------------------------------------------------------ sinks
+# The sink is the fp32 value of 3 U scale; at D 128 that is up to half an fp32 ulp of 67.9 (3.8e-6 nats) off the targets'
+# exact score, which moves the shares by 1.3e-6 of themselves: the identities hold to that, not to the 2e-6 of values
+# near 4 that the sink-free pair rows reach.
+SINK_RESID = 1e-5
+F32_LSE = 1e-5                                                # the oracle returns its LSE in fp32: half an ulp at 128 is 7.6e-6
+
+
+def _tie_head(c):
+    """the head the mistakes go into: the last one whose sink ties with the targets (the last head without sinks)"""
+    if c.sinks is None:
+        return c.hq - 1
+    return max(h for h in range(c.hq) if c.sinks[h] == w.sink_tie(c.D))
+
+
+def _grad_factors(g1, g0):
+    """change of (dq, dk, dv, dsinks) relative to max |ref| of each, in units of the gradient gate"""
+    return [_rel(x1, x0, max(np.abs(x0).max(), 1e-30)) / GATE["grad"] for x1, x0 in zip(g1, g0)]
+
+
+def _sink_backward_mistakes(c, o, lse, g, rowsets, say):
+    """the backward's P drops the sink / counts it twice in each row set: the band must reach FACTOR on one of dq, dk, dv,
+    dsinks; what it does to each is printed"""
+    for where, rows in rowsets:
+        for kind in ("drop", "twice"):
+            f = _grad_factors(c.backward(o, lse, "bf16", rows, kind), g)
+            say(f"  sink {kind} in {where}: dq {f[0]:.1f} dk {f[1]:.1f} dv {f[2]:.1f} dsinks {f[3]:.1f} x the bf16 gradient gate")
+            assert max(f) >= FACTOR, f"sink {kind} in {where}: only {max(f):.1f} x the gradient gates"
+
+
+@pytest.mark.parametrize("cid", [c[0] for c in w.SINK_DENSE_CASES])
+def test_sink_dense_case_is_decisive(cid, unit, capsys):
+    """Measured here, in units of the bf16 gradient gate: the sink dropped from the backward's P in a 32-row band of one tie
+    head / in one single row (counted twice: half of each figure) -
+      300 x 520 D 128 window random   band dq 33.8 dk 13.9 dv 16.5 dsinks  2.9   row dq 31.3
+      400 x 400 D 64 causal random    band dq 33.0 dk  4.5 dv  7.9 dsinks  3.4   row dq 29.8
+      520 x 300 D 64 causal random    band dq 32.8 dk  5.3 dv  6.8 dsinks  4.4   row dq 28.8
+      300 x 520 D 256 window random   band dq 34.6 dk 12.9 dv 13.2 dsinks 59.7   row dq 32.0
+      520 x 520 D 128 window random   band dq 34.0 dk 10.7 dv 10.9 dsinks  7.1   row dq 33.6
+    dq is decisive everywhere, a single row included; dk and dv for a band under a window.  dsinks itself is NOT decisive
+    on this data: it is -sum_i exp(s - LSE_i) D_i over every row of a head with D_i of either sign, so a band that
+    forgets the sink moves it by anything from 2.9 to 60 x its gate, a single row by 0.8 - 4.8 x, and even a whole head
+    without the sink by 8 - 71 x.  dsinks is held to the reference by its gate; the localised mistakes are caught by dq.
+    With `tiles` targets (400 x 400, D 64, causal) the band moved dq by 2.4 x only: that case was replaced by `random`."""
+    kw = next(c[2] for c in w.SINK_DENSE_CASES if c[0] == cid)
+    c = w.SinkDense(**kw)
+    pairs, bad = c.design()
+    assert bad == 0 and pairs > 0, f"{bad} of {pairs} pair rows miss the tie or the one-unit margin"
+    o, lse = _timed(c.forward, unit, "forward")
+    g = _timed(lambda: c.backward(o, lse, "bf16"), unit, "backward")          # (asserts the gradient cap)
+    assert np.abs(g[3]).max() < w.GRAD_CAP
+    # the identities: (V_a + V_b) / 3 or V_a / 2 on tie heads, a row without keys gives out 0 and LSE = s_h
+    assert np.abs(o - c.pair_out()).max() < SINK_RESID
+    nokey = c.vis.sum(axis=1) == 0
+    assert not o[:, :, nokey].any() and np.array_equal(lse[:, :, nokey], np.broadcast_to(c.sinks[None, :, None], lse[:, :, nokey].shape))
+    # a sink of -inf is the no-sink oracle, a sink 16 nats behind changes nothing
+    o0, l0 = w.Dense.forward(c)
+    shares = w.sink_shares(c.sinks, c.D, c.a, c.b)
+    for h in range(c.hq):
+        if c.sinks[h] != w.sink_tie(c.D):
+            assert np.abs(o[:, h] - o0[:, h]).max() < 1e-6 and (shares[:, h] == 1.0).all()
+            key = ~nokey
+            assert np.abs(lse[:, h][:, key] - l0[:, h][:, key]).max() < F32_LSE
+    assert sorted(set(np.round(shares.reshape(-1), 6))) in ([0.5, 0.666667, 1.0], [0.666667, 1.0])
+    # the backward used as the reference is ref_dense's autograd (on the exact O)
+    qt, kt, vt, dot, st = c.torch_inputs()
+    for x in (qt, kt, vt, st):
+        x.requires_grad_(True)
+    ot, _ = ref_dense(qt, kt, vt, st, c.scale, causal=c.causal, window=c.window)
+    auto = torch.autograd.grad(ot, (qt, kt, vt, st), dot)
+    mine = c.backward(o, lse, None)
+    for name, x, y in zip(("dq", "dk", "dv"), mine, auto):
+        assert _rel(x, y.numpy().transpose(0, 2, 1, 3), np.abs(x).max()) < 1e-9, name
+    assert _rel(mine[3], auto[3].numpy(), np.abs(mine[3]).max()) < 1e-9, "dsinks"
+    # sensitivity
+    h = _tie_head(c)
+    band, row = w._rows(c.b[0, h] >= 0)
+    sets = []
+    for where, r in (("band", band), ("row", row)):
+        m = np.zeros(lse.shape, dtype=bool)
+        m[0, h, r] = True
+        sets.append((f"{where}{r[0]}", m))
+    whole = np.zeros(lse.shape, dtype=bool)
+    whole[:, h] = True
+    with capsys.disabled():
+        print(f"\n{cid}")
+        _sink_backward_mistakes(c, o, lse, g, sets, print)
+        f = _grad_factors(c.backward(o, lse, "bf16", whole, "drop"), g)
+        print(f"  sink drop in the whole head: dsinks {f[3]:.1f} x")
+
+
+@pytest.mark.parametrize("cid,kw", w.SINK_VARLEN_CASES, ids=[c[0] for c in w.SINK_VARLEN_CASES])
+def test_sink_varlen_case_is_decisive(cid, kw, unit, capsys):
+    c = w.SinkVarlen(**kw)
+    pairs, bad = c.design()
+    assert bad == 0, f"{bad} of {pairs} pair rows miss the tie or the one-unit margin"
+    o, lse = _timed(c.forward, unit, "forward")
+    assert np.abs(o).max() < 8.0, "a poisoned row reached the reference"
+    a, b = c.targets()
+    h = _tie_head(c)
+    s = int(np.argmax(c.lens_q))
+    q0 = int(c.cu_q[s])
+    band, row = w._rows(b[h, q0:q0 + c.lens_q[s]] >= 0)
+    if c.page:                                                # forward only: out and the LSE see the sink
+        for r in (band, row):
+            o1, l1 = w.sink_mistake(o[q0:, h], lse[h, q0:], c.sinks[h], r, "drop")
+            o2, l2 = w.sink_mistake(o[q0:, h], lse[h, q0:], c.sinks[h], r, "twice")
+            for x, y in ((o1, l1), (o2, l2)):
+                assert _fwd_factor(x, y, o[q0:, h], lse[h, q0:], np.abs(o).max(), w.lse_atol(lse)) >= FACTOR
+        return
+    assert np.abs(o - c.pair_out()).max() < SINK_RESID
+    g = _timed(lambda: c.backward(o, lse, "bf16"), unit, "backward")
+    ts = [torch.from_numpy(x).requires_grad_(True) for x in (c.q, c.k, c.v, c.sinks)]
+    ot, lt = ref_varlen(*ts[:3], c.cu_q.tolist(), c.cu_k.tolist(), ts[3], c.scale, causal=True)
+    assert np.abs(ot.detach().numpy() - o).max() < SINK_RESID and np.abs(lt.detach().numpy() - lse).max() < F32_LSE
+    auto = torch.autograd.grad(ot, ts, torch.from_numpy(c.do))
+    for name, x, y in zip(("dq", "dk", "dv", "dsinks"), c.backward(o, lse, None), auto):       # (P from the oracle's fp32 LSE)
+        assert _rel(x, y.numpy(), np.abs(x).max()) < SINK_RESID, name
+    sets = []
+    for where, r in (("band", band), ("row", row)):
+        m = np.zeros(lse.shape, dtype=bool)
+        m[h, q0 + r] = True
+        sets.append((f"{where}{r[0]}", m))
+    with capsys.disabled():
+        print(f"\n{cid}")
+        _sink_backward_mistakes(c, o, lse, g, sets, print)
+
+
+# ------------------------------------------------------------------------------------------------ kv-cache: sinks, routes
+def _kv_gates(c, lse):
+    """(out gate, LSE gate) of the GPU test: fp8 caches 1.5 x and LSE_ATOL_FP8, both grown with the fp32 ulp"""
+    return GATE["out"] * (1.5 if c.fp8 else 1.0), w.lse_atol(lse, LSE_ATOL_FP8 if c.fp8 else LSE_ATOL)
+
+
+def _factor(o1, l1, o0, l0, otop, gates):
+    return max(_rel(o1, o0, otop) / gates[0], w.lse_ratio(l1, l0, gates[1]))
+
+
+def _cache_case_is_decisive(c, o, lse, kc, vc, sks):
+    """For every sequence of a cache case (KVCache, Tree rows under their own mask, SharedPrefix suffixes): one row, then
+    all rows (T < 32), of the tie head lose a target / see a poisoned row / drop or double the sink."""
+    gates = _kv_gates(c, lse)
+    kp, vp = _poison(c.D)
+    h, grp = _tie_head(c), c.hq // c.hk
+    sink = None if c.sinks is None else c.sinks[h]
+    otop = np.abs(o).max()
+    for s in range(c.B):
+        vis = c.vis[s]
+        T = vis.shape[0]
+        kk, vv = (x[:, h // grp] for x in w.gather_cache(c, s, kc, vc, sks[s]))
+        pre = getattr(c, "S_p", 0)
+        if pre:
+            kk, vv = np.concatenate([c.pk[:, h // grp], kk]), np.concatenate([c.pv[:, h // grp], vv])
+        qq = c.q[s, :, h]
+        o0, l0 = w.masked_forward(qq, kk, vv, vis, c.scale, sink)
+        assert np.abs(o0 - o[s, :, h]).max() < (1e-9 if sink is None else SINK_RESID) and w.lse_ratio(l0, lse[s, h], F32_LSE) <= 1.0
+        a, b = c.a[s], c.b[s]
+        decoy = getattr(c, "variant", "edges") == "decoy"
+        for rows in (np.arange(T), np.array([T - 1]), np.array([T // 2])):
+            bad = vis.copy()
+            for t, x, y in zip(rows, a[rows], b[rows]):       # pair rows lose their later target, decoy rows gain both decoys
+                for j in ((x, y) if decoy else (y if y >= 0 else x,)):
+                    if j >= 0:
+                        bad[t, j] = decoy
+            if not np.array_equal(bad, vis):
+                f = _factor(*w.masked_forward(qq, kk, vv, bad, c.scale, sink), o0, l0, otop, gates)
+                assert f >= FACTOR, f"sequence {s}, rows {rows}: a wrong mask bit moves out / LSE by {f:.1f} x the gates only"
+            o1, l1 = w.with_sink(*w.leak_forward(qq, kk, vv, vis, c.scale, rows, kp, vp), sink)
+            f = _factor(o1, l1, o0, l0, otop, gates)
+            assert f >= FACTOR, f"sequence {s}, rows {rows}: a poisoned row seen moves out / LSE by {f:.1f} x the gates only"
+            live = rows[l0[rows] > sink + 0.1] if sink is not None else rows[:0]     # (rows whose keys weigh against the sink)
+            if live.size:
+                for kind in ("drop", "twice"):
+                    f = _factor(*w.sink_mistake(o0, l0, sink, live, kind), o0, l0, otop, gates)
+                    assert f >= FACTOR, f"sequence {s}, rows {rows}: sink {kind} moves out / LSE by {f:.1f} x the gates only"
+
+
+@pytest.mark.parametrize("cid,kw", [c[:2] for c in w.SINK_KVCACHE_CASES + w.ROUTE_CASES],
+                         ids=[c[0] for c in w.SINK_KVCACHE_CASES + w.ROUTE_CASES])
+def test_kvcache_sink_and_route_case_is_decisive(cid, kw, unit):
+    c = w.KVCache(**kw)
+    pairs, bad = c.design()
+    assert bad == 0 and pairs > 0, f"{bad} of {pairs} pair rows miss the tie or the one-unit margin"
+    o, lse, kc, vc = _timed(c.forward, unit, "forward")
+    assert np.abs(o).max() < 8.0, "a poisoned row reached the reference"
+    _cache_case_is_decisive(c, o, lse, kc, vc, [v.shape[1] for v in c.vis])
+    kp, vp = _poison(c.D)
+    kd, vd = c.kd or 1.0, c.vd or 1.0
+    if c.bidx is not None:                                    # the unreferenced batch rows hold poison, before and after
+        for r in set(range(kc.shape[0])) - set(c.bidx.tolist()):
+            assert (kc[r] * kd == kp).all() and (vc[r] * vd == vp).all()
+    if c.sinks is not None:                                   # the sink carries 1/3 of a pair row, 1/2 of a one-target row
+        sh = w.sink_shares(c.sinks, c.D, *(np.broadcast_to(np.stack(x)[:, None, :], lse.shape) for x in (c.a, c.b)))
+        assert set(np.round(sh[:, _tie_head(c)].reshape(-1), 6)) <= {0.5, 0.666667}
+    if not c.append:                                          # k=None: the call leaves the caches as they are
+        assert np.array_equal(kc, c.kc) and np.array_equal(vc, c.vc)
+
+
+# ------------------------------------------------------------------------------------------------ tree masks
+@pytest.mark.parametrize("cid,kw,splits", w.TREE_CASES, ids=[c[0] for c in w.TREE_CASES])
+def test_tree_case_is_decisive(cid, kw, splits, unit):
+    """Besides the mistakes of every cache case (a tree target's bit lost, both decoy bits gained, poison, sinks): each bit
+    at a word boundary on its own - column 31, 32, 63 lost by the row that owns it, gained by the row before it -, and V
+    of a tree column taken from the neighbouring slot while K is right, which only `out` can see."""
+    c = w.Tree(**kw)
+    pairs, bad = c.design()
+    assert bad == 0, f"{bad} rows miss the design ({pairs} pair rows)"
+    o, lse, kc, vc = _timed(lambda: c.forward(mask=c.mask), unit, "forward")      # (with a mask: not the memoised result)
+    assert np.abs(o).max() < 8.0, "a poisoned row reached the reference"
+    assert (c.variant == "decoy") == (pairs == 0)
+    _cache_case_is_decisive(c, o, lse, kc, vc, [v.shape[1] for v in c.vis])
+    gates = _kv_gates(c, lse)
+    otop = np.abs(o).max()
+    h = _tie_head(c)
+    s = c.B - 1
+    L = int(c.seqlens[s])
+    for col in (31, 32, 63):
+        if col >= c.T:
+            continue
+        if c.variant == "own":                                # row `col` loses its own bit, and nothing else changes
+            t = col
+            assert c.b[s][t] == L + col
+        elif c.variant == "decoy":                            # row col - 1 gains bit `col`
+            t = col - 1
+            assert c.b[s][t] == L + col and not c.mask[s, t, col]
+        else:
+            continue
+        m = c.mask.copy()
+        m[s, t, col] = c.variant == "decoy"
+        o1, l1 = c.forward(mask=m)[:2]
+        keep = np.ones(c.T, dtype=bool)
+        keep[t] = False
+        assert np.array_equal(o1[s, keep], o[s, keep])
+        f = _factor(o1[s, t, h], l1[s, h, t], o[s, t, h], lse[s, h, t], otop, gates)
+        assert f >= FACTOR, f"bit {col} of row {t}: {f:.1f} x the gates only"
+    if c.T >= 33 and c.variant == "decoy":
+        assert c.a[s][32] == L + 31, "column 31 is the decoy of row 32 (its parent is 30)"
+    if c.T == 64 and c.variant == "root":
+        assert c.mask[s, 63, 31] and not c.mask[s, 63, 62]
+    if c.variant != "decoy":                                  # V of the row's tree target read one slot further on
+        for t in sorted({c.T - 1, min(31, c.T - 2)}):
+            col = int(c.b[s][t]) - L
+            other = col + 1 if col + 1 < c.T else col - 1
+            v2 = vc.copy()
+            v2[c.slot(s, L + col)], v2[c.slot(s, L + other)] = vc[c.slot(s, L + other)], vc[c.slot(s, L + col)]
+            o1, l1 = c.forward(caches=(kc, v2))[:2]
+            assert np.array_equal(l1, lse)
+            f = _rel(o1[s, t, h], o[s, t, h], otop) / gates[0]
+            assert f >= FACTOR, f"V of column {col} from slot {other}, row {t}: out moves by {f:.1f} x its gate only"
+
+
+# ------------------------------------------------------------------------------------------------ shared prefix
+@pytest.mark.parametrize("cid,kw", w.PREFIX_CASES, ids=[c[0] for c in w.PREFIX_CASES])
+def test_shared_prefix_case_is_decisive(cid, kw, unit):
+    c = w.SharedPrefix(**kw)
+    pairs, bad = c.design()
+    assert bad == 0, f"{bad} of {pairs} pair rows miss the tie or the one-unit margin"
+    o, lse = _timed(c.forward, unit, "forward")
+    assert np.abs(o).max() < 8.0, "a poisoned row reached the reference"
+    if c.variant != "decoy":
+        assert np.abs(o - c.pair_out()).max() < SINK_RESID
+    kc, vc = c.after()
+    _cache_case_is_decisive(c, o, lse, kc, vc, [v.shape[1] - c.S_p for v in c.vis])
+    # the reference is the merge of the two passes the operator makes
+    o_p, l_p, o_s, l_s = c.forward(parts=True)
+    om, lm = w.merge_states(o_p, l_p, o_s, l_s)
+    assert np.abs(om - o).max() < F32_LSE and w.lse_ratio(lm, lse, 2 * F32_LSE) <= 1.0
+    if not c.append:
+        assert np.isneginf(l_s[0]).all() and np.array_equal(om[0], o_p[0])
+    if c.variant == "split":                                  # weights 1/2, 1/2 (tie sink: 1/3 prefix, 2/3 suffix with its sink)
+        want = 0.5 if c.sinks is None else np.where(c.sinks == w.sink_tie(c.D), 1 / 3, 0.5)[None, :, None]
+        assert np.abs(np.exp(l_p - lm) - want).max() < 1e-5
+    if c.variant != "mixed":
+        return
+    # one sequence merged with the weights of its neighbour: both partial LSEs stay right, only `out` can tell
+    gates = _kv_gates(c, lse)
+    h = _tie_head(c)
+    for s in range(c.B):
+        n = (s + 1) % c.B
+        for rows in (np.arange(c.T), np.array([c.T - 1])):
+            ob = w.merge_states(o_p[s], l_p[n], o_s[s], l_s[n])[0]
+            f = _rel(ob[rows, h], o[s][rows, h], np.abs(o).max()) / gates[0]
+            assert f >= FACTOR, f"sequence {s} merged with the weights of {n}, rows {rows}: {f:.1f} x the out gate only"
+
+
+# ------------------------------------------------------------------------------------------------ the gap, again
+def test_random_inputs_hide_a_forgotten_sink_and_a_misplaced_v_row(capsys):
+    """The two mistakes the LSE cannot see, on N(0, 1) bf16 inputs, 6 draws each (max error / max |ref|):
+      * S 520, D 128, causal, one head, sink N(0, 1): the backward's P forgets the sink in rows 256..287.  Measured here:
+        dq 1.0e-4 .. 4.6e-3, dk 5.1e-5 .. 5.3e-3, dv 3.7e-5 .. 3.8e-3 - 0.01 to 0.38 x the bf16 gradient gate (1.4e-2):
+        HIDDEN in 6 draws of 6.  The witness cases answer it with 29 x that gate or more, in a single row.
+      * a tree call, T 33 behind 500 cached keys, D 128: V of tree column 32 is read from slot 31.  Measured here: out
+        1.7e-2 .. 5.7e-2, 2.5 to 8.2 x the bf16 out gate (7e-3), 17 to 57 x the fp16 one: NOT hidden in any draw.  The row
+        that owns the column gives it a weight of several per cent, and its out is small next to max |V|.  So the claim
+        that random data hides a misplaced V row is dropped; what random data cannot do is tell WHICH row and column
+        went wrong, and the LSE gate cannot see it in any dtype.
+    Only the directions measured are asserted."""
+    S, D, draws = 520, 128, 6
+    lines, hidden_sink, hidden_v = [], 0, 0
+    rows = np.zeros((1, 1, S), dtype=bool)
+    rows[..., 256:288] = True
+    for d in range(draws):
+        q, k, v, do = (rand16((1, 1, S, D), "bf16", 300 * d + i, device="cpu").double().numpy() for i in range(4))
+        sink = np.array([float(rand16((1,), "bf16", 300 * d + 9, device="cpu")[0])])
+        t = lambda x: torch.from_numpy(np.ascontiguousarray(x.transpose(0, 2, 1, 3)))
+        o, lse = ref_dense(t(q), t(k), t(v), torch.from_numpy(sink), D ** -0.5, causal=True)
+        o, lse = o.numpy().transpose(0, 2, 1, 3), lse.numpy()
+        o16 = oracle.round_to(o, "bf16")
+        g = []
+        for kind in (None, "drop"):
+            lp, ds = w.sink_grads(do, o16, lse, sink, 1, rows, kind)
+            g.append(oracle.attn_bwd(do, q, k, v, o16, lp, D ** -0.5, causal=True)[:3] + (ds,))
+        e = [_rel(x1, x0, np.abs(x0).max()) for x1, x0 in zip(g[1], g[0])]
+        hidden_sink += max(e[:3]) <= 2 * TOL_MAXREL["bf16"]
+        lines.append(f"sink draw {d}: dq {e[0]:.1e} dk {e[1]:.1e} dv {e[2]:.1e} dsinks {e[3]:.1e}  "
+                     f"({max(e[:3]) / (2 * TOL_MAXREL['bf16']):.2f} x the bf16 gate)")
+    T, L, H = 33, 500, 2
+    for d in range(draws):
+        rng = np.random.default_rng(d)
+        q = rand16((1, T, H, D), "bf16", 700 * d, device="cpu").double().numpy()
+        kc, vc = (rand16((1, L + T, H, D), "bf16", 700 * d + i, device="cpu").double().numpy() for i in (1, 2))
+        mask = tree_ref.mask_from_parents(w.tree_parents(T, rng))
+        o0 = tree_ref.ref_tree(q, kc, vc, mask, cache_seqlens=np.array([L + T]))[0]
+        v2 = vc.copy()
+        v2[0, L + 32] = vc[0, L + 31]
+        o1 = tree_ref.ref_tree(q, kc, v2, mask, cache_seqlens=np.array([L + T]))[0]
+        e = _rel(o1, o0, np.abs(o0).max())
+        hidden_v += e <= TOL_MAXREL["bf16"]
+        lines.append(f"tree draw {d}: out {e:.1e}  ({e / TOL_MAXREL['bf16']:.2f} x the bf16 gate, {e / TOL_MAXREL['fp16']:.1f} x the fp16 gate)")
+    with capsys.disabled():
+        print("\n" + "\n".join(lines))
+        print(f"hidden from the bf16 gates: the forgotten sink in {hidden_sink} of {draws} draws, the misplaced V row in {hidden_v} of {draws}")
+    assert hidden_sink > draws // 2, f"the bf16 gates caught the forgotten sink in {draws - hidden_sink} of {draws} draws: no gap"
+    assert hidden_v < draws // 2, "the misplaced V row is hidden on random data after all: record it"
 
 
 def test_lse_gate_follows_the_fp32_ulp():
