@@ -48,6 +48,9 @@ void launch_cross_entropy_bwd(const fa_cross_entropy_bwd_params& s, hipStream_t 
 size_t cross_entropy_workspace_bytes(int64_t rows, int vocab, int dtype);                    // the chunk partials of its launch plan
 int64_t ce_nchunks(int vocab, int dtype);                                                    // forward / backward workgroups per row
 int64_t ce_bwd_nchunks(int vocab);
+void launch_sample(const fa_sample_params& s, hipStream_t stream);                           // fa_sample.hip: temperature / top-k / min-p / top-p token sampling
+size_t sample_workspace_bytes(int64_t rows, int vocab, int dtype);                           // the per-row records, bins and partials of its split plan
+int64_t sample_chunks_per_row(int vocab);                                                    // workgroups per row of its launch plan
 void launch_act_mul(const fa_act_mul_params& s, hipStream_t stream);                         // fa_act_mul.hip: act(gate) * up, element-wise
 void launch_act_mul_bwd(const fa_act_mul_bwd_params& s, hipStream_t stream);                 // its backward (dgate, dup)
 struct ActPlan { int chunk_pieces; int64_t nchunks, items; int grid; };                      // its launch plan: runs per row, items, grid
@@ -229,6 +232,7 @@ size_t fa_add_norm_params_size(void) { return sizeof(fa_add_norm_params); }
 size_t fa_add_norm_bwd_params_size(void) { return sizeof(fa_add_norm_bwd_params); }
 size_t fa_cross_entropy_params_size(void) { return sizeof(fa_cross_entropy_params); }
 size_t fa_cross_entropy_bwd_params_size(void) { return sizeof(fa_cross_entropy_bwd_params); }
+size_t fa_sample_params_size(void) { return sizeof(fa_sample_params); }
 size_t fa_act_mul_params_size(void) { return sizeof(fa_act_mul_params); }
 size_t fa_act_mul_bwd_params_size(void) { return sizeof(fa_act_mul_bwd_params); }
 size_t fa_quant_fp8_params_size(void) { return sizeof(fa_quant_fp8_params); }
@@ -1291,6 +1295,53 @@ static int cross_entropy_bwd_check(const fa_cross_entropy_bwd_params& s) {
     return check_overlaps(op, &out, 1, in, 4, false, exempt, inplace ? 1 : 0);
 }
 
+// fa_sample's argument rules.  query: the workspace itself and where the tensors lie are not looked at
+static int sample_check(const fa_sample_params& s, bool query) {
+    const char* op = "sample";
+    FA_CHECK(s.logits, "%s: logits must not be NULL", op);
+    FA_CHECK(s.ids || s.filtered, "%s: at least one of ids and filtered must be given", op);
+    FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16 || s.dtype == FA_FP32, "%s: dtype must be fp16, bf16 or fp32", op);
+    const int esize = s.dtype == FA_FP32 ? 4 : 2;
+    FA_CHECK(s.vocab >= 1, "%s: vocab must be at least 1, got %d", op, s.vocab);
+    FA_CHECK(s.rows >= 0, "%s: rows must be non-negative", op);
+    // (a row that is greedy whatever its logits - the host temperature is not above 0 - never reads u)
+    FA_CHECK(!s.ids || s.u || (!s.temperature && !(s.temperature_value > 0.f)),
+             "%s: ids needs u (one uniform number per row) unless the temperature is the host scalar 0", op);
+    FA_CHECK(ce_stride_ok(s.logits_row_stride, s.rows, s.vocab) && (!s.filtered || ce_stride_ok(s.filtered_row_stride, s.rows, s.vocab)),
+             "%s: row strides must be non-negative and (rows > 1) at least vocab", op);
+    FA_CHECK(addr(s.logits) % esize == 0 && addr(s.filtered) % esize == 0 &&
+             ((addr(s.u) | addr(s.temperature) | addr(s.top_k) | addr(s.top_p) | addr(s.min_p) | addr(s.ids) | addr(s.n_kept) | addr(s.lse)) & 3) == 0,
+             "%s: logits / filtered must be aligned to their element, every [rows] array to 4 bytes", op);
+    if (s.vocab > (1 << 20)) return fail(FA_ERR_UNSUPPORTED, "%s: vocab %d is above 2^20 (the integer masses of a row must fit 64 bits)", op, s.vocab);
+    if (s.rows > 0x7fffffffLL / fa::sample_chunks_per_row(s.vocab))
+        return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (rows x chunks) in one launch", op);
+    if (query) return FA_OK;
+    const size_t need = fa::sample_workspace_bytes(s.rows, s.vocab, s.dtype);
+    if (need)
+        FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_sample_workspace_bytes() reports %zu",
+                 op, s.workspace ? s.workspace_bytes : (size_t)0, need);
+    FA_CHECK(addr(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+    const uint64_t vbytes = s.rows > 0 ? (uint64_t)s.rows * 4 : 0;
+    const View in[] = {
+        view_rows("logits", s.logits, s.rows, s.logits_row_stride, s.vocab, esize),
+        view_flat("u", s.u, vbytes),
+        view_flat("temperature", s.temperature, vbytes),
+        view_flat("top_k", s.top_k, vbytes),
+        view_flat("top_p", s.top_p, vbytes),
+        view_flat("min_p", s.min_p, vbytes),
+    };
+    const View out[] = {
+        view_rows("filtered", s.filtered, s.rows, s.filtered_row_stride, s.vocab, esize),
+        view_flat("ids", s.ids, vbytes),
+        view_flat("n_kept", s.n_kept, vbytes),
+        view_flat("lse", s.lse, vbytes),
+        view_flat("workspace", need ? s.workspace : nullptr, need),
+    };
+    return check_overlaps(op, out, 5, in, 6, true);
+}
+
 // what fa_act_mul and fa_act_mul_bwd share: dtype, activation, n, rows, and that rows x runs fits a grid index
 static int act_mul_common_check(const char* op, int dtype, int activation, int n, int64_t rows) {
     FA_TRY(check_io_dtype(op, dtype, "dtype"));
@@ -1766,6 +1817,22 @@ int fa_cross_entropy(const fa_cross_entropy_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_cross_entropy(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_cross_entropy launch");
+}
+
+size_t fa_sample_workspace_bytes(const fa_sample_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_sample_params)) return 0;
+    if (sample_check(*sp, true) != FA_OK) return 0;
+    return fa::sample_workspace_bytes(sp->rows, sp->vocab, sp->dtype);
+}
+
+int fa_sample(const fa_sample_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_sample_params"));
+    fa_sample_params s = *sp;
+    FA_TRY(sample_check(s, false));
+    if (s.rows == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_sample(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_sample launch");
 }
 
 int fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* sp, void* stream) {

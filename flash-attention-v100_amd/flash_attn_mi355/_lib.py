@@ -330,6 +330,23 @@ class FaCrossEntropyBwdParams(ctypes.Structure):
     ]
 
 
+class FaSampleParams(ctypes.Structure):
+    """Mirror of `struct fa_sample_params` (include/fa_mi355.h): fa_sample, temperature / top-k / min-p / top-p token sampling from
+    [rows, vocab] logits with one caller-supplied uniform number per row.  struct_size must be set to sizeof(FaSampleParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("logits", _ptr), ("u", _ptr),                        # [rows, vocab] of dtype; fp32 [rows]
+        ("temperature", _ptr), ("top_k", _ptr), ("top_p", _ptr), ("min_p", _ptr),   # [rows] arrays, or NULL: the *_value
+        ("ids", _ptr), ("n_kept", _ptr), ("lse", _ptr), ("filtered", _ptr),         # written; NULL: skipped
+        ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("logits_row_stride", _i64), ("filtered_row_stride", _i64),
+        ("rows", _i64),
+        ("vocab", _i32), ("dtype", _i32),
+        ("temperature_value", _f32), ("top_k_value", _i32), ("top_p_value", _f32), ("min_p_value", _f32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 class FaActMulParams(ctypes.Structure):
     """Mirror of `struct fa_act_mul_params` (include/fa_mi355.h): fa_act_mul, the gated activation act(gate) * up of the MLP
     (up NULL: act(gate)).  struct_size must be set to sizeof(FaActMulParams)."""
@@ -506,6 +523,7 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_add_norm_bwd", "fa_add_norm_bwd_workspace_bytes", "fa_add_norm_bwd_params_size",
            "fa_cross_entropy", "fa_cross_entropy_workspace_bytes", "fa_cross_entropy_params_size",
            "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size",
+           "fa_sample", "fa_sample_workspace_bytes", "fa_sample_params_size",
            "fa_act_mul", "fa_act_mul_params_size", "fa_act_mul_plan", "fa_act_mul_bwd", "fa_act_mul_bwd_params_size",
            "fa_quant_fp8", "fa_quant_fp8_params_size", "fa_add_norm_quant", "fa_add_norm_quant_params_size",
            "fa_act_mul_quant", "fa_act_mul_quant_params_size",
@@ -529,6 +547,7 @@ ROW_OPS = [
     ("fa_add_norm_bwd", FaAddNormBwdParams, "fa_add_norm_bwd_workspace_bytes"),
     ("fa_cross_entropy", FaCrossEntropyParams, "fa_cross_entropy_workspace_bytes"),
     ("fa_cross_entropy_bwd", FaCrossEntropyBwdParams, None),
+    ("fa_sample", FaSampleParams, "fa_sample_workspace_bytes"),
     ("fa_act_mul", FaActMulParams, None),
     ("fa_act_mul_bwd", FaActMulBwdParams, None),
     ("fa_quant_fp8", FaQuantFp8Params, None),
@@ -669,8 +688,9 @@ def _workspace_query(query):
 call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
-# call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd;
-# qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes, cross_entropy_workspace_bytes, moe_sort_workspace_bytes
+# call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
+# call_sample; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes, cross_entropy_workspace_bytes,
+# sample_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
     if _query:

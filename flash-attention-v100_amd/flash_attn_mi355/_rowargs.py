@@ -1,4 +1,4 @@
-"""What the wrappers of the row ops share (rope_store, qk_norm, kv_store, kv_gather, add_norm, cross_entropy, act_mul): the
+"""What the wrappers of the row ops share (rope_store, qk_norm, kv_store, kv_gather, add_norm, cross_entropy, act_mul, sample): the
 validators of their common arguments and the fillers of the parameter-block fields that go with them.  Every validator takes `op`,
 the prefix of the wrapper's messages ("rope_store", "qk_norm", "kv_store", "kv_gather", "add_norm", "cross_entropy", "act_mul"), and
 raises RuntimeError; a filler writes
@@ -71,6 +71,22 @@ def loss_scalars(op, label_smoothing, logit_scale, lse_square_scale, ignore_inde
     if not (-2 ** 63 <= ignore_index < 2 ** 63):
         raise RuntimeError(f"{op}: ignore_index must fit an int64, got {ignore_index}")
     return label_smoothing, logit_scale, lse_square_scale, ignore_index
+
+
+def row_param(op, value, rows, dtype, name):
+    """a per-row parameter (sample): a number for every row, or a tensor of `rows` values (any shape that flattens to it; cast to
+    `dtype`, made contiguous).  Returns (tensor or None, number or None) - exactly one is set"""
+    if isinstance(value, torch.Tensor):
+        if value.numel() != rows:
+            raise RuntimeError(f"{op}: {name} must be a number or a tensor of one value per row ({rows}), got {tuple(value.shape)}")
+        if value.is_floating_point() != dtype.is_floating_point or value.dtype == torch.bool:
+            raise RuntimeError(f"{op}: {name} must be {'a floating-point' if dtype.is_floating_point else 'an integer'} tensor, "
+                               f"got {value.dtype}")
+        return value.reshape(-1).to(dtype).contiguous(), None
+    try:
+        return None, (float(value) if dtype.is_floating_point else int(value))
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{op}: {name} must be a number or a tensor of one value per row, got {type(value).__name__}") from None
 
 
 def same_device(op, tensors, ref, whose):

@@ -14,7 +14,8 @@ in place, fa_act_mul / fa_act_mul_bwd; `quant_fp8` / `add_norm_quant` / `act_mul
 quantisation alone and fused behind the forwards of add_norm and act_mul, fa_quant_fp8 / fa_add_norm_quant / fa_act_mul_quant, not
 differentiable; `moe_route` / `moe_route_bwd` / `moe_sort` / `moe_permute` / `moe_combine` / `moe_combine_bwd`: top-k routing, the
 stable sort of the (token, k) slots by expert, the permutation into per-expert segments and the weighted combine of a
-mixture-of-experts block with autograd formulas, fa_moe_* - registered, but not listed in `__all__`).
+mixture-of-experts block with autograd formulas, fa_moe_*; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
+sampling from logits and the filtered logits alone, fa_sample, not differentiable - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -49,6 +50,7 @@ from . import qk_norm as _qk_norm
 from . import quant as _quant
 from . import rope_store as _rope_store
 from . import rotary as _rotary
+from . import sample as _sample
 
 _NS = "flash_attn_mi355"
 
@@ -764,6 +766,48 @@ def _cross_entropy_backward(ctx, dlosses, dz_losses, dlse):
 
 
 cross_entropy.register_autograd(_cross_entropy_backward, setup_context=_cross_entropy_setup)
+
+
+# ------------------------------------------------------------------------------------------
+# token sampling from logits (flash_attn_mi355.sample; csrc/fa_sample.hip).  Each of the four parameters is an optional
+# [rows] tensor plus the number that holds where the tensor is None.
+# Reached as torch.ops.flash_attn_mi355.sample / .sample_filter; not in __all__
+# ------------------------------------------------------------------------------------------
+def _sample_params(temperature, temperature_value, top_k, top_k_value, top_p, top_p_value, min_p, min_p_value):
+    return dict(temperature=temperature_value if temperature is None else temperature,
+                top_k=top_k_value if top_k is None else top_k,
+                top_p=top_p_value if top_p is None else top_p,
+                min_p=min_p_value if min_p is None else min_p)
+
+
+@torch.library.custom_op(f"{_NS}::sample", mutates_args=(), device_types="cuda")
+def sample(logits: Tensor, u: Tensor, temperature: Optional[Tensor], temperature_value: float, top_k: Optional[Tensor],
+           top_k_value: int, top_p: Optional[Tensor], top_p_value: float, min_p: Optional[Tensor],
+           min_p_value: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """sample.sample_forward: (ids int32, n_kept int32, lse fp32) of shape logits.shape[:-1] from one uniform number per row"""
+    return _sample.sample_forward(logits, u, **_sample_params(temperature, temperature_value, top_k, top_k_value, top_p,
+                                                              top_p_value, min_p, min_p_value))
+
+
+@sample.register_fake
+def _(logits, u, temperature, temperature_value, top_k, top_k_value, top_p, top_p_value, min_p, min_p_value):
+    lead = logits.shape[:-1]
+    return (logits.new_empty(lead, dtype=torch.int32), logits.new_empty(lead, dtype=torch.int32),
+            logits.new_empty(lead, dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{_NS}::sample_filter", mutates_args=(), device_types="cuda")
+def sample_filter(logits: Tensor, temperature: Optional[Tensor], temperature_value: float, top_k: Optional[Tensor],
+                  top_k_value: int, top_p: Optional[Tensor], top_p_value: float, min_p: Optional[Tensor],
+                  min_p_value: float) -> Tensor:
+    """sample.filter_forward: the logits with everything outside the kept set at -inf, a fresh contiguous tensor"""
+    return _sample.filter_forward(logits, **_sample_params(temperature, temperature_value, top_k, top_k_value, top_p, top_p_value,
+                                                           min_p, min_p_value))
+
+
+@sample_filter.register_fake
+def _(logits, temperature, temperature_value, top_k, top_k_value, top_p, top_p_value, min_p, min_p_value):
+    return logits.new_empty(logits.shape)
 
 
 # ------------------------------------------------------------------------------------------

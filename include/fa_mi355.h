@@ -1002,6 +1002,95 @@ int    fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* s, void* stream);
 size_t fa_cross_entropy_bwd_params_size(void);
 
 /*
+ * fa_sample - token sampling from logits: temperature, top-k, min-p, top-p (in that order: the nucleus is taken over what the
+ * other two leave, renormalised - the vLLM / HF order) and ONE inverse-CDF draw per row from a caller-supplied uniform number
+ * (additive: fa_params and FA_ABI_VERSION are unchanged).  The serving-side end of the row ops: [rows, vocab] logits in, token
+ * ids out.  logits: `dtype` FA_FP16, FA_BF16 or FA_FP32, last dimension contiguous, any row stride >= vocab (elements), element
+ * alignment only.  The op holds no RNG: u is fp32 [rows], drawn by the caller (uniform in [0, 1)), so a call is deterministic and
+ * capturable in a graph.  Each of the four parameters is a device [rows] array (fp32; top_k: int32) or, where the array is NULL,
+ * the host value `*_value` for every row; both forms follow the same per-row rules, non-finite values included.
+ *
+ * Row r has raw values v_j = float(logits[r, j]), j < vocab; a NaN counts as -inf (and -0 as +0).  The ORDER: a before b iff
+ * v_a > v_b, or v_a == v_b and a < b; j* is the first token in it.  Selection is on the raw values, exact whatever the temperature.
+ *  1. Empty row: every v_j == -inf: id = -1, n_kept = 0, lse = -inf, a filtered row of -inf.  No address is formed from an id.
+ *  2. Greedy: T = the row's temperature; the row is greedy when !(T > 0) (0, negative, NaN), when v_{j*} == +inf, or when T is
+ *     so small that x_{j*} = v_{j*} * (1 / T) is not finite in fp32.  Then id = j*, n_kept = 1, the filtered row keeps j* alone
+ *     and u is not read; lse is taken at inv_t = 1 for !(T > 0) (a row that holds +inf: NaN) and is not finite in the overflow
+ *     case.  T = +inf is sampled with inv_t = 0: uniform over the tokens above -inf (a -inf logit has x = NaN: mass 0, lse NaN).
+ *  3. Masses: otherwise inv_t = 1 / T (fp32); x_j = v_j * inv_t (ONE rounding); m = x_{j*}; e_j = e(x_j - m), e(t) = exp2(t *
+ *     log2(e)): one fp32 product, one hardware exp2 (csrc/fa_lse.h).  The INTEGER MASS q_j = floor(e_j * 2^40) as an unsigned
+ *     64-bit value (0 for -inf; q_{j*} = 2^40).  Everything below is integer arithmetic on the q_j: sums of up to 2^20 of them fit
+ *     64 bits and do not depend on the order of addition, so a result cannot depend on the launch plan, rows or the row's index.
+ *  4. Filters, each the length of a kept PREFIX of the order; n0 = the number of tokens above -inf.
+ *       top_k:  n1 = k if 1 <= k < n0, else n0.
+ *       min_p:  on when min_p > 0 (a NaN is off); mp = min(min_p, 1); n2 = the number of tokens among the first n1 with
+ *               e_j >= mp (fp32 compare) - a prefix that holds at least j*.  Off: n2 = n1.
+ *       top_p:  on when top_p < 1 (a NaN is off); Q2 = the sum of q over the first n2, Tq = max(1, ceil((double)top_p *
+ *               (double)Q2)); n3 = the smallest n whose first-n mass is >= Tq (top_p <= 0 keeps one token).  Off: n3 = n2.
+ *     Tokens tied at a cut enter in index order.
+ *  5. Draw: Q = the sum of q over the kept set (the first n3); uu = u with a NaN or a negative value read as 0;
+ *     rr = min(floor((double)uu * (double)Q), Q - 1); id = the kept token of smallest INDEX whose index-order running sum of kept
+ *     q exceeds rr.
+ *  6. Outputs, each optional (NULL: not written) but at least one of ids / filtered must be given:
+ *       ids      int32 [rows]
+ *       n_kept   int32 [rows]: n3 (greedy: 1, empty: 0)
+ *       lse      fp32 [rows]: m + log(s) of fa_lse.h's running (max, sum-exp) over x in a fixed order - bitwise repeatable; the
+ *                caller's log-probability of the UNFILTERED distribution is x_id - lse
+ *       filtered [rows, vocab] of `dtype`, its own row stride: the logit's own bits where kept, -inf elsewhere.  Not in place.
+ *     u may be NULL only where ids is NULL, or where temperature is NULL and !(temperature_value > 0).
+ * Launch plan, a function of vocab alone.  vocab < 32768: one workgroup of 1024 lanes per row, one launch, no workspace.  vocab >=
+ * 32768 (the split plan): a row is cut into ceil(vocab / 16384) chunks, one workgroup each, and every step that meets over the whole
+ * row is a launch of its own on the stream - chunk statistics; then, as often as the longest row can need (a function of the dtype
+ * and of which filters can be on), a sweep over the chunks followed by a one-workgroup-per-row step that takes its result and
+ * decides the row's next sweep; then `filtered`.  The chunks' integer histograms and sums meet in the workspace by integer atomic
+ * adds, the float partials of lse are merged in chunk order; no workgroup waits for another and the workspace needs no
+ * initialisation.  fa_sample_workspace_bytes() = rows x (3392 + 160 x chunks, rounded up to 256) bytes there.  In both plans a row
+ * is swept once for the statistics, once for the masses (min_p, or top_p without top_k), once per 8 key bits for each of top_k and
+ * top_p (16-bit logits: 2 sweeps, fp32: 4: a radix select over the order-preserving integer key of v_j with a 256-bin histogram
+ * of counts and masses), once for a tied class that is cut, once for the draw and once for `filtered`; a sweep that a row does
+ * not need is left out (split plan: its workgroups leave at once).  Every loop's trip count is a function of vocab alone.  No
+ * float atomics, no host synchronisation; a row's bits depend on (vocab, dtype), its values and its parameters alone.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL logits; neither ids nor filtered; a missing u; a dtype
+ * other than FA_FP16 / FA_BF16 / FA_FP32; vocab < 1; negative rows or row strides, or (rows > 1) a row stride below vocab; logits
+ * / filtered not aligned to their element, a [rows] array not 4-byte aligned, a workspace not 16-byte aligned or smaller than
+ * reported; an output that overlaps an input, another output or the workspace; non-zero reserved fields.  vocab > 2^20 or
+ * rows > 2^31 - 1: FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
+ * Not covered: repetition / presence / frequency penalties and logit bias; an in-kernel RNG and per-row seeds; top-n log-prob
+ * outputs; rejection sampling and draft-tree verification for speculative decoding; typical-p and the like; vocab > 2^20; in-place
+ * `filtered`.
+ */
+typedef struct fa_sample_params {
+    size_t         struct_size;      /* sizeof(fa_sample_params) as the caller compiled it */
+    const void*    logits;           /* [rows, vocab] of `dtype` */
+    const float*   u;                /* device fp32 [rows]: one uniform number in [0, 1) per row */
+    const float*   temperature;      /* device fp32 [rows], or NULL: temperature_value */
+    const int32_t* top_k;            /* device int32 [rows], or NULL: top_k_value */
+    const float*   top_p;            /* device fp32 [rows], or NULL: top_p_value */
+    const float*   min_p;            /* device fp32 [rows], or NULL: min_p_value */
+    int32_t*       ids;              /* device [rows], or NULL */
+    int32_t*       n_kept;           /* device [rows], or NULL */
+    float*         lse;              /* device [rows], or NULL */
+    void*          filtered;         /* [rows, vocab] of `dtype`, or NULL */
+    void*          workspace;        /* fa_sample_workspace_bytes() bytes, 16-byte aligned; may be NULL where that is 0 */
+    size_t         workspace_bytes;
+    int64_t        logits_row_stride, filtered_row_stride;   /* elements */
+    int64_t        rows;
+    int32_t        vocab;            /* 1 .. 2^20 */
+    int32_t        dtype;            /* FA_FP16, FA_BF16 or FA_FP32 */
+    float          temperature_value;    /* !(T > 0): greedy */
+    int32_t        top_k_value;      /* < 1 or >= n0: off */
+    float          top_p_value;      /* >= 1 or NaN: off */
+    float          min_p_value;      /* <= 0 or NaN: off */
+    int64_t        reserved[4];      /* 0 */
+} fa_sample_params;
+
+int    fa_sample(const fa_sample_params* s, void* stream);
+/* the workspace of that call: a function of (rows, vocab, dtype) and of which filters can be on; `workspace`, `workspace_bytes` and
+ * where the tensors lie are not looked at; 0 for a block that the call rejects for any other reason */
+size_t fa_sample_workspace_bytes(const fa_sample_params* s);
+size_t fa_sample_params_size(void);
+
+/*
  * fa_act_mul - the gated activation of the MLP, act(gate) * up: SwiGLU, GeGLU and their ungated forms, forward (additive:
  * fa_params and FA_ABI_VERSION are unchanged).  gate, up, out: [rows, n] of `dtype` (FA_FP16 or FA_BF16), last dimension
  * contiguous, each with a row stride of its own >= n (elements).  The packed [rows, 2 n] form needs nothing more: gate = base,
