@@ -3,6 +3,9 @@
 Shapes are drawn around the tile edges of the kernels (multiples of 32 / 64 / 128 / 256, +-1), features are drawn
 independently (causal / one- and two-sided windows, GQA / MQA, ALiBi, softcap, dropout, head dims 32..256, ragged and
 empty sequences, paged caches, rotary, left padding), sizes stay where the fp64 oracle finishes in well under a second.
+The kind `dropout` draws dense and packed cases with dropout always on (p 0.1 / 0.3 / 0.5, no softcap) and holds the sign
+pattern of the returned dmask to the oracle's Philox mask on every visible element, as the dense kind does where it draws
+dropout.
 The fp8_* kinds run the fp8-e4m3 q / k / v forward (input magnitudes, softmax scales, descales, seqused_k, packed and
 head-sliced views) inside the gate of tests/fp8_gate.py and report the worst error / gate ratio per kind.
 
@@ -121,8 +124,15 @@ def _o_rounding_slack(g_rounded, g_exact, k=2.0):
             for a, b in zip(g_rounded, g_exact)]
 
 
+def _check_dmask(dm, keep, vis, desc):
+    """dm [readings, sq, sk] (+1 kept, -1 dropped, 0 never visited): on every visible element the sign is the oracle's keep bit"""
+    assert set(np.unique(dm)).issubset({-1.0, 0.0, 1.0}), f"dmask: values other than -1, 0, 1  [{desc}]"
+    bad = np.argwhere((((dm > 0) != keep[None]) | (dm == 0)) & vis[None])
+    assert bad.size == 0, f"dmask differs from the Philox oracle at (reading, i, j) {bad[:4].tolist()}  [{desc}]"
+
+
 # ------------------------------------------------------------------------------------------------ dense fwd + bwd
-def dense_case(rng, idx, long=False):
+def dense_case(rng, idx, long=False, drop=False):
     B = int(rng.integers(1, 3))
     Hk = int(rng.choice([1, 2, 4]))
     Hq = Hk * int(rng.choice([1, 1, 2, 4]))
@@ -138,7 +148,10 @@ def dense_case(rng, idx, long=False):
     dt = str(rng.choice(["fp16", "bf16"]))
     causal, window = _mask(rng, Sq, Sk)
     softcap, slopes = _features(rng, Hq)
-    pdrop = float(rng.choice([0.1, 0.3])) if rng.random() < 0.12 else 0.0
+    if drop:                                # (the `dropout` kind: its own stream, so its own draw)
+        pdrop = float(rng.choice([0.1, 0.3, 0.5]))
+    else:
+        pdrop = float(rng.choice([0.1, 0.3])) if rng.random() < 0.12 else 0.0
     if pdrop:
         softcap = 0.0                       # the op rejects softcap + dropout, as the reference's does
     bwd = rng.random() < 0.8
@@ -150,12 +163,15 @@ def dense_case(rng, idx, long=False):
     v = rand16((B, Sk, Hk, D), dt, s + 3).requires_grad_(True)
     do = rand16((B, Sq, Hq, D), dt, s + 4)
     seed, offset = _gen_state()
-    out, lse, _ = _fa().flash_attn_func(q, k, v, dropout_p=pdrop, causal=causal, window_size=window, softcap=softcap,
-                                        alibi_slopes=slopes, return_attn_probs=True)
+    out, lse, dmask = _fa().flash_attn_func(q, k, v, dropout_p=pdrop, causal=causal, window_size=window, softcap=softcap,
+                                            alibi_slopes=slopes, return_attn_probs=True)
     t = lambda x: f64(x).transpose(0, 2, 1, 3)
     kw = dict(causal=causal, window=window, softcap=softcap, alibi_slopes=None if slopes is None else f64(slopes))
     if pdrop:
         kw.update(dropout_p=pdrop, seed=seed, offset=offset)
+        c_, wl_, wr_ = oracle.normalize_flags(Sq, Sk, causal, window[0], window[1], slopes is not None)
+        _check_dmask(f64(dmask).reshape(B * Hq, Sq, Sk), oracle.dropout_keep_mask(seed, offset, pdrop, Sq, Sk),
+                     oracle.attention.visible_mask(Sq, Sk, c_, wl_, wr_), desc)
     o_ref, lse_ref, _ = oracle.attn_fwd(t(q), t(k), t(v), D ** -0.5, **kw)
     m = 1.5 if pdrop else 1.0
     _check(t(out), o_ref, dt, "out", m, desc)
@@ -177,7 +193,7 @@ def dense_case(rng, idx, long=False):
 
 
 # ------------------------------------------------------------------------------------------------ varlen fwd + bwd
-def varlen_case(rng, idx, long=False):
+def varlen_case(rng, idx, long=False, drop=False):
     B = int(rng.integers(1, 6))
     Hk = int(rng.choice([1, 2, 4]))
     Hq = Hk * int(rng.choice([1, 1, 2, 4]))
@@ -204,9 +220,12 @@ def varlen_case(rng, idx, long=False):
     used = None                             # seqused_k (forward only): keys actually used of each sequence
     if rng.random() < 0.15:
         used = [int(rng.integers(0, l + 1)) for l in lens_k]
+    pdrop = 0.0
+    if drop:                                # the `dropout` kind: contiguous K / V, every key used, no softcap (the op rejects it)
+        pdrop, softcap, paged, used = float(rng.choice([0.1, 0.3, 0.5])), 0.0, False, None
     bwd = (not paged) and used is None and rng.random() < 0.8
     desc = f"varlen{'_long' if long else ''}#{idx} lens_q={lens_q} lens_k={lens_k} Hq{Hq} Hk{Hk} D{D} {dt} causal={causal} window={window} " \
-           f"softcap={softcap} alibi={slopes is not None} paged={paged} seqused_k={used} bwd={bwd}"
+           f"softcap={softcap} alibi={slopes is not None} paged={paged} seqused_k={used} bwd={bwd}" + (f" dropout={pdrop}" if drop else "")
     s = 5000 + 10 * idx
     Tq, Tk = sum(lens_q), sum(lens_k)
     cu = lambda l: torch.tensor(np.concatenate([[0], np.cumsum(l)]), dtype=torch.int32, device="cuda")
@@ -239,11 +258,24 @@ def varlen_case(rng, idx, long=False):
     else:
         k = rand16((Tk, Hk, D), dt, s + 2).requires_grad_(bwd)
         v = rand16((Tk, Hk, D), dt, s + 3).requires_grad_(bwd)
-        out, lse, _ = _fa().flash_attn_varlen_func(q, k, v, cu_q, cu_k, mq, mk, causal=causal, window_size=window,
-                                                   softcap=softcap, alibi_slopes=slopes, return_attn_probs=True, **extra)
+        if pdrop:
+            seed, offset = _gen_state()
+            extra["dropout_p"] = pdrop
+            kw.update(dropout_p=pdrop, seed=seed, offset=offset)
+        out, lse, dmask = _fa().flash_attn_varlen_func(q, k, v, cu_q, cu_k, mq, mk, causal=causal, window_size=window,
+                                                       softcap=softcap, alibi_slopes=slopes, return_attn_probs=True, **extra)
         o_ref, lse_ref = oracle.varlen_fwd(f64(q), f64(k), f64(v), cu_q.cpu().numpy(), cu_k.cpu().numpy(), mq, mk,
                                            D ** -0.5, **kw)
-    _check(f64(out), o_ref, dt, "out", 1.0, desc)
+        if pdrop:                           # dmask [T_q, Hq, max_seqlen_k]; the mask's N_glob is max_seqlen_k
+            c_, wl_, wr_ = oracle.normalize_flags(mq, mk, causal, window[0], window[1], slopes is not None)
+            dm, q0 = f64(dmask), 0
+            for lq, lk in zip(lens_q, lens_k):
+                if lq and lk:
+                    _check_dmask(dm[q0:q0 + lq, :, :lk].transpose(1, 0, 2),
+                                 oracle.dropout_keep_mask(seed, offset, pdrop, lq, lk, row0=q0, n_glob=mk),
+                                 oracle.attention.visible_mask(lq, lk, c_, wl_, wr_), desc)
+                q0 += lq
+    _check(f64(out), o_ref, dt, "out", 1.5 if pdrop else 1.0, desc)
     _check_lse(f64(lse), lse_ref, "lse", desc)
     if bwd:
         dq, dk, dv = torch.autograd.grad(out, (q, k, v), do)
@@ -252,10 +284,17 @@ def varlen_case(rng, idx, long=False):
         gx = oracle.varlen_bwd(f64(do), f64(q), f64(k), f64(v), o_ref, lse_ref.astype(np.float64),
                                cu_q.cpu().numpy(), cu_k.cpu().numpy(), mq, mk, D ** -0.5, **kw)
         sl = _o_rounding_slack(g, gx)
-        _check(f64(dq), g[0], dt, "dq", 2.0, desc, slack=sl[0])
-        _check(f64(dk), g[1], dt, "dk", 2.0, desc, slack=sl[1])
-        _check(f64(dv), g[2], dt, "dv", 2.0, desc)
+        m = 3.0 if pdrop else 2.0
+        _check(f64(dq), g[0], dt, "dq", m, desc, slack=sl[0])
+        _check(f64(dk), g[1], dt, "dk", m, desc, slack=sl[1])
+        _check(f64(dv), g[2], dt, "dv", m, desc)
     return desc
+
+
+# ------------------------------------------------------------------------------------------------ dropout always on
+def dropout_case(rng, idx):
+    """the dense and varlen draws (shapes, masks, GQA, ALiBi, head dims) with dropout in every case and the dmask checked"""
+    return varlen_case(rng, idx, drop=True) if rng.random() < 0.4 else dense_case(rng, idx, drop=True)
 
 
 # ------------------------------------------------------------------------------------------------ kvcache
@@ -527,12 +566,13 @@ KINDS = {"dense": dense_case, "varlen": varlen_case, "kvcache": kvcache_case,
          "varlen_long": lambda rng, i: varlen_case(rng, i, long=True),
          "fp8_dense": fp8_dense_case, "fp8_varlen": fp8_varlen_case,
          "fp8_dense_long": lambda rng, i: fp8_dense_case(rng, i, long=True),
-         "fp8_varlen_long": lambda rng, i: fp8_varlen_case(rng, i, long=True)}
+         "fp8_varlen_long": lambda rng, i: fp8_varlen_case(rng, i, long=True),
+         "dropout": dropout_case}
 
 
 # (appended only: a kind's id seeds its random stream, and pinned cases replay by (kind, seed, i))
 KIND_ID = {"dense": 0, "kvcache": 1, "varlen": 2, "dense_long": 3, "varlen_long": 4,
-           "fp8_dense": 5, "fp8_varlen": 6, "fp8_dense_long": 7, "fp8_varlen_long": 8}
+           "fp8_dense": 5, "fp8_varlen": 6, "fp8_dense_long": 7, "fp8_varlen_long": 8, "dropout": 9}
 
 
 def run_one(kind, seed, i):

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import oracle
-from util import assert_close, f64, rand16
+from util import LSE_ATOL, assert_close, assert_lse_close, f64, rand16
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +49,7 @@ def test_dense_dropout_mask_output_and_grads(case):
     kw = dict(causal=causal, dropout_p=pdrop, seed=seed, offset=offset)
     o_ref, lse_ref, _ = oracle.attn_fwd(t(q), t(k), t(v), D ** -0.5, **kw)
     assert_close(t(out), o_ref, dt, "out", mult=1.5)
-    assert np.abs(f64(lse) - lse_ref).max() < 2e-3                 # LSE is pre-dropout
+    assert_lse_close(f64(lse), lse_ref, "lse", atol=LSE_ATOL)      # LSE is pre-dropout
     dq, dk, dv = torch.autograd.grad(out, (q, k, v), do)
     g = oracle.attn_bwd(t(do), t(q), t(k), t(v), o_ref, lse_ref.astype(np.float64), D ** -0.5, **kw)
     assert_close(t(dq), g[0], dt, "dq", mult=3.0)

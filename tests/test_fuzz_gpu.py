@@ -8,7 +8,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("kind,n", [("dense", 48), ("varlen", 32), ("kvcache", 40), ("dense_long", 12), ("varlen_long", 12),
-                                    ("fp8_dense", 48), ("fp8_varlen", 32), ("fp8_dense_long", 8), ("fp8_varlen_long", 8)])
+                                    ("fp8_dense", 48), ("fp8_varlen", 32), ("fp8_dense_long", 8), ("fp8_varlen_long", 8),
+                                    ("dropout", 24)])
 def test_random_cases_agree_with_oracle(kind, n):
     fuzz_cases.run(kind, seed=20260928, n=n)
 

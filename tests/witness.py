@@ -37,7 +37,9 @@ sequences.  KVCache also takes cache_batch_idx (unreferenced batch rows are pois
 
 Out of scope, on purpose, and no weaker variant of these exists here: softcap (tanh squeezes the one-unit margin: at D 128
 and softcap 30 the targets sit 2 nats ahead instead of 16), rotary (rotated values are not exact in the io types), ALiBi
-together with sinks, and the fp8 q / k / v forward (it has its own gate in tests/fp8_gate.py).
+together with sinks, the fp8 q / k / v forward (it has its own gate in tests/fp8_gate.py), and dropout: a keep bit is not
+a mask edge, and two targets per row cannot show WHICH bit of a row a kernel replayed wrongly - tests/dropout_readout.py
+reads the whole keep mask out of O, dQ, dK and dV element by element instead.
 """
 import numpy as np
 import torch
