@@ -109,12 +109,7 @@ __global__ void __launch_bounds__(ROW_THREADS) add_norm_bwd_small_kernel(const A
 #pragma unroll
             for (int i = 0; i < 8; ++i) z[i] = 0.f;
         }
-        if constexpr (LN) {
-            const float mean = rms_group_sum(row_piece_sum(z), lanes) / (float)a.n;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) z[i] = act ? z[i] - mean : 0.f;
-        }
-        const float rstd = rms_rstd(rms_group_sum(row_piece_ss(z), lanes), a.n, a.eps);
+        const float rstd = row_small_stats<LN>(z, act, lanes, a.n, a.eps);
         float xh[8], av[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) { xh[i] = z[i] * rstd; av[i] = dy[i] * g[i]; }
@@ -203,21 +198,7 @@ __global__ void __launch_bounds__(ROW_THREADS * RW) add_norm_bwd_wide_kernel(con
                 for (int i = 0; i < 8; ++i) z[p][i] = 0.f;
             }
         }
-        if constexpr (LN) {
-            float s = row_piece_sum(z[0]);
-#pragma unroll
-            for (int p = 1; p < NP; ++p) s += row_piece_sum(z[p]);
-            const float mean = row_block_sum(s, red[0][grp], nwaves, wave) / (float)a.n;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) z[p][i] = on[p] ? z[p][i] - mean : 0.f;
-            }
-        }
-        float ss = row_piece_ss(z[0]);
-#pragma unroll
-        for (int p = 1; p < NP; ++p) ss += row_piece_ss(z[p]);
-        const float rstd = rms_rstd(row_block_sum(ss, red[1][grp], nwaves, wave), a.n, a.eps);
+        const float rstd = row_wide_stats<LN, NP>(z, on, red[0][grp], red[1][grp], nwaves, wave, a.n, a.eps);
         // z becomes xhat, dy stays (dweight / dbias), av = dy g
         float av[NP][8];
 #pragma unroll

@@ -8,8 +8,8 @@
 //     code_j = e4m3(fminf(fmaxf(y_j * inv, -448), 448))        to_fp8x8 (fa_fp8_cvt.h)
 // STATIC: the caller's scale, the last two lines alone - fa_kv_store's rule.  Every kernel holds y as the PACKED 16-bit pieces a
 // 16-bit store would have written (u32x4 = 8 columns), so "after the rounding" is by construction, and the fused forms have the
-// bits of fa_quant_fp8 on the 16-bit op's output: fa_add_norm_quant restates fa_add_norm.hip's two kernels line for line up to the
-// store (that source is left as it is; the sums are fa_rowsum.h's in their order), fa_act_mul_quant evaluates fa_act.h's act_eval.
+// bits of fa_quant_fp8 on the 16-bit op's output: fa_add_norm_quant runs the bodies fa_add_norm runs (fa_add_norm.h) with an
+// epilogue that packs instead of storing, fa_act_mul_quant evaluates fa_act.h's act_eval.
 // Ownership:
 //   fa_quant_fp8, n <= 512 (quant_small_kernel): a row lies one piece per lane in G adjacent lanes of a wave, G the smallest power
 //     of two with 8 G >= n; a workgroup of 256 lanes takes 256 / G consecutive rows; no LDS.  Lanes past the row or past the last
@@ -17,13 +17,14 @@
 //   fa_quant_fp8 at n > 512 and fa_act_mul_quant at every n (quant_wide_kernel): one workgroup per row - whole waves, at most 256
 //     lanes up to FA_QUANT_WIDE_PIECES pieces (16384 columns) and 1024 lanes above - lane t owns the pieces t, t + threads, ..
 //     (at most 8).  Every load of the row is issued before the first store.
-//   fa_add_norm_quant: fa_add_norm's (fa_rowsum.h's row_shape): n <= 256 G lanes a row, above one workgroup of <= 256 lanes.
+//   fa_add_norm_quant: fa_add_norm.h's, which is fa_add_norm's: n <= 256 G lanes a row, above one workgroup of <= 256 lanes.
 //   A group of 128 columns is 16 pieces: in every form 16 adjacent lanes, aligned at 16, hold them - one xor butterfly, no LDS.
 //   The row maximum of the wide forms meets through LDS (row_block_max).
 // A row of a 16-bit input that does not start on a 16-byte boundary is loaded element by element, a row of codes that does not
 // start on an 8-byte boundary is stored byte by byte: the same bits.  No workspace, one launch, no atomics, every offset 64-bit.
 #include <cstdint>
 #include "fa_act.h"
+#include "fa_add_norm.h"
 #include "fa_fp8_cvt.h"
 #include "fa_rowmax.h"
 #include "fa_rowops.h"
@@ -316,155 +317,49 @@ void launch_act_mul_quant(const fa_act_mul_quant_params& s, hipStream_t stream) 
     else                    launch_quant_act_kind<fp16_tag>(a, s.activation, sh, stream);
 }
 
-// ---- fa_add_norm_quant: fa_add_norm.hip's kernels up to the store, restated (AnqNorm, anq_z8 and anq_y8 are that source's
-// AnArgs without `out`, its an_z8 and the arithmetic of its an_out8; a change there must be repeated here -
-// tests/test_quant_gpu.py holds the two together bit for bit)
-struct AnqNorm {
-    const uint16_t* x;
-    const void* res;                                      // nullptr: no residual
-    void* res_out;                                        // nullptr: not written
-    const void* w;
-    const void* b;                                        // nullptr: no bias
-    int64_t x_rs, res_rs, ro_rs;                          // row strides, elements
-    int64_t rows;
-    int n, group_log2;
-    int res_fp32, ro_fp32, w_fp32;
-    float eps, w_offset;
-};
-
-// z of one piece: the loads, the add and the rounding to residual_out's type
-template <typename T>
-__device__ __forceinline__ void anq_z8(const AnqNorm& a, int64_t row, int d, float (&z)[8]) {
-    row_load8<T>(a.x, row * a.x_rs + d, false, z);
-    if (a.res) {
-        float r[8];
-        row_load8<T>(a.res, row * a.res_rs + d, a.res_fp32 != 0, r);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) z[i] += r[i];
-        if (!a.ro_fp32) row_round8<T>(z);
-    }
-}
-
-// the fp32 value fa_add_norm rounds `out` from, of one piece, from xhat's two factors: v = z (RMSNorm) or z - mean
-template <typename T>
-__device__ __forceinline__ void anq_y8(const AnqNorm& a, int d, const float (&v)[8], float rstd, float (&y)[8]) {
-    float g[8];
-    rms_gains<T>(a.w, d, a.w_fp32 != 0, a.w_offset, g);
-    if (a.b) {
-        float b[8];
-        row_load8<T>(a.b, d, a.w_fp32 != 0, b);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) y[i] = fmaf(v[i] * rstd, g[i], b[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) y[i] = (v[i] * rstd) * g[i];
-    }
-}
-
+// ---- fa_add_norm_quant: fa_add_norm.h's two bodies - the code fa_add_norm runs - with the epilogue below in place of the store
 struct AnqArgs {
-    AnqNorm an;
+    AnArgs an;
     uint8_t* codes;
     float* scales;
     int64_t codes_rs;
     QRule q;
 };
 
-template <typename T>
-__device__ __forceinline__ u32x4 anq_pack8(const float (&y)[8]) {
-    using E = Elem<T>;
-    u32x4 r;
+// the lane's pieces of `out` packed as fa_add_norm's store would have written them (absent pieces: +0), then the rule on the row
+template <typename T, int NP>
+struct AnqEmit {
+    const AnqArgs& aq;
+    float* red_max;                                       // quant_emit_wide's LDS (the small form: nullptr)
+    u32x4 y[NP];
+    __device__ __forceinline__ AnqEmit(const AnqArgs& aq_, float* red_max_) : aq(aq_), red_max(red_max_) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = E::pack2(y[2 * i], y[2 * i + 1]);         // (row_store8's rounding)
-    return r;
-}
+        for (int p = 0; p < NP; ++p) y[p] = u32x4{0, 0, 0, 0};
+    }
+    __device__ __forceinline__ void piece(const AnArgs&, int p, int64_t, int, const float (&v)[8]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[p][i] = Elem<T>::pack2(v[2 * i], v[2 * i + 1]);   // (row_store8's rounding)
+    }
+    __device__ __forceinline__ void row(int64_t row, bool act, int d, int lanes) {
+        quant_emit_small<T>(aq.q, aq.codes + row * aq.codes_rs, true, aq.scales, row, aq.an.n, y[0], act, d, lanes);
+    }
+    __device__ __forceinline__ void row(int64_t row, const bool (&on)[NP], const int (&d)[NP]) {
+        quant_emit_wide<T, NP>(aq.q, aq.codes + row * aq.codes_rs, true, aq.scales, row, aq.an.n, y, on, d, red_max);
+    }
+};
 
 template <typename T, bool LN>
 __global__ void __launch_bounds__(ROW_THREADS) add_norm_quant_small_kernel(const AnqArgs aq) {
-    const AnqNorm& a = aq.an;
-    const int lanes = 1 << a.group_log2;
-    const int j = (int)threadIdx.x & (lanes - 1);
-    const bool piece = 8 * j < a.n;
-    const int d = piece ? 8 * j : 0;                      // (clamped: the loads stay inside the row)
-    const int64_t r = (int64_t)blockIdx.x * (ROW_THREADS >> a.group_log2) + ((int)threadIdx.x >> a.group_log2);
-    const bool act = piece && r < a.rows;
-    const int64_t row = r < a.rows ? r : 0;               // (a slot past the last row: row 0)
-    float z[8];
-    anq_z8<T>(a, row, d, z);
-    if (act && a.res_out) row_store8<T>(a.res_out, row * a.ro_rs + d, a.ro_fp32 != 0, z);
-    if (!act) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) z[i] = 0.f;
-    }
-    if constexpr (LN) {
-        const float mean = rms_group_sum(row_piece_sum(z), lanes) / (float)a.n;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) z[i] = act ? z[i] - mean : 0.f;
-    }
-    const float rstd = rms_rstd(rms_group_sum(row_piece_ss(z), lanes), a.n, a.eps);
-    u32x4 y = {0, 0, 0, 0};
-    if (act) {
-        float yf[8];
-        anq_y8<T>(a, d, z, rstd, yf);
-        y = anq_pack8<T>(yf);
-    }
-    quant_emit_small<T>(aq.q, aq.codes + row * aq.codes_rs, true, aq.scales, row, a.n, y, act, d, lanes);
+    AnqEmit<T, 1> epi(aq, nullptr);
+    an_small_body<T, LN>(aq.an, epi);
 }
 
 template <typename T, bool LN, int NP>
 __global__ void __launch_bounds__(ROW_THREADS) add_norm_quant_wide_kernel(const AnqArgs aq) {
     __shared__ float red[2][ROW_WAVES];
     __shared__ float red_max[QUANT_MAX_WAVES];
-    const AnqNorm& a = aq.an;
-    const int threads = (int)blockDim.x, nwaves = threads >> 6;
-    const int64_t row = blockIdx.x;
-    float z[NP][8];
-    int d[NP];
-    bool on[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const int c = 8 * ((int)threadIdx.x + p * threads);
-        on[p] = c < a.n;
-        d[p] = on[p] ? c : 0;
-        anq_z8<T>(a, row, d[p], z[p]);
-    }
-    if (a.res_out) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p)
-            if (on[p]) row_store8<T>(a.res_out, row * a.ro_rs + d[p], a.ro_fp32 != 0, z[p]);
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        if (!on[p]) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) z[p][i] = 0.f;
-        }
-    }
-    if constexpr (LN) {
-        float s = row_piece_sum(z[0]);
-#pragma unroll
-        for (int p = 1; p < NP; ++p) s += row_piece_sum(z[p]);
-        const float mean = row_block_sum(s, red[0], nwaves, (int)threadIdx.x >> 6) / (float)a.n;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) z[p][i] = on[p] ? z[p][i] - mean : 0.f;
-        }
-    }
-    float ss = row_piece_ss(z[0]);
-#pragma unroll
-    for (int p = 1; p < NP; ++p) ss += row_piece_ss(z[p]);
-    const float rstd = rms_rstd(row_block_sum(ss, red[1], nwaves, (int)threadIdx.x >> 6), a.n, a.eps);
-    u32x4 y[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        y[p] = u32x4{0, 0, 0, 0};
-        if (on[p]) {
-            float yf[8];
-            anq_y8<T>(a, d[p], z[p], rstd, yf);
-            y[p] = anq_pack8<T>(yf);
-        }
-    }
-    quant_emit_wide<T, NP>(aq.q, aq.codes + row * aq.codes_rs, true, aq.scales, row, a.n, y, on, d, red_max);
+    AnqEmit<T, NP> epi(aq, red_max);
+    an_wide_body<T, LN, NP>(aq.an, red, epi);
 }
 
 template <typename T, bool LN>
@@ -489,19 +384,7 @@ void launch_add_norm_quant(const fa_add_norm_quant_params& sq, hipStream_t strea
     const fa_add_norm_params& s = sq.norm;
     const RowShape sh = row_shape(s.n);
     AnqArgs aq = {};
-    AnqNorm& a = aq.an;
-    a.x = static_cast<const uint16_t*>(s.x);
-    a.res = s.residual;
-    a.res_out = s.residual_out;
-    a.w = s.weight;
-    a.b = s.bias;
-    a.x_rs = s.x_row_stride; a.res_rs = s.residual_row_stride; a.ro_rs = s.residual_out_row_stride;
-    a.rows = s.rows;
-    a.n = s.n; a.group_log2 = sh.group_log2;
-    a.res_fp32 = s.residual_dtype == FA_FP32;
-    a.ro_fp32 = s.residual_out_dtype == FA_FP32;
-    a.w_fp32 = s.weight_dtype == FA_FP32;
-    a.eps = s.eps; a.w_offset = s.weight_offset;
+    aq.an = an_args(s, sh);                               // (out: null, never stored to)
     aq.codes = static_cast<uint8_t*>(sq.codes);
     aq.scales = static_cast<float*>(sq.scales);
     aq.codes_rs = sq.codes_row_stride;

@@ -1,7 +1,8 @@
-// fa_rowsum.h - the fixed-order sums over one row of N columns (N % 8 == 0, 8 <= N <= 16384) that fa_add_norm (fa_add_norm.hip)
-// and fa_add_norm_bwd (fa_add_norm_bwd.hip) share: sum z, sum z^2 (or sum (z - mean)^2), sum a, sum a xhat.  The order of every
-// sum depends on N ALONE - never on the number of rows, the row's index or the device - so a row's bits do not depend on what else
-// is in the batch, and the backward recomputes mean / rstd with the forward's bits.
+// fa_rowsum.h - the fixed-order sums over one row of N columns (N % 8 == 0, 8 <= N <= 16384) that fa_add_norm, fa_add_norm_quant
+// (fa_add_norm.h) and fa_add_norm_bwd (fa_add_norm_bwd.hip) share: sum z, sum z^2 (or sum (z - mean)^2), sum a, sum a xhat.  The
+// order of every sum depends on N ALONE - never on the number of rows, the row's index or the device - so a row's bits do not
+// depend on what else is in the batch.  mean / rstd are row_small_stats / row_wide_stats in the forward and in the backward: the
+// backward recomputes them with the forward's bits because it calls the forward's function.
 //   N <= 256 (row_small): fa_rmsnorm.h's ownership - a row lies 8 columns per lane (one piece) in G adjacent lanes of a wave, G the
 //     smallest power of two with 8 G >= N, several rows per wave:
 //       - in a lane: the 8 columns in column order, s = v0 * v0 then s = fmaf(vi, vi, s) (row_piece_ss: the operations of
@@ -68,6 +69,42 @@ __device__ __forceinline__ float row_block_sum(float s, float* slot, int nwaves,
     float t = slot[0];
     for (int w = 1; w < nwaves; ++w) t += slot[w];
     return t;
+}
+
+// mean and rstd of a row that lies one piece per lane in `lanes` adjacent lanes of a wave (act: the lane has a piece of a row; a
+// lane without one hands in z = +0): z is centred in place for LN, an absent piece stays +0; returns rstd.  EVERY lane of the wave
+// must call this
+template <bool LN>
+__device__ __forceinline__ float row_small_stats(float (&z)[8], bool act, int lanes, int n, float eps) {
+    if constexpr (LN) {
+        const float mean = rms_group_sum(row_piece_sum(z), lanes) / (float)n;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) z[i] = act ? z[i] - mean : 0.f;
+    }
+    return rms_rstd(rms_group_sum(row_piece_ss(z), lanes), n, eps);
+}
+
+// .. and of a row owned by `nwaves` whole waves, lane t the pieces t, t + threads, .. (on: the piece is inside the row; a piece
+// past it comes in as +0 and stays +0); sum_slot, ss_slot: row_block_sum's LDS for the two sums.  EVERY lane of the workgroup must
+// call this
+template <bool LN, int NP>
+__device__ __forceinline__ float row_wide_stats(float (&z)[NP][8], const bool (&on)[NP], float* sum_slot, float* ss_slot,
+                                                int nwaves, int wave, int n, float eps) {
+    if constexpr (LN) {
+        float s = row_piece_sum(z[0]);
+#pragma unroll
+        for (int p = 1; p < NP; ++p) s += row_piece_sum(z[p]);
+        const float mean = row_block_sum(s, sum_slot, nwaves, wave) / (float)n;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) z[p][i] = on[p] ? z[p][i] - mean : 0.f;
+        }
+    }
+    float ss = row_piece_ss(z[0]);
+#pragma unroll
+    for (int p = 1; p < NP; ++p) ss += row_piece_ss(z[p]);
+    return rms_rstd(row_block_sum(ss, ss_slot, nwaves, wave), n, eps);
 }
 
 // 8 columns of a 16-bit (one 16-byte load) or fp32 (two) tensor as fp32
