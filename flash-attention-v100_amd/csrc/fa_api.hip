@@ -51,6 +51,10 @@ int64_t ce_bwd_nchunks(int vocab);
 void launch_sample(const fa_sample_params& s, hipStream_t stream);                           // fa_sample.hip: temperature / top-k / min-p / top-p token sampling
 size_t sample_workspace_bytes(int64_t rows, int vocab, int dtype);                           // the per-row records, bins and partials of its split plan
 int64_t sample_chunks_per_row(int vocab);                                                    // workgroups per row of its launch plan
+void launch_spec_accept(const fa_spec_accept_params& s, hipStream_t stream);                 // fa_spec_verify.hip: rejection sampling per draft node
+void launch_spec_walk(const fa_spec_walk_params& s, hipStream_t stream);                     // .. and the walk over the decisions
+size_t spec_accept_workspace_bytes(int64_t rows, int vocab);                                 // the chunk partials and sums of its launch plan
+int64_t spec_accept_chunks(int vocab);                                                       // workgroups per node of its launch plan
 void launch_act_mul(const fa_act_mul_params& s, hipStream_t stream);                         // fa_act_mul.hip: act(gate) * up, element-wise
 void launch_act_mul_bwd(const fa_act_mul_bwd_params& s, hipStream_t stream);                 // its backward (dgate, dup)
 struct ActPlan { int chunk_pieces; int64_t nchunks, items; int grid; };                      // its launch plan: runs per row, items, grid
@@ -233,6 +237,8 @@ size_t fa_add_norm_bwd_params_size(void) { return sizeof(fa_add_norm_bwd_params)
 size_t fa_cross_entropy_params_size(void) { return sizeof(fa_cross_entropy_params); }
 size_t fa_cross_entropy_bwd_params_size(void) { return sizeof(fa_cross_entropy_bwd_params); }
 size_t fa_sample_params_size(void) { return sizeof(fa_sample_params); }
+size_t fa_spec_accept_params_size(void) { return sizeof(fa_spec_accept_params); }
+size_t fa_spec_walk_params_size(void) { return sizeof(fa_spec_walk_params); }
 size_t fa_act_mul_params_size(void) { return sizeof(fa_act_mul_params); }
 size_t fa_act_mul_bwd_params_size(void) { return sizeof(fa_act_mul_bwd_params); }
 size_t fa_quant_fp8_params_size(void) { return sizeof(fa_quant_fp8_params); }
@@ -1342,6 +1348,92 @@ static int sample_check(const fa_sample_params& s, bool query) {
     return check_overlaps(op, out, 5, in, 6, true);
 }
 
+// fa_spec_accept's argument rules.  query: the workspace itself and where the tensors lie are not looked at
+static int spec_accept_check(const fa_spec_accept_params& s, bool query) {
+    const char* op = "spec_accept";
+    FA_CHECK(s.target_logits && s.draft_probs && s.draft_ids && s.accept && s.recovered,
+             "%s: target_logits, draft_probs, draft_ids, accept and recovered must not be NULL", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.dtype == FA_FP16 || s.dtype == FA_BF16 || s.dtype == FA_FP32, "%s: dtype must be fp16, bf16 or fp32", op);
+    FA_CHECK(s.probs_dtype == FA_FP16 || s.probs_dtype == FA_BF16 || s.probs_dtype == FA_FP32, "%s: probs_dtype must be fp16, bf16 or fp32", op);
+    const int esize = s.dtype == FA_FP32 ? 4 : 2, qsize = s.probs_dtype == FA_FP32 ? 4 : 2;
+    FA_CHECK(s.nodes >= 1 && s.nodes <= 64, "%s: nodes must be in 1 .. 64, got %d", op, s.nodes);
+    FA_CHECK(s.vocab >= 1, "%s: vocab must be at least 1, got %d", op, s.vocab);
+    FA_CHECK(s.batch >= 0, "%s: batch must be non-negative", op);
+    // (a node that is greedy whatever its logits - the host temperature is not above 0 - never reads the uniform numbers)
+    FA_CHECK((s.u_accept && s.u_recover) || (!s.temperature && !(s.temperature_value > 0.f)),
+             "%s: u_accept and u_recover are needed unless the temperature is the host scalar 0", op);
+    if (s.batch > 0x7fffffffLL / s.nodes) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 nodes in one launch", op);
+    const int64_t rows = s.batch * s.nodes;
+    FA_CHECK(ce_stride_ok(s.logits_row_stride, rows, s.vocab) && ce_stride_ok(s.probs_row_stride, rows, s.vocab),
+             "%s: row strides must be non-negative and (batch x nodes > 1) at least vocab", op);
+    FA_CHECK(s.parents_batch_stride >= 0, "%s: parents_batch_stride must be non-negative", op);
+    FA_CHECK(addr(s.target_logits) % esize == 0 && addr(s.draft_probs) % qsize == 0 &&
+             ((addr(s.draft_ids) | addr(s.parents) | addr(s.u_accept) | addr(s.u_recover) | addr(s.temperature) | addr(s.accept) | addr(s.recovered)) & 3) == 0,
+             "%s: target_logits / draft_probs must be aligned to their element, every int32 / fp32 array to 4 bytes", op);
+    if (s.vocab > (1 << 20)) return fail(FA_ERR_UNSUPPORTED, "%s: vocab %d is above 2^20 (the integer masses of a row must fit 64 bits)", op, s.vocab);
+    if (rows > 0x7fffffffLL / fa::spec_accept_chunks(s.vocab))
+        return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 workgroups (nodes x chunks) in one launch", op);
+    if (query) return FA_OK;
+    const size_t need = fa::spec_accept_workspace_bytes(rows, s.vocab);
+    if (need)
+        FA_CHECK(s.workspace && s.workspace_bytes >= need, "%s: the workspace holds %zu bytes, fa_spec_accept_workspace_bytes() reports %zu",
+                 op, s.workspace ? s.workspace_bytes : (size_t)0, need);
+    FA_CHECK(addr(s.workspace) % 16 == 0, "%s: the workspace must be 16-byte aligned", op);
+    const uint64_t vbytes = (uint64_t)rows * 4;
+    const uint64_t pbytes = rows > 0 ? (uint64_t)((s.batch - 1) * s.parents_batch_stride + s.nodes) * 4 : 0;
+    const View in[] = {
+        view_rows("target_logits", s.target_logits, rows, s.logits_row_stride, s.vocab, esize),
+        view_rows("draft_probs", s.draft_probs, rows, s.probs_row_stride, s.vocab, qsize),
+        view_flat("draft_ids", s.draft_ids, vbytes),
+        view_flat("parents", s.parents, pbytes),
+        view_flat("u_accept", s.u_accept, vbytes),
+        view_flat("u_recover", s.u_recover, vbytes),
+        view_flat("temperature", s.temperature, s.batch > 0 ? (uint64_t)s.batch * 4 : 0),
+    };
+    const View out[] = {
+        view_flat("accept", s.accept, vbytes),
+        view_flat("recovered", s.recovered, vbytes),
+        view_flat("workspace", need ? s.workspace : nullptr, need),
+    };
+    return check_overlaps(op, out, 3, in, 7, true);
+}
+
+// fa_spec_walk's argument rules
+static int spec_walk_check(const fa_spec_walk_params& s) {
+    const char* op = "spec_walk";
+    FA_CHECK(s.draft_ids && s.target_ids && s.out_tokens && s.num_out && s.path_nodes,
+             "%s: draft_ids, target_ids, out_tokens, num_out and path_nodes must not be NULL", op);
+    FA_CHECK(!s.accept == !s.recovered, "%s: accept and recovered go together (both, or neither: deterministic drafts)", op);
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.nodes >= 1 && s.nodes <= 64, "%s: nodes must be in 1 .. 64, got %d", op, s.nodes);
+    FA_CHECK(s.batch >= 0, "%s: batch must be non-negative", op);
+    FA_CHECK(s.parents_batch_stride >= 0 && s.target_ids_batch_stride >= 0 && s.target_ids_node_stride >= 0,
+             "%s: strides must be non-negative", op);
+    FA_CHECK(((addr(s.parents) | addr(s.draft_ids) | addr(s.target_ids) | addr(s.accept) | addr(s.recovered) | addr(s.out_tokens) |
+               addr(s.num_out) | addr(s.path_nodes)) & 3) == 0, "%s: every array must be 4-byte aligned", op);
+    if (s.batch > 0x7fffffffLL / s.nodes) return fail(FA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 nodes in one launch", op);
+    const bool any = s.batch > 0;
+    const uint64_t vbytes = any ? (uint64_t)s.batch * s.nodes * 4 : 0;
+    const uint64_t pbytes = any ? (uint64_t)((s.batch - 1) * s.parents_batch_stride + s.nodes) * 4 : 0;
+    const uint64_t tbytes = any ? (uint64_t)((s.batch - 1) * s.target_ids_batch_stride + (s.nodes - 1) * s.target_ids_node_stride + 1) * 4 : 0;
+    const View in[] = {
+        view_flat("parents", s.parents, pbytes),
+        view_flat("draft_ids", s.draft_ids, vbytes),
+        view_flat("target_ids", s.target_ids, tbytes),
+        view_flat("accept", s.accept, vbytes),
+        view_flat("recovered", s.recovered, vbytes),
+    };
+    const View out[] = {
+        view_flat("out_tokens", s.out_tokens, vbytes),
+        view_flat("num_out", s.num_out, any ? (uint64_t)s.batch * 4 : 0),
+        view_flat("path_nodes", s.path_nodes, vbytes),
+    };
+    return check_overlaps(op, out, 3, in, 5, true);
+}
+
 // what fa_act_mul and fa_act_mul_bwd share: dtype, activation, n, rows, and that rows x runs fits a grid index
 static int act_mul_common_check(const char* op, int dtype, int activation, int n, int64_t rows) {
     FA_TRY(check_io_dtype(op, dtype, "dtype"));
@@ -1833,6 +1925,32 @@ int fa_sample(const fa_sample_params* sp, void* stream) {
     s.struct_size = sizeof(s);
     fa::launch_sample(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_sample launch");
+}
+
+size_t fa_spec_accept_workspace_bytes(const fa_spec_accept_params* sp) {
+    if (!sp || sp->struct_size < sizeof(fa_spec_accept_params)) return 0;
+    if (spec_accept_check(*sp, true) != FA_OK) return 0;
+    return fa::spec_accept_workspace_bytes(sp->batch * sp->nodes, sp->vocab);
+}
+
+int fa_spec_accept(const fa_spec_accept_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_spec_accept_params"));
+    fa_spec_accept_params s = *sp;
+    FA_TRY(spec_accept_check(s, false));
+    if (s.batch == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_spec_accept(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_spec_accept launch");
+}
+
+int fa_spec_walk(const fa_spec_walk_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_spec_walk_params"));
+    fa_spec_walk_params s = *sp;
+    FA_TRY(spec_walk_check(s));
+    if (s.batch == 0) return FA_OK;
+    s.struct_size = sizeof(s);
+    fa::launch_spec_walk(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_spec_walk launch");
 }
 
 int fa_cross_entropy_bwd(const fa_cross_entropy_bwd_params* sp, void* stream) {

@@ -347,6 +347,40 @@ class FaSampleParams(ctypes.Structure):
     ]
 
 
+class FaSpecAcceptParams(ctypes.Structure):
+    """Mirror of `struct fa_spec_accept_params` (include/fa_mi355.h): fa_spec_accept, the rejection-sampling decision of every
+    draft node of a speculative-decoding step.  struct_size must be set to sizeof(FaSpecAcceptParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("target_logits", _ptr), ("draft_probs", _ptr),       # [batch x nodes, vocab] of dtype / probs_dtype
+        ("draft_ids", _ptr), ("parents", _ptr),               # int32 [batch, nodes]; int32 or NULL: the chain
+        ("u_accept", _ptr), ("u_recover", _ptr),              # fp32 [batch x nodes]
+        ("temperature", _ptr),                                # fp32 [batch], or NULL: temperature_value
+        ("accept", _ptr), ("recovered", _ptr),                # int32 [batch x nodes], written
+        ("workspace", _ptr), ("workspace_bytes", ctypes.c_size_t),
+        ("logits_row_stride", _i64), ("probs_row_stride", _i64), ("parents_batch_stride", _i64),
+        ("batch", _i64),
+        ("nodes", _i32), ("vocab", _i32), ("dtype", _i32), ("probs_dtype", _i32),
+        ("temperature_value", _f32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaSpecWalkParams(ctypes.Structure):
+    """Mirror of `struct fa_spec_walk_params` (include/fa_mi355.h): fa_spec_walk, the walk over a request's draft tree that
+    emits the tokens and the accepted path.  struct_size must be set to sizeof(FaSpecWalkParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("parents", _ptr), ("draft_ids", _ptr), ("target_ids", _ptr),
+        ("accept", _ptr), ("recovered", _ptr),                # fa_spec_accept's outputs, or both NULL: deterministic drafts
+        ("out_tokens", _ptr), ("num_out", _ptr), ("path_nodes", _ptr),   # written
+        ("parents_batch_stride", _i64), ("target_ids_batch_stride", _i64), ("target_ids_node_stride", _i64),
+        ("batch", _i64),
+        ("nodes", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 class FaActMulParams(ctypes.Structure):
     """Mirror of `struct fa_act_mul_params` (include/fa_mi355.h): fa_act_mul, the gated activation act(gate) * up of the MLP
     (up NULL: act(gate)).  struct_size must be set to sizeof(FaActMulParams)."""
@@ -524,6 +558,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_cross_entropy", "fa_cross_entropy_workspace_bytes", "fa_cross_entropy_params_size",
            "fa_cross_entropy_bwd", "fa_cross_entropy_bwd_params_size",
            "fa_sample", "fa_sample_workspace_bytes", "fa_sample_params_size",
+           "fa_spec_accept", "fa_spec_accept_workspace_bytes", "fa_spec_accept_params_size",
+           "fa_spec_walk", "fa_spec_walk_params_size",
            "fa_act_mul", "fa_act_mul_params_size", "fa_act_mul_plan", "fa_act_mul_bwd", "fa_act_mul_bwd_params_size",
            "fa_quant_fp8", "fa_quant_fp8_params_size", "fa_add_norm_quant", "fa_add_norm_quant_params_size",
            "fa_act_mul_quant", "fa_act_mul_quant_params_size",
@@ -548,6 +584,8 @@ ROW_OPS = [
     ("fa_cross_entropy", FaCrossEntropyParams, "fa_cross_entropy_workspace_bytes"),
     ("fa_cross_entropy_bwd", FaCrossEntropyBwdParams, None),
     ("fa_sample", FaSampleParams, "fa_sample_workspace_bytes"),
+    ("fa_spec_accept", FaSpecAcceptParams, "fa_spec_accept_workspace_bytes"),
+    ("fa_spec_walk", FaSpecWalkParams, None),
     ("fa_act_mul", FaActMulParams, None),
     ("fa_act_mul_bwd", FaActMulBwdParams, None),
     ("fa_quant_fp8", FaQuantFp8Params, None),
@@ -689,8 +727,8 @@ call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
 # call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
-# call_sample; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes, cross_entropy_workspace_bytes,
-# sample_workspace_bytes, moe_sort_workspace_bytes
+# call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
+# cross_entropy_workspace_bytes, sample_workspace_bytes, spec_accept_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
     if _query:

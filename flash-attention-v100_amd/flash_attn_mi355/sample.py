@@ -20,8 +20,8 @@ exp(t) is exp2(t * log2(e)) on the hardware's exp2; `lse` (return_lse) is m + lo
 csrc/fa_lse.h over x: the log-probability of a token under the UNFILTERED distribution is x_id - lse.
 
 Not covered: repetition / presence / frequency penalties and logit bias; an in-kernel RNG and per-row seeds; top-n log-prob
-outputs; rejection sampling and draft-tree verification for speculative decoding; typical-p and the like; vocab > 2^20; in-place
-`top_k_top_p_filter`.  Nothing here is exported through the packages' `__all__` lists."""
+outputs; typical-p and the like; vocab > 2^20; in-place `top_k_top_p_filter` (rejection sampling and draft-tree verification for
+speculative decoding: `spec_decode`).  Nothing here is exported through the packages' `__all__` lists."""
 import ctypes
 
 import torch

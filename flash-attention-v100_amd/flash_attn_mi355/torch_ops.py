@@ -15,7 +15,8 @@ quantisation alone and fused behind the forwards of add_norm and act_mul, fa_qua
 differentiable; `moe_route` / `moe_route_bwd` / `moe_sort` / `moe_permute` / `moe_combine` / `moe_combine_bwd`: top-k routing, the
 stable sort of the (token, k) slots by expert, the permutation into per-expert segments and the weighted combine of a
 mixture-of-experts block with autograd formulas, fa_moe_*; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
-sampling from logits and the filtered logits alone, fa_sample, not differentiable - registered, but not listed in `__all__`).
+sampling from logits and the filtered logits alone, fa_sample, not differentiable; `spec_accept` / `spec_walk` / `spec_verify`:
+speculative-decoding verification, fa_spec_accept / fa_spec_walk, not differentiable - registered, but not listed in `__all__`).
 
 Counterpart of the reference's TorchBind block (kernel/fused_mha_api.cpp:308-358: `fwd`, `bwd`,
 `varlen_fwd`, `varlen_bwd`, `fwd_kvcache` under `flash_attn_v100_cuda`).  The argument ORDER follows
@@ -51,6 +52,7 @@ from . import quant as _quant
 from . import rope_store as _rope_store
 from . import rotary as _rotary
 from . import sample as _sample
+from . import spec_decode as _spec
 
 _NS = "flash_attn_mi355"
 
@@ -808,6 +810,57 @@ def sample_filter(logits: Tensor, temperature: Optional[Tensor], temperature_val
 @sample_filter.register_fake
 def _(logits, temperature, temperature_value, top_k, top_k_value, top_p, top_p_value, min_p, min_p_value):
     return logits.new_empty(logits.shape)
+
+
+# ------------------------------------------------------------------------------------------
+# speculative-decoding verification (flash_attn_mi355.spec_decode; csrc/fa_spec_verify.hip).  The temperature is an optional
+# [B] tensor plus the number that holds where the tensor is None.
+# Reached as torch.ops.flash_attn_mi355.spec_accept / .spec_walk / .spec_verify; not in __all__
+# ------------------------------------------------------------------------------------------
+@torch.library.custom_op(f"{_NS}::spec_accept", mutates_args=(), device_types="cuda")
+def spec_accept(target_logits: Tensor, draft_probs: Tensor, draft_ids: Tensor, u_accept: Tensor, u_recover: Tensor,
+                parents: Optional[Tensor], temperature: Optional[Tensor], temperature_value: float) -> Tuple[Tensor, Tensor]:
+    """spec_decode.accept_forward: (accept int32 [B, T], recovered int32 [B, T])"""
+    return _spec.accept_forward(target_logits, draft_probs, draft_ids, u_accept, u_recover, parents=parents,
+                                temperature=temperature_value if temperature is None else temperature)
+
+
+@spec_accept.register_fake
+def _(target_logits, draft_probs, draft_ids, u_accept, u_recover, parents, temperature, temperature_value):
+    shape = draft_ids.shape
+    return draft_ids.new_empty(shape, dtype=torch.int32), draft_ids.new_empty(shape, dtype=torch.int32)
+
+
+def _spec_walk_fake(draft_ids):
+    B, T = draft_ids.shape
+    return (draft_ids.new_empty((B, T), dtype=torch.int32), draft_ids.new_empty((B,), dtype=torch.int32),
+            draft_ids.new_empty((B, T), dtype=torch.int32))
+
+
+@torch.library.custom_op(f"{_NS}::spec_walk", mutates_args=(), device_types="cuda")
+def spec_walk(draft_ids: Tensor, target_ids: Tensor, parents: Optional[Tensor], accept: Optional[Tensor],
+              recovered: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """spec_decode.walk: (out_tokens int32 [B, T], num_out int32 [B], path_nodes int32 [B, T])"""
+    return _spec.walk(draft_ids, target_ids, parents=parents, accept=accept, recovered=recovered)
+
+
+@spec_walk.register_fake
+def _(draft_ids, target_ids, parents, accept, recovered):
+    return _spec_walk_fake(draft_ids)
+
+
+@torch.library.custom_op(f"{_NS}::spec_verify", mutates_args=(), device_types="cuda")
+def spec_verify(target_logits: Tensor, draft_ids: Tensor, draft_probs: Optional[Tensor], parents: Optional[Tensor],
+                temperature: Optional[Tensor], temperature_value: float, u_sample: Tensor, u_accept: Optional[Tensor],
+                u_recover: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """spec_decode.verify_forward: (out_tokens, num_out, path_nodes) of a whole verification step"""
+    return _spec.verify_forward(target_logits, draft_ids, draft_probs, parents,
+                                temperature_value if temperature is None else temperature, u_sample, u_accept, u_recover)
+
+
+@spec_verify.register_fake
+def _(target_logits, draft_ids, draft_probs, parents, temperature, temperature_value, u_sample, u_accept, u_recover):
+    return _spec_walk_fake(draft_ids)
 
 
 # ------------------------------------------------------------------------------------------

@@ -1056,8 +1056,8 @@ size_t fa_cross_entropy_bwd_params_size(void);
  * reported; an output that overlaps an input, another output or the workspace; non-zero reserved fields.  vocab > 2^20 or
  * rows > 2^31 - 1: FA_ERR_UNSUPPORTED.  rows == 0: FA_OK without a launch.
  * Not covered: repetition / presence / frequency penalties and logit bias; an in-kernel RNG and per-row seeds; top-n log-prob
- * outputs; rejection sampling and draft-tree verification for speculative decoding; typical-p and the like; vocab > 2^20; in-place
- * `filtered`.
+ * outputs; typical-p and the like; vocab > 2^20; in-place `filtered`.  (Rejection sampling and draft-tree verification for
+ * speculative decoding: fa_spec_accept / fa_spec_walk below.)
  */
 typedef struct fa_sample_params {
     size_t         struct_size;      /* sizeof(fa_sample_params) as the caller compiled it */
@@ -1089,6 +1089,122 @@ int    fa_sample(const fa_sample_params* s, void* stream);
  * where the tensors lie are not looked at; 0 for a block that the call rejects for any other reason */
 size_t fa_sample_workspace_bytes(const fa_sample_params* s);
 size_t fa_sample_params_size(void);
+
+/*
+ * fa_spec_accept / fa_spec_walk - speculative-decoding verification: the rejection-sampling decision per draft node and the walk
+ * that turns the decisions into the emitted tokens and the accepted path (additive: fa_params and FA_ABI_VERSION are unchanged).
+ * What stands between fa_fwd_kvcache_tree (the draft chain or tree scored in one pass), fa_sample (ids from logits) and the commit
+ * of the accepted path (fa_kv_gather + fa_kv_store by slot).  Neither op holds an RNG: the uniform numbers are the caller's.
+ *
+ * The data model.  A request has `nodes` = T nodes, 1 <= T <= 64: the query tokens of the tree-attention call.  Node 0 is the root,
+ * the last token that is already accepted.  Node t >= 1 has parents[t] in [0, t); any other value (negative, or >= t) marks a
+ * PADDING node, which is never visited - ragged draft lengths inside a fixed-shape batch.  parents is int32, request b's at
+ * parents + b x parents_batch_stride (0: one tree for every request); NULL: the chain parents[t] = t - 1.  parents[0] is not
+ * read.  draft_ids is int32 [batch, T] (entry 0 is not read).  Row (b, t) of a [batch x T, vocab] tensor is row b T + t.
+ *
+ * fa_spec_accept: per node t >= 1 that is no padding node, from the TARGET row P = (b, parents[t]) of target_logits (`dtype`
+ * FA_FP16 / FA_BF16 / FA_FP32; it may hold fa_sample's `filtered` output: -inf outside a kept set) and the DRAFT row (b, t) of
+ * draft_probs (`probs_dtype`, one of the same three; q_j = float(draft_probs[(b, t), j]) as it is, never renormalised), with
+ * d = draft_ids[b, t] and T_b = request b's temperature (temperature[b], or temperature_value where the array is NULL):
+ *  1. The target row's values v_j, the order, j*, "empty" and "greedy" are fa_sample's (rules 1 and 2 above, with T_b).
+ *       empty row:   accept = 0, recovered = -1.
+ *       greedy row:  (!(T_b > 0), v_{j*} = +inf, or x_{j*} not finite):  accept = (d == j*), recovered = j*; q and the uniform
+ *                    numbers are not read.
+ *  2. Masses, otherwise: inv_t, x_j, m = x_{j*} and e_j exactly as in fa_sample's rule 3.  s = the sum-exp of fa_lse.h's running
+ *     (max, sum-exp) pair over x in this op's fixed order (8-column pieces in column order; a lane's pieces; the wave butterfly;
+ *     the waves of a chunk in index order; the chunks in index order) - its maximum IS m.  p_j = e_j * (1.0f / s): one fp32 division
+ *     for the row, one product per token.
+ *  3. Accept: uu = u_accept[b T + t] with a NaN or a negative value read as 0; accept = (uu * q_d < p_d): one fp32 product, one
+ *     compare (a NaN q_d rejects).  d outside [0, vocab): accept = 0, and no address is formed from d.
+ *  4. Recovered token: r_j = min(max(p_j - q_j, 0), 1) - one fp32 subtraction; a NaN difference counts as 0 (the cap at 1 can
+ *     only bind where q_j < 0).  The integer mass R_j = floor(r_j * 2^40) (uint64), R = the sum of the R_j: integer, so
+ *     order-free.  If R == 0 (q covers p everywhere): R_j := floor(e_j * 2^40), fa_sample's q_j - the target's own masses.
+ *     uu_r = u_recover[b T + t] read like uu; rr = min(floor((double)uu_r * (double)R), R - 1); recovered = the smallest index
+ *     whose index-order running sum of R_j exceeds rr.
+ *  Node 0 and padding nodes: accept = 0, recovered = -1.  Every element of accept / recovered (int32 [batch x T]) is written.
+ * Launch plan, a function of vocab alone: a row is cut into C = ceil(vocab / 16384) chunks, one workgroup of 1024 lanes each, and
+ * three kernels follow each other on the stream - (1) batch x T x C workgroups: the chunk's (m, s), first maximum and count of
+ * values above -inf over the target row, one 32-byte partial each (plain stores); (2) batch x T x C workgroups: every chunk merges
+ * the node's partials in chunk order (so all get the same m and s) and writes the chunk's sum of R_j and of floor(e_j 2^40)
+ * (plain stores); (3) batch x T workgroups: the node's totals, the accept test (two element loads), the chunk that holds rr, and
+ * one sweep of that chunk for the index.  A piece is one 16-byte load (fp32: two) where the row starts on a 16-byte boundary and
+ * the piece lies inside the row, element loads otherwise: the same bits.  No float atomics, no workgroup waits for another, the
+ * workspace needs no initialisation: fa_spec_accept_workspace_bytes() = batch x T x (48 x C rounded up to 64) bytes.  A node's
+ * result depends on (vocab, the dtypes), its two rows, d, T_b and its two uniform numbers alone.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL target_logits, draft_probs, draft_ids, accept or
+ * recovered; a missing u_accept / u_recover (they may be NULL only where temperature is NULL and !(temperature_value > 0)); a
+ * dtype other than the three; nodes outside 1 .. 64; vocab < 1; a negative batch or stride, or (batch x T > 1) a row stride below
+ * vocab; rows not aligned to their element, an int32 / fp32 array not 4-byte aligned, a workspace not 16-byte aligned or smaller
+ * than reported; an output that overlaps an input, the other output or the workspace; non-zero reserved fields.  vocab > 2^20 or
+ * more than 2^31 - 1 workgroups: FA_ERR_UNSUPPORTED.  batch == 0: FA_OK without a launch.
+ *
+ * fa_spec_walk: one wave per request, lane t owns node t, at most T steps whatever the data (a step ends the walk or moves to a
+ * node of higher index).  c = 0; target_ids is int32, node t of request b at target_ids[b x target_ids_batch_stride + t x
+ * target_ids_node_stride] (node stride 0: one id per request - a chain's bonus token).
+ *   accept == NULL (deterministic drafts; recovered must be NULL too): emit y = target_ids[c]; if y == -1 stop; t = the child of c
+ *     of LOWEST index with draft_ids[t] == y; none: stop; else append t to the path, c = t, repeat.
+ *   accept given (with recovered: fa_spec_accept's outputs): t = the child of c of lowest index - its siblings are NOT looked at;
+ *     none: emit target_ids[c] (the bonus token), stop; accept[t] != 0: emit draft_ids[t], append t, c = t, repeat; else emit
+ *     recovered[t], stop.
+ * Outputs, int32, every element written: out_tokens [batch, T] - the emitted tokens in order, then -1; num_out [batch] - their
+ * number, 1 .. T; path_nodes [batch, T] - 0, t_1, t_2, .. (the accepted nodes, root included), then -1.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL draft_ids, target_ids or output; accept without recovered
+ * or the reverse; nodes outside 1 .. 64; a negative batch or stride; an array not 4-byte aligned; an output that overlaps an input
+ * or another output; non-zero reserved fields.  batch == 0: FA_OK without a launch.
+ * Not covered: multi-child trees with draft probabilities (SpecInfer's multi-round rule: with draft_probs only the first child
+ * of a node is tried); typical acceptance; an in-kernel RNG; a fused commit of the accepted path into the cache; vocab > 2^20.
+ */
+typedef struct fa_spec_accept_params {
+    size_t         struct_size;      /* sizeof(fa_spec_accept_params) as the caller compiled it */
+    const void*    target_logits;    /* [batch x nodes, vocab] of `dtype` */
+    const void*    draft_probs;      /* [batch x nodes, vocab] of `probs_dtype` */
+    const int32_t* draft_ids;        /* device int32 [batch, nodes] */
+    const int32_t* parents;          /* device int32, or NULL: the chain */
+    const float*   u_accept;         /* device fp32 [batch x nodes] */
+    const float*   u_recover;        /* device fp32 [batch x nodes] */
+    const float*   temperature;      /* device fp32 [batch], or NULL: temperature_value */
+    int32_t*       accept;           /* device [batch x nodes], written */
+    int32_t*       recovered;        /* device [batch x nodes], written */
+    void*          workspace;        /* fa_spec_accept_workspace_bytes() bytes, 16-byte aligned */
+    size_t         workspace_bytes;
+    int64_t        logits_row_stride, probs_row_stride;   /* elements */
+    int64_t        parents_batch_stride;                  /* elements; 0: one tree for every request */
+    int64_t        batch;
+    int32_t        nodes;            /* 1 .. 64 */
+    int32_t        vocab;            /* 1 .. 2^20 */
+    int32_t        dtype;            /* FA_FP16, FA_BF16 or FA_FP32 */
+    int32_t        probs_dtype;      /* FA_FP16, FA_BF16 or FA_FP32 */
+    float          temperature_value;    /* !(T > 0): greedy */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_spec_accept_params;
+
+int    fa_spec_accept(const fa_spec_accept_params* s, void* stream);
+/* the workspace of that call: a function of (batch, nodes, vocab) alone; `workspace`, `workspace_bytes` and where the tensors lie
+ * are not looked at; 0 for a block that the call rejects for any other reason */
+size_t fa_spec_accept_workspace_bytes(const fa_spec_accept_params* s);
+size_t fa_spec_accept_params_size(void);
+
+typedef struct fa_spec_walk_params {
+    size_t         struct_size;      /* sizeof(fa_spec_walk_params) as the caller compiled it */
+    const int32_t* parents;          /* device int32, or NULL: the chain */
+    const int32_t* draft_ids;        /* device int32 [batch, nodes] */
+    const int32_t* target_ids;       /* device int32, strided (below) */
+    const int32_t* accept;           /* device int32 [batch x nodes], or NULL: deterministic drafts */
+    const int32_t* recovered;        /* device int32 [batch x nodes]; NULL exactly where accept is */
+    int32_t*       out_tokens;       /* device [batch, nodes], written */
+    int32_t*       num_out;          /* device [batch], written */
+    int32_t*       path_nodes;       /* device [batch, nodes], written */
+    int64_t        parents_batch_stride;                           /* elements; 0: one tree for every request */
+    int64_t        target_ids_batch_stride, target_ids_node_stride;   /* elements */
+    int64_t        batch;
+    int32_t        nodes;            /* 1 .. 64 */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_spec_walk_params;
+
+int    fa_spec_walk(const fa_spec_walk_params* s, void* stream);
+size_t fa_spec_walk_params_size(void);
 
 /*
  * fa_act_mul - the gated activation of the MLP, act(gate) * up: SwiGLU, GeGLU and their ungated forms, forward (additive:
