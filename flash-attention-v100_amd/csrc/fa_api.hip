@@ -14,6 +14,7 @@
 #include <string>
 #include "fa_common.h"
 #include "fa_moe.h"                                   // fa_moe.hip: the limits, the sort plan and the launchers of fa_moe_*
+#include "fa_moe_gemm.h"                              // fa_moe_gemm.hip: the limits, the launch plan and the launcher of fa_moe_gemm
 
 namespace fa {
 int launch_fwd(const KArgs& a, hipStream_t stream);
@@ -250,6 +251,7 @@ size_t fa_moe_sort_params_size(void) { return sizeof(fa_moe_sort_params); }
 size_t fa_moe_permute_params_size(void) { return sizeof(fa_moe_permute_params); }
 size_t fa_moe_combine_params_size(void) { return sizeof(fa_moe_combine_params); }
 size_t fa_moe_combine_bwd_params_size(void) { return sizeof(fa_moe_combine_bwd_params); }
+size_t fa_moe_gemm_params_size(void) { return sizeof(fa_moe_gemm_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1745,6 +1747,62 @@ static int moe_permute_check(const fa_moe_permute_params& s) {
     return check_overlaps(op, &out, 1, in, 3, false, nullptr, 0);
 }
 
+// the shape arguments fa_moe_gemm and fa_moe_gemm_plan share
+static int moe_gemm_shape_check(const char* op, int64_t rows, int n, int k, int num_experts, int layout, int dtype) {
+    FA_CHECK(rows >= 0, "%s: rows must be non-negative", op);
+    FA_TRY(check_io_dtype(op, dtype, "dtype"));
+    FA_CHECK(layout == FA_MOE_W_NK || layout == FA_MOE_W_KN, "%s: layout must be FA_MOE_W_NK or FA_MOE_W_KN, got %d", op, layout);
+    if (num_experts < 2 || num_experts > fa::MOE_MAX_EXPERTS)
+        return fail(FA_ERR_UNSUPPORTED, "%s: num_experts must be in [2, %d], got %d", op, fa::MOE_MAX_EXPERTS, num_experts);
+    if (n < 8 || n > fa::MOE_GEMM_MAX_N || n % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: n must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_GEMM_MAX_N, n);
+    if (k < 8 || k > fa::MOE_GEMM_MAX_K || k % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: k must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_GEMM_MAX_K, k);
+    if (rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: rows must stay below 2^31", op);
+    if (fa::moe_gemm_plan(rows, n, k, num_experts, layout, dtype).grid_m >= (1 << 24))
+        return fail(FA_ERR_UNSUPPORTED, "%s: rows = %lld needs more row tiles than one launch has", op, (long long)rows);
+    return FA_OK;
+}
+
+static int moe_gemm_check(const fa_moe_gemm_params& s) {
+    const char* op = "moe_gemm";
+    FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(moe_gemm_shape_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
+    const bool gather = s.sorted_slot != nullptr;
+    if (gather) {
+        FA_CHECK(s.tokens >= 0, "%s: tokens must be non-negative", op);
+        if (s.top_k < 1 || s.top_k > fa::MOE_MAX_TOPK)
+            return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, %d], got %d", op, fa::MOE_MAX_TOPK, s.top_k);
+        if (s.tokens > 0x7fffffffLL / s.top_k) return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k must stay below 2^31", op);
+    }
+    if (s.w_expert_stride < (int64_t)s.n * s.k || s.w_expert_stride % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: w_expert_stride must be a multiple of 8 and at least n x k = %lld, got %lld", op,
+                    (long long)s.n * s.k, (long long)s.w_expert_stride);
+    if (s.x_row_stride < 0 || s.x_row_stride % 8 != 0 || s.x_row_stride > fa::MOE_GEMM_MAX_ROW_STRIDE)
+        return fail(FA_ERR_UNSUPPORTED, "%s: x_row_stride must be a multiple of 8 in [0, 2^22], got %lld", op, (long long)s.x_row_stride);
+    if (s.out_row_stride < 0 || s.out_row_stride % 8 != 0 || s.out_row_stride > fa::MOE_GEMM_MAX_ROW_STRIDE)
+        return fail(FA_ERR_UNSUPPORTED, "%s: out_row_stride must be a multiple of 8 in [0, 2^22], got %lld", op, (long long)s.out_row_stride);
+    if (s.bias && s.bias_dtype != s.dtype && s.bias_dtype != FA_FP32)
+        return fail(FA_ERR_UNSUPPORTED, "%s: bias_dtype must be dtype or fp32", op);
+    if (s.rows == 0) return FA_OK;
+    const int64_t x_rows = gather ? s.tokens : s.rows;
+    FA_CHECK(s.out && s.w && s.expert_offsets && (x_rows == 0 || s.x), "%s: x, w, expert_offsets and out must not be NULL", op);
+    FA_CHECK(s.rows <= 1 || s.out_row_stride >= s.n, "%s: out rows must not overlap (out_row_stride >= n)", op);
+    FA_CHECK(x_rows <= 1 || s.x_row_stride >= s.k, "%s: x_row_stride must be at least k", op);
+    FA_CHECK(((addr(s.x) | addr(s.w) | addr(s.out)) & 15) == 0, "%s: x, w and out must be 16-byte aligned", op);
+    FA_CHECK(((addr(s.expert_offsets) | addr(s.sorted_slot)) & 3) == 0 && (addr(s.bias) & (s.bias_dtype == FA_FP32 ? 3 : 1)) == 0,
+             "%s: expert_offsets, sorted_slot and bias must be aligned to their elements", op);
+    const View in[] = {
+        view_rows("x", s.x, x_rows, s.x_row_stride, s.k, 2),
+        view_rows("w", s.w, s.num_experts, s.w_expert_stride, (int64_t)s.n * s.k, 2),
+        view_flat("bias", s.bias, (uint64_t)s.num_experts * s.n * (s.bias_dtype == FA_FP32 ? 4 : 2)),
+        view_flat("expert_offsets", s.expert_offsets, (uint64_t)(s.num_experts + 1) * 4),
+        view_flat("sorted_slot", s.sorted_slot, (uint64_t)s.rows * 4),
+    };
+    const View out = view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2);
+    return check_overlaps(op, &out, 1, in, 5, false, nullptr, 0);
+}
+
 static int moe_combine_check(const fa_moe_combine_params& s) {
     const char* op = "moe_combine";
     FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
@@ -2093,6 +2151,28 @@ int fa_moe_combine_bwd(const fa_moe_combine_bwd_params* sp, void* stream) {
     if (s.rows == 0) s.dy = nullptr;
     fa::launch_moe_combine_bwd(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_combine_bwd launch");
+}
+
+int fa_moe_gemm_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                     int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n) {
+    FA_TRY(moe_gemm_shape_check("moe_gemm_plan", rows, n, k, num_experts, layout, dtype));
+    const fa::MoeGemmPlan pl = fa::moe_gemm_plan(rows, n, k, num_experts, layout, dtype);
+    if (block_m) *block_m = pl.bm;
+    if (block_n) *block_n = pl.bn;
+    if (block_k) *block_k = pl.bk;
+    if (grid_m) *grid_m = pl.grid_m;
+    if (grid_n) *grid_n = pl.grid_n;
+    return FA_OK;
+}
+
+int fa_moe_gemm(const fa_moe_gemm_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_gemm_params"));
+    fa_moe_gemm_params s = *sp;
+    FA_TRY(moe_gemm_check(s));
+    if (s.rows == 0) return FA_OK;
+    if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
+    fa::launch_moe_gemm(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_gemm launch");
 }
 
 }  // extern "C"

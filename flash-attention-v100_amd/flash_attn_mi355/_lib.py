@@ -18,6 +18,7 @@ FA_FLAG_TREE_MASK = 16
 FA_ACT_SILU, FA_ACT_GELU, FA_ACT_GELU_TANH, FA_ACT_RELU, FA_ACT_RELU2 = 0, 1, 2, 3, 4    # enum fa_act
 FA_QUANT_ROW, FA_QUANT_GROUP, FA_QUANT_STATIC = 0, 1, 2                                  # enum fa_quant_mode
 FA_MOE_SOFTMAX, FA_MOE_SIGMOID = 0, 1                                                    # enum fa_moe_scoring
+FA_MOE_W_NK, FA_MOE_W_KN = 0, 1                                                          # enum fa_moe_w_layout
 
 _i64, _i32, _f32, _u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
 _ptr = ctypes.c_void_p
@@ -543,6 +544,21 @@ class FaMoeCombineBwdParams(ctypes.Structure):
     ]
 
 
+class FaMoeGemmParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_gemm_params` (include/fa_mi355.h): fa_moe_gemm, the grouped expert GEMM over the segments of
+    expert_offsets.  struct_size must be set to sizeof(FaMoeGemmParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("x", _ptr), ("w", _ptr), ("bias", _ptr), ("expert_offsets", _ptr), ("sorted_slot", _ptr),
+        ("out", _ptr),
+        ("x_row_stride", _i64), ("out_row_stride", _i64), ("w_expert_stride", _i64),
+        ("rows", _i64), ("tokens", _i64),
+        ("num_experts", _i32), ("top_k", _i32), ("n", _i32), ("k", _i32),
+        ("dtype", _i32), ("bias_dtype", _i32), ("layout", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -566,7 +582,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_moe_route", "fa_moe_route_params_size", "fa_moe_route_bwd", "fa_moe_route_bwd_params_size",
            "fa_moe_sort", "fa_moe_sort_params_size", "fa_moe_sort_workspace_bytes", "fa_moe_sort_plan",
            "fa_moe_permute", "fa_moe_permute_params_size", "fa_moe_combine", "fa_moe_combine_params_size",
-           "fa_moe_combine_bwd", "fa_moe_combine_bwd_params_size"] + EXT_OPS
+           "fa_moe_combine_bwd", "fa_moe_combine_bwd_params_size",
+           "fa_moe_gemm", "fa_moe_gemm_params_size", "fa_moe_gemm_plan"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -597,6 +614,7 @@ ROW_OPS = [
     ("fa_moe_permute", FaMoePermuteParams, None),
     ("fa_moe_combine", FaMoeCombineParams, None),
     ("fa_moe_combine_bwd", FaMoeCombineBwdParams, None),
+    ("fa_moe_gemm", FaMoeGemmParams, None),
 ]
 
 
@@ -646,6 +664,8 @@ def _load():
     lib.fa_act_mul_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
     lib.fa_moe_sort_plan.restype = ctypes.c_int
     lib.fa_moe_sort_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
+    lib.fa_moe_gemm_plan.restype = ctypes.c_int
+    lib.fa_moe_gemm_plan.argtypes = [i64] + [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.POINTER(i64)] * 2
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
     lib.fa_scatter_rows.restype = ctypes.c_int
@@ -727,6 +747,7 @@ call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
 # call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
+# call_moe_gemm,
 # call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes, sample_workspace_bytes, spec_accept_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
@@ -760,3 +781,14 @@ def moe_sort_plan(slots, num_experts):
     if rc != 0:
         raise RuntimeError(f"fa_moe_sort_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
     return tuple(o.value for o in out)
+
+
+def moe_gemm_plan(rows, n, k, num_experts, layout, dtype):
+    """fa_moe_gemm_plan: (block_m, block_n, block_k, grid_m, grid_n) of fa_moe_gemm, a function of its arguments alone; needs
+    no device"""
+    blk = [ctypes.c_int32() for _ in range(3)]
+    grid = [ctypes.c_int64() for _ in range(2)]
+    rc = lib.fa_moe_gemm_plan(rows, n, k, num_experts, layout, dtype, *(ctypes.byref(o) for o in blk + grid))
+    if rc != 0:
+        raise RuntimeError(f"fa_moe_gemm_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+    return tuple(o.value for o in blk + grid)

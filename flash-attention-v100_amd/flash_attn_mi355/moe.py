@@ -1,12 +1,14 @@
 """What surrounds the expert GEMMs of a mixture-of-experts block, on the library's `fa_moe_*` kernels (csrc/fa_moe.hip): top-k
 routing with its gradient, the stable sort of the (token, k) slots by expert, the permutation of the activations into per-expert
-segments and the weighted combine with its backward.  The GEMMs themselves stay with hipBLASLt / `torch._grouped_mm`: they see
-contiguous, `align`-padded segments of `xp` described by `expert_offsets`.
+segments and the weighted combine with its backward - and, on csrc/fa_moe_gemm.hip, the forward grouped expert GEMM `moe_gemm`
+over the contiguous, `align`-padded segments of `xp` that `expert_offsets` describes (its docstring has its contract; the weight
+gradient stays with hipBLASLt / `torch._grouped_mm`).
 
     weights, ids = moe_route(logits, k)                         # fp32 [T, K], int32 [T, K]
     sorted_slot, pos, expert_offsets = moe_sort(ids, E, align=16)
     xp = moe_permute(x, sorted_slot, k, pos=pos)                # [M_max, N], M_max = T K + E (align - 1)
-    yp = experts(xp, expert_offsets)                            # the caller's grouped GEMMs
+    yp = experts(xp, expert_offsets)                            # the grouped GEMMs: moe_gemm(xp, w, expert_offsets), or the
+                                                                # first one as moe_gemm(x, w, .., sorted_slot=.., top_k=k) without xp
     out = moe_combine(yp, weights, pos)                         # [T, N]
 
 No function synchronises with the host, every result is a pure function of its inputs (no ordering depends on an atomic, two calls
@@ -61,8 +63,8 @@ Limits (outside them: RuntimeError naming the argument, before any device work):
 multiple of 8 up to 16384 in fp16 / bf16, T K + E (align - 1) < 2^31, 1 <= align <= 256.  CPU tensors raise: there is no fallback.
 
 Not covered: grouped top-k (`n_group` / `topk_group`), capacity factors and token dropping by load, the auxiliary load-balancing
-loss, a gradient for the bias or for permute's scale, an fp8 / quantised permute, fusing into the expert GEMMs, the GEMMs
-themselves, expert-parallel all-to-all, E > 512, K > 16, fp32 activations, a double backward.  Nothing here is exported through
+loss, a gradient for the bias or for permute's scale, an fp8 / quantised permute, fusing an activation or the combine into the
+expert GEMMs, their weight gradient, expert-parallel all-to-all, E > 512, K > 16, fp32 activations, a double backward.  Nothing here is exported through
 the packages' `__all__` lists."""
 import ctypes
 
@@ -73,6 +75,8 @@ from . import _rowargs as _ra
 from . import flash_attn_interface as _fi
 
 MAX_EXPERTS, MAX_TOPK, MAX_ALIGN, MAX_N = 512, 16, 256, 16384
+GEMM_MAX_K, GEMM_MAX_N, GEMM_MAX_ROW_STRIDE = 32768, 65536, 2 ** 22
+W_LAYOUTS = {"nk": _lib.FA_MOE_W_NK, "kn": _lib.FA_MOE_W_KN}
 SCORINGS = {"softmax": _lib.FA_MOE_SOFTMAX, "sigmoid": _lib.FA_MOE_SIGMOID}
 _LOGIT_DTYPES = {torch.float16: _lib.FA_FP16, torch.bfloat16: _lib.FA_BF16, torch.float32: _lib.FA_FP32}
 
@@ -396,3 +400,124 @@ def moe_combine(y, weights, pos):
     _fi._check_device(y, weights, pos)
     from . import torch_ops as _ops
     return _ops.moe_combine(y, weights, pos)
+
+
+def _gemm_dim(op, v, name, most):
+    if v < 8 or v > most or v % 8:
+        raise RuntimeError(f"{op}: {name} must be a multiple of 8 in [8, {most}], got {v}")
+
+
+def _gemm_rows(op, t, name):
+    """a [rows, cols] operand of the GEMM as the kernel takes it: nothing is copied, a layout it cannot read raises"""
+    if t.stride(1) != 1 and t.shape[1] != 1:
+        raise RuntimeError(f"{op}: {name} must have a contiguous last dimension, got strides {tuple(t.stride())}")
+    if t.data_ptr() % 16 or t.stride(0) % 8 or t.stride(0) > GEMM_MAX_ROW_STRIDE or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise RuntimeError(f"{op}: {name} must be 16-byte aligned with a row stride that is a multiple of 8, at least its row "
+                           f"length and at most 2^22, got offset {t.data_ptr() % 16} and stride {t.stride(0)}")
+
+
+def moe_gemm_plan(M_max, N, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):
+    """(block_m, block_n, block_k, grid_m, grid_n) of `moe_gemm`: a function of these arguments alone, no device"""
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"moe_gemm_plan: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if dtype not in _fi._DTYPES:
+        raise RuntimeError(f"moe_gemm_plan: dtype must be fp16 or bf16, got {dtype}")
+    return _lib.moe_gemm_plan(int(M_max), int(N), int(K), int(num_experts), W_LAYOUTS[w_layout], _fi._DTYPES[dtype])
+
+
+def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None, top_k=None, out=None):
+    """The grouped expert GEMM (csrc/fa_moe_gemm.hip), forward, fp16 / bf16 with fp32 accumulation: out [M_max, N] with
+
+        out[r] = round16(sum_k float(a_r[k]) * float(W_e[k, n]) (+ float(bias[e, n])))    expert_offsets[e] <= r < expert_offsets[e + 1]
+        out[r] = +0                                                                       expert_offsets[E] <= r < M_max
+
+    one launch, no workspace, nothing read on the host: `expert_offsets` (int32 [E + 1], moe_sort's) stays on the device, so a
+    decode step with its host-known M_max is capturable.  M_max is out.shape[0]; without `sorted_slot` it is x.shape[0] and
+    a_r = x[r] (x = moe_permute's output).  With `sorted_slot` (int32 [M_max]) and `top_k`, x is the un-permuted [T, K] and
+    a_r = x[sorted_slot[r] // top_k], a slot outside [0, T top_k) - the -1 padding - being a row of +0 that forms no address:
+    the bits of moe_gemm(moe_permute(x, sorted_slot, top_k), ...) without the permute launch and the xp buffer.
+
+    w_layout "nk": w [E, N, K] (nn.Linear, vLLM, DeepSeek); "kn": w [E, K, N] (HF gpt-oss) - also the data gradient of an "nk"
+    layer, dx = moe_gemm(dy, w, offsets, w_layout="kn"), N and K exchanged.  w may be a view with any expert stride >= N K (a
+    multiple of 8) and contiguous experts, 16-byte aligned.  bias [E, N] of the io dtype or fp32.  x and out: 16-byte aligned,
+    contiguous last dimension, row strides multiples of 8 (nothing is copied; another layout raises).
+
+    Every output element is one fp32 accumulator chain of v_mfma_f32_32x32x16 over k ascending in steps of 16 from +0, in both
+    tile shapes (`moe_gemm_plan`); the bias is added to the finished sum.  A row's bits depend on its source row, W_e, bias[e]
+    and K alone.  expert_offsets values are only compared and clamped to [0, M_max]: a malformed table gives wrong rows, never
+    an address outside out, x or w.
+
+    Limits: 2 <= E <= 512, K and N multiples of 8 with K <= 32768 and N <= 65536, row strides of x and out at most 2^22 elements,
+    M_max >= 0 (0 launches nothing); expert_offsets[0] is 0 (moe_sort's: rows below a positive first offset are not written).  No autograd:
+    an input that requires grad raises.  Not covered: the weight gradient, fp8 / block-scaled operands, an activation or the
+    combine fused into the epilogue, a per-row routing weight, E > 512."""
+    op = "moe_gemm"
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"{op}: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    for name, t in (("x", x), ("w", w), ("bias", bias)):
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{op}: {name} requires grad, and moe_gemm has no autograd (detach it, or run under no_grad)")
+    if x.dtype not in _fi._DTYPES:
+        raise RuntimeError(f"{op}: x must be fp16 or bf16, got {x.dtype}")
+    if x.dim() != 2:
+        raise RuntimeError(f"{op}: x must be [rows, K], got {tuple(x.shape)}")
+    if w.dtype != x.dtype or w.dim() != 3:
+        raise RuntimeError(f"{op}: w must be a {x.dtype} tensor [E, N, K] ('nk') or [E, K, N] ('kn'), got {w.dtype} {tuple(w.shape)}")
+    K = x.shape[1]
+    E = w.shape[0]
+    N = w.shape[1] if w_layout == "nk" else w.shape[2]
+    if (w.shape[2] if w_layout == "nk" else w.shape[1]) != K:
+        raise RuntimeError(f"{op}: w {tuple(w.shape)} in layout {w_layout!r} does not contract with x's K = {K}")
+    if not (2 <= E <= MAX_EXPERTS):
+        raise RuntimeError(f"{op}: num_experts (w.shape[0]) must be in [2, {MAX_EXPERTS}], got {E}")
+    _gemm_dim(op, K, "K", GEMM_MAX_K)
+    _gemm_dim(op, N, "N", GEMM_MAX_N)
+    if w.stride(2) != 1 or w.stride(1) != w.shape[2] or w.stride(0) < N * K or w.stride(0) % 8 or w.data_ptr() % 16:
+        raise RuntimeError(f"{op}: w must be 16-byte aligned with contiguous experts and an expert stride that is a multiple of 8 "
+                           f"and at least N K, got strides {tuple(w.stride())}")
+    expert_offsets = _table(op, expert_offsets, (E + 1,), torch.int32, "expert_offsets")
+    if (sorted_slot is None) != (top_k is None):
+        raise RuntimeError(f"{op}: sorted_slot and top_k go together")
+    if sorted_slot is not None:
+        top_k = int(top_k)
+        _topk(op, top_k)
+        _slots(op, x.shape[0], top_k)
+        if sorted_slot.dtype != torch.int32 or sorted_slot.dim() != 1:
+            raise RuntimeError(f"{op}: sorted_slot must be an int32 tensor [M_max], got {sorted_slot.dtype} {tuple(sorted_slot.shape)}")
+        M = sorted_slot.shape[0]
+        sorted_slot = sorted_slot.contiguous()
+    else:
+        M = x.shape[0]
+    if M >= 2 ** 31:
+        raise RuntimeError(f"{op}: M_max must stay below 2^31, got {M}")
+    if bias is not None and (bias.dtype not in (x.dtype, torch.float32) or tuple(bias.shape) != (E, N)):
+        raise RuntimeError(f"{op}: bias must be {x.dtype} or fp32 of shape {(E, N)}, got {bias.dtype} {tuple(bias.shape)}")
+    if out is not None and (out.dtype != x.dtype or tuple(out.shape) != (M, N)):
+        raise RuntimeError(f"{op}: out must be {x.dtype} of shape {(M, N)}, got {out.dtype} {tuple(out.shape)}")
+    if x.shape[0]:
+        _gemm_rows(op, x, "x")
+    if out is not None and M:
+        _gemm_rows(op, out, "out")
+    _ra.same_device(op, [x, w, expert_offsets, bias, sorted_slot, out], x, "x's")
+    dev = x.device
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=dev)
+    if M == 0:
+        return out
+    bi = None if bias is None else bias.contiguous()
+    s = _lib.FaMoeGemmParams()
+    s.struct_size = ctypes.sizeof(_lib.FaMoeGemmParams)
+    s.x, s.x_row_stride = (x.data_ptr() if x.shape[0] else 0), x.stride(0)
+    s.w, s.w_expert_stride = w.data_ptr(), w.stride(0)
+    if bi is not None:
+        s.bias, s.bias_dtype = bi.data_ptr(), (_lib.FA_FP32 if bi.dtype == torch.float32 else _fi._DTYPES[bi.dtype])
+    s.expert_offsets = expert_offsets.data_ptr()
+    if sorted_slot is not None:
+        s.sorted_slot, s.tokens, s.top_k = sorted_slot.data_ptr(), x.shape[0], top_k
+    s.out, s.out_row_stride = out.data_ptr(), out.stride(0)
+    s.rows, s.num_experts, s.n, s.k = M, E, N, K
+    s.dtype, s.layout = _fi._DTYPES[x.dtype], W_LAYOUTS[w_layout]
+    with _fi._on_device(dev):
+        _lib.call_moe_gemm(s, _fi._stream(dev))
+    del bi, expert_offsets, sorted_slot
+    return out

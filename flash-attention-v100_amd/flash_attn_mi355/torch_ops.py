@@ -14,7 +14,8 @@ in place, fa_act_mul / fa_act_mul_bwd; `quant_fp8` / `add_norm_quant` / `act_mul
 quantisation alone and fused behind the forwards of add_norm and act_mul, fa_quant_fp8 / fa_add_norm_quant / fa_act_mul_quant, not
 differentiable; `moe_route` / `moe_route_bwd` / `moe_sort` / `moe_permute` / `moe_combine` / `moe_combine_bwd`: top-k routing, the
 stable sort of the (token, k) slots by expert, the permutation into per-expert segments and the weighted combine of a
-mixture-of-experts block with autograd formulas, fa_moe_*; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
+mixture-of-experts block with autograd formulas, fa_moe_*, and `moe_gemm`, its forward grouped expert GEMM over `expert_offsets`,
+fa_moe_gemm, not differentiable; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
 sampling from logits and the filtered logits alone, fa_sample, not differentiable; `spec_accept` / `spec_walk` / `spec_verify`:
 speculative-decoding verification, fa_spec_accept / fa_spec_walk, not differentiable - registered, but not listed in `__all__`).
 
@@ -1217,3 +1218,18 @@ def _moe_combine_backward(ctx, dout):
 
 
 moe_combine.register_autograd(_moe_combine_backward, setup_context=_moe_combine_setup)
+
+
+# the grouped expert GEMM between permute and combine (moe.moe_gemm; csrc/fa_moe_gemm.hip): torch.ops.flash_attn_mi355.moe_gemm
+@torch.library.custom_op(f"{_NS}::moe_gemm", mutates_args=(), device_types="cuda")
+def moe_gemm(x: Tensor, w: Tensor, expert_offsets: Tensor, w_layout: str, bias: Optional[Tensor], sorted_slot: Optional[Tensor],
+             top_k: Optional[int]) -> Tensor:
+    """moe.moe_gemm: out [M_max, N], a fresh contiguous tensor (M_max = sorted_slot's length, or x's rows).  Functional and
+    capturable: expert_offsets is device data and the output shape does not depend on it.  No autograd is registered."""
+    return _moe.moe_gemm(x, w, expert_offsets, w_layout=w_layout, bias=bias, sorted_slot=sorted_slot, top_k=top_k)
+
+
+@moe_gemm.register_fake
+def _(x, w, expert_offsets, w_layout, bias, sorted_slot, top_k):
+    M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
+    return x.new_empty((M, w.shape[1] if w_layout == "nk" else w.shape[2]))

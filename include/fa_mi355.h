@@ -1588,6 +1588,67 @@ int    fa_moe_combine_bwd(const fa_moe_combine_bwd_params* s, void* stream);
 size_t fa_moe_combine_bwd_params_size(void);
 
 /*
+ * fa_moe_gemm: the grouped expert GEMM of a mixture-of-experts block, forward, fp16 / bf16 with fp32 accumulation
+ * (csrc/fa_moe_gemm.hip).  One launch, no workspace, no atomics, no host synchronisation: expert_offsets (int32 [E + 1], as
+ * fa_moe_sort writes it) stays on the device.  rows = M_max, the rows of out.
+ *   segment rows   expert_offsets[e] <= r < expert_offsets[e + 1]:
+ *                  out[r, n] = round(sum_k float(a_r[k]) * float(W_e[k, n]) (+ float(bias[e, n]))), fp32 accumulation, ONE rounding
+ *   other rows     expert_offsets[E] <= r < rows: +0.  With expert_offsets[0] == 0 (fa_moe_sort's) every element of out is written
+ *                  exactly once; rows below a positive expert_offsets[0] belong to no segment and are left unwritten.
+ *   a_r            sorted_slot NULL: x[r], x being [rows, k] (fa_moe_permute's output).  sorted_slot (int32 [rows]) given: x is the
+ *                  un-permuted [tokens, k] and a_r = x[sorted_slot[r] / top_k]; a slot outside [0, tokens * top_k) - the -1 padding -
+ *                  reads as a row of +0 and forms no address.  fa_moe_gemm with sorted_slot has the bits of fa_moe_permute followed
+ *                  by fa_moe_gemm.
+ *   layout         FA_MOE_W_NK: w is [E, n, k] (W_e[k, n] = w[e, n, k], nn.Linear);  FA_MOE_W_KN: w is [E, k, n].  The "kn" call
+ *                  with n and k exchanged is the data gradient of an "nk" layer.
+ *   order          every output element has one accumulator chain of v_mfma_f32_32x32x16 over k ascending in steps of 16 from +0,
+ *                  in every tile shape; the bias is added to the finished sum in fp32.  A row's bits are a function of its source
+ *                  row, W_e, bias[e] and k alone - not of rows, of the row's place in its segment or of the other experts.
+ *   tensors        w: 16-byte aligned, w_expert_stride >= n * k and a multiple of 8 (elements; every offset is 64-bit).  x, out:
+ *                  16-byte aligned, row strides multiples of 8, at most 2^22, out's at least n.  bias: [E, n] contiguous of `dtype`
+ *                  or FA_FP32 (bias_dtype), or NULL.
+ *   limits         2 <= num_experts <= 512; n, k multiples of 8, n <= 65536, k <= 32768; 0 <= rows < 2^31 (rows == 0 launches
+ *                  nothing); with sorted_slot 1 <= top_k <= 16 and tokens * top_k < 2^31.  Outside: FA_ERR_UNSUPPORTED, before
+ *                  any device work.
+ *   offsets        expert_offsets values are only compared and clamped to [0, rows]: a decreasing or out-of-range table gives
+ *                  wrong rows, never an address outside out, x or w.
+ * fa_moe_gemm_plan: the launch plan, a function of its arguments alone; needs no device.  block_m is 128 (prefill) or 32 (decode:
+ *   rows <= 32 * num_experts), block_n 128, block_k 64; grid_m = floor(rows / block_m) + num_experts + 1 bounds the tiles that
+ *   num_experts segments and the +0 tail can need (a workgroup finds its (expert, tile) from expert_offsets; one without a tile
+ *   leaves), grid_n = ceil(n / block_n).  Each output pointer may be NULL.
+ */
+typedef enum fa_moe_w_layout {
+    FA_MOE_W_NK = 0,
+    FA_MOE_W_KN = 1
+} fa_moe_w_layout;
+
+typedef struct fa_moe_gemm_params {
+    size_t         struct_size;      /* sizeof(fa_moe_gemm_params) as the caller compiled it */
+    const void*    x;                /* [rows, k], or with sorted_slot [tokens, k], of `dtype` */
+    const void*    w;                /* [num_experts, n, k] (FA_MOE_W_NK) or [num_experts, k, n] (FA_MOE_W_KN) of `dtype` */
+    const void*    bias;             /* [num_experts, n] of `bias_dtype`, contiguous; NULL: none */
+    const void*    expert_offsets;   /* int32 [num_experts + 1], device */
+    const void*    sorted_slot;      /* int32 [rows]; NULL: the plain form */
+    void*          out;              /* [rows, n] of `dtype` */
+    int64_t        x_row_stride, out_row_stride;   /* elements, multiples of 8 */
+    int64_t        w_expert_stride;  /* elements, >= n * k, a multiple of 8 */
+    int64_t        rows;             /* M_max */
+    int64_t        tokens;           /* rows of x with sorted_slot; ignored without */
+    int32_t        num_experts, top_k;              /* top_k: with sorted_slot only */
+    int32_t        n, k;
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        bias_dtype;       /* `dtype` or FA_FP32; ignored without bias */
+    int32_t        layout;           /* fa_moe_w_layout */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_gemm_params;
+
+int    fa_moe_gemm(const fa_moe_gemm_params* s, void* stream);
+size_t fa_moe_gemm_params_size(void);
+int    fa_moe_gemm_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                        int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
