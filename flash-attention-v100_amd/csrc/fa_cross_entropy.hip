@@ -37,44 +37,22 @@ constexpr int CE_BWD_CHUNK = CE_UNROLL * CE_STEP;         // columns per backwar
 static_assert(FA_CE_CHUNK16 % CE_STEP == 0 && FA_CE_CHUNK32 % CE_STEP == 0 && FA_CE_CHUNK16 > 0 && FA_CE_CHUNK32 > 0,
               "a chunk is whole steps of the workgroup");
 
-struct fp32_tag {};
-
-// one element / one whole piece of the logits' type
-template <typename T> struct CeIo {
-    static constexpr int ESIZE = 2;
-    static __device__ __forceinline__ float load1(const void* p, int64_t at) {
-        return Elem<T>::lo((uint32_t) static_cast<const uint16_t*>(p)[at]);
-    }
-    static __device__ __forceinline__ void store1(void* p, int64_t at, float v) {
-        static_cast<uint16_t*>(p)[at] = (uint16_t)Elem<T>::pack2(v, 0.f);
-    }
-    static __device__ __forceinline__ void load8(const void* p, int64_t at, float (&v)[8]) { row_load8<T>(p, at, false, v); }
-    static __device__ __forceinline__ void store8(void* p, int64_t at, const float (&v)[8]) { row_store8<T>(p, at, false, v); }
-};
-template <> struct CeIo<fp32_tag> {
-    static constexpr int ESIZE = 4;
-    static __device__ __forceinline__ float load1(const void* p, int64_t at) { return static_cast<const float*>(p)[at]; }
-    static __device__ __forceinline__ void store1(void* p, int64_t at, float v) { static_cast<float*>(p)[at] = v; }
-    static __device__ __forceinline__ void load8(const void* p, int64_t at, float (&v)[8]) { row_load8<bf16_tag>(p, at, true, v); }
-    static __device__ __forceinline__ void store8(void* p, int64_t at, const float (&v)[8]) { row_store8<bf16_tag>(p, at, true, v); }
-};
-
 // the row starts on a 16-byte boundary: its whole pieces are taken with vector accesses
 template <typename T>
 __device__ __forceinline__ bool ce_row_vec(const void* base, int64_t rowoff) {
-    return ((reinterpret_cast<uintptr_t>(base) + (uint64_t)rowoff * CeIo<T>::ESIZE) & 15) == 0;
+    return ((reinterpret_cast<uintptr_t>(base) + (uint64_t)rowoff * RowIo<T>::ESIZE) & 15) == 0;
 }
 
 // l of the piece at column `col` of the row at element offset `rowoff`; columns >= V: -inf
 template <typename T>
 __device__ __forceinline__ void ce_load_piece(const void* x, int64_t rowoff, int64_t col, int V, bool vec, float scale, float (&l)[8]) {
     if (vec && col + 8 <= V) {
-        CeIo<T>::load8(x, rowoff + col, l);
+        RowIo<T>::load8(x, rowoff + col, l);
 #pragma unroll
         for (int i = 0; i < 8; ++i) l[i] = scale * l[i];
     } else {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) l[i] = col + i < V ? scale * CeIo<T>::load1(x, rowoff + col + i) : -INFINITY;
+        for (int i = 0; i < 8; ++i) l[i] = col + i < V ? scale * RowIo<T>::load1(x, rowoff + col + i) : -INFINITY;
     }
 }
 
@@ -109,7 +87,7 @@ __device__ __forceinline__ void ce_finish(const CeArgs& a, int64_t row, const Ls
         if (lab < 0 || lab >= a.V) {
             loss = z = NAN;
         } else {
-            const float ll = a.scale * CeIo<T>::load1(a.x, row * a.x_rs + lab);
+            const float ll = a.scale * RowIo<T>::load1(a.x, row * a.x_rs + lab);
             loss = fmaf(-a.one_minus_ls, ll, lse);
             if (a.smooth) loss = fmaf(-a.ls_over_v, sum_l, loss);
             z = (a.zscale * lse) * lse;
@@ -228,11 +206,11 @@ __global__ void __launch_bounds__(CE_THREADS) ce_bwd_kernel(const CeBwdArgs a) {
         const int64_t col = base + (int64_t)u * CE_STEP;
         if (col >= a.V) continue;
         if (vec_out && col + 8 <= a.V) {
-            CeIo<T>::store8(a.dx, doff + col, v[u]);
+            RowIo<T>::store8(a.dx, doff + col, v[u]);
         } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (col + i < a.V) CeIo<T>::store1(a.dx, doff + col + i, v[u][i]);
+                if (col + i < a.V) RowIo<T>::store1(a.dx, doff + col + i, v[u][i]);
         }
     }
 }

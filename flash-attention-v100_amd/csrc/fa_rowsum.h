@@ -138,6 +138,28 @@ __device__ __forceinline__ void row_store8(void* base, int64_t at, bool fp32, co
     }
 }
 
+// one element / one whole piece of a row of type T (fp32: fp32_tag): the accessor of fa_cross_entropy, fa_sample and fa_spec_accept
+// (fa_moe.hip keeps a loader of its own on purpose: it tests the alignment per piece and fills with 0)
+struct fp32_tag {};
+template <typename T> struct RowIo {
+    static constexpr int ESIZE = 2;
+    static __device__ __forceinline__ float load1(const void* p, int64_t at) {
+        return Elem<T>::lo((uint32_t) static_cast<const uint16_t*>(p)[at]);
+    }
+    static __device__ __forceinline__ void store1(void* p, int64_t at, float v) {
+        static_cast<uint16_t*>(p)[at] = (uint16_t)Elem<T>::pack2(v, 0.f);
+    }
+    static __device__ __forceinline__ void load8(const void* p, int64_t at, float (&v)[8]) { row_load8<T>(p, at, false, v); }
+    static __device__ __forceinline__ void store8(void* p, int64_t at, const float (&v)[8]) { row_store8<T>(p, at, false, v); }
+};
+template <> struct RowIo<fp32_tag> {
+    static constexpr int ESIZE = 4;
+    static __device__ __forceinline__ float load1(const void* p, int64_t at) { return static_cast<const float*>(p)[at]; }
+    static __device__ __forceinline__ void store1(void* p, int64_t at, float v) { static_cast<float*>(p)[at] = v; }
+    static __device__ __forceinline__ void load8(const void* p, int64_t at, float (&v)[8]) { row_load8<bf16_tag>(p, at, true, v); }
+    static __device__ __forceinline__ void store8(void* p, int64_t at, const float (&v)[8]) { row_store8<bf16_tag>(p, at, true, v); }
+};
+
 // v rounded to the 16-bit type and widened again: the value a 16-bit store of v leaves
 template <typename T>
 __device__ __forceinline__ void row_round8(float (&v)[8]) {

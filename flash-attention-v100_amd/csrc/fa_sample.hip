@@ -1,7 +1,7 @@
 // fa_sample.hip - token sampling from [rows, vocab] logits (fa_sample, include/fa_mi355.h): temperature, top-k, min-p, top-p and
 // one inverse-CDF draw from a caller-supplied uniform number per row; fp16 / bf16 / fp32 logits.  The rules are in the header; in
-// short, with v_j the raw values (a NaN counts as -inf, -0 as +0) in the order "larger value, then lower index":
-//     x_j = v_j * inv_t (one rounding),  m = x_{j*},  e_j = e(x_j - m) (fa_lse.h's e),  q_j = floor(e_j * 2^40)  (uint64)
+// short, the row's statistics, its e_j and its integer masses q_j = floor(e_j * 2^40) are fa_mass.h's - the arithmetic this op shares
+// with fa_spec_accept (fa_spec_verify.hip), the row view, the statistics sweep, the draw target and the walk step included -
 // and every decision after that is INTEGER arithmetic on the q_j - a sum of them does not depend on the order of addition, so the
 // LDS integer adds below cost no repeatability.  No float atomics, no host synchronisation, no RNG: capturable.
 // Launch plan below SM_SPLIT_MIN columns: ONE workgroup of 1024 lanes per row, no workspace (the split plan for longer rows is
@@ -21,38 +21,12 @@
 //     draw             per-wave kept mass -> Q, rr = min(floor(u Q), Q - 1), then the one wave that holds rr walks its run again
 //     filtered         the logit's own bits where kept, -inf elsewhere
 // Every walk is an in-wave shuffle scan; no loop depends on the data.
-#include <cmath>
-#include <cstdint>
-#include "fa_lse.h"
+#include "fa_mass.h"
 
 namespace fa {
 
-constexpr int SM_THREADS = 1024;
-constexpr int SM_WAVES = SM_THREADS / 64;
 constexpr int SM_REP = 8;                                 // copies of every histogram bin
-constexpr int SM_ALL = 0x7fffffff;                        // tie index: the whole class is kept
-
-struct fp32_tag {};
-
-// one element / one whole piece of the logits' type (fa_cross_entropy.hip's CeIo)
-template <typename T> struct SmIo {
-    static constexpr int ESIZE = 2;
-    static __device__ __forceinline__ float load1(const void* p, int64_t at) {
-        return Elem<T>::lo((uint32_t) static_cast<const uint16_t*>(p)[at]);
-    }
-    static __device__ __forceinline__ void store1(void* p, int64_t at, float v) {
-        static_cast<uint16_t*>(p)[at] = (uint16_t)Elem<T>::pack2(v, 0.f);
-    }
-    static __device__ __forceinline__ void load8(const void* p, int64_t at, float (&v)[8]) { row_load8<T>(p, at, false, v); }
-    static __device__ __forceinline__ void store8(void* p, int64_t at, const float (&v)[8]) { row_store8<T>(p, at, false, v); }
-};
-template <> struct SmIo<fp32_tag> {
-    static constexpr int ESIZE = 4;
-    static __device__ __forceinline__ float load1(const void* p, int64_t at) { return static_cast<const float*>(p)[at]; }
-    static __device__ __forceinline__ void store1(void* p, int64_t at, float v) { static_cast<float*>(p)[at] = v; }
-    static __device__ __forceinline__ void load8(const void* p, int64_t at, float (&v)[8]) { row_load8<bf16_tag>(p, at, true, v); }
-    static __device__ __forceinline__ void store8(void* p, int64_t at, const float (&v)[8]) { row_store8<bf16_tag>(p, at, true, v); }
-};
+constexpr int SM_ALL = MASS_NONE;                         // tie index: the whole class is kept
 
 // the order-preserving integer key of a canonical value (no NaN, no -0): a larger value has a larger key, equal values equal keys
 __device__ __forceinline__ uint32_t sm_key32(float v) {
@@ -76,42 +50,15 @@ template <> struct SmKey<fp16_tag> {
     }
 };
 
-__device__ __forceinline__ float sm_canon(float v) { return v != v ? -INFINITY : (v == 0.f ? 0.f : v); }
-
-// e_j and q_j
-__device__ __forceinline__ float sm_e(float v, float inv_t, float m) { return lse_exp(v * inv_t - m); }
-__device__ __forceinline__ uint64_t sm_q(float e) { return e > 0.f ? (uint64_t)(e * 1099511627776.0f) : 0ull; }
-
-__device__ __forceinline__ uint64_t sm_shfl_up64(uint64_t v, int off) {
-    const uint32_t lo = __shfl_up((uint32_t)v, off), hi = __shfl_up((uint32_t)(v >> 32), off);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t sm_shfl_xor64(uint64_t v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t sm_shfl64(uint64_t v, int lane) {
-    const uint32_t lo = __shfl((uint32_t)v, lane), hi = __shfl((uint32_t)(v >> 32), lane);
-    return ((uint64_t)hi << 32) | lo;
-}
-// the inclusive sum over the lanes 0 .. own of the wave
-__device__ __forceinline__ uint64_t sm_wave_scan64(uint64_t v, int lane) {
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t t = sm_shfl_up64(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
 struct SmShared {
     uint64_t mass[256 * SM_REP];
     uint64_t tmass[256];
-    uint64_t slot64[2 * SM_WAVES];
+    uint64_t slot64[2 * MASS_WAVES];
     uint64_t cum_m, sel_mass;
     uint32_t cnt[256 * SM_REP];
     uint32_t tcnt[256];
-    uint32_t slot32[2 * SM_WAVES];
-    float slotf[3 * SM_WAVES];
+    uint32_t slot32[2 * MASS_WAVES];
+    float slotf[3 * MASS_WAVES];
     uint32_t sel_bin, cum_c, sel_cnt;
     int found;
 };
@@ -133,41 +80,17 @@ struct SmArgs {
     int32_t top_k_value;
 };
 
-// a row as a lane sees it
-template <typename T> struct SmRow {
-    const void* x;
-    int64_t rowoff;
-    int V, iters, wave, lane;
-    int gw;                                               // the wave's run among all runs of the row (one workgroup: == wave)
-    bool vec;
-    __device__ __forceinline__ int col(int i) const { return 8 * ((gw * iters + i) * 64 + lane); }
-    // the raw values of the piece at column c (c < V); columns >= V: -inf
-    __device__ __forceinline__ void raw(int c, float (&r)[8]) const {
-        if (vec && c + 8 <= V) {
-            SmIo<T>::load8(x, rowoff + c, r);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r[i] = c + i < V ? SmIo<T>::load1(x, rowoff + c + i) : -INFINITY;
-        }
-    }
-    __device__ __forceinline__ void values(int c, float (&v)[8]) const {
-        raw(c, v);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = sm_canon(v[i]);
-    }
-};
-
 // the kept set: every key above K and the keys equal to K at an index <= I
 struct SmCut { uint32_t K; int I; };
 __device__ __forceinline__ bool sm_kept(const SmCut& c, uint32_t key, int idx) { return key > c.K || (key == c.K && idx <= c.I); }
 
 // block sums / minimum: EVERY lane of the workgroup calls them (they hold barriers)
 __device__ __forceinline__ uint64_t sm_block_sum64(uint64_t v, SmShared& sh, int wave, int lane) {
-    for (int m = 1; m < 64; m <<= 1) v += sm_shfl_xor64(v, m);
+    for (int m = 1; m < 64; m <<= 1) v += shfl_xor64(v, m);
     if (lane == 0) sh.slot64[wave] = v;
     __syncthreads();
     uint64_t t = 0;
-    for (int w = 0; w < SM_WAVES; ++w) t += sh.slot64[w];
+    for (int w = 0; w < MASS_WAVES; ++w) t += sh.slot64[w];
     __syncthreads();
     return t;
 }
@@ -176,7 +99,7 @@ __device__ __forceinline__ uint32_t sm_block_sum32(uint32_t v, SmShared& sh, int
     if (lane == 0) sh.slot32[wave] = v;
     __syncthreads();
     uint32_t t = 0;
-    for (int w = 0; w < SM_WAVES; ++w) t += sh.slot32[w];
+    for (int w = 0; w < MASS_WAVES; ++w) t += sh.slot32[w];
     __syncthreads();
     return t;
 }
@@ -185,7 +108,7 @@ __device__ __forceinline__ uint32_t sm_block_min32(uint32_t v, SmShared& sh, int
     if (lane == 0) sh.slot32[wave] = v;
     __syncthreads();
     uint32_t t = 0xffffffffu;
-    for (int w = 0; w < SM_WAVES; ++w) t = sh.slot32[w] < t ? sh.slot32[w] : t;
+    for (int w = 0; w < MASS_WAVES; ++w) t = sh.slot32[w] < t ? sh.slot32[w] : t;
     __syncthreads();
     return t;
 }
@@ -211,7 +134,7 @@ __device__ __forceinline__ void sm_find_bin(SmShared& sh, uint64_t target, int l
         if (lane >= off) ic += t;
     }
     uint32_t run_c = ic - sc;
-    uint64_t run_m = sm_wave_scan64(sm, lane) - sm;
+    uint64_t run_m = wave_scan64(sm, lane) - sm;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint64_t cum = BY_MASS ? run_m : (uint64_t)run_c;
@@ -233,7 +156,7 @@ struct SmSel { uint32_t K, above_c, cls; uint64_t above_m, qK, rest; };   // res
 // the radix select over the keys of the values above -inf: the key K at which the running count (BY_MASS: mass), taken in
 // descending key order, reaches `target`
 template <typename T, bool BY_MASS>
-__device__ __forceinline__ SmSel sm_select(const SmRow<T>& r, SmShared& sh, float inv_t, float m, uint64_t target) {
+__device__ __forceinline__ SmSel sm_select(const MassRow<T>& r, SmShared& sh, float inv_t, float m, uint64_t target) {
     constexpr int BITS = SmKey<T>::BITS;
     const uint32_t kneg = SmKey<T>::key(-INFINITY);
     const int tid = r.wave * 64 + r.lane;
@@ -241,7 +164,7 @@ __device__ __forceinline__ SmSel sm_select(const SmRow<T>& r, SmShared& sh, floa
     uint64_t cls_mass = 0;
     for (int d = 0; d < BITS / 8; ++d) {
         const int shift = BITS - 8 * (d + 1);
-        for (int j = tid; j < 256 * SM_REP; j += SM_THREADS) { sh.cnt[j] = 0; sh.mass[j] = 0; }
+        for (int j = tid; j < 256 * SM_REP; j += MASS_THREADS) { sh.cnt[j] = 0; sh.mass[j] = 0; }
         if (tid == 0) { sh.sel_bin = 0; sh.cum_c = 0; sh.cum_m = 0; sh.sel_cnt = 0; sh.sel_mass = 0; }
         __syncthreads();
         int cur = -1;
@@ -267,7 +190,7 @@ __device__ __forceinline__ SmSel sm_select(const SmRow<T>& r, SmShared& sh, floa
                         cur = bin; cur_c = 0; cur_m = 0;
                     }
                     cur_c += 1;
-                    cur_m += sm_q(sm_e(v[e], inv_t, m));
+                    cur_m += mass_q(mass_e(v[e], inv_t, m));
                 }
             }
         }
@@ -302,7 +225,7 @@ __device__ __forceinline__ SmSel sm_select(const SmRow<T>& r, SmShared& sh, floa
 
 // the per-wave sums of a weight over the row (sh.slot64[wave]); returns their total.  EVERY lane calls it
 template <typename T, typename W>
-__device__ __forceinline__ uint64_t sm_wave_totals(const SmRow<T>& r, SmShared& sh, const W& weight) {
+__device__ __forceinline__ uint64_t sm_wave_totals(const MassRow<T>& r, SmShared& sh, const W& weight) {
     uint64_t s = 0;
     for (int i = 0; i < r.iters; ++i) {
         const int c = r.col(i);
@@ -312,22 +235,22 @@ __device__ __forceinline__ uint64_t sm_wave_totals(const SmRow<T>& r, SmShared& 
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += weight(v[e], c + e);
     }
-    for (int m = 1; m < 64; m <<= 1) s += sm_shfl_xor64(s, m);
-    if (r.lane == 0) sh.slot64[SM_WAVES + r.wave] = s;
+    for (int m = 1; m < 64; m <<= 1) s += shfl_xor64(s, m);
+    if (r.lane == 0) sh.slot64[MASS_WAVES + r.wave] = s;
     __syncthreads();
     uint64_t t = 0;
-    for (int w = 0; w < SM_WAVES; ++w) t += sh.slot64[SM_WAVES + w];
+    for (int w = 0; w < MASS_WAVES; ++w) t += sh.slot64[MASS_WAVES + w];
     return t;
 }
 
 // behind sm_wave_totals of the same weight: the smallest index whose index-order running weight exceeds `at`; `fallback` where
 // the total does not.  EVERY lane calls it
 template <typename T, typename W>
-__device__ __forceinline__ int sm_find_index(const SmRow<T>& r, SmShared& sh, const W& weight, uint64_t at, int fallback) {
+__device__ __forceinline__ int sm_find_index(const MassRow<T>& r, SmShared& sh, const W& weight, uint64_t at, int fallback) {
     uint64_t base = 0;
     int wstar = -1;
-    for (int w = 0; w < SM_WAVES; ++w) {
-        const uint64_t t = sh.slot64[SM_WAVES + w];
+    for (int w = 0; w < MASS_WAVES; ++w) {
+        const uint64_t t = sh.slot64[MASS_WAVES + w];
         if (wstar < 0) {
             if (base + t > at) wstar = w;
             else base += t;
@@ -350,16 +273,7 @@ __device__ __forceinline__ int sm_find_index(const SmRow<T>& r, SmShared& sh, co
 #pragma unroll
                 for (int e = 0; e < 8; ++e) wv[e] = 0;
             }
-            const uint64_t incl = sm_wave_scan64(ls, r.lane);
-            uint64_t a = running + (incl - ls);
-            if (a <= at && at < a + ls) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    if (a <= at && at < a + wv[e]) sh.found = c + e;
-                    a += wv[e];
-                }
-            }
-            running += sm_shfl64(incl, 63);
+            mass_walk_step(wv, ls, running, at, c, r.lane, sh.found);
         }
     }
     __syncthreads();
@@ -367,92 +281,39 @@ __device__ __forceinline__ int sm_find_index(const SmRow<T>& r, SmShared& sh, co
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SM_THREADS) sample_kernel(const SmArgs a) {
+__global__ void __launch_bounds__(MASS_THREADS) sample_kernel(const SmArgs a) {
     __shared__ SmShared sh;
     const int64_t row = blockIdx.x;
-    SmRow<T> r;
-    r.x = a.x;
-    r.rowoff = row * a.x_rs;
-    r.V = a.V;
-    r.iters = a.iters;
-    r.wave = r.gw = (int)threadIdx.x >> 6;
-    r.lane = (int)threadIdx.x & 63;
-    r.vec = ((reinterpret_cast<uintptr_t>(a.x) + (uint64_t)r.rowoff * SmIo<T>::ESIZE) & 15) == 0;
+    const MassRow<T> r = mass_row_whole<T>(a.x, row * a.x_rs, a.V, a.iters);
     const bool lane0 = threadIdx.x == 0;
 
+    // ---- stats: (m, s) over x, the first maximum, n0 - in every lane
     const float temp = a.temperature ? a.temperature[row] : a.temperature_value;
-    const bool cold = !(temp > 0.f);
-    const float inv_t = cold ? 1.0f : 1.0f / temp;
-
-    // ---- stats: (m, s) over x, the first maximum, n0
-    LseState st = {-INFINITY, 0.f};
-    float bv = -INFINITY;
-    int bi = SM_ALL;
-    uint32_t n0 = 0;
-    for (int i = 0; i < r.iters; ++i) {
-        const int c = r.col(i);
-        if (c >= r.V) continue;
-        float v[8], x[8];
-        r.values(c, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            x[e] = v[e] * inv_t;
-            if (v[e] > bv) { bv = v[e]; bi = c + e; }
-            n0 += v[e] > -INFINITY ? 1u : 0u;
-        }
-        lse_piece(st, x);
-    }
-    st = lse_wave(st);
-    for (int m = 1; m < 64; m <<= 1) {
-        const float ov = __shfl_xor(bv, m);
-        const int oi = __shfl_xor(bi, m);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        n0 += __shfl_xor(n0, m);
-    }
-    if (r.lane == 0) {
-        sh.slotf[r.wave] = st.m;
-        sh.slotf[SM_WAVES + r.wave] = st.s;
-        sh.slotf[2 * SM_WAVES + r.wave] = bv;
-        sh.slot32[r.wave] = (uint32_t)bi;
-        sh.slot32[SM_WAVES + r.wave] = n0;
-    }
-    __syncthreads();
-    st = LseState{sh.slotf[0], sh.slotf[SM_WAVES]};
-    bv = sh.slotf[2 * SM_WAVES];
-    bi = (int)sh.slot32[0];
-    n0 = sh.slot32[SM_WAVES];
-    for (int w = 1; w < SM_WAVES; ++w) {
-        st = lse_merge(st, LseState{sh.slotf[w], sh.slotf[SM_WAVES + w]});
-        const float ov = sh.slotf[2 * SM_WAVES + w];
-        const int oi = (int)sh.slot32[w];
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        n0 += sh.slot32[SM_WAVES + w];
-    }
-    __syncthreads();
+    const MassStat stat = mass_stats(r, mass_inv_t(temp), sh.slotf, sh.slot32, true);
+    __syncthreads();                                              // (the slots are used again below)
+    const MassNode n = mass_node(stat, temp);
+    const float inv_t = n.inv_t, m = n.m;
 
     const uint32_t kneg = SmKey<T>::key(-INFINITY);
-    const bool empty = n0 == 0;
-    const float m = bv * inv_t;                                   // x_{j*}
-    const bool greedy = cold || !(fabsf(m) < INFINITY);           // (+inf in the row, or 1 / T overflows the product)
     int id = -1;
     uint32_t n_kept = 0;
     SmCut cut = {SmKey<T>::key(INFINITY), -1};                    // nothing
-    if (lane0 && a.lse) a.lse[row] = empty ? -INFINITY : st.m + logf(st.s);
+    if (lane0 && a.lse) a.lse[row] = n.empty ? -INFINITY : n.st.m + logf(n.st.s);
 
-    if (!empty && greedy) {
-        id = bi;
+    if (!n.empty && n.greedy) {
+        id = n.bi;
         n_kept = 1;
-        cut = SmCut{SmKey<T>::key(bv), bi};
-    } else if (!empty) {
+        cut = SmCut{SmKey<T>::key(n.bv), n.bi};
+    } else if (!n.empty) {
         const int32_t k = a.top_k ? a.top_k[row] : a.top_k_value;
         const float top_p = a.top_p ? a.top_p[row] : a.top_p_value;
         const float min_p = a.min_p ? a.min_p[row] : a.min_p_value;
-        const bool k_on = k >= 1 && (uint32_t)k < n0;
+        const bool k_on = k >= 1 && (uint32_t)k < n.n0;
         const bool p_on = top_p < 1.0f;
         const bool mp_on = min_p > 0.f;
         const float mp = fminf(min_p, 1.0f);
 
-        uint32_t K = kneg, c = 0, cls = 0, above_c = n0;          // the cut (K, c): every value above -inf
+        uint32_t K = kneg, c = 0, cls = 0, above_c = n.n0;        // the cut (K, c): every value above -inf
         uint64_t mass = 0;                                        // the kept mass, where a later step needs it
         if (k_on) {
             const SmSel s = sm_select<T, false>(r, sh, inv_t, m, (uint64_t)k);
@@ -469,8 +330,8 @@ __global__ void __launch_bounds__(SM_THREADS) sample_kernel(const SmArgs a) {
                 r.values(cc, v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float ee = sm_e(v[e], inv_t, m);
-                    const uint64_t q = sm_q(ee);
+                    const float ee = mass_e(v[e], inv_t, m);
+                    const uint64_t q = mass_q(ee);
                     qtot += q;
                     if (v[e] > -INFINITY && ee >= mp) {
                         const uint32_t key = SmKey<T>::key(v[e]);
@@ -513,15 +374,10 @@ __global__ void __launch_bounds__(SM_THREADS) sample_kernel(const SmArgs a) {
         if (a.ids) {
             const SmCut kc = cut;
             auto kept_q = [kc, inv_t, m](float v, int idx) -> uint64_t {
-                return sm_kept(kc, SmKey<T>::key(v), idx) ? sm_q(sm_e(v, inv_t, m)) : 0ull;
+                return sm_kept(kc, SmKey<T>::key(v), idx) ? mass_q(mass_e(v, inv_t, m)) : 0ull;
             };
             const uint64_t Q = sm_wave_totals(r, sh, kept_q);
-            const float u = a.u[row];
-            const double uu = u > 0.f ? (double)u : 0.0;
-            const double d = floor(uu * (double)Q);
-            uint64_t rr = d >= 18446744073709551615.0 ? Q : (uint64_t)d;
-            if (rr > Q - 1) rr = Q - 1;
-            id = sm_find_index(r, sh, kept_q, rr, bi);
+            id = sm_find_index(r, sh, kept_q, mass_draw_target(a.u[row], Q), n.bi);
         }
     }
     if (lane0) {
@@ -531,26 +387,26 @@ __global__ void __launch_bounds__(SM_THREADS) sample_kernel(const SmArgs a) {
     if (!a.filtered) return;
     // ---- filtered: the logit's own bits where kept
     const int64_t foff = row * a.f_rs;
-    const bool vec_out = ((reinterpret_cast<uintptr_t>(a.filtered) + (uint64_t)foff * SmIo<T>::ESIZE) & 15) == 0;
+    const bool vec_out = mass_row_vec<T>(a.filtered, foff);
     for (int i = 0; i < r.iters; ++i) {
         const int c = r.col(i);
         if (c >= r.V) continue;
         float v[8];
-        r.raw(c, v);
+        r.raw(c, -INFINITY, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = sm_kept(cut, SmKey<T>::key(sm_canon(v[e])), c + e) ? v[e] : -INFINITY;
+        for (int e = 0; e < 8; ++e) v[e] = sm_kept(cut, SmKey<T>::key(mass_canon(v[e])), c + e) ? v[e] : -INFINITY;
         if (vec_out && c + 8 <= r.V) {
-            SmIo<T>::store8(a.filtered, foff + c, v);
+            RowIo<T>::store8(a.filtered, foff + c, v);
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                if (c + e < r.V) SmIo<T>::store1(a.filtered, foff + c + e, v[e]);
+                if (c + e < r.V) RowIo<T>::store1(a.filtered, foff + c + e, v[e]);
         }
     }
 }
 
 // ================================================================================================================================
-// The split plan (vocab >= SM_SPLIT_MIN): a row is cut into C = ceil(vocab / SM_CHUNK) chunks, one workgroup of 1024 lanes each
+// The split plan (vocab >= SM_SPLIT_MIN): a row is cut into C = ceil(vocab / MASS_CHUNK) chunks, one workgroup of 1024 lanes each
 // (2 pieces per lane; wave w of chunk c owns run c * 16 + w of the row, so the index order of the runs is the one-workgroup plan's),
 // and every step of the one-workgroup kernel that meets over the whole row becomes a launch of its own on the stream:
 //     stats    rows x C   chunk (m, s), first maximum, n0                    -> ws: one 32-byte partial per chunk (plain stores)
@@ -564,9 +420,7 @@ __global__ void __launch_bounds__(SM_THREADS) sample_kernel(const SmArgs a) {
 //     filtered rows x C   the kept set of the record
 // No workgroup waits for another; the workspace needs no initialisation (the first resolve zeroes the bins before any add).
 // Integer adds commute, the float partials are merged in chunk order: a row's bits depend on (vocab, dtype) and its values alone.
-constexpr int SM_CHUNK = 16384;                           // columns per workgroup of the split plan
-constexpr int SM_CHUNK_ITERS = SM_CHUNK / 8 / SM_THREADS;
-constexpr int SM_SPLIT_MIN = 2 * SM_CHUNK;
+constexpr int SM_SPLIT_MIN = 2 * MASS_CHUNK;
 enum { SM_DONE = 0, SM_SELK = 1, SM_MASS = 2, SM_SELP = 3, SM_TIE = 4, SM_DRAW = 5 };
 
 struct SmRec {
@@ -576,9 +430,8 @@ struct SmRec {
     uint32_t sel_prefix, sel_above_c;
     uint64_t mass, sel_above_m, sel_target;
 };
-struct SmStat { float m, s, bv; int bi; uint32_t n0, pad[3]; };
 struct SmMassAcc { unsigned long long qtot, m_mp; uint32_t n_mp, kmp_inv, pad[2]; };
-static_assert(sizeof(SmRec) <= 256 && sizeof(SmStat) == 32 && sizeof(SmMassAcc) == 32, "the workspace layout");
+static_assert(sizeof(SmRec) <= 256 && sizeof(SmMassAcc) == 32, "the workspace layout");
 
 // a row's part of the workspace
 struct SmWs {
@@ -590,32 +443,23 @@ struct SmWs {
     __device__ __forceinline__ SmMassAcc* acc(int64_t r) const { return reinterpret_cast<SmMassAcc*>(row(r) + 256); }
     __device__ __forceinline__ uint32_t* cnt(int64_t r) const { return reinterpret_cast<uint32_t*>(row(r) + 320); }
     __device__ __forceinline__ unsigned long long* mass(int64_t r) const { return reinterpret_cast<unsigned long long*>(row(r) + 1344); }
-    __device__ __forceinline__ SmStat* stat(int64_t r) const { return reinterpret_cast<SmStat*>(row(r) + 3392); }
+    __device__ __forceinline__ MassStat* stat(int64_t r) const { return reinterpret_cast<MassStat*>(row(r) + 3392); }
     __device__ __forceinline__ uint64_t* tot(int64_t r) const { return reinterpret_cast<uint64_t*>(row(r) + 3392 + 32 * C); }
 };
-inline int sample_chunks(int V) { return (V + SM_CHUNK - 1) / SM_CHUNK; }
+inline int sample_chunks(int V) { return (V + MASS_CHUNK - 1) / MASS_CHUNK; }
 inline int64_t sample_ws_per_row(int V) {
     const int64_t C = sample_chunks(V);
-    return (3392 + 32 * C + 8 * SM_WAVES * C + 255) / 256 * 256;
+    return (3392 + 32 * C + 8 * MASS_WAVES * C + 255) / 256 * 256;
 }
 
 template <typename T>
-__device__ __forceinline__ SmRow<T> sm_chunk_row(const SmArgs& a, int64_t row, int chunk) {
-    SmRow<T> r;
-    r.x = a.x;
-    r.rowoff = row * a.x_rs;
-    r.V = a.V;
-    r.iters = SM_CHUNK_ITERS;
-    r.wave = (int)threadIdx.x >> 6;
-    r.lane = (int)threadIdx.x & 63;
-    r.gw = chunk * SM_WAVES + r.wave;
-    r.vec = ((reinterpret_cast<uintptr_t>(a.x) + (uint64_t)r.rowoff * SmIo<T>::ESIZE) & 15) == 0;
-    return r;
+__device__ __forceinline__ MassRow<T> sm_chunk_row(const SmArgs& a, int64_t row, int chunk) {
+    return mass_row_chunk<T>(a.x, row * a.x_rs, a.V, chunk);
 }
 
 // f(column, canonical values) for the lane's pieces that have a column < V, in index order
 template <typename T, typename F>
-__device__ __forceinline__ void sm_pieces(const SmRow<T>& r, F&& f) {
+__device__ __forceinline__ void sm_pieces(const MassRow<T>& r, F&& f) {
     for (int i = 0; i < r.iters; ++i) {
         const int c = r.col(i);
         if (c >= r.V) continue;
@@ -630,76 +474,34 @@ template <typename T>
 __device__ __forceinline__ uint64_t sm_rec_weight(const SmRec& rc, float v, int idx) {
     const uint32_t key = SmKey<T>::key(v);
     if (rc.next == SM_TIE) return key == rc.K ? 1ull : 0ull;
-    return sm_kept(SmCut{rc.K, rc.I}, key, idx) ? sm_q(sm_e(v, rc.inv_t, rc.m)) : 0ull;
+    return sm_kept(SmCut{rc.K, rc.I}, key, idx) ? mass_q(mass_e(v, rc.inv_t, rc.m)) : 0ull;
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SM_THREADS) sample_stats_kernel(const SmArgs a, const SmWs ws) {
+__global__ void __launch_bounds__(MASS_THREADS) sample_stats_kernel(const SmArgs a, const SmWs ws) {
     __shared__ SmShared sh;
     const int64_t row = (int64_t)blockIdx.x / ws.C;
     const int chunk = (int)((int64_t)blockIdx.x - row * ws.C);
-    const SmRow<T> r = sm_chunk_row<T>(a, row, chunk);
+    const MassRow<T> r = sm_chunk_row<T>(a, row, chunk);
     const float temp = a.temperature ? a.temperature[row] : a.temperature_value;
-    const float inv_t = !(temp > 0.f) ? 1.0f : 1.0f / temp;
-    LseState st = {-INFINITY, 0.f};
-    float bv = -INFINITY;
-    int bi = SM_ALL;
-    uint32_t n0 = 0;
-    sm_pieces(r, [&](int c, const float (&v)[8]) {
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            x[e] = v[e] * inv_t;
-            if (v[e] > bv) { bv = v[e]; bi = c + e; }
-            n0 += v[e] > -INFINITY ? 1u : 0u;
-        }
-        lse_piece(st, x);
-    });
-    st = lse_wave(st);
-    for (int m = 1; m < 64; m <<= 1) {
-        const float ov = __shfl_xor(bv, m);
-        const int oi = __shfl_xor(bi, m);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        n0 += __shfl_xor(n0, m);
-    }
-    if (r.lane == 0) {
-        sh.slotf[r.wave] = st.m;
-        sh.slotf[SM_WAVES + r.wave] = st.s;
-        sh.slotf[2 * SM_WAVES + r.wave] = bv;
-        sh.slot32[r.wave] = (uint32_t)bi;
-        sh.slot32[SM_WAVES + r.wave] = n0;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    st = LseState{sh.slotf[0], sh.slotf[SM_WAVES]};
-    bv = sh.slotf[2 * SM_WAVES];
-    bi = (int)sh.slot32[0];
-    n0 = sh.slot32[SM_WAVES];
-    for (int w = 1; w < SM_WAVES; ++w) {
-        st = lse_merge(st, LseState{sh.slotf[w], sh.slotf[SM_WAVES + w]});
-        const float ov = sh.slotf[2 * SM_WAVES + w];
-        const int oi = (int)sh.slot32[w];
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        n0 += sh.slot32[SM_WAVES + w];
-    }
-    SmStat o = {st.m, st.s, bv, bi, n0, {0, 0, 0}};
-    ws.stat(row)[chunk] = o;
+    const MassStat o = mass_stats(r, mass_inv_t(temp), sh.slotf, sh.slot32, threadIdx.x == 0);
+    if (threadIdx.x == 0) ws.stat(row)[chunk] = o;
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SM_THREADS) sample_phase_kernel(const SmArgs a, const SmWs ws) {
+__global__ void __launch_bounds__(MASS_THREADS) sample_phase_kernel(const SmArgs a, const SmWs ws) {
     __shared__ SmShared sh;
     const int64_t row = (int64_t)blockIdx.x / ws.C;
     const int chunk = (int)((int64_t)blockIdx.x - row * ws.C);
     const SmRec rc = *ws.rec(row);
     if (rc.next == SM_DONE) return;
-    const SmRow<T> r = sm_chunk_row<T>(a, row, chunk);
+    const MassRow<T> r = sm_chunk_row<T>(a, row, chunk);
     const int tid = (int)threadIdx.x;
     if (rc.next == SM_SELK || rc.next == SM_SELP) {
         constexpr int BITS = SmKey<T>::BITS;
         const uint32_t kneg = SmKey<T>::key(-INFINITY);
         const int shift = BITS - 8 * (rc.digit + 1);
-        for (int j = tid; j < 256 * SM_REP; j += SM_THREADS) { sh.cnt[j] = 0; sh.mass[j] = 0; }
+        for (int j = tid; j < 256 * SM_REP; j += MASS_THREADS) { sh.cnt[j] = 0; sh.mass[j] = 0; }
         __syncthreads();
         int cur = -1;
         uint32_t cur_c = 0;
@@ -720,7 +522,7 @@ __global__ void __launch_bounds__(SM_THREADS) sample_phase_kernel(const SmArgs a
                         cur = bin; cur_c = 0; cur_m = 0;
                     }
                     cur_c += 1;
-                    cur_m += sm_q(sm_e(v[e], rc.inv_t, rc.m));
+                    cur_m += mass_q(mass_e(v[e], rc.inv_t, rc.m));
                 }
             }
         });
@@ -743,8 +545,8 @@ __global__ void __launch_bounds__(SM_THREADS) sample_phase_kernel(const SmArgs a
         sm_pieces(r, [&](int, const float (&v)[8]) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float ee = sm_e(v[e], rc.inv_t, rc.m);
-                const uint64_t q = sm_q(ee);
+                const float ee = mass_e(v[e], rc.inv_t, rc.m);
+                const uint64_t q = mass_q(ee);
                 qtot += q;
                 if (v[e] > -INFINITY && ee >= rc.mp) {
                     const uint32_t key = SmKey<T>::key(v[e]);
@@ -771,8 +573,8 @@ __global__ void __launch_bounds__(SM_THREADS) sample_phase_kernel(const SmArgs a
 #pragma unroll
             for (int e = 0; e < 8; ++e) s += sm_rec_weight<T>(rc, v[e], c + e);
         });
-        for (int m = 1; m < 64; m <<= 1) s += sm_shfl_xor64(s, m);
-        if (r.lane == 0) ws.tot(row)[r.gw] = s;
+        for (int m = 1; m < 64; m <<= 1) s += shfl_xor64(s, m);
+        if (r.lane == 0) ws.tot(row)[r.run] = s;
     }
 }
 
@@ -792,7 +594,7 @@ __device__ __forceinline__ void sm_start_top_p(SmRec& rc) {
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs a, const SmWs ws, const int first) {
+__global__ void __launch_bounds__(MASS_THREADS) sample_resolve_kernel(const SmArgs a, const SmWs ws, const int first) {
     __shared__ SmShared sh;
     const int64_t row = blockIdx.x;
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -801,36 +603,20 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
     const bool want_ids = a.ids != nullptr;
     SmRec rc;
     if (first) {
-        const SmStat* sp = ws.stat(row);
-        SmStat o = sp[0];
-        LseState st = {o.m, o.s};
-        float bv = o.bv;
-        int bi = o.bi;
-        uint32_t n0 = o.n0;
-        for (int c = 1; c < ws.C; ++c) {
-            o = sp[c];
-            st = lse_merge(st, LseState{o.m, o.s});
-            if (o.bv > bv || (o.bv == bv && o.bi < bi)) { bv = o.bv; bi = o.bi; }
-            n0 += o.n0;
-        }
-        const float temp = a.temperature ? a.temperature[row] : a.temperature_value;
-        const bool cold = !(temp > 0.f);
-        const float inv_t = cold ? 1.0f : 1.0f / temp;
-        const bool empty = n0 == 0;
-        const float m = bv * inv_t;
-        const bool greedy = cold || !(fabsf(m) < INFINITY);
-        if (tid == 0 && a.lse) a.lse[row] = empty ? -INFINITY : st.m + logf(st.s);
+        const MassStat stat = mass_merge(ws.stat(row), ws.C);
+        const MassNode n = mass_node(stat, a.temperature ? a.temperature[row] : a.temperature_value);
+        if (tid == 0 && a.lse) a.lse[row] = n.empty ? -INFINITY : n.st.m + logf(n.st.s);
         if (tid < 256) { ws.cnt(row)[tid] = 0; ws.mass(row)[tid] = 0; }
         if (tid == 0) { SmMassAcc z = {0, 0, 0, 0, {0, 0}}; *ws.acc(row) = z; }
         rc = SmRec{};
-        rc.m = m; rc.inv_t = inv_t; rc.bv = bv; rc.bi = bi; rc.n0 = n0;
-        if (empty || greedy) {
+        rc.m = n.m; rc.inv_t = n.inv_t; rc.bv = n.bv; rc.bi = n.bi; rc.n0 = n.n0;
+        if (n.empty || n.greedy) {
             rc.next = SM_DONE;
-            rc.K = empty ? SmKey<T>::key(INFINITY) : SmKey<T>::key(bv);
-            rc.I = empty ? -1 : bi;
+            rc.K = n.empty ? SmKey<T>::key(INFINITY) : SmKey<T>::key(n.bv);
+            rc.I = n.empty ? -1 : n.bi;
             if (tid == 0) {
-                if (a.ids) a.ids[row] = empty ? -1 : bi;
-                if (a.n_kept) a.n_kept[row] = empty ? 0 : 1;
+                if (a.ids) a.ids[row] = n.empty ? -1 : n.bi;
+                if (a.n_kept) a.n_kept[row] = n.empty ? 0 : 1;
                 *ws.rec(row) = rc;
             }
             return;
@@ -838,11 +624,11 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
         const int32_t k = a.top_k ? a.top_k[row] : a.top_k_value;
         const float min_p = a.min_p ? a.min_p[row] : a.min_p_value;
         rc.top_p = a.top_p ? a.top_p[row] : a.top_p_value;
-        rc.k_on = k >= 1 && (uint32_t)k < n0;
+        rc.k_on = k >= 1 && (uint32_t)k < n.n0;
         rc.p_on = rc.top_p < 1.0f;
         rc.mp_on = min_p > 0.f;
         rc.mp = fminf(min_p, 1.0f);
-        rc.K = kneg; rc.c = 0; rc.cls = 0; rc.above_c = n0; rc.mass = 0;
+        rc.K = kneg; rc.c = 0; rc.cls = 0; rc.above_c = n.n0; rc.mass = 0;
         if (rc.k_on) sm_start_select(rc, SM_SELK, (uint64_t)k);
         else if (rc.mp_on || rc.p_on) rc.next = SM_MASS;
         else sm_after_filters(rc, want_ids);
@@ -897,8 +683,8 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
             if (rc.p_on) sm_start_top_p(rc);
             else sm_after_filters(rc, want_ids);
         } else {                                          // SM_TIE / SM_DRAW: the run that holds the target, then its walk
-            const int U = ws.C * SM_WAVES;
-            for (int j = tid; j < U; j += SM_THREADS) sh.mass[j] = ws.tot(row)[j];
+            const int U = ws.C * MASS_WAVES;
+            for (int j = tid; j < U; j += MASS_THREADS) sh.mass[j] = ws.tot(row)[j];
             if (tid == 0) sh.found = rc.next == SM_TIE ? SM_ALL : rc.bi;
             __syncthreads();
             uint64_t at;
@@ -907,11 +693,7 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
             } else {
                 uint64_t Q = 0;
                 for (int j = 0; j < U; ++j) Q += sh.mass[j];
-                const float u = a.u[row];
-                const double uu = u > 0.f ? (double)u : 0.0;
-                const double d = floor(uu * (double)Q);
-                at = d >= 18446744073709551615.0 ? Q : (uint64_t)d;
-                if (at > Q - 1) at = Q - 1;
+                at = mass_draw_target(a.u[row], Q);
             }
             uint64_t base = 0;
             int ustar = -1;
@@ -923,8 +705,8 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
                 }
             }
             if (wave == 0 && ustar >= 0) {
-                SmRow<T> r = sm_chunk_row<T>(a, row, 0);
-                r.gw = ustar;
+                MassRow<T> r = sm_chunk_row<T>(a, row, 0);
+                r.run = ustar;
                 uint64_t running = base;
                 for (int i = 0; i < r.iters; ++i) {
                     const int c = r.col(i);
@@ -939,16 +721,7 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
 #pragma unroll
                         for (int e = 0; e < 8; ++e) wv[e] = 0;
                     }
-                    const uint64_t incl = sm_wave_scan64(ls, lane);
-                    uint64_t p = running + (incl - ls);
-                    if (p <= at && at < p + ls) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            if (p <= at && at < p + wv[e]) sh.found = c + e;
-                            p += wv[e];
-                        }
-                    }
-                    running += sm_shfl64(incl, 63);
+                    mass_walk_step(wv, ls, running, at, c, lane, sh.found);
                 }
             }
             __syncthreads();
@@ -970,27 +743,27 @@ __global__ void __launch_bounds__(SM_THREADS) sample_resolve_kernel(const SmArgs
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SM_THREADS) sample_filtered_kernel(const SmArgs a, const SmWs ws) {
+__global__ void __launch_bounds__(MASS_THREADS) sample_filtered_kernel(const SmArgs a, const SmWs ws) {
     const int64_t row = (int64_t)blockIdx.x / ws.C;
     const int chunk = (int)((int64_t)blockIdx.x - row * ws.C);
     const SmRec rc = *ws.rec(row);
     const SmCut cut = {rc.K, rc.I};
-    const SmRow<T> r = sm_chunk_row<T>(a, row, chunk);
+    const MassRow<T> r = sm_chunk_row<T>(a, row, chunk);
     const int64_t foff = row * a.f_rs;
-    const bool vec_out = ((reinterpret_cast<uintptr_t>(a.filtered) + (uint64_t)foff * SmIo<T>::ESIZE) & 15) == 0;
+    const bool vec_out = mass_row_vec<T>(a.filtered, foff);
     for (int i = 0; i < r.iters; ++i) {
         const int c = r.col(i);
         if (c >= r.V) continue;
         float v[8];
-        r.raw(c, v);
+        r.raw(c, -INFINITY, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = sm_kept(cut, SmKey<T>::key(sm_canon(v[e])), c + e) ? v[e] : -INFINITY;
+        for (int e = 0; e < 8; ++e) v[e] = sm_kept(cut, SmKey<T>::key(mass_canon(v[e])), c + e) ? v[e] : -INFINITY;
         if (vec_out && c + 8 <= r.V) {
-            SmIo<T>::store8(a.filtered, foff + c, v);
+            RowIo<T>::store8(a.filtered, foff + c, v);
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                if (c + e < r.V) SmIo<T>::store1(a.filtered, foff + c + e, v[e]);
+                if (c + e < r.V) RowIo<T>::store1(a.filtered, foff + c + e, v[e]);
         }
     }
 }
@@ -999,7 +772,7 @@ __global__ void __launch_bounds__(SM_THREADS) sample_filtered_kernel(const SmArg
 // can be on) alone
 int sample_iters(int V) {
     const int64_t pieces = ((int64_t)V + 7) / 8;
-    return (int)((pieces + SM_THREADS - 1) / SM_THREADS);
+    return (int)((pieces + MASS_THREADS - 1) / MASS_THREADS);
 }
 int64_t sample_chunks_per_row(int V) { return V >= SM_SPLIT_MIN ? sample_chunks(V) : 1; }
 size_t sample_workspace_bytes(int64_t rows, int V, int) {
@@ -1012,7 +785,7 @@ static void launch_sample_split(const fa_sample_params& s, const SmArgs& a, hipS
     ws.base = static_cast<char*>(s.workspace);
     ws.C = sample_chunks(s.vocab);
     ws.per_row = sample_ws_per_row(s.vocab);
-    const dim3 gc((unsigned)(s.rows * ws.C)), gr((unsigned)s.rows), b(SM_THREADS);
+    const dim3 gc((unsigned)(s.rows * ws.C)), gr((unsigned)s.rows), b(MASS_THREADS);
     // the sweeps the longest row can need
     const bool sampled = s.temperature || s.temperature_value > 0.f;
     const bool k_can = s.top_k || s.top_k_value >= 1;
@@ -1045,7 +818,7 @@ void launch_sample(const fa_sample_params& s, hipStream_t stream) {
         else launch_sample_split<fp32_tag>(s, a, stream);
         return;
     }
-    const dim3 g((unsigned)s.rows), b(SM_THREADS);
+    const dim3 g((unsigned)s.rows), b(MASS_THREADS);
     if (s.dtype == FA_BF16) hipLaunchKernelGGL((sample_kernel<bf16_tag>), g, b, 0, stream, a);
     else if (s.dtype == FA_FP16) hipLaunchKernelGGL((sample_kernel<fp16_tag>), g, b, 0, stream, a);
     else hipLaunchKernelGGL((sample_kernel<fp32_tag>), g, b, 0, stream, a);

@@ -9,6 +9,7 @@ The launch plan (csrc/fa_spec_verify.hip): a row is cut into chunks of 16384 col
 at and just above the boundaries: piece 7, 8, 9; a lane's second piece 8191, 8192, 8193; one chunk -> two 16383, 16384, 16385;
 two -> three 32767, 32768, 32769; four chunks 49153; ten chunks 151936."""
 import ctypes
+import math
 
 import numpy as np
 import pytest
@@ -144,6 +145,51 @@ def _exact_spelled_out(got, V, d, dk, top, rnd, filt):
     assert [g[0] for g in got[16:20]] == [0, 0, 0, 0]
     assert got[20] == got[21] == (0, -1) and got[22] == (1, 41) and got[23] == (0, 41)
     assert got[24:30] == [(1, top), (0, top)] * 3 and got[30] == (1, top)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("V", [1000, 16385, 32768, 32777])
+def test_recovered_is_fa_sample_where_the_residual_is_empty(V, dtype):
+    """the two ops against each other, the reference takes no part: with a draft row of all 1.0f every r_j = min(max(p_j - 1, 0), 1)
+    is 0, so R == 0 and `recovered` is the index-order inverse CDF over the target's own masses at u_recover - fa_sample's `ids`
+    for the parent's row, the same temperature and u = u_recover, no filter: the same int32, bit for bit.  A chain of T = 3 (nodes
+    1 and 2 read rows 0 and 1), B = 2; V: one chunk with a scalar tail, two chunks in spec where sample still runs one workgroup,
+    sample's first split vocab, the split plan with a ragged last piece.  Temperature 0.7, a per-request tensor (a sampled and a
+    greedy request) and 0.0; u_recover holds 0.0, 0.99999994 and seeded random numbers.  Every row holds its maximum twice: a
+    greedy row must give the first one in both ops.  That R == 0 for these inputs is confirmed here on the CPU with
+    spec_verify_ref's fp32 emulation: the residual masses that accept_ref(..., emulate=True) sums add up to 0, and accept_ref
+    returns the draw over the target's own masses."""
+    D = _D()
+    import flash_attn_mi355.sample as S
+    B, T = 2, 3
+    target = torch.stack([torch.stack([R.randn_row(V, dtype, seed=V + 10 * b + t) for t in range(T)]) for b in range(B)])
+    target[:, :, V - 1] = target[:, :, :V - 1].max(dim=-1).values
+    gen = torch.Generator().manual_seed(V)
+    u_recover = torch.rand(B, T, generator=gen)
+    u_recover[0, 1], u_recover[1, 2] = 0.0, 0.99999994
+    u_accept = torch.rand(B, T, generator=gen)
+    draft_ids = torch.randint(0, V, (B, T), generator=gen, dtype=torch.int32)
+    ones = torch.ones(B, T, V)
+    first = [[int(np.flatnonzero(v == v.max())[0]) for v in (R.values(target[b, t]) for t in range(T - 1))] for b in range(B)]
+    for temperature in (0.7, torch.tensor([1.3, 0.0]), 0.0):
+        temps = temperature.tolist() if isinstance(temperature, torch.Tensor) else [temperature] * B
+        for b, t in [(b, t) for b in range(B) for t in range(1, T) if temps[b] > 0]:     # the CPU side: R == 0 on every sampled node
+            p, qm = SR.probs(R.values(target[b, t - 1]), temps[b], emulate=True)
+            assert int(SR.residual(p, np.ones(V), emulate=True)[1].sum()) == 0
+            rr = min(math.floor(float(u_recover[b, t]) * int(qm.sum())), int(qm.sum()) - 1)
+            own = int(np.searchsorted(np.cumsum(qm), np.uint64(rr), side="right"))
+            assert SR.accept_ref(target[b, t - 1], ones[b, t], 0, temps[b], 0.5, float(u_recover[b, t]), emulate=True)[1] == own
+        on_gpu = temperature.cuda() if isinstance(temperature, torch.Tensor) else temperature
+        _, recovered = D.accept_forward(target.cuda(), ones.cuda(), draft_ids.cuda(), u_accept.cuda(), u_recover.cuda(), temperature=on_gpu)
+        rows = on_gpu.repeat_interleave(T - 1) if isinstance(temperature, torch.Tensor) else temperature
+        ids, _, _ = S.sample_forward(target[:, :T - 1].contiguous().cuda(), u_recover[:, 1:].contiguous().cuda(), temperature=rows)
+        torch.cuda.synchronize()
+        assert recovered.dtype == ids.dtype == torch.int32
+        assert torch.equal(recovered[:, 1:].cpu(), ids.cpu()), (V, dtype, temperature, recovered.cpu(), ids.cpu())
+        assert (recovered[:, 0] == -1).all()
+        for b in range(B):
+            if not temps[b] > 0:
+                assert recovered[b, 1:].tolist() == first[b] == ids[b].tolist(), (V, dtype, temperature, b)
 
 
 def _random_walk_inputs(T, B, seed):
