@@ -252,6 +252,7 @@ size_t fa_moe_permute_params_size(void) { return sizeof(fa_moe_permute_params); 
 size_t fa_moe_combine_params_size(void) { return sizeof(fa_moe_combine_params); }
 size_t fa_moe_combine_bwd_params_size(void) { return sizeof(fa_moe_combine_bwd_params); }
 size_t fa_moe_gemm_params_size(void) { return sizeof(fa_moe_gemm_params); }
+size_t fa_moe_gemm_wgrad_params_size(void) { return sizeof(fa_moe_gemm_wgrad_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1747,8 +1748,8 @@ static int moe_permute_check(const fa_moe_permute_params& s) {
     return check_overlaps(op, &out, 1, in, 3, false, nullptr, 0);
 }
 
-// the shape arguments fa_moe_gemm and fa_moe_gemm_plan share
-static int moe_gemm_shape_check(const char* op, int64_t rows, int n, int k, int num_experts, int layout, int dtype) {
+// the shape arguments fa_moe_gemm, fa_moe_gemm_wgrad and their plans share
+static int moe_gemm_dims_check(const char* op, int64_t rows, int n, int k, int num_experts, int layout, int dtype) {
     FA_CHECK(rows >= 0, "%s: rows must be non-negative", op);
     FA_TRY(check_io_dtype(op, dtype, "dtype"));
     FA_CHECK(layout == FA_MOE_W_NK || layout == FA_MOE_W_KN, "%s: layout must be FA_MOE_W_NK or FA_MOE_W_KN, got %d", op, layout);
@@ -1759,6 +1760,12 @@ static int moe_gemm_shape_check(const char* op, int64_t rows, int n, int k, int 
     if (k < 8 || k > fa::MOE_GEMM_MAX_K || k % 8 != 0)
         return fail(FA_ERR_UNSUPPORTED, "%s: k must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_GEMM_MAX_K, k);
     if (rows > 0x7fffffffLL) return fail(FA_ERR_UNSUPPORTED, "%s: rows must stay below 2^31", op);
+    return FA_OK;
+}
+
+// the same and the forward's grid bound
+static int moe_gemm_shape_check(const char* op, int64_t rows, int n, int k, int num_experts, int layout, int dtype) {
+    FA_TRY(moe_gemm_dims_check(op, rows, n, k, num_experts, layout, dtype));
     if (fa::moe_gemm_plan(rows, n, k, num_experts, layout, dtype).grid_m >= (1 << 24))
         return fail(FA_ERR_UNSUPPORTED, "%s: rows = %lld needs more row tiles than one launch has", op, (long long)rows);
     return FA_OK;
@@ -1801,6 +1808,50 @@ static int moe_gemm_check(const fa_moe_gemm_params& s) {
     };
     const View out = view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2);
     return check_overlaps(op, &out, 1, in, 5, false, nullptr, 0);
+}
+
+static int moe_gemm_wgrad_check(const fa_moe_gemm_wgrad_params& s) {
+    const char* op = "moe_gemm_wgrad";
+    FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(moe_gemm_dims_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
+    const bool gather = s.sorted_slot != nullptr;
+    if (gather) {
+        FA_CHECK(s.tokens >= 0, "%s: tokens must be non-negative", op);
+        if (s.top_k < 1 || s.top_k > fa::MOE_MAX_TOPK)
+            return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, %d], got %d", op, fa::MOE_MAX_TOPK, s.top_k);
+        if (s.tokens > 0x7fffffffLL / s.top_k) return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k must stay below 2^31", op);
+    }
+    if (s.dw_dtype != s.dtype && s.dw_dtype != FA_FP32) return fail(FA_ERR_UNSUPPORTED, "%s: dw_dtype must be dtype or fp32", op);
+    if (s.accumulate && s.dw_dtype != FA_FP32) return fail(FA_ERR_UNSUPPORTED, "%s: accumulate needs an fp32 dw (dw_dtype)", op);
+    if (s.dbias && s.dbias_dtype != s.dtype && s.dbias_dtype != FA_FP32)
+        return fail(FA_ERR_UNSUPPORTED, "%s: dbias_dtype must be dtype or fp32", op);
+    if (s.dw && (s.dw_expert_stride < (int64_t)s.n * s.k || s.dw_expert_stride % 8 != 0))
+        return fail(FA_ERR_UNSUPPORTED, "%s: dw_expert_stride must be a multiple of 8 and at least n x k = %lld, got %lld", op,
+                    (long long)s.n * s.k, (long long)s.dw_expert_stride);
+    if (s.dy_row_stride < 0 || s.dy_row_stride % 8 != 0 || s.dy_row_stride > fa::MOE_GEMM_MAX_ROW_STRIDE)
+        return fail(FA_ERR_UNSUPPORTED, "%s: dy_row_stride must be a multiple of 8 in [0, 2^22], got %lld", op, (long long)s.dy_row_stride);
+    if (s.x_row_stride < 0 || s.x_row_stride % 8 != 0 || s.x_row_stride > fa::MOE_GEMM_MAX_ROW_STRIDE)
+        return fail(FA_ERR_UNSUPPORTED, "%s: x_row_stride must be a multiple of 8 in [0, 2^22], got %lld", op, (long long)s.x_row_stride);
+    FA_CHECK(s.expert_offsets, "%s: expert_offsets must not be NULL", op);
+    const int64_t x_rows = gather ? s.tokens : s.rows;
+    FA_CHECK((s.rows == 0 || s.dy) && (s.rows == 0 || !s.dw || x_rows == 0 || s.x), "%s: dy and x must not be NULL", op);
+    FA_CHECK(s.rows <= 1 || s.dy_row_stride >= s.n, "%s: dy_row_stride must be at least n", op);
+    FA_CHECK(x_rows <= 1 || s.x_row_stride >= s.k, "%s: x_row_stride must be at least k", op);
+    FA_CHECK(((addr(s.dy) | addr(s.x) | addr(s.dw)) & 15) == 0, "%s: dy, x and dw must be 16-byte aligned", op);
+    FA_CHECK(((addr(s.expert_offsets) | addr(s.sorted_slot)) & 3) == 0 && (addr(s.dbias) & (s.dbias_dtype == FA_FP32 ? 3 : 1)) == 0,
+             "%s: expert_offsets, sorted_slot and dbias must be aligned to their elements", op);
+    const int wsz = s.dw_dtype == FA_FP32 ? 4 : 2;
+    const View in[] = {
+        view_rows("dy", s.dy, s.rows, s.dy_row_stride, s.n, 2),
+        view_rows("x", s.x, x_rows, s.x_row_stride, s.k, 2),
+        view_flat("expert_offsets", s.expert_offsets, (uint64_t)(s.num_experts + 1) * 4),
+        view_flat("sorted_slot", s.sorted_slot, (uint64_t)s.rows * 4),
+    };
+    const View out[] = {
+        view_rows("dw", s.dw, s.num_experts, s.dw_expert_stride, (int64_t)s.n * s.k, wsz),
+        view_flat("dbias", s.dbias, (uint64_t)s.num_experts * s.n * (s.dbias_dtype == FA_FP32 ? 4 : 2)),
+    };
+    return check_overlaps(op, out, 2, in, 4, true, nullptr, 0);
 }
 
 static int moe_combine_check(const fa_moe_combine_params& s) {
@@ -2173,6 +2224,30 @@ int fa_moe_gemm(const fa_moe_gemm_params* sp, void* stream) {
     if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
     fa::launch_moe_gemm(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_gemm launch");
+}
+
+int fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                           int32_t* block_n, int32_t* block_k, int32_t* block_rows,
+                           int64_t* grid_n, int64_t* grid_k, int64_t* grid_e) {
+    FA_TRY(moe_gemm_dims_check("moe_gemm_wgrad_plan", 0, n, k, num_experts, layout, dtype));
+    const fa::MoeWgradPlan pl = fa::moe_gemm_wgrad_plan(n, k, num_experts, layout, dtype);
+    if (block_n) *block_n = pl.bn;
+    if (block_k) *block_k = pl.bk;
+    if (block_rows) *block_rows = pl.br;
+    if (grid_n) *grid_n = pl.grid_n;
+    if (grid_k) *grid_k = pl.grid_k;
+    if (grid_e) *grid_e = pl.grid_e;
+    return FA_OK;
+}
+
+int fa_moe_gemm_wgrad(const fa_moe_gemm_wgrad_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_gemm_wgrad_params"));
+    fa_moe_gemm_wgrad_params s = *sp;
+    FA_TRY(moe_gemm_wgrad_check(s));
+    if (!s.dw && !s.dbias) return FA_OK;
+    if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
+    fa::launch_moe_gemm_wgrad(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_gemm_wgrad launch");
 }
 
 }  // extern "C"

@@ -33,4 +33,24 @@ static inline MoeGemmPlan moe_gemm_plan(int64_t m_max, int n, int k, int E, int 
 
 void launch_moe_gemm(const fa_moe_gemm_params& s, hipStream_t stream);
 
+// fa_moe_gemm_wgrad (fa_moe_gemm_wgrad.hip): one workgroup per 128 x 128 tile of one expert's dW, the segment's rows staged 64 a
+// step.  dW is dense, so the grid is (ceil(n / 128), ceil(k / 128), E) whatever the segments hold.
+constexpr int MOE_WGRAD_BN = 128;                         // tile extent along n (the columns of dy)
+constexpr int MOE_WGRAD_BK = 128;                         // tile extent along k (the columns of x)
+constexpr int MOE_WGRAD_BR = 64;                          // segment rows staged per step: four MFMA steps of 16
+struct MoeWgradPlan { int bn, bk, br; int64_t grid_n, grid_k, grid_e; };
+static inline MoeWgradPlan moe_gemm_wgrad_plan(int n, int k, int E, int layout, int dtype) {
+    (void)layout; (void)dtype;
+    MoeWgradPlan pl;
+    pl.bn = MOE_WGRAD_BN;
+    pl.bk = MOE_WGRAD_BK;
+    pl.br = MOE_WGRAD_BR;
+    pl.grid_n = (n + MOE_WGRAD_BN - 1) / MOE_WGRAD_BN;
+    pl.grid_k = (k + MOE_WGRAD_BK - 1) / MOE_WGRAD_BK;
+    pl.grid_e = E;
+    return pl;
+}
+
+void launch_moe_gemm_wgrad(const fa_moe_gemm_wgrad_params& s, hipStream_t stream);
+
 }  // namespace fa

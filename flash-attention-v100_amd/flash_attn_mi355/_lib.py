@@ -559,6 +559,22 @@ class FaMoeGemmParams(ctypes.Structure):
     ]
 
 
+class FaMoeGemmWgradParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_gemm_wgrad_params` (include/fa_mi355.h): fa_moe_gemm_wgrad, the weight and bias gradients of the
+    grouped expert GEMM.  struct_size must be set to sizeof(FaMoeGemmWgradParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dy", _ptr), ("x", _ptr), ("expert_offsets", _ptr), ("sorted_slot", _ptr),
+        ("dw", _ptr), ("dbias", _ptr),                          # NULL: skipped
+        ("dy_row_stride", _i64), ("x_row_stride", _i64), ("dw_expert_stride", _i64),
+        ("rows", _i64), ("tokens", _i64),
+        ("num_experts", _i32), ("top_k", _i32), ("n", _i32), ("k", _i32),
+        ("dtype", _i32), ("dw_dtype", _i32), ("dbias_dtype", _i32), ("layout", _i32),
+        ("accumulate", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -583,7 +599,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_moe_sort", "fa_moe_sort_params_size", "fa_moe_sort_workspace_bytes", "fa_moe_sort_plan",
            "fa_moe_permute", "fa_moe_permute_params_size", "fa_moe_combine", "fa_moe_combine_params_size",
            "fa_moe_combine_bwd", "fa_moe_combine_bwd_params_size",
-           "fa_moe_gemm", "fa_moe_gemm_params_size", "fa_moe_gemm_plan"] + EXT_OPS
+           "fa_moe_gemm", "fa_moe_gemm_params_size", "fa_moe_gemm_plan",
+           "fa_moe_gemm_wgrad", "fa_moe_gemm_wgrad_params_size", "fa_moe_gemm_wgrad_plan"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -615,6 +632,7 @@ ROW_OPS = [
     ("fa_moe_combine", FaMoeCombineParams, None),
     ("fa_moe_combine_bwd", FaMoeCombineBwdParams, None),
     ("fa_moe_gemm", FaMoeGemmParams, None),
+    ("fa_moe_gemm_wgrad", FaMoeGemmWgradParams, None),
 ]
 
 
@@ -666,6 +684,8 @@ def _load():
     lib.fa_moe_sort_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
     lib.fa_moe_gemm_plan.restype = ctypes.c_int
     lib.fa_moe_gemm_plan.argtypes = [i64] + [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.POINTER(i64)] * 2
+    lib.fa_moe_gemm_wgrad_plan.restype = ctypes.c_int
+    lib.fa_moe_gemm_wgrad_plan.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.POINTER(i64)] * 3
     lib.fa_gather_rows.restype = ctypes.c_int
     lib.fa_gather_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64, i64, i64, i64, ctypes.c_void_p]
     lib.fa_scatter_rows.restype = ctypes.c_int
@@ -747,7 +767,7 @@ call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
 # call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
-# call_moe_gemm,
+# call_moe_gemm, call_moe_gemm_wgrad,
 # call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes, sample_workspace_bytes, spec_accept_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
@@ -791,4 +811,15 @@ def moe_gemm_plan(rows, n, k, num_experts, layout, dtype):
     rc = lib.fa_moe_gemm_plan(rows, n, k, num_experts, layout, dtype, *(ctypes.byref(o) for o in blk + grid))
     if rc != 0:
         raise RuntimeError(f"fa_moe_gemm_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
+    return tuple(o.value for o in blk + grid)
+
+
+def moe_gemm_wgrad_plan(n, k, num_experts, layout, dtype):
+    """fa_moe_gemm_wgrad_plan: (block_n, block_k, block_rows, grid_n, grid_k, grid_e) of fa_moe_gemm_wgrad, a function of the
+    shapes alone; needs no device"""
+    blk = [ctypes.c_int32() for _ in range(3)]
+    grid = [ctypes.c_int64() for _ in range(3)]
+    rc = lib.fa_moe_gemm_wgrad_plan(n, k, num_experts, layout, dtype, *(ctypes.byref(o) for o in blk + grid))
+    if rc != 0:
+        raise RuntimeError(f"fa_moe_gemm_wgrad_plan failed ({rc}): {lib.fa_last_error().decode(errors='replace')}")
     return tuple(o.value for o in blk + grid)

@@ -1,8 +1,9 @@
 """What surrounds the expert GEMMs of a mixture-of-experts block, on the library's `fa_moe_*` kernels (csrc/fa_moe.hip): top-k
 routing with its gradient, the stable sort of the (token, k) slots by expert, the permutation of the activations into per-expert
 segments and the weighted combine with its backward - and, on csrc/fa_moe_gemm.hip, the forward grouped expert GEMM `moe_gemm`
-over the contiguous, `align`-padded segments of `xp` that `expert_offsets` describes (its docstring has its contract; the weight
-gradient stays with hipBLASLt / `torch._grouped_mm`).
+over the contiguous, `align`-padded segments of `xp` that `expert_offsets` describes, on csrc/fa_moe_gemm_wgrad.hip its weight and
+bias gradients `moe_gemm_wgrad`, and on the two of them `moe_linear`, the expert layer autograd differentiates (their docstrings
+have their contracts).
 
     weights, ids = moe_route(logits, k)                         # fp32 [T, K], int32 [T, K]
     sorted_slot, pos, expert_offsets = moe_sort(ids, E, align=16)
@@ -10,6 +11,10 @@ gradient stays with hipBLASLt / `torch._grouped_mm`).
     yp = experts(xp, expert_offsets)                            # the grouped GEMMs: moe_gemm(xp, w, expert_offsets), or the
                                                                 # first one as moe_gemm(x, w, .., sorted_slot=.., top_k=k) without xp
     out = moe_combine(yp, weights, pos)                         # [T, N]
+
+  training, the experts as differentiable layers (no xp; dx by moe_gemm + moe_combine, dw and dbias by moe_gemm_wgrad):
+    h = moe_linear(x, w1, expert_offsets, sorted_slot=sorted_slot, top_k=k, pos=pos)      # gate-up, fused gather
+    yp = moe_linear(act_and_mul(h), w2, expert_offsets)                                   # down
 
 No function synchronises with the host, every result is a pure function of its inputs (no ordering depends on an atomic, two calls
 give the same bits), all are capturable in a HIP graph.
@@ -63,8 +68,9 @@ Limits (outside them: RuntimeError naming the argument, before any device work):
 multiple of 8 up to 16384 in fp16 / bf16, T K + E (align - 1) < 2^31, 1 <= align <= 256.  CPU tensors raise: there is no fallback.
 
 Not covered: grouped top-k (`n_group` / `topk_group`), capacity factors and token dropping by load, the auxiliary load-balancing
-loss, a gradient for the bias or for permute's scale, an fp8 / quantised permute, fusing an activation or the combine into the
-expert GEMMs, their weight gradient, expert-parallel all-to-all, E > 512, K > 16, fp32 activations, a double backward.  Nothing here is exported through
+loss, a gradient for the router's bias or for permute's scale, an fp8 / quantised permute, fusing an activation or the combine
+into the expert GEMMs, a split over rows in their weight gradient, a gradient through the tables, expert-parallel all-to-all,
+E > 512, K > 16, fp32 activations, a double backward.  Nothing here is exported through
 the packages' `__all__` lists."""
 import ctypes
 
@@ -449,7 +455,7 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
 
     Limits: 2 <= E <= 512, K and N multiples of 8 with K <= 32768 and N <= 65536, row strides of x and out at most 2^22 elements,
     M_max >= 0 (0 launches nothing); expert_offsets[0] is 0 (moe_sort's: rows below a positive first offset are not written).  No autograd:
-    an input that requires grad raises.  Not covered: the weight gradient, fp8 / block-scaled operands, an activation or the
+    an input that requires grad raises (`moe_linear` is the differentiable name).  Not covered: fp8 / block-scaled operands, an activation or the
     combine fused into the epilogue, a per-row routing weight, E > 512."""
     op = "moe_gemm"
     if w_layout not in W_LAYOUTS:
@@ -521,3 +527,146 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
         _lib.call_moe_gemm(s, _fi._stream(dev))
     del bi, expert_offsets, sorted_slot
     return out
+
+
+def moe_gemm_wgrad_plan(N, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):
+    """(block_n, block_k, block_rows, grid_n, grid_k, grid_e) of `moe_gemm_wgrad`: a function of these arguments alone, no device"""
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"moe_gemm_wgrad_plan: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if dtype not in _fi._DTYPES:
+        raise RuntimeError(f"moe_gemm_wgrad_plan: dtype must be fp16 or bf16, got {dtype}")
+    return _lib.moe_gemm_wgrad_plan(int(N), int(K), int(num_experts), W_LAYOUTS[w_layout], _fi._DTYPES[dtype])
+
+
+def _grad_dtype(op, dtype, io, name):
+    """the code of a gradient's dtype: None is the io dtype"""
+    dtype = io if dtype is None else dtype
+    if dtype not in (io, torch.float32):
+        raise RuntimeError(f"{op}: {name} must be {io} or torch.float32, got {dtype}")
+    return dtype, (_lib.FA_FP32 if dtype == torch.float32 else _fi._DTYPES[dtype])
+
+
+def moe_gemm_wgrad(dy, x, expert_offsets, *, w_layout="nk", sorted_slot=None, top_k=None, dw_dtype=None, out=None,
+                   accumulate=False, need_dbias=False, dbias_dtype=None, need_dw=True):
+    """The weight gradient of `moe_gemm` (csrc/fa_moe_gemm_wgrad.hip): dw [E, N, K] ("nk") or [E, K, N] ("kn") with
+
+        dW_e[n, k]  = round(sum_r float(dy[r, n]) * float(a_r[k]))  (+ the old dw with accumulate)
+        dbias[e, n] = round(sum_r float(dy[r, n]))                     over expert_offsets[e] <= r < expert_offsets[e + 1]
+
+    and +0 for an empty expert (with accumulate: its slab is left as it is).  Returns dw, or (dw, dbias) with need_dbias (dbias
+    [E, N] of `dbias_dtype`: the io dtype or fp32; need_dw=False: dw is None and only the dbias launch runs).  dy is [M_max, N];
+    a_r is x[r] (x [M_max, K]) or, with `sorted_slot` / `top_k`, x[sorted_slot[r] // top_k] (x [T, K]) exactly as in `moe_gemm`:
+    the weight gradient of a fused-gather layer needs no permuted copy of x.  E is len(expert_offsets) - 1.
+
+    One launch for dw over a grid known on the host (`moe_gemm_wgrad_plan`), a second small one for dbias; no workspace, no
+    atomics, nothing read on the host.  Every element of dw is one fp32 accumulator chain of v_mfma_f32_32x32x16 from +0 over the
+    segment's rows, ascending from its first row in steps of 16, rounded once: its bits are a function of the segment's rows of
+    dy and a alone - not of the other experts, of E, of where the segment lies or of the rows behind expert_offsets[E].  Rows
+    outside the segment are never loaded, so a NaN there stays there.  dbias adds 16 interleaved fp32 partial sums in a fixed
+    order that depends on the segment's length alone.
+
+    `dw_dtype` is the io dtype (default) or torch.float32; `out` is written in place of a fresh tensor and may be a view with
+    any expert stride >= N K that is a multiple of 8, contiguous experts, 16-byte aligned; `accumulate` (fp32 dw only, with
+    `out`) adds to it, one fp32 add.  Nothing is copied: dy and x must be 16-byte aligned with a contiguous last dimension and
+    row strides that are multiples of 8 (another layout raises).  Limits as `moe_gemm`; M_max == 0 still writes +0.  No autograd.
+    Not covered: a split over rows for very long segments (one chain per tile: an expert that holds most rows is the slow
+    case), fp8 operands."""
+    op = "moe_gemm_wgrad"
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"{op}: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if dy.dtype not in _fi._DTYPES:
+        raise RuntimeError(f"{op}: dy must be fp16 or bf16, got {dy.dtype}")
+    if dy.dim() != 2:
+        raise RuntimeError(f"{op}: dy must be [rows, N], got {tuple(dy.shape)}")
+    if x.dtype != dy.dtype or x.dim() != 2:
+        raise RuntimeError(f"{op}: x must be a {dy.dtype} tensor [rows, K], got {x.dtype} {tuple(x.shape)}")
+    io = dy.dtype
+    M, N = dy.shape
+    K = x.shape[1]
+    _gemm_dim(op, K, "K", GEMM_MAX_K)
+    _gemm_dim(op, N, "N", GEMM_MAX_N)
+    if expert_offsets.dtype != torch.int32 or expert_offsets.dim() != 1:
+        raise RuntimeError(f"{op}: expert_offsets must be an int32 tensor [E + 1], got {expert_offsets.dtype} {tuple(expert_offsets.shape)}")
+    E = expert_offsets.shape[0] - 1
+    if not (2 <= E <= MAX_EXPERTS):
+        raise RuntimeError(f"{op}: num_experts (len(expert_offsets) - 1) must be in [2, {MAX_EXPERTS}], got {E}")
+    expert_offsets = expert_offsets.contiguous()
+    if (sorted_slot is None) != (top_k is None):
+        raise RuntimeError(f"{op}: sorted_slot and top_k go together")
+    if sorted_slot is not None:
+        top_k = int(top_k)
+        _topk(op, top_k)
+        _slots(op, x.shape[0], top_k)
+        if sorted_slot.dtype != torch.int32 or tuple(sorted_slot.shape) != (M,):
+            raise RuntimeError(f"{op}: sorted_slot must be an int32 tensor of dy's {M} rows, got {sorted_slot.dtype} {tuple(sorted_slot.shape)}")
+        sorted_slot = sorted_slot.contiguous()
+    elif x.shape[0] != M:
+        raise RuntimeError(f"{op}: x must have dy's {M} rows, got {tuple(x.shape)}")
+    if M >= 2 ** 31:
+        raise RuntimeError(f"{op}: M_max must stay below 2^31, got {M}")
+    dw_dtype, dw_code = _grad_dtype(op, dw_dtype if out is None or dw_dtype is not None else out.dtype, io, "dw_dtype")
+    dbias_dtype, dbias_code = _grad_dtype(op, dbias_dtype, io, "dbias_dtype")
+    if accumulate and dw_dtype != torch.float32:
+        raise RuntimeError(f"{op}: accumulate needs an fp32 dw (dw_dtype=torch.float32), got {dw_dtype}")
+    if accumulate and out is None:
+        raise RuntimeError(f"{op}: accumulate needs out, the tensor to add to")
+    if (out is not None or accumulate) and not need_dw:
+        raise RuntimeError(f"{op}: out and accumulate go with need_dw")
+    shape = (E, N, K) if w_layout == "nk" else (E, K, N)
+    if out is not None:
+        if out.dtype != dw_dtype or tuple(out.shape) != shape:
+            raise RuntimeError(f"{op}: out must be {dw_dtype} of shape {shape}, got {out.dtype} {tuple(out.shape)}")
+        if out.stride(2) != 1 or out.stride(1) != out.shape[2] or out.stride(0) < N * K or out.stride(0) % 8 or out.data_ptr() % 16:
+            raise RuntimeError(f"{op}: out must be 16-byte aligned with contiguous experts and an expert stride that is a multiple "
+                               f"of 8 and at least N K, got strides {tuple(out.stride())}")
+    if M:
+        _gemm_rows(op, dy, "dy")
+    if x.shape[0]:
+        _gemm_rows(op, x, "x")
+    _ra.same_device(op, [dy, x, expert_offsets, sorted_slot, out], dy, "dy's")
+    dev = dy.device
+    dw = out
+    if need_dw and dw is None:
+        dw = torch.empty(shape, dtype=dw_dtype, device=dev)
+    dbias = torch.empty((E, N), dtype=dbias_dtype, device=dev) if need_dbias else None
+    if dw is None and dbias is None:
+        return None
+    s = _lib.FaMoeGemmWgradParams()
+    s.struct_size = ctypes.sizeof(_lib.FaMoeGemmWgradParams)
+    s.dy, s.dy_row_stride = (dy.data_ptr() if M else 0), dy.stride(0)
+    s.x, s.x_row_stride = (x.data_ptr() if x.shape[0] else 0), x.stride(0)
+    s.expert_offsets = expert_offsets.data_ptr()
+    if sorted_slot is not None:
+        s.sorted_slot, s.tokens, s.top_k = sorted_slot.data_ptr(), x.shape[0], top_k
+    if dw is not None:
+        s.dw, s.dw_expert_stride = dw.data_ptr(), dw.stride(0)
+    if dbias is not None:
+        s.dbias = dbias.data_ptr()
+    s.rows, s.num_experts, s.n, s.k = M, E, N, K
+    s.dtype, s.dw_dtype, s.dbias_dtype, s.layout = _fi._DTYPES[io], dw_code, dbias_code, W_LAYOUTS[w_layout]
+    s.accumulate = 1 if accumulate else 0
+    with _fi._on_device(dev):
+        _lib.call_moe_gemm_wgrad(s, _fi._stream(dev))
+    del expert_offsets, sorted_slot
+    return (dw, dbias) if need_dbias else dw
+
+
+def moe_linear(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None, top_k=None, pos=None):
+    """The differentiable expert layer: the forward is `moe_gemm(x, w, expert_offsets, ...)`, bit for bit, with the same
+    arguments and limits.  The backward, from dy made conforming (a copy only where its layout cannot be read):
+
+        dx        moe_gemm(dy, w, expert_offsets, the other layout); in the gather form followed by moe_combine_forward(.., None,
+                  pos) - pass `pos`, moe_sort's third result; without it the backward inverts sorted_slot on the device first
+        dw, dbias moe_gemm_wgrad(dy, x, expert_offsets, the same layout and gather), in w's and bias' dtypes
+
+    Only the gradients autograd asks for are computed.  The tables have no gradient; no double backward."""
+    op = "moe_linear"
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"{op}: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if (sorted_slot is None) != (top_k is None):
+        raise RuntimeError(f"{op}: sorted_slot and top_k go together")
+    if pos is not None and sorted_slot is None:
+        raise RuntimeError(f"{op}: pos goes with sorted_slot (the gather form)")
+    _fi._check_device(x, w, expert_offsets, bias, sorted_slot, pos)
+    from . import torch_ops as _ops
+    return _ops.moe_linear(x, w, expert_offsets, w_layout, bias, sorted_slot, None if top_k is None else int(top_k), pos)

@@ -15,7 +15,8 @@ quantisation alone and fused behind the forwards of add_norm and act_mul, fa_qua
 differentiable; `moe_route` / `moe_route_bwd` / `moe_sort` / `moe_permute` / `moe_combine` / `moe_combine_bwd`: top-k routing, the
 stable sort of the (token, k) slots by expert, the permutation into per-expert segments and the weighted combine of a
 mixture-of-experts block with autograd formulas, fa_moe_*, and `moe_gemm`, its forward grouped expert GEMM over `expert_offsets`,
-fa_moe_gemm, not differentiable; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
+fa_moe_gemm, not differentiable, `moe_gemm_wgrad`, its weight and bias gradients, fa_moe_gemm_wgrad, and `moe_linear`, the
+differentiable expert layer built on them; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
 sampling from logits and the filtered logits alone, fa_sample, not differentiable; `spec_accept` / `spec_walk` / `spec_verify`:
 speculative-decoding verification, fa_spec_accept / fa_spec_walk, not differentiable - registered, but not listed in `__all__`).
 
@@ -1233,3 +1234,78 @@ def moe_gemm(x: Tensor, w: Tensor, expert_offsets: Tensor, w_layout: str, bias: 
 def _(x, w, expert_offsets, w_layout, bias, sorted_slot, top_k):
     M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
     return x.new_empty((M, w.shape[1] if w_layout == "nk" else w.shape[2]))
+
+
+# the weight / bias gradient of the grouped expert GEMM (moe.moe_gemm_wgrad; csrc/fa_moe_gemm_wgrad.hip) and the differentiable
+# expert layer built on moe_gemm, moe_combine and it (moe.moe_linear): torch.ops.flash_attn_mi355.moe_gemm_wgrad / .moe_linear
+@torch.library.custom_op(f"{_NS}::moe_gemm_wgrad", mutates_args=(), device_types="cuda")
+def moe_gemm_wgrad(dy: Tensor, x: Tensor, expert_offsets: Tensor, w_layout: str, sorted_slot: Optional[Tensor], top_k: Optional[int],
+                   need_dw: bool, need_dbias: bool, dw_fp32: bool, dbias_fp32: bool) -> Tuple[Tensor, Tensor]:
+    """moe.moe_gemm_wgrad: (dw [E, N, K] / [E, K, N], dbias [E, N]), fresh contiguous tensors of dy's dtype (fp32 with dw_fp32 /
+    dbias_fp32); a gradient that is not needed is an empty tensor of shape (0,)"""
+    res = _moe.moe_gemm_wgrad(dy, x, expert_offsets, w_layout=w_layout, sorted_slot=sorted_slot, top_k=top_k,
+                              dw_dtype=torch.float32 if dw_fp32 else None, need_dbias=need_dbias,
+                              dbias_dtype=torch.float32 if dbias_fp32 else None, need_dw=need_dw)
+    dw, dbias = res if need_dbias else (res, None)
+    return (dy.new_empty((0,), dtype=torch.float32 if dw_fp32 else dy.dtype) if dw is None else dw,
+            dy.new_empty((0,), dtype=torch.float32 if dbias_fp32 else dy.dtype) if dbias is None else dbias)
+
+
+@moe_gemm_wgrad.register_fake
+def _(dy, x, expert_offsets, w_layout, sorted_slot, top_k, need_dw, need_dbias, dw_fp32, dbias_fp32):
+    E, N, K = expert_offsets.shape[0] - 1, dy.shape[1], x.shape[1]
+    shape = (E, N, K) if w_layout == "nk" else (E, K, N)
+    return (dy.new_empty(shape if need_dw else (0,), dtype=torch.float32 if dw_fp32 else dy.dtype),
+            dy.new_empty((E, N) if need_dbias else (0,), dtype=torch.float32 if dbias_fp32 else dy.dtype))
+
+
+@torch.library.custom_op(f"{_NS}::moe_linear", mutates_args=(), device_types="cuda")
+def moe_linear(x: Tensor, w: Tensor, expert_offsets: Tensor, w_layout: str, bias: Optional[Tensor], sorted_slot: Optional[Tensor],
+               top_k: Optional[int], pos: Optional[Tensor]) -> Tensor:
+    """moe.moe_linear: moe_gemm's out, differentiable in x, w and bias (moe_gemm with the other layout, moe_combine over pos,
+    moe_gemm_wgrad); pos is only read by the backward."""
+    return _moe.moe_gemm(x.detach(), w.detach(), expert_offsets, w_layout=w_layout, bias=None if bias is None else bias.detach(),
+                         sorted_slot=sorted_slot, top_k=top_k)
+
+
+@moe_linear.register_fake
+def _(x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, pos):
+    M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
+    return x.new_empty((M, w.shape[1] if w_layout == "nk" else w.shape[2]))
+
+
+def _moe_linear_setup(ctx, inputs, output):
+    x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, pos = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(x, w, expert_offsets, sorted_slot, pos)
+    ctx.args = (w_layout, top_k, None if bias is None else bias.dtype)
+
+
+def _moe_linear_backward(ctx, dy):
+    none = (None,) * 8
+    need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+    if dy is None or not (need_dx or need_dw or need_db):
+        return none
+    x, w, expert_offsets, sorted_slot, pos = ctx.saved_tensors
+    w_layout, top_k, bias_dtype = ctx.args
+    if not (dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.stride(0) >= dy.shape[1] and dy.stride(0) <= _moe.GEMM_MAX_ROW_STRIDE
+            and dy.storage_offset() % 8 == 0):
+        dy = dy.contiguous()
+    dx = dw = db = None
+    if need_dx:
+        dx = moe_gemm(dy, w, expert_offsets, "kn" if w_layout == "nk" else "nk", None, None, None)
+        if sorted_slot is not None:
+            T = x.shape[0]
+            if pos is None:
+                # the inverse of sorted_slot, without a host synchronisation (as moe_permute's backward)
+                idx = torch.where(sorted_slot >= 0, sorted_slot, T * top_k).long()
+                rows = torch.arange(sorted_slot.shape[0], dtype=torch.int32, device=sorted_slot.device)
+                pos = torch.full((T * top_k + 1,), -1, dtype=torch.int32, device=sorted_slot.device).scatter_(0, idx, rows)[:T * top_k].view(T, top_k)
+            dx = moe_combine(dx, None, pos)
+    if need_dw or need_db:
+        dw, db = moe_gemm_wgrad(dy, x, expert_offsets, w_layout, sorted_slot, top_k, need_dw, need_db, False,
+                                bias_dtype == torch.float32)
+    return dx, (dw if need_dw else None), None, None, (db if need_db else None), None, None, None
+
+
+moe_linear.register_autograd(_moe_linear_backward, setup_context=_moe_linear_setup)

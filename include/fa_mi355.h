@@ -1649,6 +1649,60 @@ int    fa_moe_gemm_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts,
                         int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
 
 /*
+ * fa_moe_gemm_wgrad: the weight gradient of fa_moe_gemm, and the bias gradient (csrc/fa_moe_gemm_wgrad.hip).  No workspace, no
+ * atomics, no host synchronisation; expert_offsets is read as fa_moe_gemm reads it (clamped to [0, rows], only compared).
+ *   dw             FA_MOE_W_NK: [E, n, k];  FA_MOE_W_KN: [E, k, n].  With L_e the rows expert_offsets[e] <= r < expert_offsets[e + 1],
+ *                  dW_e[n, k] = round(sum_{r in L_e} float(dy[r, n]) * float(a_r[k])) (+ the old dw with accumulate), fp32
+ *                  accumulation, ONE rounding.  An empty expert's dW is +0 (with accumulate: left as it is).  Rows in no
+ *                  segment - below a positive expert_offsets[0], from expert_offsets[E] on - contribute nothing.
+ *   a_r            as in fa_moe_gemm: x[r], or with sorted_slot x[sorted_slot[r] / top_k], a slot outside [0, tokens * top_k)
+ *                  being a row of +0 that forms no address.
+ *   dbias          [E, n] of dbias_dtype (`dtype` or FA_FP32), or NULL: round(sum_{r in L_e} float(dy[r, n])), +0 for an empty
+ *                  expert.  A second, small launch: 16 fp32 partial sums per column (rows first + j, first + j + 16, ...
+ *                  ascending), added in ascending j - an order that depends on the segment's length alone.  dw NULL: dbias alone.
+ *   order          every element of dW is one accumulator chain of v_mfma_f32_32x32x16 from +0 over the segment's rows, from its
+ *                  first row ascending in steps of 16: no split over rows.  A tile's bits are a function of its segment's rows
+ *                  of dy and a alone - not of the other segments, of E, of where the segment lies, or of the tail.  Rows at or
+ *                  behind a segment's end are never loaded (they are zero-filled): a NaN in a neighbouring segment stays there.
+ *   tensors        dy [rows, n], x [rows, k] or [tokens, k]: 16-byte aligned, row strides multiples of 8, at least the row
+ *                  length, at most 2^22.  dw: 16-byte aligned, of dw_dtype (`dtype`, or FA_FP32), dw_expert_stride >= n * k and a
+ *                  multiple of 8 (elements).  accumulate != 0 (dw = dw + sum, one fp32 add; every element has one writer) needs
+ *                  an FA_FP32 dw.
+ *   limits         those of fa_moe_gemm, FA_ERR_UNSUPPORTED outside them before any device work.  rows == 0 still writes every
+ *                  dW and dbias +0 (unless accumulating).
+ * fa_moe_gemm_wgrad_plan: tile extents along n, along k and the rows staged per step (128, 128, 64) and the grid
+ *   (ceil(n / 128), ceil(k / 128), num_experts): a function of the shapes alone.  Each output pointer may be NULL.
+ */
+typedef struct fa_moe_gemm_wgrad_params {
+    size_t         struct_size;      /* sizeof(fa_moe_gemm_wgrad_params) as the caller compiled it */
+    const void*    dy;               /* [rows, n] of `dtype` */
+    const void*    x;                /* [rows, k], or with sorted_slot [tokens, k], of `dtype` */
+    const void*    expert_offsets;   /* int32 [num_experts + 1], device */
+    const void*    sorted_slot;      /* int32 [rows]; NULL: the plain form */
+    void*          dw;               /* [num_experts, n, k] / [num_experts, k, n] of `dw_dtype`; NULL: not computed */
+    void*          dbias;            /* [num_experts, n] of `dbias_dtype`, contiguous; NULL: not computed */
+    int64_t        dy_row_stride, x_row_stride;    /* elements, multiples of 8 */
+    int64_t        dw_expert_stride; /* elements, >= n * k, a multiple of 8 */
+    int64_t        rows;             /* M_max */
+    int64_t        tokens;           /* rows of x with sorted_slot; ignored without */
+    int32_t        num_experts, top_k;              /* top_k: with sorted_slot only */
+    int32_t        n, k;
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        dw_dtype;         /* `dtype` or FA_FP32 */
+    int32_t        dbias_dtype;      /* `dtype` or FA_FP32; ignored without dbias */
+    int32_t        layout;           /* fa_moe_w_layout */
+    int32_t        accumulate;       /* != 0: dw += (FA_FP32 dw only) */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_gemm_wgrad_params;
+
+int    fa_moe_gemm_wgrad(const fa_moe_gemm_wgrad_params* s, void* stream);
+size_t fa_moe_gemm_wgrad_params_size(void);
+int    fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                              int32_t* block_n, int32_t* block_k, int32_t* block_rows,
+                              int64_t* grid_n, int64_t* grid_k, int64_t* grid_e);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
