@@ -498,8 +498,8 @@ __global__ void __launch_bounds__(FWD_THREADS, (D > 128 ? 1 : FA_FWD_OCC)) fa_fw
     // in the key position j = n0 + pos.  Its row- and tile-constant part slope (n0 - i - off) only
     // shifts the row maximum (`shift`, one VALU per tile); the pos-dependent part slope * pos is
     // added by the matrix pipe: one extra MFMA per 32-key block whose A operand holds pos (exact
-    // in 16 bits) in contraction slots 0 and 1 and whose B operand holds slope / softmax_scale
-    // split into a 16-bit head and tail.  No per-element VALU work is left, versus 5 per element
+    // in 16 bits) in contraction slots 0 .. 2 and whose B operand holds slope / softmax_scale
+    // split into three 16-bit pieces.  No per-element VALU work is left, versus 5 per element
     // on the general path below (measured at BASELINE config 5's shard: 652 -> see DESIGN.md).
     constexpr bool lin = BIAS == 2;        // host guarantees: slopes given, no softcap, wr == 0
     const float c = ((BIAS == 1) || (BIAS == 3)) ? 1.0f : a.scale_log2e * (KV8 ? p.k_descale : 1.0f);
@@ -508,10 +508,17 @@ __global__ void __launch_bounds__(FWD_THREADS, (D > 128 ? 1 : FA_FWD_OCC)) fa_fw
     u32x4 slope_b = {0, 0, 0, 0};
     if (BIAS && lin && g == 0) {
         const float sv = slope / p.softmax_scale;
+        // three 16-bit pieces in contraction slots 0 .. 2: 24 bits of the slope in bf16 as in fp16.  (Two pieces are 16 bits
+        // in bf16 - a bias off by slope * pos * 2^-17, up to 1e-3 at slope 2 and pos 63: the LSE of bf16 causal-ALiBi rows
+        // was 7e-5 .. 4e-4 from the fp64 value where every other 16-bit path is within 1e-5.)
         const float head = E::lo(E::pack2(sv, 0.f));
-        slope_b[0] = E::pack2(head, sv - head);
+        const float mid = E::lo(E::pack2(sv - head, 0.f));
+        slope_b[0] = E::pack2(head, mid);
+        slope_b[1] = E::pack2(sv - head - mid, 0.f);
         pos_a[0][0] = E::pack2((float)l31, (float)l31);
+        pos_a[0][1] = E::pack2((float)l31, 0.f);
         pos_a[1][0] = E::pack2((float)(32 + l31), (float)(32 + l31));
+        pos_a[1][1] = E::pack2((float)(32 + l31), 0.f);
     }
 
     // one KV tile for this wave; STAGE is a compile-time constant (all LDS offsets immediates)

@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "flash-attention-v100_amd"))
 
 import oracle                                                     # noqa: E402
-from util import DT, f64, rand16                                  # noqa: E402
+from util import DT, LSE_ATOL, f64, rand16                        # noqa: E402
 
 # The differential fuzz draws TINY shapes as well (two rows, one head, one visible key): there a gradient element can be a single
 # 16-bit rounding of a sum that cancels, and "max error / max reference" over a handful of elements is not the statistic the
@@ -104,11 +104,19 @@ def _check(got, ref, dt, name, mult, desc, absfloor=2e-3, slack=None):
         f"{name}: max-rel {mr:.3e} (tol {TOL_MAXREL[dt] * mult:.1e}) fro {fro:.3e} (tol {TOL_FRO[dt] * mult:.1e})  [{desc}]"
 
 
-def _check_lse(got, ref, name, desc, atol=2e-3):
+WORST_LSE_ABS = {}                          # kind -> (largest |LSE - ref| over its draws gated at LSE_ATOL, case)
+_KIND = [""]                                # the kind run() / run_one() is drawing from
+
+
+def _check_lse(got, ref, name, desc, atol=LSE_ATOL):
+    # the LSE is one fp32 scalar per row: the 16-bit draws without rotary and without an fp8 cache are held to the
+    # calibrated gate of tests/util.py, tiny shapes included (the wide element gates above are about 16-bit outputs)
     got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
     inf_ref = np.isneginf(ref)
     assert (np.isneginf(got) == inf_ref).all(), f"{name}: -inf pattern differs  [{desc}]"
     d = np.abs(got[~inf_ref] - ref[~inf_ref])
+    if atol == LSE_ATOL and d.size and d.max() > WORST_LSE_ABS.get(_KIND[0], (-1.0, ""))[0]:
+        WORST_LSE_ABS[_KIND[0]] = (float(d.max()), desc)
     assert d.size == 0 or d.max() <= atol, f"{name}: max abs diff {d.max():.3e}  [{desc}]"
 
 
@@ -394,7 +402,7 @@ def kvcache_case(rng, idx):
     assert np.abs(f64(kc) - kc_ref).max() <= tol * max(1.0, np.abs(kc_ref).max()), f"k cache differs  [{desc}]"
     assert np.array_equal(f64(vc), vc_ref), f"v cache differs  [{desc}]"
     _check(f64(out), o_ref, dt, "out", 2.0 if rd else 1.0, desc)
-    _check_lse(f64(lse), lse_ref, "lse", desc, atol=2e-2 if rd else 2e-3)
+    _check_lse(f64(lse), lse_ref, "lse", desc, **(dict(atol=2e-2) if rd else {}))      # (rotary: the scores carry 16-bit rounding)
     return desc
 
 
@@ -582,12 +590,14 @@ def run_one(kind, seed, i):
         rng.integers(0, 2 ** 31)
     sub = np.random.default_rng(rng.integers(0, 2 ** 31))
     torch.manual_seed(seed * 100003 + i)
+    _KIND[0] = kind
     return KINDS[kind](sub, i)
 
 
 def run(kind, seed, n, verbose=False, keep_going=False):
     rng = np.random.default_rng([seed, KIND_ID[kind]])
     failures = []
+    _KIND[0] = kind
     for i in range(n):
         sub = np.random.default_rng(rng.integers(0, 2 ** 31))      # one stream per case: cases reproduce by (seed, i)
         torch.manual_seed(seed * 100003 + i)
@@ -602,6 +612,8 @@ def run(kind, seed, n, verbose=False, keep_going=False):
             print("FAIL", failures[-1], flush=True)
     if kind in WORST:
         print(f"{kind}: worst out error / gate {WORST[kind][0]:.3f}  [{WORST[kind][1]}]", flush=True)
+    if kind in WORST_LSE_ABS:
+        print(f"{kind}: worst |LSE - ref| (gate {LSE_ATOL:.0e}) {WORST_LSE_ABS[kind][0]:.2e}  [{WORST_LSE_ABS[kind][1]}]", flush=True)
     if kind in WORST_LSE:
         print(f"{kind}: worst |LSE - ref| / (scale sum_d |q_d k_d|) {WORST_LSE[kind][0]:.2e}  [{WORST_LSE[kind][1]}]",
               flush=True)

@@ -10,7 +10,15 @@ Runs ONLY in the build container (needs /root/reference).  It
   2. imports the reference's Python operator layer with a recording stub in place of the
      CUDA extension and stores the positional argument tuples it builds at the extension
      boundary (flash_attn_v100/flash_attn_interface.py:60,99,210,256,366).
+  3. cuts the reference's host C++ check functions `cpu_attention_forward` / `cpu_attention_backward` out of
+     utils/sass/mma_kernel/backward_kernel.cu (oracle/ref_hostcpp.py: by name, into oracle/_ref/, compiled with g++) and
+     runs them on inputs drawn here that are exact in fp16 AND bf16.
 Only data (inputs / expected outputs / call shapes) is written - no reference source.
+
+What is pinned to what: O, dQ, dK and dV of the dense path are pinned to test.py's `ref_mha_forward` / `ref_mha_backward`
+(dense_*.npz, config1_*.npz).  The LSE - which test.py never computes - and a second, independently written set of O and
+gradients are pinned to the host C++ (hostcpp_*.npz): LSE = max + logf(sum_exp) as `cpu_attention_forward` returns it,
+dQ / dK / dV as `cpu_attention_backward` derives them from the forward's own fp32 O.
 """
 import ast
 import json
@@ -140,8 +148,55 @@ def gen_boundary_calls():
     print("wrote boundary_calls.json")
 
 
+# (M, N, D, causal, scale): the smallest shapes that still cross each boundary.  The host C++ masks top-left (j > i), which
+# is this project's bottom-right convention only where M == N: causal is used there alone.
+HOSTCPP_CASES = [
+    (128, 128, 128, False, 0.125),          # the reference file's own problem
+    (128, 128, 128, True, 0.125),
+    (200, 200, 64, True, None),             # ragged last tile, D 64
+    (130, 130, 256, True, None),            # D 256, two rows past a tile
+    (65, 65, 40, True, None),               # padded head dim
+    (192, 192, 96, False, None),            # D 96
+    (77, 300, 128, False, None),            # Sq < Sk
+    (300, 129, 64, False, None),            # Sq > Sk, one key past a tile
+    (1, 65, 64, False, None),               # single query
+]
+
+
+def _exact_in_16bit(x):
+    t = torch.from_numpy(x)
+    return bool((t.to(torch.float16).float() == t).all()) and bool((t.to(torch.bfloat16).float() == t).all())
+
+
+def gen_hostcpp():
+    sys.path.insert(0, os.path.join(OUT, "..", ".."))
+    from oracle import ref_hostcpp
+    exe = ref_hostcpp.build()
+    for n, (M, N, D, causal, scale) in enumerate(HOSTCPP_CASES):
+        assert not causal or M == N
+        rng = np.random.default_rng([421, n])
+        if (M, N, D) == (128, 128, 128):    # the range of the reference file's own +-0.1 inputs, on a 2^-10 grid
+            draw = lambda *s: (rng.integers(-102, 103, size=s) * 2.0 ** -10).astype(np.float32)
+        else:                               # randn scale with an 8-bit significand
+            draw = lambda *s: (np.clip(np.round(rng.standard_normal(s) * 64), -255, 255) * 2.0 ** -6).astype(np.float32)
+        q, k, v, do = draw(M, D), draw(N, D), draw(N, D), draw(M, D)
+        for x in (q, k, v, do):
+            assert _exact_in_16bit(x), "hostcpp inputs must be exact in fp16 and bf16"
+        scale = D ** -0.5 if scale is None else scale
+        r = ref_hostcpp.run(exe, q, k, v, do, scale, causal)
+        for x in r.values():
+            assert np.isfinite(x).all()
+        name = f"hostcpp_M{M}N{N}D{D}_c{int(causal)}.npz"
+        b = lambda x: x[None, None]         # [B=1, H=1, ...]: the layout of the dense_*.npz fixtures
+        np.savez(os.path.join(OUT, name), q=b(q).astype(np.float16), k=b(k).astype(np.float16),
+                 v=b(v).astype(np.float16), do=b(do).astype(np.float16), o=b(r["o"]), lse=b(r["lse"]),
+                 dq=b(r["dq"]), dk=b(r["dk"]), dv=b(r["dv"]), scale=np.float64(scale), causal=np.bool_(causal))
+        print("wrote", name)
+
+
 if __name__ == "__main__":
     assert os.path.isdir(REF), "reference checkout not present - run in the build container"
     fwd, bwd = load_ref_oracle()
     gen_dense(fwd, bwd)
     gen_boundary_calls()
+    gen_hostcpp()

@@ -4,6 +4,8 @@ unpacked API itself is checked against the oracle elsewhere (test_fwd_gpu / test
 import pytest
 import torch
 
+from util import LSE_ATOL, assert_close, assert_lse_close, f64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -148,5 +150,5 @@ def test_context_parallel_merge_with_kernel_lse():
             o1, l1, _ = fa.flash_attn_func(q, k[:, :h], v[:, :h], return_attn_probs=True)
             o2, l2, _ = fa.flash_attn_func(q, k[:, h:], v[:, h:], return_attn_probs=True)
         out, lse = merge_attention_shards([o1, o2], [l1, l2])
-        assert torch.allclose(out.float(), full.float(), atol=2e-2, rtol=2e-2), causal
-        assert torch.allclose(lse, lse_full, atol=2e-3), causal
+        assert_close(f64(out), f64(full), "bf16", f"merged out, causal={causal}", mult=1.0)
+        assert_lse_close(f64(lse), f64(lse_full), f"merged lse, causal={causal}", atol=LSE_ATOL)

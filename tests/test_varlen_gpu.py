@@ -422,11 +422,13 @@ def test_varlen_with_empty_sequences():
     # sequence 1 has keys but no queries: zero dk/dv there
     k0 = lens_k[0]
     assert (dk[k0:k0 + 20] == 0).all() and (dv[k0:k0 + 20] == 0).all()
-    # the ordinary sequences match a per-sequence dense call
+    # the ordinary sequences ARE a per-sequence dense call, bit for bit: at D 64 without a mask both ops launch the same
+    # fa_fwd_kernel instantiation over the same 128-row query blocks (fa_api.hip: make_args(p, 128) in fa_fwd and fa_varlen_fwd,
+    # no mirrored pairs without a mask); the flat work list only changes which workgroup takes which block
     for b in (0, 3):
         qs, qe = int(cu_q[b]), int(cu_q[b + 1]); ks, ke = int(cu_k[b]), int(cu_k[b + 1])
         ref = flash_attn.flash_attn_func(q[qs:qe][None], k[ks:ke][None], v[ks:ke][None])
-        assert torch.allclose(out[qs:qe].float(), ref[0].float(), atol=2e-3, rtol=2e-3)
+        assert torch.equal(out[qs:qe], ref[0])
 
 
 def test_varlen_flat_work_list_many_sequences(monkeypatch):
