@@ -17,7 +17,10 @@ SOURCES = ["fa_api.hip", "fa_fwd.hip", "fa_fwd_d256.hip", "fa_fwd_asm.hip", "fa_
 GENERATED = [("gen_fwd_asm.py", "fa_fwd_asm_gen.h", []),
              ("gen_bwd_dkdv_asm.py", "fa_bwd_asm_gen.h", []),
              ("gen_bwd_dq_asm.py", "fa_bwd_dq_asm_gen.h", [])]  # (generator, header, arguments): hand-scheduled asm bodies
-EXTRA_FLAGS = {"fa_fwd_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}      # per-source compiler switches (see the file's header)
+EXTRA_FLAGS = {"fa_fwd_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],     # per-source compiler switches (see the file's header)
+               # the gated epilogue's fp32 arithmetic as scalar-lane VALU instructions, none of them packed (v_pk_*_f32); the
+               # fa_moe_gemm kernels of the same source hold no packed fp32 instruction with or without the switch
+               "fa_moe_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 ASM_SOURCES = ("fa_fwd_asm.hip", "fa_bwd_asm.hip", "fa_bwd_dq_asm.hip")   # kernels whose body is one hand-scheduled asm statement
 RESOURCES = os.path.join(OUT_DIR, "kernel_resources.json")              # their register / scratch use, checked at build time
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),

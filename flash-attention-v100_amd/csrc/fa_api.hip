@@ -252,6 +252,7 @@ size_t fa_moe_permute_params_size(void) { return sizeof(fa_moe_permute_params); 
 size_t fa_moe_combine_params_size(void) { return sizeof(fa_moe_combine_params); }
 size_t fa_moe_combine_bwd_params_size(void) { return sizeof(fa_moe_combine_bwd_params); }
 size_t fa_moe_gemm_params_size(void) { return sizeof(fa_moe_gemm_params); }
+size_t fa_moe_gemm_glu_params_size(void) { return sizeof(fa_moe_gemm_glu_params); }
 size_t fa_moe_gemm_wgrad_params_size(void) { return sizeof(fa_moe_gemm_wgrad_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
@@ -1771,8 +1772,9 @@ static int moe_gemm_shape_check(const char* op, int64_t rows, int n, int k, int 
     return FA_OK;
 }
 
-static int moe_gemm_check(const fa_moe_gemm_params& s) {
-    const char* op = "moe_gemm";
+// fa_moe_gemm's block, and fa_moe_gemm_glu's restated as one (moe_gemm_glu_check): s.n is the weight's and the bias' width,
+// out_n out's (the same, or half of it)
+static int moe_gemm_check(const char* op, const fa_moe_gemm_params& s, int out_n) {
     FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
     FA_TRY(moe_gemm_shape_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
     const bool gather = s.sorted_slot != nullptr;
@@ -1794,7 +1796,7 @@ static int moe_gemm_check(const fa_moe_gemm_params& s) {
     if (s.rows == 0) return FA_OK;
     const int64_t x_rows = gather ? s.tokens : s.rows;
     FA_CHECK(s.out && s.w && s.expert_offsets && (x_rows == 0 || s.x), "%s: x, w, expert_offsets and out must not be NULL", op);
-    FA_CHECK(s.rows <= 1 || s.out_row_stride >= s.n, "%s: out rows must not overlap (out_row_stride >= n)", op);
+    FA_CHECK(s.rows <= 1 || s.out_row_stride >= out_n, "%s: out rows must not overlap (out_row_stride >= n)", op);
     FA_CHECK(x_rows <= 1 || s.x_row_stride >= s.k, "%s: x_row_stride must be at least k", op);
     FA_CHECK(((addr(s.x) | addr(s.w) | addr(s.out)) & 15) == 0, "%s: x, w and out must be 16-byte aligned", op);
     FA_CHECK(((addr(s.expert_offsets) | addr(s.sorted_slot)) & 3) == 0 && (addr(s.bias) & (s.bias_dtype == FA_FP32 ? 3 : 1)) == 0,
@@ -1806,8 +1808,25 @@ static int moe_gemm_check(const fa_moe_gemm_params& s) {
         view_flat("expert_offsets", s.expert_offsets, (uint64_t)(s.num_experts + 1) * 4),
         view_flat("sorted_slot", s.sorted_slot, (uint64_t)s.rows * 4),
     };
-    const View out = view_rows("out", s.out, s.rows, s.out_row_stride, s.n, 2);
+    const View out = view_rows("out", s.out, s.rows, s.out_row_stride, out_n, 2);
     return check_overlaps(op, &out, 1, in, 5, false, nullptr, 0);
+}
+
+// fa_moe_gemm_glu: its own two fields, then fa_moe_gemm's checks on the packed width 2 n
+static int moe_gemm_glu_check(const fa_moe_gemm_glu_params& s) {
+    const char* op = "moe_gemm_glu";
+    FA_CHECK(s.activation >= FA_ACT_SILU && s.activation <= FA_ACT_RELU2, "%s: unknown activation %d", op, s.activation);
+    if (s.n < 8 || s.n > fa::MOE_GEMM_MAX_N / 2 || s.n % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: n must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_GEMM_MAX_N / 2, s.n);
+    fa_moe_gemm_params g = {};
+    g.struct_size = sizeof(g);
+    g.x = s.x, g.w = s.w, g.bias = s.bias, g.expert_offsets = s.expert_offsets, g.sorted_slot = s.sorted_slot, g.out = s.out;
+    g.x_row_stride = s.x_row_stride, g.out_row_stride = s.out_row_stride, g.w_expert_stride = s.w_expert_stride;
+    g.rows = s.rows, g.tokens = s.tokens, g.num_experts = s.num_experts, g.top_k = s.top_k;
+    g.n = 2 * s.n, g.k = s.k, g.dtype = s.dtype, g.bias_dtype = s.bias_dtype, g.layout = s.layout;
+    g.reserved0 = s.reserved0 | s.reserved1;
+    for (int i = 0; i < 4; ++i) g.reserved[i] = s.reserved[i];
+    return moe_gemm_check(op, g, s.n);
 }
 
 static int moe_gemm_wgrad_check(const fa_moe_gemm_wgrad_params& s) {
@@ -2219,11 +2238,35 @@ int fa_moe_gemm_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, in
 int fa_moe_gemm(const fa_moe_gemm_params* sp, void* stream) {
     FA_TRY(check_header(sp, "fa_moe_gemm_params"));
     fa_moe_gemm_params s = *sp;
-    FA_TRY(moe_gemm_check(s));
+    FA_TRY(moe_gemm_check("moe_gemm", s, s.n));
     if (s.rows == 0) return FA_OK;
     if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
     fa::launch_moe_gemm(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_gemm launch");
+}
+
+int fa_moe_gemm_glu_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                         int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n) {
+    if (n < 8 || n > fa::MOE_GEMM_MAX_N / 2 || n % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "moe_gemm_glu_plan: n must be a multiple of 8 in [8, %d], got %d", fa::MOE_GEMM_MAX_N / 2, n);
+    FA_TRY(moe_gemm_shape_check("moe_gemm_glu_plan", rows, 2 * n, k, num_experts, layout, dtype));
+    const fa::MoeGemmPlan pl = fa::moe_gemm_glu_plan(rows, n, k, num_experts, layout, dtype);
+    if (block_m) *block_m = pl.bm;
+    if (block_n) *block_n = pl.bn;
+    if (block_k) *block_k = pl.bk;
+    if (grid_m) *grid_m = pl.grid_m;
+    if (grid_n) *grid_n = pl.grid_n;
+    return FA_OK;
+}
+
+int fa_moe_gemm_glu(const fa_moe_gemm_glu_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_gemm_glu_params"));
+    fa_moe_gemm_glu_params s = *sp;
+    FA_TRY(moe_gemm_glu_check(s));
+    if (s.rows == 0) return FA_OK;
+    if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
+    fa::launch_moe_gemm_glu(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_gemm_glu launch");
 }
 
 int fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,

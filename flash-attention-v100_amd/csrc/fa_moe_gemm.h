@@ -33,6 +33,18 @@ static inline MoeGemmPlan moe_gemm_plan(int64_t m_max, int n, int k, int E, int 
 
 void launch_moe_gemm(const fa_moe_gemm_params& s, hipStream_t stream);
 
+// fa_moe_gemm_glu (the GLU instantiations of fa_moe_gemm.hip's kernel): n counts OUTPUT columns.  A tile stages the same 128
+// weight columns - 64 gate, the 64 matching up - and writes BM x 64; the rows are cut as above.
+constexpr int MOE_GEMM_GLU_BN = MOE_GEMM_BN / 2;
+static inline MoeGemmPlan moe_gemm_glu_plan(int64_t m_max, int n, int k, int E, int layout, int dtype) {
+    MoeGemmPlan pl = moe_gemm_plan(m_max, 2 * n, k, E, layout, dtype);
+    pl.bn = MOE_GEMM_GLU_BN;
+    pl.grid_n = (n + MOE_GEMM_GLU_BN - 1) / MOE_GEMM_GLU_BN;
+    return pl;
+}
+
+void launch_moe_gemm_glu(const fa_moe_gemm_glu_params& s, hipStream_t stream);
+
 // fa_moe_gemm_wgrad (fa_moe_gemm_wgrad.hip): one workgroup per 128 x 128 tile of one expert's dW, the segment's rows staged 64 a
 // step.  dW is dense, so the grid is (ceil(n / 128), ceil(k / 128), E) whatever the segments hold.
 constexpr int MOE_WGRAD_BN = 128;                         // tile extent along n (the columns of dy)

@@ -28,7 +28,19 @@
 // blockIdx.x - or leaves: the grid is the host's bound (fa_moe_gemm.h).  Segment E is the +0 tail; rows below a positive
 // expert_offsets[0] (fa_moe_sort writes 0) are in no segment and are not written.  Offsets are only compared and clamped: a
 // malformed table gives wrong rows, never an address outside out, x or w.
+//
+// fa_moe_gemm_glu (GLU = true): the same body over a packed gate-up weight of 2 n columns, writing out[r, j] = round16(act(g) * u)
+// with g, u = the two sums of output column j (+ bias), each ROUNDED to the io type first - the bits of fa_moe_gemm followed by
+// fa_act_mul (fa_act.h's act_eval), without h.  A tile is BM x 64 OUTPUT columns over the same 128-wide weight image: tile column
+// c < 64 is weight column n0 + c (gate), c >= 64 is n + n0 + (c - 64) (its up) - for "nk" a second source base for the LDS-DMA
+// instructions of waves 2 - 3, for "kn" a per-lane source column; a column is out of range where n0 + c % 64 >= n, which masks a
+// gate and its up together.  Wide plan: wave (wm, wn) takes the gate block at tile column 32 wn and the up block at 64 + 32 wn,
+// so acc[0][mb] and acc[1][mb] hold g and u of one element in one lane and register and the epilogue is lane-local.  Decode
+// plan: waves 0 - 1 hold gate blocks, waves 2 - 3 the up blocks; behind the k loop's last barrier the staging buffers are free,
+// every wave writes its rounded block into a [32][128] image there and each lane then takes 8 gates and 8 ups of one row.  The
+// activation is a wave-uniform run-time switch around the epilogue, not a template parameter.
 #include "fa_common.h"
+#include "fa_act.h"
 #include "fa_moe_gemm.h"
 #include <type_traits>
 
@@ -101,10 +113,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t span_rsrc(uint64_t at, int64_t
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, (int)n, 0x00020000);
 }
 
-template <typename T, int BM, bool KN, bool GATHER>
-__global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gemm_params s) {
+// The one body of fa_moe_gemm's kernels (GLU false: P = fa_moe_gemm_params) and fa_moe_gemm_glu's (GLU true: P =
+// fa_moe_gemm_glu_params, whose n counts OUTPUT columns).  GLU changes which weight rows / columns a tile stages and what the
+// epilogue does with the accumulators, nothing else; with GLU false every `if constexpr (GLU)` falls away.
+template <typename T, int BM, bool KN, bool GATHER, bool GLU, typename P>
+__device__ __forceinline__ void moe_gemm_body(const P& s) {
     using E = Elem<T>;
     constexpr int BN = MOE_GEMM_BN, BK = MOE_GEMM_BK;
+    constexpr int BNO = GLU ? MOE_GEMM_GLU_BN : BN;              // output columns of a tile; GLU: the weight image's halves pair up
     constexpr int WM = BM == 128 ? 2 : 1, WN = 4 / WM;          // waves along the rows | the columns of the tile
     constexpr int MB = BM / (32 * WM), NB = BN / (32 * WN);      // 32 x 32 blocks a wave owns: 2 x 2 | 1 x 1
     constexpr int X_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2, STAGE = X_BYTES + W_BYTES;
@@ -117,21 +133,25 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
     const GemmTile tl = find_tile<BM>(static_cast<const int32_t*>(s.expert_offsets), nE, M, (int)blockIdx.x, lane);
     if (!tl.valid) return;
     const int seg = tl.seg, m0 = tl.m0, m_end = tl.m_end;
-    const int n0 = (int)blockIdx.y * BN;
+    const int n0 = (int)blockIdx.y * BNO;
     uint16_t* const outp = static_cast<uint16_t*>(s.out);
 
     if (seg == nE) {
         // rows behind every segment: +0, 16 bytes a thread
-        for (int c = tid; c < BM * (BN / 8); c += GEMM_THREADS) {
-            const int m = m0 + c / (BN / 8), n = n0 + (c % (BN / 8)) * 8;
+        for (int c = tid; c < BM * (BNO / 8); c += GEMM_THREADS) {
+            const int m = m0 + c / (BNO / 8), n = n0 + (c % (BNO / 8)) * 8;
             if (m < m_end && n < N) *reinterpret_cast<u32x4*>(outp + (int64_t)m * s.out_row_stride + n) = u32x4{0u, 0u, 0u, 0u};
         }
         return;
     }
 
     const int wm_base = (wave / WN) * (MB * 32), wn_base = (wave % WN) * (NB * 32);
+    // the tile column of the wave's block nb.  GLU, wide: block 0 is the gate at 32 wn, block 1 its up at 64 + 32 wn, so that
+    // acc[0][mb] and acc[1][mb] hold g and u of one element in one lane and register; GLU, decode: waves 0 - 1 gate, 2 - 3 up
+    auto wcol = [&](int nb) { return GLU && NB == 2 ? (wave % WN) * 32 + nb * (BN / 2) : wn_base + nb * 32; };
     const uint64_t w_at = reinterpret_cast<uint64_t>(s.w) + (uint64_t)((int64_t)seg * s.w_expert_stride * 2);   // this expert's slab
-    const int64_t w_bytes = (int64_t)N * K * 2;
+    constexpr int NW = GLU ? 2 : 1;                              // weight columns per output column
+    const int64_t w_bytes = (int64_t)N * K * 2 * NW;
     const uint64_t x_at = reinterpret_cast<uint64_t>(s.x);
     const int64_t x_bytes = GATHER ? 0 : ((int64_t)(M - 1) * s.x_row_stride + K) * 2;
 
@@ -164,12 +184,21 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
             const int row = inst * 4 + lane / 16;                                     // k within the step
             const int cb = swzt_row_off<BN>(row, (lane % 16) * 16) - row * BN * 2;    // logical byte column: n within the tile
             w_key[i] = row;
-            w_voff[i] = n0 + cb / 2 < N ? (uint32_t)((int64_t)row * N * 2 + cb) : kOobVoff;
+            if constexpr (GLU) {
+                // tile column c < 64: weight column n0 + c (gate); c >= 64: n + n0 + (c - 64) (its up), masked together
+                const int c = cb / 2, half = c / BNO, cc = c % BNO;
+                w_voff[i] = n0 + cc < N ? (uint32_t)((int64_t)row * N * 4 + (half * N + cc) * 2) : kOobVoff;
+            } else {
+                w_voff[i] = n0 + cb / 2 < N ? (uint32_t)((int64_t)row * N * 2 + cb) : kOobVoff;
+            }
         } else {
             const int row = inst * 8 + lane / 8;                                      // n within the tile
             const int cb = swz_row_off<BK>(row, (lane % 8) * 16) - row * BK * 2;
             w_key[i] = cb / 2;
-            w_voff[i] = n0 + row < N ? (uint32_t)((int64_t)row * K * 2 + cb) : kOobVoff;
+            if constexpr (GLU)                                                        // rows >= 64 (waves 2 - 3): the second source base of `issue`
+                w_voff[i] = n0 + row % BNO < N ? (uint32_t)((int64_t)(row % BNO) * K * 2 + cb) : kOobVoff;
+            else
+                w_voff[i] = n0 + row < N ? (uint32_t)((int64_t)row * K * 2 + cb) : kOobVoff;
         }
     }
 
@@ -177,7 +206,9 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
     auto issue = [&](int k0, int stage) {
         char* base = smem + stage * STAGE;
         // w: "nk" from W_e[n0, k0], "kn" from W_e[k0, n0]
-        const int64_t w_first = KN ? ((int64_t)k0 * N + n0) * 2 : ((int64_t)n0 * K + k0) * 2;
+        // (GLU: W_e has 2 n columns; "nk" waves 2 - 3 stage the up rows from n + n0 on)
+        const int64_t w_first = GLU ? (KN ? ((int64_t)k0 * N * 2 + n0) * 2 : ((int64_t)(n0 + (wave / 2) * N) * K + k0) * 2)
+                                    : (KN ? ((int64_t)k0 * N + n0) * 2 : ((int64_t)n0 * K + k0) * 2);
         const __amdgpu_buffer_rsrc_t wr = span_rsrc(w_at + (uint64_t)w_first, w_bytes - w_first);
 #pragma unroll
         for (int i = 0; i < WCH; ++i)
@@ -219,7 +250,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
-            w_tp[h][nb] = lds_pin(smem + X_BYTES + (KN ? swzt_row_off<BN>(4 * g + t_rr + 8 * h, (wn_base + nb * 32) * 2 + t_cb) : 0));
+            w_tp[h][nb] = lds_pin(smem + X_BYTES + (KN ? swzt_row_off<BN>(4 * g + t_rr + 8 * h, wcol(nb) * 2 + t_cb) : 0));
 
     auto compute = [&](auto stage_c) {
         constexpr int stage = decltype(stage_c)::value;
@@ -246,7 +277,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
                 for (int nb = 0; nb < NB; ++nb) lds_tr_wait(af[nb], 0);
             } else {
 #pragma unroll
-                for (int nb = 0; nb < NB; ++nb) af[nb] = lds_read_b128(sw + swz_row_off<BK>(wn_base + nb * 32 + l31, 32 * ks + 16 * g));
+                for (int nb = 0; nb < NB; ++nb) af[nb] = lds_read_b128(sw + swz_row_off<BK>(wcol(nb) + l31, 32 * ks + 16 * g));
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) bf[mb] = lds_read_b128(sx + swz_row_off<BK>(wm_base + mb * 32 + l31, 32 * ks + 16 * g));
             }
@@ -286,6 +317,92 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
         const uint32_t v = static_cast<const uint16_t*>(s.bias)[at];
         return E::lo(v);
     };
+    if constexpr (GLU) {
+        // ---- the gated epilogue: g, u = the two finished sums (+ bias) ROUNDED to the io type, out = round16(act(g) * u) -
+        // fa_act_mul's arithmetic (fa_act.h) on fa_moe_gemm's bits.  The activation is a wave-uniform run-time switch. ----
+        const bool hb = s.bias != nullptr;
+        auto bias_glu = [&](int half, int n) -> float {          // bias[seg, half n + n]; output columns >= n: +0, never read
+            if (!hb || n >= N) return 0.f;
+            const int64_t at = ((int64_t)seg * 2 + half) * N + n;
+            if (bias32) return static_cast<const float*>(s.bias)[at];
+            const uint32_t v = static_cast<const uint16_t*>(s.bias)[at];
+            return E::lo(v);
+        };
+        // 8 rounded gates and ups of one row -> 8 outputs
+        auto gated = [&](auto act_c, const u32x4& pg, const u32x4& pu) -> u32x4 {
+            constexpr int ACT = decltype(act_c)::value;
+            u32x4 o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float a0, a1, d;
+                act_eval<ACT, false>(E::lo(pg[i]), a0, d);
+                act_eval<ACT, false>(E::hi(pg[i]), a1, d);
+                o[i] = E::pack2(a0 * E::lo(pu[i]), a1 * E::hi(pu[i]));
+            }
+            return o;
+        };
+        auto with_act = [&](auto&& body) {
+            switch (s.activation) {
+                case FA_ACT_SILU:      body(std::integral_constant<int, FA_ACT_SILU>{}); break;
+                case FA_ACT_GELU:      body(std::integral_constant<int, FA_ACT_GELU>{}); break;
+                case FA_ACT_GELU_TANH: body(std::integral_constant<int, FA_ACT_GELU_TANH>{}); break;
+                case FA_ACT_RELU:      body(std::integral_constant<int, FA_ACT_RELU>{}); break;
+                default:               body(std::integral_constant<int, FA_ACT_RELU2>{}); break;
+            }
+        };
+        // the columns 8 (j >> 2) + 4 g + (j & 3) of accumulator registers 8 q + j, + bias, rounded in pairs
+        auto rounded = [&](const f32x16& a, int q, int half, int col0) -> u32x4 {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float b = bias_glu(half, col0 + 16 * q + 8 * (j >> 2) + 4 * g + (j & 3));
+                v[j] = hb ? a[8 * q + j] + b : a[8 * q + j];
+            }
+            return u32x4{E::pack2(v[0], v[1]), E::pack2(v[2], v[3]), E::pack2(v[4], v[5]), E::pack2(v[6], v[7])};
+        };
+        if constexpr (NB == 2) {
+            // wide: acc[0][mb] and acc[1][mb] are g and u of the same elements: lane-local, then fa_moe_gemm's swap and store
+            const int nb0 = n0 + wcol(0);
+            with_act([&](auto act_c) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb) {
+                        const u32x4 o = gated(act_c, rounded(acc[0][mb], q, 0, nb0), rounded(acc[1][mb], q, 1, nb0));
+                        uint32_t a0 = o[0], a1 = o[1], b0 = o[2], b1 = o[3];
+                        permlane32_swap(a0, b0);
+                        permlane32_swap(a1, b1);
+                        const int m = m0 + wm_base + mb * 32 + l31, n = nb0 + 16 * q + 8 * g;
+                        if (m < m_end && n < N) *reinterpret_cast<u32x4*>(outp + (int64_t)m * s.out_row_stride + n) = u32x4{a0, a1, b0, b1};
+                    }
+                }
+            });
+        } else {
+            // decode: waves 0 - 1 hold gate blocks, waves 2 - 3 the matching up blocks.  Both stages are free behind the k loop's
+            // last barrier: every wave writes its rounded block into a [32][128] image (swz_row_off<128>: 8 KiB), then each of the
+            // 256 lanes takes the 8 gates and 8 ups of its (row, 8 columns)
+            static_assert(BM * BN * 2 <= 2 * STAGE, "the exchange image fits the staging buffers");
+            const int half = wave / 2, col0 = n0 + (wave % 2) * 32;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const u32x4 r = rounded(acc[0][0], q, half, col0);
+                uint32_t a0 = r[0], a1 = r[1], b0 = r[2], b1 = r[3];
+                permlane32_swap(a0, b0);
+                permlane32_swap(a1, b1);                         // tile columns 32 wave + 16 q + 8 g + (0..7) of row l31
+                lds_write_b128(smem + swz_row_off<BN>(l31, (wave * 32 + 16 * q + 8 * g) * 2), u32x4{a0, a1, b0, b1});
+            }
+            __syncthreads();
+            const int row = tid / (BNO / 8), pc = tid % (BNO / 8);
+            const u32x4 pg = lds_read_b128(smem + swz_row_off<BN>(row, pc * 16));
+            const u32x4 pu = lds_read_b128(smem + swz_row_off<BN>(row, (BNO / 8 + pc) * 16));
+            const int m = m0 + row, n = n0 + pc * 8;
+            with_act([&](auto act_c) {
+                const u32x4 o = gated(act_c, pg, pu);
+                if (m < m_end && n < N) *reinterpret_cast<u32x4*>(outp + (int64_t)m * s.out_row_stride + n) = o;
+            });
+        }
+        return;
+    }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         const int nb0 = n0 + wn_base + nb * 32;
@@ -313,18 +430,36 @@ __global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gem
     }
 }
 
-template <typename T, int BM, bool KN>
-void launch_g(const fa_moe_gemm_params& s, dim3 grid, hipStream_t stream) {
-    if (s.sorted_slot) hipLaunchKernelGGL((moe_gemm_kernel<T, BM, KN, true>), grid, dim3(GEMM_THREADS), 0, stream, s);
-    else hipLaunchKernelGGL((moe_gemm_kernel<T, BM, KN, false>), grid, dim3(GEMM_THREADS), 0, stream, s);
+template <typename T, int BM, bool KN, bool GATHER>
+__global__ void __launch_bounds__(GEMM_THREADS) moe_gemm_kernel(const fa_moe_gemm_params s) {
+    moe_gemm_body<T, BM, KN, GATHER, false>(s);
 }
-template <typename T, int BM>
-void launch_l(const fa_moe_gemm_params& s, dim3 grid, hipStream_t stream) {
+template <typename T, int BM, bool KN, bool GATHER>
+__global__ void __launch_bounds__(GEMM_THREADS) moe_glu_kernel(const fa_moe_gemm_glu_params s) {
+    moe_gemm_body<T, BM, KN, GATHER, true>(s);
+}
+
+template <typename T, int BM, bool KN, bool GATHER>
+void launch_k(const fa_moe_gemm_params& s, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((moe_gemm_kernel<T, BM, KN, GATHER>), grid, dim3(GEMM_THREADS), 0, stream, s);
+}
+template <typename T, int BM, bool KN, bool GATHER>
+void launch_k(const fa_moe_gemm_glu_params& s, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((moe_glu_kernel<T, BM, KN, GATHER>), grid, dim3(GEMM_THREADS), 0, stream, s);
+}
+// P: fa_moe_gemm_params or fa_moe_gemm_glu_params
+template <typename T, int BM, bool KN, typename P>
+void launch_g(const P& s, dim3 grid, hipStream_t stream) {
+    if (s.sorted_slot) launch_k<T, BM, KN, true>(s, grid, stream);
+    else launch_k<T, BM, KN, false>(s, grid, stream);
+}
+template <typename T, int BM, typename P>
+void launch_l(const P& s, dim3 grid, hipStream_t stream) {
     if (s.layout == FA_MOE_W_KN) launch_g<T, BM, true>(s, grid, stream);
     else launch_g<T, BM, false>(s, grid, stream);
 }
-template <typename T>
-void launch_t(const fa_moe_gemm_params& s, const MoeGemmPlan& pl, hipStream_t stream) {
+template <typename T, typename P>
+void launch_t(const P& s, const MoeGemmPlan& pl, hipStream_t stream) {
     const dim3 grid((unsigned)pl.grid_m, (unsigned)pl.grid_n);
     if (pl.bm == MOE_GEMM_BM_DECODE) launch_l<T, MOE_GEMM_BM_DECODE>(s, grid, stream);
     else launch_l<T, MOE_GEMM_BM_WIDE>(s, grid, stream);
@@ -334,6 +469,12 @@ void launch_t(const fa_moe_gemm_params& s, const MoeGemmPlan& pl, hipStream_t st
 
 void launch_moe_gemm(const fa_moe_gemm_params& s, hipStream_t stream) {
     const MoeGemmPlan pl = moe_gemm_plan(s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype);
+    if (s.dtype == FA_BF16) launch_t<bf16_tag>(s, pl, stream);
+    else launch_t<fp16_tag>(s, pl, stream);
+}
+
+void launch_moe_gemm_glu(const fa_moe_gemm_glu_params& s, hipStream_t stream) {
+    const MoeGemmPlan pl = moe_gemm_glu_plan(s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype);
     if (s.dtype == FA_BF16) launch_t<bf16_tag>(s, pl, stream);
     else launch_t<fp16_tag>(s, pl, stream);
 }

@@ -15,6 +15,9 @@ have their contracts).
   training, the experts as differentiable layers (no xp; dx by moe_gemm + moe_combine, dw and dbias by moe_gemm_wgrad):
     h = moe_linear(x, w1, expert_offsets, sorted_slot=sorted_slot, top_k=k, pos=pos)      # gate-up, fused gather
     yp = moe_linear(act_and_mul(h), w2, expert_offsets)                                   # down
+  or, with the gated activation in the gate-up GEMM's epilogue (`moe_gemm_glu`: the same bits, no h, one launch less):
+    a = moe_glu_linear(x, w1, expert_offsets, sorted_slot=sorted_slot, top_k=k, pos=pos)  # inference: moe_gemm_glu(...)
+    yp = moe_linear(a, w2, expert_offsets)
 
 No function synchronises with the host, every result is a pure function of its inputs (no ordering depends on an atomic, two calls
 give the same bits), all are capturable in a HIP graph.
@@ -78,6 +81,7 @@ import torch
 
 from . import _lib
 from . import _rowargs as _ra
+from . import act_mul as _am
 from . import flash_attn_interface as _fi
 
 MAX_EXPERTS, MAX_TOPK, MAX_ALIGN, MAX_N = 512, 16, 256, 16384
@@ -455,14 +459,22 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
 
     Limits: 2 <= E <= 512, K and N multiples of 8 with K <= 32768 and N <= 65536, row strides of x and out at most 2^22 elements,
     M_max >= 0 (0 launches nothing); expert_offsets[0] is 0 (moe_sort's: rows below a positive first offset are not written).  No autograd:
-    an input that requires grad raises (`moe_linear` is the differentiable name).  Not covered: fp8 / block-scaled operands, an activation or the
-    combine fused into the epilogue, a per-row routing weight, E > 512."""
-    op = "moe_gemm"
+    an input that requires grad raises (`moe_linear` is the differentiable name).  Not covered: fp8 / block-scaled operands, the
+    combine fused into the epilogue, a per-row routing weight, E > 512 (the gated activation in the epilogue: `moe_gemm_glu`)."""
+    return _gemm("moe_gemm", x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, None)
+
+
+def _gemm(op, x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, activation):
+    """moe_gemm (activation None) and moe_gemm_glu: one set of argument checks, one launch.  N is the width of w and bias; out has
+    N columns, or with an activation N / 2"""
+    glu = activation is not None
     if w_layout not in W_LAYOUTS:
         raise RuntimeError(f"{op}: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if glu and activation not in _am.ACTIVATIONS:
+        raise RuntimeError(f"{op}: activation must be one of {sorted(_am.ACTIVATIONS)}, got {activation!r}")
     for name, t in (("x", x), ("w", w), ("bias", bias)):
         if t is not None and t.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError(f"{op}: {name} requires grad, and moe_gemm has no autograd (detach it, or run under no_grad)")
+            raise RuntimeError(f"{op}: {name} requires grad, and {op} has no autograd (detach it, or run under no_grad)")
     if x.dtype not in _fi._DTYPES:
         raise RuntimeError(f"{op}: x must be fp16 or bf16, got {x.dtype}")
     if x.dim() != 2:
@@ -477,7 +489,10 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
     if not (2 <= E <= MAX_EXPERTS):
         raise RuntimeError(f"{op}: num_experts (w.shape[0]) must be in [2, {MAX_EXPERTS}], got {E}")
     _gemm_dim(op, K, "K", GEMM_MAX_K)
-    _gemm_dim(op, N, "N", GEMM_MAX_N)
+    if glu and N % 16:
+        raise RuntimeError(f"{op}: w packs gate and up, I columns each with I a multiple of 8: its width must be a multiple of 16, got {N}")
+    _gemm_dim(op, N, "2 I" if glu else "N", GEMM_MAX_N)
+    NO = N // 2 if glu else N                                 # out's columns
     if w.stride(2) != 1 or w.stride(1) != w.shape[2] or w.stride(0) < N * K or w.stride(0) % 8 or w.data_ptr() % 16:
         raise RuntimeError(f"{op}: w must be 16-byte aligned with contiguous experts and an expert stride that is a multiple of 8 "
                            f"and at least N K, got strides {tuple(w.stride())}")
@@ -498,8 +513,8 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
         raise RuntimeError(f"{op}: M_max must stay below 2^31, got {M}")
     if bias is not None and (bias.dtype not in (x.dtype, torch.float32) or tuple(bias.shape) != (E, N)):
         raise RuntimeError(f"{op}: bias must be {x.dtype} or fp32 of shape {(E, N)}, got {bias.dtype} {tuple(bias.shape)}")
-    if out is not None and (out.dtype != x.dtype or tuple(out.shape) != (M, N)):
-        raise RuntimeError(f"{op}: out must be {x.dtype} of shape {(M, N)}, got {out.dtype} {tuple(out.shape)}")
+    if out is not None and (out.dtype != x.dtype or tuple(out.shape) != (M, NO)):
+        raise RuntimeError(f"{op}: out must be {x.dtype} of shape {(M, NO)}, got {out.dtype} {tuple(out.shape)}")
     if x.shape[0]:
         _gemm_rows(op, x, "x")
     if out is not None and M:
@@ -507,12 +522,12 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
     _ra.same_device(op, [x, w, expert_offsets, bias, sorted_slot, out], x, "x's")
     dev = x.device
     if out is None:
-        out = torch.empty((M, N), dtype=x.dtype, device=dev)
+        out = torch.empty((M, NO), dtype=x.dtype, device=dev)
     if M == 0:
         return out
     bi = None if bias is None else bias.contiguous()
-    s = _lib.FaMoeGemmParams()
-    s.struct_size = ctypes.sizeof(_lib.FaMoeGemmParams)
+    s = _lib.FaMoeGemmGluParams() if glu else _lib.FaMoeGemmParams()
+    s.struct_size = ctypes.sizeof(s)
     s.x, s.x_row_stride = (x.data_ptr() if x.shape[0] else 0), x.stride(0)
     s.w, s.w_expert_stride = w.data_ptr(), w.stride(0)
     if bi is not None:
@@ -521,12 +536,42 @@ def moe_gemm(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=None
     if sorted_slot is not None:
         s.sorted_slot, s.tokens, s.top_k = sorted_slot.data_ptr(), x.shape[0], top_k
     s.out, s.out_row_stride = out.data_ptr(), out.stride(0)
-    s.rows, s.num_experts, s.n, s.k = M, E, N, K
+    s.rows, s.num_experts, s.n, s.k = M, E, NO, K
     s.dtype, s.layout = _fi._DTYPES[x.dtype], W_LAYOUTS[w_layout]
+    if glu:
+        s.activation = _am.ACTIVATIONS[activation]
     with _fi._on_device(dev):
-        _lib.call_moe_gemm(s, _fi._stream(dev))
+        (_lib.call_moe_gemm_glu if glu else _lib.call_moe_gemm)(s, _fi._stream(dev))
     del bi, expert_offsets, sorted_slot
     return out
+
+
+def moe_gemm_glu_plan(M_max, I, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):
+    """(block_m, block_n, block_k, grid_m, grid_n) of `moe_gemm_glu` with I output columns: a function of these arguments alone,
+    no device.  block_m as `moe_gemm_plan`; block_n is 64 output columns (64 gate and 64 up weight columns), grid_n = ceil(I / 64)"""
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"moe_gemm_glu_plan: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if dtype not in _fi._DTYPES:
+        raise RuntimeError(f"moe_gemm_glu_plan: dtype must be fp16 or bf16, got {dtype}")
+    return _lib.moe_gemm_plan(int(M_max), int(I), int(K), int(num_experts), W_LAYOUTS[w_layout], _fi._DTYPES[dtype],
+                              entry="fa_moe_gemm_glu_plan")
+
+
+def moe_gemm_glu(x, w, expert_offsets, *, activation="silu", w_layout="nk", bias=None, sorted_slot=None, top_k=None, out=None):
+    """The gate-up grouped expert GEMM with the gated activation in its epilogue (csrc/fa_moe_gemm.hip, the GLU instantiations):
+    out [M_max, I] from a packed weight of 2 I columns per expert, gate first, then up - w [E, 2 I, K] ("nk": Wg_e = rows [0, I),
+    Wu_e = rows [I, 2 I)) or [E, K, 2 I] ("kn", columns likewise) - and bias [E, 2 I]:
+
+        g = float(round16(sum_k a_r[k] Wg_e[k, j] (+ bias[e, j])))      u = float(round16(sum_k a_r[k] Wu_e[k, j] (+ bias[e, I + j])))
+        out[r, j] = round16(act(g) * u)                                 rows from expert_offsets[E] on: +0
+
+    The result has EXACTLY the bits of act_mul_forward(h[:, :I], h[:, I:], activation=...) with h = moe_gemm(x, w, ...) - the
+    same accumulator chains, the same intermediate rounding, act_mul's one definition of act - without the [M_max, 2 I] buffer,
+    its round trip through memory and the second launch.  One launch, no workspace, capturable.  A tile is block_m rows by 64
+    output columns over the 128-wide weight image of `moe_gemm` (`moe_gemm_glu_plan`).  Every other argument, limit and
+    guarantee is `moe_gemm`'s, with 2 I in the place of N (I a multiple of 8, 2 I <= 65536).  No autograd (`moe_glu_linear`).
+    Not covered: interleaved gate / up columns, a clamped activation, a quantised output, fp8 operands."""
+    return _gemm("moe_gemm_glu", x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, activation)
 
 
 def moe_gemm_wgrad_plan(N, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):
@@ -670,3 +715,23 @@ def moe_linear(x, w, expert_offsets, *, w_layout="nk", bias=None, sorted_slot=No
     _fi._check_device(x, w, expert_offsets, bias, sorted_slot, pos)
     from . import torch_ops as _ops
     return _ops.moe_linear(x, w, expert_offsets, w_layout, bias, sorted_slot, None if top_k is None else int(top_k), pos)
+
+
+def moe_glu_linear(x, w, expert_offsets, *, activation="silu", w_layout="nk", bias=None, sorted_slot=None, top_k=None, pos=None):
+    """The differentiable gate-up expert layer: the forward is `moe_gemm_glu(x, w, expert_offsets, ...)`, bit for bit, and saves
+    only its inputs.  The backward recomputes h = moe_gemm(x, w, ...) - by moe_gemm_glu's contract the very h whose activation
+    the forward returned -, turns dy into dh in place with act_mul_backward(dy, h[:, :I], h[:, I:], inplace=True) and runs
+    `moe_linear`'s backward on dh: the gradients have the bits of autograd through act_and_mul(moe_linear(...)).  Only the
+    gradients autograd asks for are computed.  The tables have no gradient; no double backward."""
+    op = "moe_glu_linear"
+    if w_layout not in W_LAYOUTS:
+        raise RuntimeError(f"{op}: w_layout must be one of {sorted(W_LAYOUTS)}, got {w_layout!r}")
+    if activation not in _am.ACTIVATIONS:
+        raise RuntimeError(f"{op}: activation must be one of {sorted(_am.ACTIVATIONS)}, got {activation!r}")
+    if (sorted_slot is None) != (top_k is None):
+        raise RuntimeError(f"{op}: sorted_slot and top_k go together")
+    if pos is not None and sorted_slot is None:
+        raise RuntimeError(f"{op}: pos goes with sorted_slot (the gather form)")
+    _fi._check_device(x, w, expert_offsets, bias, sorted_slot, pos)
+    from . import torch_ops as _ops
+    return _ops.moe_glu_linear(x, w, expert_offsets, activation, w_layout, bias, sorted_slot, None if top_k is None else int(top_k), pos)

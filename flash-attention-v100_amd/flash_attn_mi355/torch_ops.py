@@ -16,7 +16,8 @@ differentiable; `moe_route` / `moe_route_bwd` / `moe_sort` / `moe_permute` / `mo
 stable sort of the (token, k) slots by expert, the permutation into per-expert segments and the weighted combine of a
 mixture-of-experts block with autograd formulas, fa_moe_*, and `moe_gemm`, its forward grouped expert GEMM over `expert_offsets`,
 fa_moe_gemm, not differentiable, `moe_gemm_wgrad`, its weight and bias gradients, fa_moe_gemm_wgrad, and `moe_linear`, the
-differentiable expert layer built on them; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
+differentiable expert layer built on them, `moe_gemm_glu`, the gate-up GEMM with the gated activation in its epilogue,
+fa_moe_gemm_glu, and `moe_glu_linear`, its differentiable form; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
 sampling from logits and the filtered logits alone, fa_sample, not differentiable; `spec_accept` / `spec_walk` / `spec_verify`:
 speculative-decoding verification, fa_spec_accept / fa_spec_walk, not differentiable - registered, but not listed in `__all__`).
 
@@ -1281,13 +1282,9 @@ def _moe_linear_setup(ctx, inputs, output):
     ctx.args = (w_layout, top_k, None if bias is None else bias.dtype)
 
 
-def _moe_linear_backward(ctx, dy):
-    none = (None,) * 8
-    need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4]
-    if dy is None or not (need_dx or need_dw or need_db):
-        return none
-    x, w, expert_offsets, sorted_slot, pos = ctx.saved_tensors
-    w_layout, top_k, bias_dtype = ctx.args
+def _moe_linear_grads(dy, x, w, expert_offsets, sorted_slot, pos, w_layout, top_k, bias_dtype, need_dx, need_dw, need_db):
+    """(dx, dw, dbias) of out = moe_gemm(x, w, ...) from dy, None where not needed: moe_linear's backward, and moe_glu_linear's
+    once dy has become dh"""
     if not (dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.stride(0) >= dy.shape[1] and dy.stride(0) <= _moe.GEMM_MAX_ROW_STRIDE
             and dy.storage_offset() % 8 == 0):
         dy = dy.contiguous()
@@ -1305,7 +1302,75 @@ def _moe_linear_backward(ctx, dy):
     if need_dw or need_db:
         dw, db = moe_gemm_wgrad(dy, x, expert_offsets, w_layout, sorted_slot, top_k, need_dw, need_db, False,
                                 bias_dtype == torch.float32)
-    return dx, (dw if need_dw else None), None, None, (db if need_db else None), None, None, None
+    return dx, (dw if need_dw else None), (db if need_db else None)
+
+
+def _moe_linear_backward(ctx, dy):
+    need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+    if dy is None or not (need_dx or need_dw or need_db):
+        return (None,) * 8
+    x, w, expert_offsets, sorted_slot, pos = ctx.saved_tensors
+    dx, dw, db = _moe_linear_grads(dy, x, w, expert_offsets, sorted_slot, pos, *ctx.args, need_dx, need_dw, need_db)
+    return dx, dw, None, None, db, None, None, None
 
 
 moe_linear.register_autograd(_moe_linear_backward, setup_context=_moe_linear_setup)
+
+
+# the gate-up grouped expert GEMM with the gated activation in its epilogue (moe.moe_gemm_glu; csrc/fa_moe_gemm.hip) and the
+# differentiable layer on it (moe.moe_glu_linear): torch.ops.flash_attn_mi355.moe_gemm_glu / .moe_glu_linear
+def _glu_fake(x, w, w_layout, sorted_slot):
+    M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
+    return x.new_empty((M, (w.shape[1] if w_layout == "nk" else w.shape[2]) // 2))
+
+
+@torch.library.custom_op(f"{_NS}::moe_gemm_glu", mutates_args=(), device_types="cuda")
+def moe_gemm_glu(x: Tensor, w: Tensor, expert_offsets: Tensor, activation: str, w_layout: str, bias: Optional[Tensor],
+                 sorted_slot: Optional[Tensor], top_k: Optional[int]) -> Tensor:
+    """moe.moe_gemm_glu: out [M_max, I], a fresh contiguous tensor (I: half of w's packed width).  Functional and capturable; no
+    autograd is registered."""
+    return _moe.moe_gemm_glu(x, w, expert_offsets, activation=activation, w_layout=w_layout, bias=bias, sorted_slot=sorted_slot,
+                             top_k=top_k)
+
+
+@moe_gemm_glu.register_fake
+def _(x, w, expert_offsets, activation, w_layout, bias, sorted_slot, top_k):
+    return _glu_fake(x, w, w_layout, sorted_slot)
+
+
+@torch.library.custom_op(f"{_NS}::moe_glu_linear", mutates_args=(), device_types="cuda")
+def moe_glu_linear(x: Tensor, w: Tensor, expert_offsets: Tensor, activation: str, w_layout: str, bias: Optional[Tensor],
+                   sorted_slot: Optional[Tensor], top_k: Optional[int], pos: Optional[Tensor]) -> Tensor:
+    """moe.moe_glu_linear: moe_gemm_glu's out, differentiable in x, w and bias; pos is only read by the backward."""
+    return _moe.moe_gemm_glu(x.detach(), w.detach(), expert_offsets, activation=activation, w_layout=w_layout,
+                             bias=None if bias is None else bias.detach(), sorted_slot=sorted_slot, top_k=top_k)
+
+
+@moe_glu_linear.register_fake
+def _(x, w, expert_offsets, activation, w_layout, bias, sorted_slot, top_k, pos):
+    return _glu_fake(x, w, w_layout, sorted_slot)
+
+
+def _moe_glu_linear_setup(ctx, inputs, output):
+    x, w, expert_offsets, activation, w_layout, bias, sorted_slot, top_k, pos = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(x, w, expert_offsets, bias, sorted_slot, pos)
+    ctx.args = (activation, w_layout, top_k)
+
+
+def _moe_glu_linear_backward(ctx, dy):
+    need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[5]
+    if dy is None or not (need_dx or need_dw or need_db):
+        return (None,) * 9
+    x, w, expert_offsets, bias, sorted_slot, pos = ctx.saved_tensors
+    activation, w_layout, top_k = ctx.args
+    # h again - the forward's own gate and up, bit for bit (moe_gemm_glu's contract) - and dh over it
+    h = moe_gemm(x, w, expert_offsets, w_layout, bias, sorted_slot, top_k)
+    I = h.shape[1] // 2
+    act_mul_bwd_(dy, h[:, :I], h[:, I:], activation)
+    dx, dw, db = _moe_linear_grads(h, x, w, expert_offsets, sorted_slot, pos, w_layout, top_k,
+                                   None if bias is None else bias.dtype, need_dx, need_dw, need_db)
+    return dx, dw, None, None, None, db, None, None, None
+
+
+moe_glu_linear.register_autograd(_moe_glu_linear_backward, setup_context=_moe_glu_linear_setup)

@@ -1649,6 +1649,56 @@ int    fa_moe_gemm_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts,
                         int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
 
 /*
+ * fa_moe_gemm_glu: the gate-up grouped expert GEMM with the gated activation in its epilogue (csrc/fa_moe_gemm.hip, the GLU
+ * instantiations of fa_moe_gemm's kernel).  One launch, no workspace, no atomics, no host synchronisation.  n is the number of
+ * OUTPUT columns (the intermediate size I); an expert's weight has 2 n columns, gate first, then up (fa_act_mul's packed form):
+ *   FA_MOE_W_NK    w is [E, 2 n, k]: Wg_e = rows [0, n), Wu_e = rows [n, 2 n);   FA_MOE_W_KN: w is [E, k, 2 n], columns likewise
+ *   segment rows   g = float(round(sum_k a_r[k] Wg_e[k, j] (+ bias[e, j]))),  u = float(round(sum_k a_r[k] Wu_e[k, j] (+ bias[e, n + j])))
+ *                  out[r, j] = round(act(g) * u)          other rows (expert_offsets[E] <= r < rows): +0
+ *   contract       out has EXACTLY the bits of fa_act_mul(gate = h[:, :n], up = h[:, n:]) with h = fa_moe_gemm(x, w, n' = 2 n, ...):
+ *                  g and u are each fa_moe_gemm's accumulator chain (v_mfma_f32_32x32x16 over k ascending in steps of 16 from
+ *                  +0), the bias is added to the finished sum in fp32, both are rounded to `dtype` and widened again, act is
+ *                  fa_act_mul's (csrc/fa_act.h, one definition), the product is one fp32 multiply and one rounding.  So the fused
+ *                  op can replace the two launches without any change of results, and a backward may recompute h with
+ *                  fa_moe_gemm.
+ *   activation     fa_act (FA_ACT_SILU .. FA_ACT_RELU2); another value: FA_ERR_INVALID_ARGUMENT.
+ *   everything else (a_r plain or through sorted_slot / top_k, expert_offsets only compared and clamped, 64-bit expert bases,
+ *                  strided x and out, bias [E, 2 n] of `dtype` or FA_FP32) is fa_moe_gemm's.
+ *   limits         2 <= num_experts <= 512; n, k multiples of 8, 2 n <= 65536, k <= 32768; w_expert_stride >= 2 n k and a multiple
+ *                  of 8; out_row_stride >= n.  Outside: FA_ERR_UNSUPPORTED, before any device work.
+ * fa_moe_gemm_glu_plan: block_m 128 or 32 by fa_moe_gemm_plan's rule, block_n 64 (OUTPUT columns: a tile stages 64 gate and 64 up
+ *   weight columns, the 128-wide weight image of fa_moe_gemm), block_k 64, grid_m = floor(rows / block_m) + num_experts + 1,
+ *   grid_n = ceil(n / 64).  Each output pointer may be NULL.
+ */
+typedef struct fa_moe_gemm_glu_params {
+    size_t         struct_size;      /* sizeof(fa_moe_gemm_glu_params) as the caller compiled it */
+    const void*    x;                /* [rows, k], or with sorted_slot [tokens, k], of `dtype` */
+    const void*    w;                /* [num_experts, 2 n, k] (FA_MOE_W_NK) or [num_experts, k, 2 n] (FA_MOE_W_KN) of `dtype` */
+    const void*    bias;             /* [num_experts, 2 n] of `bias_dtype`, contiguous; NULL: none */
+    const void*    expert_offsets;   /* int32 [num_experts + 1], device */
+    const void*    sorted_slot;      /* int32 [rows]; NULL: the plain form */
+    void*          out;              /* [rows, n] of `dtype` */
+    int64_t        x_row_stride, out_row_stride;   /* elements, multiples of 8 */
+    int64_t        w_expert_stride;  /* elements, >= 2 n * k, a multiple of 8 */
+    int64_t        rows;             /* M_max */
+    int64_t        tokens;           /* rows of x with sorted_slot; ignored without */
+    int32_t        num_experts, top_k;              /* top_k: with sorted_slot only */
+    int32_t        n, k;             /* n: output columns; the weight has 2 n */
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        bias_dtype;       /* `dtype` or FA_FP32; ignored without bias */
+    int32_t        layout;           /* fa_moe_w_layout */
+    int32_t        activation;       /* fa_act */
+    int32_t        reserved0;        /* 0 */
+    int32_t        reserved1;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_gemm_glu_params;
+
+int    fa_moe_gemm_glu(const fa_moe_gemm_glu_params* s, void* stream);
+size_t fa_moe_gemm_glu_params_size(void);
+int    fa_moe_gemm_glu_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                            int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
+
+/*
  * fa_moe_gemm_wgrad: the weight gradient of fa_moe_gemm, and the bias gradient (csrc/fa_moe_gemm_wgrad.hip).  No workspace, no
  * atomics, no host synchronisation; expert_offsets is read as fa_moe_gemm reads it (clamped to [0, rows], only compared).
  *   dw             FA_MOE_W_NK: [E, n, k];  FA_MOE_W_KN: [E, k, n].  With L_e the rows expert_offsets[e] <= r < expert_offsets[e + 1],
