@@ -13,14 +13,15 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "flash_attn_mi355")
 LIB = os.path.join(OUT_DIR, "libfa_mi355.so")
-SOURCES = ["fa_api.hip", "fa_fwd.hip", "fa_fwd_d256.hip", "fa_fwd_asm.hip", "fa_fwd_fp8.hip", "fa_bwd.hip", "fa_bwd_d256.hip", "fa_bwd_asm.hip", "fa_bwd_dq_asm.hip", "fa_bwd_dq_ds.hip", "fa_kvcache.hip", "fa_decode.hip", "fa_rows.hip", "fa_merge.hip", "fa_rotary.hip", "fa_kv_store.hip", "fa_kv_gather.hip", "fa_rope_store.hip", "fa_qk_norm_rope_store.hip", "fa_qk_norm_rope_bwd.hip", "fa_add_norm.hip", "fa_add_norm_bwd.hip", "fa_cross_entropy.hip", "fa_sample.hip", "fa_spec_verify.hip", "fa_act_mul.hip", "fa_quant.hip", "fa_moe.hip", "fa_moe_gemm.hip", "fa_moe_gemm_wgrad.hip"]
+SOURCES = ["fa_api.hip", "fa_fwd.hip", "fa_fwd_d256.hip", "fa_fwd_asm.hip", "fa_fwd_fp8.hip", "fa_bwd.hip", "fa_bwd_d256.hip", "fa_bwd_asm.hip", "fa_bwd_dq_asm.hip", "fa_bwd_dq_ds.hip", "fa_kvcache.hip", "fa_decode.hip", "fa_rows.hip", "fa_merge.hip", "fa_rotary.hip", "fa_kv_store.hip", "fa_kv_gather.hip", "fa_rope_store.hip", "fa_qk_norm_rope_store.hip", "fa_qk_norm_rope_bwd.hip", "fa_add_norm.hip", "fa_add_norm_bwd.hip", "fa_cross_entropy.hip", "fa_sample.hip", "fa_spec_verify.hip", "fa_act_mul.hip", "fa_quant.hip", "fa_moe.hip", "fa_moe_gemm.hip", "fa_moe_gemm_wgrad.hip", "fa_moe_gemm_mxfp4.hip"]
 GENERATED = [("gen_fwd_asm.py", "fa_fwd_asm_gen.h", []),
              ("gen_bwd_dkdv_asm.py", "fa_bwd_asm_gen.h", []),
              ("gen_bwd_dq_asm.py", "fa_bwd_dq_asm_gen.h", [])]  # (generator, header, arguments): hand-scheduled asm bodies
 EXTRA_FLAGS = {"fa_fwd_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],     # per-source compiler switches (see the file's header)
                # the gated epilogue's fp32 arithmetic as scalar-lane VALU instructions, none of them packed (v_pk_*_f32); the
                # fa_moe_gemm kernels of the same source hold no packed fp32 instruction with or without the switch
-               "fa_moe_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "fa_moe_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "fa_moe_gemm_mxfp4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 ASM_SOURCES = ("fa_fwd_asm.hip", "fa_bwd_asm.hip", "fa_bwd_dq_asm.hip")   # kernels whose body is one hand-scheduled asm statement
 RESOURCES = os.path.join(OUT_DIR, "kernel_resources.json")              # their register / scratch use, checked at build time
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),

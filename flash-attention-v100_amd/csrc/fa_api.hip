@@ -254,6 +254,7 @@ size_t fa_moe_combine_bwd_params_size(void) { return sizeof(fa_moe_combine_bwd_p
 size_t fa_moe_gemm_params_size(void) { return sizeof(fa_moe_gemm_params); }
 size_t fa_moe_gemm_glu_params_size(void) { return sizeof(fa_moe_gemm_glu_params); }
 size_t fa_moe_gemm_wgrad_params_size(void) { return sizeof(fa_moe_gemm_wgrad_params); }
+size_t fa_moe_gemm_mxfp4_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1773,8 +1774,9 @@ static int moe_gemm_shape_check(const char* op, int64_t rows, int n, int k, int 
 }
 
 // fa_moe_gemm's block, and fa_moe_gemm_glu's restated as one (moe_gemm_glu_check): s.n is the weight's and the bias' width,
-// out_n out's (the same, or half of it)
-static int moe_gemm_check(const char* op, const fa_moe_gemm_params& s, int out_n) {
+// out_n out's (the same, or half of it).  fa_moe_gemm_mxfp4 restates its block too (moe_gemm_mxfp4_check): s.w is then the
+// codes, and `wq` their view and the scales' - it has checked their strides - in place of the 16-bit weight's
+static int moe_gemm_check(const char* op, const fa_moe_gemm_params& s, int out_n, const View* wq = nullptr) {
     FA_CHECK(s.reserved0 == 0 && moe_reserved_zero(s), "%s: reserved fields must be 0 (zero-initialise the struct)", op);
     FA_TRY(moe_gemm_shape_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
     const bool gather = s.sorted_slot != nullptr;
@@ -1784,7 +1786,7 @@ static int moe_gemm_check(const char* op, const fa_moe_gemm_params& s, int out_n
             return fail(FA_ERR_UNSUPPORTED, "%s: top_k must be in [1, %d], got %d", op, fa::MOE_MAX_TOPK, s.top_k);
         if (s.tokens > 0x7fffffffLL / s.top_k) return fail(FA_ERR_UNSUPPORTED, "%s: tokens x top_k must stay below 2^31", op);
     }
-    if (s.w_expert_stride < (int64_t)s.n * s.k || s.w_expert_stride % 8 != 0)
+    if (!wq && (s.w_expert_stride < (int64_t)s.n * s.k || s.w_expert_stride % 8 != 0))
         return fail(FA_ERR_UNSUPPORTED, "%s: w_expert_stride must be a multiple of 8 and at least n x k = %lld, got %lld", op,
                     (long long)s.n * s.k, (long long)s.w_expert_stride);
     if (s.x_row_stride < 0 || s.x_row_stride % 8 != 0 || s.x_row_stride > fa::MOE_GEMM_MAX_ROW_STRIDE)
@@ -1795,21 +1797,56 @@ static int moe_gemm_check(const char* op, const fa_moe_gemm_params& s, int out_n
         return fail(FA_ERR_UNSUPPORTED, "%s: bias_dtype must be dtype or fp32", op);
     if (s.rows == 0) return FA_OK;
     const int64_t x_rows = gather ? s.tokens : s.rows;
-    FA_CHECK(s.out && s.w && s.expert_offsets && (x_rows == 0 || s.x), "%s: x, w, expert_offsets and out must not be NULL", op);
+    const char* wn = wq ? wq[0].name : "w";                   // the argument s.w stands for
+    FA_CHECK(s.out && s.w && s.expert_offsets && (x_rows == 0 || s.x), "%s: x, %s, expert_offsets and out must not be NULL", op, wn);
     FA_CHECK(s.rows <= 1 || s.out_row_stride >= out_n, "%s: out rows must not overlap (out_row_stride >= n)", op);
     FA_CHECK(x_rows <= 1 || s.x_row_stride >= s.k, "%s: x_row_stride must be at least k", op);
-    FA_CHECK(((addr(s.x) | addr(s.w) | addr(s.out)) & 15) == 0, "%s: x, w and out must be 16-byte aligned", op);
+    FA_CHECK(((addr(s.x) | addr(s.w) | addr(s.out)) & 15) == 0, "%s: x, %s and out must be 16-byte aligned", op, wn);
     FA_CHECK(((addr(s.expert_offsets) | addr(s.sorted_slot)) & 3) == 0 && (addr(s.bias) & (s.bias_dtype == FA_FP32 ? 3 : 1)) == 0,
              "%s: expert_offsets, sorted_slot and bias must be aligned to their elements", op);
     const View in[] = {
         view_rows("x", s.x, x_rows, s.x_row_stride, s.k, 2),
-        view_rows("w", s.w, s.num_experts, s.w_expert_stride, (int64_t)s.n * s.k, 2),
+        wq ? wq[0] : view_rows("w", s.w, s.num_experts, s.w_expert_stride, (int64_t)s.n * s.k, 2),
         view_flat("bias", s.bias, (uint64_t)s.num_experts * s.n * (s.bias_dtype == FA_FP32 ? 4 : 2)),
         view_flat("expert_offsets", s.expert_offsets, (uint64_t)(s.num_experts + 1) * 4),
         view_flat("sorted_slot", s.sorted_slot, (uint64_t)s.rows * 4),
+        wq ? wq[1] : View{},
     };
     const View out = view_rows("out", s.out, s.rows, s.out_row_stride, out_n, 2);
-    return check_overlaps(op, &out, 1, in, 5, false, nullptr, 0);
+    return check_overlaps(op, &out, 1, in, wq ? 6 : 5, false, nullptr, 0);
+}
+
+// what fa_moe_gemm_mxfp4 and its plan narrow of fa_moe_gemm's shapes: "nk", bf16, k in whole scale groups
+static int moe_gemm_mxfp4_shape_check(const char* op, int64_t rows, int n, int k, int num_experts, int layout, int dtype) {
+    if (dtype != FA_BF16) return fail(FA_ERR_UNSUPPORTED, "%s: dtype must be bf16", op);
+    if (layout != FA_MOE_W_NK) return fail(FA_ERR_UNSUPPORTED, "%s: layout must be FA_MOE_W_NK", op);
+    if (k < 32 || k % 32 != 0) return fail(FA_ERR_UNSUPPORTED, "%s: k must be a multiple of 32, got %d", op, k);
+    return moe_gemm_shape_check(op, rows, n, k, num_experts, layout, dtype);
+}
+
+// fa_moe_gemm_mxfp4: the two weight tensors, then fa_moe_gemm's checks on everything else
+static int moe_gemm_mxfp4_check(const fa_moe_gemm_mxfp4_params& s) {
+    const char* op = "moe_gemm_mxfp4";
+    FA_TRY(moe_gemm_mxfp4_shape_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
+    const int64_t wb = (int64_t)s.n * s.k / 2, cb = (int64_t)s.n * s.k / 32;
+    if (s.w_blocks_expert_stride < wb || s.w_blocks_expert_stride % 16 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: w_blocks_expert_stride must be a multiple of 16 and at least n x k / 2 = %lld bytes, got %lld",
+                    op, (long long)wb, (long long)s.w_blocks_expert_stride);
+    if (s.w_scales_expert_stride < cb)
+        return fail(FA_ERR_UNSUPPORTED, "%s: w_scales_expert_stride must be at least n x k / 32 = %lld bytes, got %lld", op,
+                    (long long)cb, (long long)s.w_scales_expert_stride);
+    FA_CHECK(s.rows == 0 || s.w_scales, "%s: w_scales must not be NULL", op);
+    fa_moe_gemm_params g = {};
+    g.struct_size = sizeof(g);
+    g.x = s.x, g.w = s.w_blocks, g.bias = s.bias, g.expert_offsets = s.expert_offsets, g.sorted_slot = s.sorted_slot, g.out = s.out;
+    g.x_row_stride = s.x_row_stride, g.out_row_stride = s.out_row_stride;
+    g.rows = s.rows, g.tokens = s.tokens, g.num_experts = s.num_experts, g.top_k = s.top_k;
+    g.n = s.n, g.k = s.k, g.dtype = s.dtype, g.bias_dtype = s.bias_dtype, g.layout = s.layout;
+    g.reserved0 = s.reserved0;
+    for (int i = 0; i < 4; ++i) g.reserved[i] = s.reserved[i];
+    const View wq[2] = {view_rows("w_blocks", s.w_blocks, s.num_experts, s.w_blocks_expert_stride, wb, 1),
+                        view_rows("w_scales", s.w_scales, s.num_experts, s.w_scales_expert_stride, cb, 1)};
+    return moe_gemm_check(op, g, s.n, wq);
 }
 
 // fa_moe_gemm_glu: its own two fields, then fa_moe_gemm's checks on the packed width 2 n
@@ -2267,6 +2304,28 @@ int fa_moe_gemm_glu(const fa_moe_gemm_glu_params* sp, void* stream) {
     if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
     fa::launch_moe_gemm_glu(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_gemm_glu launch");
+}
+
+int fa_moe_gemm_mxfp4_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                           int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n) {
+    FA_TRY(moe_gemm_mxfp4_shape_check("moe_gemm_mxfp4_plan", rows, n, k, num_experts, layout, dtype));
+    const fa::MoeGemmPlan pl = fa::moe_gemm_mxfp4_plan(rows, n, k, num_experts);
+    if (block_m) *block_m = pl.bm;
+    if (block_n) *block_n = pl.bn;
+    if (block_k) *block_k = pl.bk;
+    if (grid_m) *grid_m = pl.grid_m;
+    if (grid_n) *grid_n = pl.grid_n;
+    return FA_OK;
+}
+
+int fa_moe_gemm_mxfp4(const fa_moe_gemm_mxfp4_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_gemm_mxfp4_params"));
+    fa_moe_gemm_mxfp4_params s = *sp;
+    FA_TRY(moe_gemm_mxfp4_check(s));
+    if (s.rows == 0) return FA_OK;
+    if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
+    fa::launch_moe_gemm_mxfp4(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_gemm_mxfp4 launch");
 }
 
 int fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,

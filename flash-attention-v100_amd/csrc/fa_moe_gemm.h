@@ -45,6 +45,21 @@ static inline MoeGemmPlan moe_gemm_glu_plan(int64_t m_max, int n, int k, int E, 
 
 void launch_moe_gemm_glu(const fa_moe_gemm_glu_params& s, hipStream_t stream);
 
+// fa_moe_gemm_mxfp4 (fa_moe_gemm_mxfp4.hip): fa_moe_gemm's two tile shapes and grid over e2m1 weights.  A weight row of BK
+// contraction elements is BK / 2 bytes, so the step is deeper than the 16-bit kernel's 64.  Decode stages 256: a 16 KiB weight
+// image and x [32][256] (16 KiB) per stage, 64 KiB for two stages and two workgroups a CU.  Prefill is MFMA-bound and stages
+// 128: w 8 KiB + x [128][128] 32 KiB per stage, 80 KiB - again two workgroups in a CU's 160 KiB.
+// The kernels are built for two waves a SIMD (at most 256 registers: 122 - 197 are used), so that LDS and registers both allow it.
+constexpr int MOE_GEMM_MXFP4_BK = 256;                    // decode plan
+constexpr int MOE_GEMM_MXFP4_BK_WIDE = 128;               // prefill plan
+static inline MoeGemmPlan moe_gemm_mxfp4_plan(int64_t m_max, int n, int k, int E) {
+    MoeGemmPlan pl = moe_gemm_plan(m_max, n, k, E, FA_MOE_W_NK, FA_BF16);
+    pl.bk = pl.bm == MOE_GEMM_BM_DECODE ? MOE_GEMM_MXFP4_BK : MOE_GEMM_MXFP4_BK_WIDE;
+    return pl;
+}
+
+void launch_moe_gemm_mxfp4(const fa_moe_gemm_mxfp4_params& s, hipStream_t stream);
+
 // fa_moe_gemm_wgrad (fa_moe_gemm_wgrad.hip): one workgroup per 128 x 128 tile of one expert's dW, the segment's rows staged 64 a
 // step.  dW is dense, so the grid is (ceil(n / 128), ceil(k / 128), E) whatever the segments hold.
 constexpr int MOE_WGRAD_BN = 128;                         // tile extent along n (the columns of dy)

@@ -496,6 +496,17 @@ def _gemm(op, x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, act
     if w.stride(2) != 1 or w.stride(1) != w.shape[2] or w.stride(0) < N * K or w.stride(0) % 8 or w.data_ptr() % 16:
         raise RuntimeError(f"{op}: w must be 16-byte aligned with contiguous experts and an expert stride that is a multiple of 8 "
                            f"and at least N K, got strides {tuple(w.stride())}")
+    s = _lib.FaMoeGemmGluParams() if glu else _lib.FaMoeGemmParams()
+    s.w, s.w_expert_stride, s.layout = w.data_ptr(), w.stride(0), W_LAYOUTS[w_layout]
+    if glu:
+        s.activation = _am.ACTIVATIONS[activation]
+    return _gemm_launch(op, s, _lib.call_moe_gemm_glu if glu else _lib.call_moe_gemm, x, [w], E, N, NO, K, expert_offsets, bias,
+                        sorted_slot, top_k, out)
+
+
+def _gemm_launch(op, s, call, x, weights, E, N, NO, K, expert_offsets, bias, sorted_slot, top_k, out):
+    """what moe_gemm, moe_gemm_glu and moe_gemm_mxfp4 share behind their weight checks: the checks of every other argument, the
+    fields of `s` (whose weight fields the caller has set) that all three structs have, and the launch through `call`"""
     expert_offsets = _table(op, expert_offsets, (E + 1,), torch.int32, "expert_offsets")
     if (sorted_slot is None) != (top_k is None):
         raise RuntimeError(f"{op}: sorted_slot and top_k go together")
@@ -519,17 +530,15 @@ def _gemm(op, x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, act
         _gemm_rows(op, x, "x")
     if out is not None and M:
         _gemm_rows(op, out, "out")
-    _ra.same_device(op, [x, w, expert_offsets, bias, sorted_slot, out], x, "x's")
+    _ra.same_device(op, [x] + weights + [expert_offsets, bias, sorted_slot, out], x, "x's")
     dev = x.device
     if out is None:
         out = torch.empty((M, NO), dtype=x.dtype, device=dev)
     if M == 0:
         return out
     bi = None if bias is None else bias.contiguous()
-    s = _lib.FaMoeGemmGluParams() if glu else _lib.FaMoeGemmParams()
     s.struct_size = ctypes.sizeof(s)
     s.x, s.x_row_stride = (x.data_ptr() if x.shape[0] else 0), x.stride(0)
-    s.w, s.w_expert_stride = w.data_ptr(), w.stride(0)
     if bi is not None:
         s.bias, s.bias_dtype = bi.data_ptr(), (_lib.FA_FP32 if bi.dtype == torch.float32 else _fi._DTYPES[bi.dtype])
     s.expert_offsets = expert_offsets.data_ptr()
@@ -537,13 +546,68 @@ def _gemm(op, x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, act
         s.sorted_slot, s.tokens, s.top_k = sorted_slot.data_ptr(), x.shape[0], top_k
     s.out, s.out_row_stride = out.data_ptr(), out.stride(0)
     s.rows, s.num_experts, s.n, s.k = M, E, NO, K
-    s.dtype, s.layout = _fi._DTYPES[x.dtype], W_LAYOUTS[w_layout]
-    if glu:
-        s.activation = _am.ACTIVATIONS[activation]
+    s.dtype = _fi._DTYPES[x.dtype]
     with _fi._on_device(dev):
-        (_lib.call_moe_gemm_glu if glu else _lib.call_moe_gemm)(s, _fi._stream(dev))
+        call(s, _fi._stream(dev))
     del bi, expert_offsets, sorted_slot
     return out
+
+
+def moe_gemm_mxfp4_plan(M_max, N, K, num_experts):
+    """(block_m, block_n, block_k, grid_m, grid_n) of `moe_gemm_mxfp4`: a function of these arguments alone, no device.  block_m
+    and the grid as `moe_gemm_plan`; block_k is 256 in the decode plan and 128 in the prefill plan"""
+    return _lib.moe_gemm_plan(int(M_max), int(N), int(K), int(num_experts), W_LAYOUTS["nk"], _fi._DTYPES[torch.bfloat16],
+                              entry="fa_moe_gemm_mxfp4_plan")
+
+
+def moe_gemm_mxfp4(x, w_blocks, w_scales, expert_offsets, *, bias=None, sorted_slot=None, top_k=None, out=None):
+    """`moe_gemm` with the expert weights in MXFP4 (csrc/fa_moe_gemm_mxfp4.hip), bf16 x and out, layout "nk" only:
+
+        W_e[n, k] = e2m1(code) * 2^(scale - 127)        e2m1: 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives (bit 3)
+
+    w_blocks uint8 [E, N, K / 2] - element k of row n in byte k // 2, the low nibble for even k, the OCP MX / HF gpt-oss order; a
+    contiguous [E, N, K / 32, 16] is the same memory - and w_scales uint8 [E, N, K / 32], one E8M0 byte per 32 k.  Both may be
+    views with contiguous experts and any expert stride (w_blocks: 16-byte aligned, its stride a multiple of 16).  The contract
+    covers scale bytes 2 ... 252, where every weight is a finite normal bf16; other bytes give unspecified values and form no
+    address.  The weights are never dequantised in memory: a decode step streams 17 / 32 of a byte per weight instead of 2.
+
+    out has EXACTLY the bits of moe_gemm(x, dequantised bf16 weights, ...): a weight is exact in bf16 and every output element is
+    the same accumulator chain of v_mfma_f32_32x32x16 over k ascending with the same operand slots, in both plans
+    (`moe_gemm_mxfp4_plan`), plain and gathered.  x, bias, expert_offsets, sorted_slot / top_k, out, the +0 tail, the limits and
+    the guarantees are `moe_gemm`'s, with K a multiple of 32.  One launch, no workspace, capturable.  No autograd: an input that
+    requires grad raises.  Not covered: fp16, the "kn" layout, MX or fp8 activations, a gated epilogue, a quantiser."""
+    op = "moe_gemm_mxfp4"
+    for name, t in (("x", x), ("bias", bias)):
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{op}: {name} requires grad, and {op} has no autograd (detach it, or run under no_grad)")
+    if x.dtype != torch.bfloat16 or x.dim() != 2:
+        raise RuntimeError(f"{op}: x must be a bf16 tensor [rows, K], got {x.dtype} {tuple(x.shape)}")
+    K = x.shape[1]
+    if K < 32 or K > GEMM_MAX_K or K % 32:
+        raise RuntimeError(f"{op}: K must be a multiple of 32 in [32, {GEMM_MAX_K}], got {K}")
+    if w_blocks.dtype != torch.uint8 or w_blocks.dim() not in (3, 4):
+        raise RuntimeError(f"{op}: w_blocks must be a uint8 tensor [E, N, K / 2] or [E, N, K / 32, 16], got {w_blocks.dtype} "
+                           f"{tuple(w_blocks.shape)}")
+    E, N = w_blocks.shape[0], w_blocks.shape[1]
+    if tuple(w_blocks.shape[2:]) not in ((K // 2,), (K // 32, 16)):
+        raise RuntimeError(f"{op}: w_blocks {tuple(w_blocks.shape)} does not contract with x's K = {K}")
+    if w_scales.dtype != torch.uint8 or tuple(w_scales.shape) != (E, N, K // 32):
+        raise RuntimeError(f"{op}: w_scales must be uint8 of shape {(E, N, K // 32)}, got {w_scales.dtype} {tuple(w_scales.shape)}")
+    if not (2 <= E <= MAX_EXPERTS):
+        raise RuntimeError(f"{op}: num_experts (w_blocks.shape[0]) must be in [2, {MAX_EXPERTS}], got {E}")
+    _gemm_dim(op, N, "N", GEMM_MAX_N)
+    if (not w_blocks[0].is_contiguous() or w_blocks.stride(0) < N * K // 2 or w_blocks.stride(0) % 16 or w_blocks.data_ptr() % 16):
+        raise RuntimeError(f"{op}: w_blocks must be 16-byte aligned with contiguous experts and an expert stride that is a multiple "
+                           f"of 16 and at least N K / 2, got strides {tuple(w_blocks.stride())}")
+    if not w_scales[0].is_contiguous() or w_scales.stride(0) < N * K // 32:
+        raise RuntimeError(f"{op}: w_scales must have contiguous experts and an expert stride of at least N K / 32, got strides "
+                           f"{tuple(w_scales.stride())}")
+    s = _lib.FaMoeGemmMxfp4Params()
+    s.w_blocks, s.w_blocks_expert_stride = w_blocks.data_ptr(), w_blocks.stride(0)
+    s.w_scales, s.w_scales_expert_stride = w_scales.data_ptr(), w_scales.stride(0)
+    s.layout = W_LAYOUTS["nk"]
+    return _gemm_launch(op, s, _lib.call_moe_gemm_mxfp4, x, [w_blocks, w_scales], E, N, N, K, expert_offsets, bias, sorted_slot,
+                        top_k, out)
 
 
 def moe_gemm_glu_plan(M_max, I, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):

@@ -1237,6 +1237,20 @@ def _(x, w, expert_offsets, w_layout, bias, sorted_slot, top_k):
     return x.new_empty((M, w.shape[1] if w_layout == "nk" else w.shape[2]))
 
 
+# the same on MXFP4 weights (moe.moe_gemm_mxfp4; csrc/fa_moe_gemm_mxfp4.hip): torch.ops.flash_attn_mi355.moe_gemm_mxfp4
+@torch.library.custom_op(f"{_NS}::moe_gemm_mxfp4", mutates_args=(), device_types="cuda")
+def moe_gemm_mxfp4(x: Tensor, w_blocks: Tensor, w_scales: Tensor, expert_offsets: Tensor, bias: Optional[Tensor],
+                   sorted_slot: Optional[Tensor], top_k: Optional[int]) -> Tensor:
+    """moe.moe_gemm_mxfp4: out [M_max, N], a fresh contiguous bf16 tensor.  Functional and capturable; no autograd is registered."""
+    return _moe.moe_gemm_mxfp4(x, w_blocks, w_scales, expert_offsets, bias=bias, sorted_slot=sorted_slot, top_k=top_k)
+
+
+@moe_gemm_mxfp4.register_fake
+def _(x, w_blocks, w_scales, expert_offsets, bias, sorted_slot, top_k):
+    M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
+    return x.new_empty((M, w_blocks.shape[1]))
+
+
 # the weight / bias gradient of the grouped expert GEMM (moe.moe_gemm_wgrad; csrc/fa_moe_gemm_wgrad.hip) and the differentiable
 # expert layer built on moe_gemm, moe_combine and it (moe.moe_linear): torch.ops.flash_attn_mi355.moe_gemm_wgrad / .moe_linear
 @torch.library.custom_op(f"{_NS}::moe_gemm_wgrad", mutates_args=(), device_types="cuda")

@@ -1753,6 +1753,53 @@ int    fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t
                               int64_t* grid_n, int64_t* grid_k, int64_t* grid_e);
 
 /*
+ * fa_moe_gemm_mxfp4: fa_moe_gemm with the expert weights in MXFP4 - OCP e2m1 codes and one E8M0 scale byte per 32 contraction
+ * elements - and bf16 activations (csrc/fa_moe_gemm_mxfp4.hip).  "nk" layout and bf16 io only.  One launch, no workspace, no
+ * atomics, no host synchronisation.
+ *   weights        W_e[n, k] = e2m1(code) * 2^(scale - 127); e2m1 = 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives (bit 3 the sign).
+ *                  w_blocks uint8 [E, n, k / 2]: element k of row n in byte k / 2, the low nibble for even k (the OCP MX / gpt-oss
+ *                  order; a contiguous [E, n, k / 32, 16] tensor is the same memory).  w_scales uint8 [E, n, k / 32].  The contract
+ *                  covers scale bytes 2 ... 252, where every weight is a normal, finite bf16; other bytes form no address.
+ *   contract       out has EXACTLY the bits of fa_moe_gemm(x, dequantised bf16 weights, ...): a weight is exact in bf16, and every
+ *                  output element is fa_moe_gemm's accumulator chain (v_mfma_f32_32x32x16 over k ascending in steps of 16 from
+ *                  +0, the 16 k of a step in the same operand slots), + bias in fp32, one rounding - in both plans, plain and
+ *                  gathered.
+ *   tensors        w_blocks: 16-byte aligned, w_blocks_expert_stride (BYTES) >= n * k / 2 and a multiple of 16.  w_scales: any
+ *                  alignment, w_scales_expert_stride (BYTES) >= n * k / 32.  x, out, bias, expert_offsets, sorted_slot, the +0 tail
+ *                  and every other rule: fa_moe_gemm's, with dtype = FA_BF16.
+ *   limits         fa_moe_gemm's, and k a multiple of 32.  Outside: FA_ERR_UNSUPPORTED, before any device work.
+ * fa_moe_gemm_mxfp4_plan: block_m 128 (prefill) or 32 (decode: rows <= 32 * num_experts), block_n 128, block_k 128 (prefill) or
+ *   256 (decode), grid_m = floor(rows / block_m) + num_experts + 1, grid_n = ceil(n / 128).  Needs no device.
+ */
+typedef struct fa_moe_gemm_mxfp4_params {
+    size_t         struct_size;      /* sizeof(fa_moe_gemm_mxfp4_params) as the caller compiled it */
+    const void*    x;                /* [rows, k], or with sorted_slot [tokens, k], bf16 */
+    const void*    w_blocks;         /* uint8 [num_experts, n, k / 2] */
+    const void*    w_scales;         /* uint8 [num_experts, n, k / 32] */
+    const void*    bias;             /* [num_experts, n] of `bias_dtype`, contiguous; NULL: none */
+    const void*    expert_offsets;   /* int32 [num_experts + 1], device */
+    const void*    sorted_slot;      /* int32 [rows]; NULL: the plain form */
+    void*          out;              /* [rows, n] bf16 */
+    int64_t        x_row_stride, out_row_stride;   /* elements, multiples of 8 */
+    int64_t        w_blocks_expert_stride;         /* bytes, >= n * k / 2, a multiple of 16 */
+    int64_t        w_scales_expert_stride;         /* bytes, >= n * k / 32 */
+    int64_t        rows;             /* M_max */
+    int64_t        tokens;           /* rows of x with sorted_slot; ignored without */
+    int32_t        num_experts, top_k;              /* top_k: with sorted_slot only */
+    int32_t        n, k;
+    int32_t        dtype;            /* FA_BF16 */
+    int32_t        bias_dtype;       /* FA_BF16 or FA_FP32; ignored without bias */
+    int32_t        layout;           /* FA_MOE_W_NK */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_gemm_mxfp4_params;
+
+int    fa_moe_gemm_mxfp4(const fa_moe_gemm_mxfp4_params* s, void* stream);
+size_t fa_moe_gemm_mxfp4_params_size(void);
+int    fa_moe_gemm_mxfp4_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                              int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
