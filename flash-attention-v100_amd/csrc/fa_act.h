@@ -45,4 +45,14 @@ __device__ __forceinline__ void act_eval(float g, float& a, float& d) {
     }
 }
 
+// FA_ACT_SWIGLU_OAI, the clamped SwiGLU of gpt-oss: a function of the gate AND the up, so not an act_eval case.  The gate has an
+// upper clamp only, the up is clamped to +-limit (limit = +inf: no clamp; a NaN stays a NaN: both comparisons are false); each
+// line is one fp32 operation per operator, in this order (include/fa_mi355.h, fa_moe_gemm_mxfp4_glu)
+__device__ __forceinline__ float act_swiglu_oai(float g, float u, float alpha, float limit) {
+    const float gc = g > limit ? limit : g;
+    const float uc = u > limit ? limit : (u < -limit ? -limit : u);
+    const float a = gc * act_sig(alpha * gc);
+    return (uc + 1.0f) * a;
+}
+
 }  // namespace fa

@@ -255,6 +255,7 @@ size_t fa_moe_gemm_params_size(void) { return sizeof(fa_moe_gemm_params); }
 size_t fa_moe_gemm_glu_params_size(void) { return sizeof(fa_moe_gemm_glu_params); }
 size_t fa_moe_gemm_wgrad_params_size(void) { return sizeof(fa_moe_gemm_wgrad_params); }
 size_t fa_moe_gemm_mxfp4_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_params); }
+size_t fa_moe_gemm_mxfp4_glu_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_glu_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1824,9 +1825,9 @@ static int moe_gemm_mxfp4_shape_check(const char* op, int64_t rows, int n, int k
     return moe_gemm_shape_check(op, rows, n, k, num_experts, layout, dtype);
 }
 
-// fa_moe_gemm_mxfp4: the two weight tensors, then fa_moe_gemm's checks on everything else
-static int moe_gemm_mxfp4_check(const fa_moe_gemm_mxfp4_params& s) {
-    const char* op = "moe_gemm_mxfp4";
+// fa_moe_gemm_mxfp4: the two weight tensors, then fa_moe_gemm's checks on everything else.  fa_moe_gemm_mxfp4_glu restates its
+// block as one (moe_gemm_mxfp4_glu_check): s.n is then the weights' and the bias' width 2 n, out_n out's
+static int moe_gemm_mxfp4_check(const fa_moe_gemm_mxfp4_params& s, const char* op = "moe_gemm_mxfp4", int out_n = -1) {
     FA_TRY(moe_gemm_mxfp4_shape_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
     const int64_t wb = (int64_t)s.n * s.k / 2, cb = (int64_t)s.n * s.k / 32;
     if (s.w_blocks_expert_stride < wb || s.w_blocks_expert_stride % 16 != 0)
@@ -1846,7 +1847,38 @@ static int moe_gemm_mxfp4_check(const fa_moe_gemm_mxfp4_params& s) {
     for (int i = 0; i < 4; ++i) g.reserved[i] = s.reserved[i];
     const View wq[2] = {view_rows("w_blocks", s.w_blocks, s.num_experts, s.w_blocks_expert_stride, wb, 1),
                         view_rows("w_scales", s.w_scales, s.num_experts, s.w_scales_expert_stride, cb, 1)};
-    return moe_gemm_check(op, g, s.n, wq);
+    return moe_gemm_check(op, g, out_n < 0 ? s.n : out_n, wq);
+}
+
+// what fa_moe_gemm_mxfp4_glu and its plan ask of the output width
+static int moe_gemm_mxfp4_glu_n_check(const char* op, int n) {
+    if (n < 8 || n > fa::MOE_GEMM_MAX_N / 2 || n % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: n must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_GEMM_MAX_N / 2, n);
+    return FA_OK;
+}
+
+// fa_moe_gemm_mxfp4_glu: its own four fields, then fa_moe_gemm_mxfp4's checks on the width 2 n
+static int moe_gemm_mxfp4_glu_check(const fa_moe_gemm_mxfp4_glu_params& s) {
+    const char* op = "moe_gemm_mxfp4_glu";
+    FA_CHECK(s.activation == FA_ACT_SILU || s.activation == FA_ACT_RELU || s.activation == FA_ACT_SWIGLU_OAI,
+             "%s: unknown activation %d (FA_ACT_SILU, FA_ACT_RELU or FA_ACT_SWIGLU_OAI)", op, s.activation);
+    FA_CHECK(s.gate_up == FA_MOE_GLU_INTERLEAVED || s.gate_up == FA_MOE_GLU_PACKED, "%s: unknown gate_up %d", op, s.gate_up);
+    if (s.activation == FA_ACT_SWIGLU_OAI) {
+        FA_CHECK(s.alpha - s.alpha == 0.f, "%s: alpha must be finite, got %g", op, (double)s.alpha);
+        FA_CHECK(s.limit > 0.f, "%s: limit must be positive (+inf: no clamp), got %g", op, (double)s.limit);
+    }
+    FA_TRY(moe_gemm_mxfp4_glu_n_check(op, s.n));
+    fa_moe_gemm_mxfp4_params q = {};
+    q.struct_size = sizeof(q);
+    q.x = s.x, q.w_blocks = s.w_blocks, q.w_scales = s.w_scales, q.bias = s.bias, q.expert_offsets = s.expert_offsets;
+    q.sorted_slot = s.sorted_slot, q.out = s.out;
+    q.x_row_stride = s.x_row_stride, q.out_row_stride = s.out_row_stride;
+    q.w_blocks_expert_stride = s.w_blocks_expert_stride, q.w_scales_expert_stride = s.w_scales_expert_stride;
+    q.rows = s.rows, q.tokens = s.tokens, q.num_experts = s.num_experts, q.top_k = s.top_k;
+    q.n = 2 * s.n, q.k = s.k, q.dtype = s.dtype, q.bias_dtype = s.bias_dtype, q.layout = s.layout;
+    q.reserved0 = s.reserved0;
+    for (int i = 0; i < 4; ++i) q.reserved[i] = s.reserved[i];
+    return moe_gemm_mxfp4_check(q, op, s.n);
 }
 
 // fa_moe_gemm_glu: its own two fields, then fa_moe_gemm's checks on the packed width 2 n
@@ -2326,6 +2358,29 @@ int fa_moe_gemm_mxfp4(const fa_moe_gemm_mxfp4_params* sp, void* stream) {
     if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
     fa::launch_moe_gemm_mxfp4(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_gemm_mxfp4 launch");
+}
+
+int fa_moe_gemm_mxfp4_glu_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                               int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n) {
+    FA_TRY(moe_gemm_mxfp4_glu_n_check("moe_gemm_mxfp4_glu_plan", n));
+    FA_TRY(moe_gemm_mxfp4_shape_check("moe_gemm_mxfp4_glu_plan", rows, 2 * n, k, num_experts, layout, dtype));
+    const fa::MoeGemmPlan pl = fa::moe_gemm_mxfp4_glu_plan(rows, n, k, num_experts);
+    if (block_m) *block_m = pl.bm;
+    if (block_n) *block_n = pl.bn;
+    if (block_k) *block_k = pl.bk;
+    if (grid_m) *grid_m = pl.grid_m;
+    if (grid_n) *grid_n = pl.grid_n;
+    return FA_OK;
+}
+
+int fa_moe_gemm_mxfp4_glu(const fa_moe_gemm_mxfp4_glu_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_gemm_mxfp4_glu_params"));
+    fa_moe_gemm_mxfp4_glu_params s = *sp;
+    FA_TRY(moe_gemm_mxfp4_glu_check(s));
+    if (s.rows == 0) return FA_OK;
+    if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
+    fa::launch_moe_gemm_mxfp4_glu(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_gemm_mxfp4_glu launch");
 }
 
 int fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,

@@ -60,6 +60,18 @@ static inline MoeGemmPlan moe_gemm_mxfp4_plan(int64_t m_max, int n, int k, int E
 
 void launch_moe_gemm_mxfp4(const fa_moe_gemm_mxfp4_params& s, hipStream_t stream);
 
+// fa_moe_gemm_mxfp4_glu (the GLU instantiations of fa_moe_gemm_mxfp4.hip's body): n counts OUTPUT columns.  A tile stages the same
+// 128-row weight image - 64 gates and their 64 ups, in both gate_up orders - with the same two stages of LDS and writes BM x 64.
+constexpr int MOE_GEMM_MXFP4_GLU_BN = MOE_GEMM_BN / 2;
+static inline MoeGemmPlan moe_gemm_mxfp4_glu_plan(int64_t m_max, int n, int k, int E) {
+    MoeGemmPlan pl = moe_gemm_mxfp4_plan(m_max, 2 * n, k, E);
+    pl.bn = MOE_GEMM_MXFP4_GLU_BN;
+    pl.grid_n = (n + MOE_GEMM_MXFP4_GLU_BN - 1) / MOE_GEMM_MXFP4_GLU_BN;
+    return pl;
+}
+
+void launch_moe_gemm_mxfp4_glu(const fa_moe_gemm_mxfp4_glu_params& s, hipStream_t stream);
+
 // fa_moe_gemm_wgrad (fa_moe_gemm_wgrad.hip): one workgroup per 128 x 128 tile of one expert's dW, the segment's rows staged 64 a
 // step.  dW is dense, so the grid is (ceil(n / 128), ceil(k / 128), E) whatever the segments hold.
 constexpr int MOE_WGRAD_BN = 128;                         // tile extent along n (the columns of dy)

@@ -16,6 +16,8 @@ FA_FLAG_DS_HANDOFF = 4
 FA_FLAG_FWD_KEY_SPLIT = 8
 FA_FLAG_TREE_MASK = 16
 FA_ACT_SILU, FA_ACT_GELU, FA_ACT_GELU_TANH, FA_ACT_RELU, FA_ACT_RELU2 = 0, 1, 2, 3, 4    # enum fa_act
+FA_ACT_SWIGLU_OAI = 5                                                                    # (fa_moe_gemm_mxfp4_glu only)
+FA_MOE_GLU_INTERLEAVED, FA_MOE_GLU_PACKED = 0, 1                                         # enum fa_moe_glu_order
 FA_QUANT_ROW, FA_QUANT_GROUP, FA_QUANT_STATIC = 0, 1, 2                                  # enum fa_quant_mode
 FA_MOE_SOFTMAX, FA_MOE_SIGMOID = 0, 1                                                    # enum fa_moe_scoring
 FA_MOE_W_NK, FA_MOE_W_KN = 0, 1                                                          # enum fa_moe_w_layout
@@ -606,6 +608,23 @@ class FaMoeGemmMxfp4Params(ctypes.Structure):
     ]
 
 
+class FaMoeGemmMxfp4GluParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_gemm_mxfp4_glu_params` (include/fa_mi355.h): fa_moe_gemm_mxfp4_glu, the gate-up grouped expert GEMM
+    on MXFP4 weights with the gated activation in its epilogue; n counts output columns.  struct_size must be set to
+    sizeof(FaMoeGemmMxfp4GluParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("x", _ptr), ("w_blocks", _ptr), ("w_scales", _ptr), ("bias", _ptr), ("expert_offsets", _ptr), ("sorted_slot", _ptr),
+        ("out", _ptr),
+        ("x_row_stride", _i64), ("out_row_stride", _i64), ("w_blocks_expert_stride", _i64), ("w_scales_expert_stride", _i64),
+        ("rows", _i64), ("tokens", _i64),
+        ("num_experts", _i32), ("top_k", _i32), ("n", _i32), ("k", _i32),
+        ("dtype", _i32), ("bias_dtype", _i32), ("layout", _i32), ("activation", _i32),
+        ("gate_up", _i32), ("alpha", _f32), ("limit", _f32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -633,7 +652,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_moe_gemm", "fa_moe_gemm_params_size", "fa_moe_gemm_plan",
            "fa_moe_gemm_glu", "fa_moe_gemm_glu_params_size", "fa_moe_gemm_glu_plan",
            "fa_moe_gemm_wgrad", "fa_moe_gemm_wgrad_params_size", "fa_moe_gemm_wgrad_plan",
-           "fa_moe_gemm_mxfp4", "fa_moe_gemm_mxfp4_params_size", "fa_moe_gemm_mxfp4_plan"] + EXT_OPS
+           "fa_moe_gemm_mxfp4", "fa_moe_gemm_mxfp4_params_size", "fa_moe_gemm_mxfp4_plan",
+           "fa_moe_gemm_mxfp4_glu", "fa_moe_gemm_mxfp4_glu_params_size", "fa_moe_gemm_mxfp4_glu_plan"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -668,6 +688,7 @@ ROW_OPS = [
     ("fa_moe_gemm_glu", FaMoeGemmGluParams, None),
     ("fa_moe_gemm_wgrad", FaMoeGemmWgradParams, None),
     ("fa_moe_gemm_mxfp4", FaMoeGemmMxfp4Params, None),
+    ("fa_moe_gemm_mxfp4_glu", FaMoeGemmMxfp4GluParams, None),
 ]
 
 
@@ -717,7 +738,7 @@ def _load():
     lib.fa_act_mul_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
     lib.fa_moe_sort_plan.restype = ctypes.c_int
     lib.fa_moe_sort_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
-    for fn in (lib.fa_moe_gemm_plan, lib.fa_moe_gemm_glu_plan, lib.fa_moe_gemm_mxfp4_plan):
+    for fn in (lib.fa_moe_gemm_plan, lib.fa_moe_gemm_glu_plan, lib.fa_moe_gemm_mxfp4_plan, lib.fa_moe_gemm_mxfp4_glu_plan):
         fn.restype = ctypes.c_int
         fn.argtypes = [i64] + [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.POINTER(i64)] * 2
     lib.fa_moe_gemm_wgrad_plan.restype = ctypes.c_int
@@ -803,7 +824,7 @@ call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
 # call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
-# call_moe_gemm, call_moe_gemm_glu, call_moe_gemm_wgrad, call_moe_gemm_mxfp4,
+# call_moe_gemm, call_moe_gemm_glu, call_moe_gemm_wgrad, call_moe_gemm_mxfp4, call_moe_gemm_mxfp4_glu,
 # call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes, sample_workspace_bytes, spec_accept_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
@@ -842,7 +863,7 @@ def moe_sort_plan(slots, num_experts):
 def moe_gemm_plan(rows, n, k, num_experts, layout, dtype, entry="fa_moe_gemm_plan"):
     """fa_moe_gemm_plan: (block_m, block_n, block_k, grid_m, grid_n) of fa_moe_gemm, a function of its arguments alone; needs
     no device.  entry "fa_moe_gemm_glu_plan": the same of fa_moe_gemm_glu (n: its output columns); "fa_moe_gemm_mxfp4_plan": of
-    fa_moe_gemm_mxfp4"""
+    fa_moe_gemm_mxfp4; "fa_moe_gemm_mxfp4_glu_plan": of fa_moe_gemm_mxfp4_glu (n: its output columns)"""
     blk = [ctypes.c_int32() for _ in range(3)]
     grid = [ctypes.c_int64() for _ in range(2)]
     rc = getattr(lib, entry)(rows, n, k, num_experts, layout, dtype, *(ctypes.byref(o) for o in blk + grid))

@@ -18,6 +18,9 @@ have their contracts).
   or, with the gated activation in the gate-up GEMM's epilogue (`moe_gemm_glu`: the same bits, no h, one launch less):
     a = moe_glu_linear(x, w1, expert_offsets, sorted_slot=sorted_slot, top_k=k, pos=pos)  # inference: moe_gemm_glu(...)
     yp = moe_linear(a, w2, expert_offsets)
+  inference on MXFP4 expert weights (gpt-oss: interleaved gate / up rows, the clamped SwiGLU), weights never dequantised in memory:
+    a = moe_gemm_mxfp4_glu(x, w1_blocks, w1_scales, expert_offsets, bias=b1, sorted_slot=sorted_slot, top_k=k)
+    yp = moe_gemm_mxfp4(a, w2_blocks, w2_scales, expert_offsets, bias=b2)
 
 No function synchronises with the host, every result is a pure function of its inputs (no ordering depends on an atomic, two calls
 give the same bits), all are capturable in a HIP graph.
@@ -76,6 +79,7 @@ into the expert GEMMs, a split over rows in their weight gradient, a gradient th
 E > 512, K > 16, fp32 activations, a double backward.  Nothing here is exported through
 the packages' `__all__` lists."""
 import ctypes
+import math
 
 import torch
 
@@ -87,6 +91,8 @@ from . import flash_attn_interface as _fi
 MAX_EXPERTS, MAX_TOPK, MAX_ALIGN, MAX_N = 512, 16, 256, 16384
 GEMM_MAX_K, GEMM_MAX_N, GEMM_MAX_ROW_STRIDE = 32768, 65536, 2 ** 22
 W_LAYOUTS = {"nk": _lib.FA_MOE_W_NK, "kn": _lib.FA_MOE_W_KN}
+GATE_UP = {"interleaved": _lib.FA_MOE_GLU_INTERLEAVED, "packed": _lib.FA_MOE_GLU_PACKED}
+GLU_MXFP4_ACTIVATIONS = {"silu": _lib.FA_ACT_SILU, "relu": _lib.FA_ACT_RELU, "swiglu_oai": _lib.FA_ACT_SWIGLU_OAI}
 SCORINGS = {"softmax": _lib.FA_MOE_SOFTMAX, "sigmoid": _lib.FA_MOE_SIGMOID}
 _LOGIT_DTYPES = {torch.float16: _lib.FA_FP16, torch.bfloat16: _lib.FA_BF16, torch.float32: _lib.FA_FP32}
 
@@ -505,8 +511,9 @@ def _gemm(op, x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, act
 
 
 def _gemm_launch(op, s, call, x, weights, E, N, NO, K, expert_offsets, bias, sorted_slot, top_k, out):
-    """what moe_gemm, moe_gemm_glu and moe_gemm_mxfp4 share behind their weight checks: the checks of every other argument, the
-    fields of `s` (whose weight fields the caller has set) that all three structs have, and the launch through `call`"""
+    """what moe_gemm, moe_gemm_glu, moe_gemm_mxfp4 and moe_gemm_mxfp4_glu share behind their weight checks: the checks of every
+    other argument, the fields of `s` (whose weight fields the caller has set) that all four structs have, and the launch
+    through `call`"""
     expert_offsets = _table(op, expert_offsets, (E + 1,), torch.int32, "expert_offsets")
     if (sorted_slot is None) != (top_k is None):
         raise RuntimeError(f"{op}: sorted_slot and top_k go together")
@@ -575,8 +582,18 @@ def moe_gemm_mxfp4(x, w_blocks, w_scales, expert_offsets, *, bias=None, sorted_s
     the same accumulator chain of v_mfma_f32_32x32x16 over k ascending with the same operand slots, in both plans
     (`moe_gemm_mxfp4_plan`), plain and gathered.  x, bias, expert_offsets, sorted_slot / top_k, out, the +0 tail, the limits and
     the guarantees are `moe_gemm`'s, with K a multiple of 32.  One launch, no workspace, capturable.  No autograd: an input that
-    requires grad raises.  Not covered: fp16, the "kn" layout, MX or fp8 activations, a gated epilogue, a quantiser."""
+    requires grad raises.  Not covered: fp16, the "kn" layout, MX or fp8 activations, a quantiser (the gated epilogue of a
+    gate-up layer: `moe_gemm_mxfp4_glu`)."""
     op = "moe_gemm_mxfp4"
+    s = _lib.FaMoeGemmMxfp4Params()
+    E, N, K = _mxfp4_weights(op, s, x, w_blocks, w_scales, bias, False)
+    return _gemm_launch(op, s, _lib.call_moe_gemm_mxfp4, x, [w_blocks, w_scales], E, N, N, K, expert_offsets, bias, sorted_slot,
+                        top_k, out)
+
+
+def _mxfp4_weights(op, s, x, w_blocks, w_scales, bias, glu):
+    """what moe_gemm_mxfp4 and moe_gemm_mxfp4_glu (glu: the weights hold N = 2 I rows) check of x and the two weight tensors before
+    `_gemm_launch`; sets the weight fields of `s` and returns (E, N, K)"""
     for name, t in (("x", x), ("bias", bias)):
         if t is not None and t.requires_grad and torch.is_grad_enabled():
             raise RuntimeError(f"{op}: {name} requires grad, and {op} has no autograd (detach it, or run under no_grad)")
@@ -595,19 +612,67 @@ def moe_gemm_mxfp4(x, w_blocks, w_scales, expert_offsets, *, bias=None, sorted_s
         raise RuntimeError(f"{op}: w_scales must be uint8 of shape {(E, N, K // 32)}, got {w_scales.dtype} {tuple(w_scales.shape)}")
     if not (2 <= E <= MAX_EXPERTS):
         raise RuntimeError(f"{op}: num_experts (w_blocks.shape[0]) must be in [2, {MAX_EXPERTS}], got {E}")
-    _gemm_dim(op, N, "N", GEMM_MAX_N)
+    if glu and N % 16:
+        raise RuntimeError(f"{op}: the weights hold a gate and an up row for each of I output columns, I a multiple of 8: their "
+                           f"rows must be a multiple of 16, got {N}")
+    _gemm_dim(op, N, "2 I" if glu else "N", GEMM_MAX_N)
     if (not w_blocks[0].is_contiguous() or w_blocks.stride(0) < N * K // 2 or w_blocks.stride(0) % 16 or w_blocks.data_ptr() % 16):
         raise RuntimeError(f"{op}: w_blocks must be 16-byte aligned with contiguous experts and an expert stride that is a multiple "
                            f"of 16 and at least N K / 2, got strides {tuple(w_blocks.stride())}")
     if not w_scales[0].is_contiguous() or w_scales.stride(0) < N * K // 32:
         raise RuntimeError(f"{op}: w_scales must have contiguous experts and an expert stride of at least N K / 32, got strides "
                            f"{tuple(w_scales.stride())}")
-    s = _lib.FaMoeGemmMxfp4Params()
     s.w_blocks, s.w_blocks_expert_stride = w_blocks.data_ptr(), w_blocks.stride(0)
     s.w_scales, s.w_scales_expert_stride = w_scales.data_ptr(), w_scales.stride(0)
     s.layout = W_LAYOUTS["nk"]
-    return _gemm_launch(op, s, _lib.call_moe_gemm_mxfp4, x, [w_blocks, w_scales], E, N, N, K, expert_offsets, bias, sorted_slot,
-                        top_k, out)
+    return E, N, K
+
+
+def moe_gemm_mxfp4_glu_plan(M_max, I, K, num_experts):
+    """(block_m, block_n, block_k, grid_m, grid_n) of `moe_gemm_mxfp4_glu` with I output columns: a function of these arguments
+    alone, no device.  block_m and block_k as `moe_gemm_mxfp4_plan`; block_n is 64 output columns (a 128-row weight image: 64
+    gates and their ups), grid_n = ceil(I / 64)"""
+    return _lib.moe_gemm_plan(int(M_max), int(I), int(K), int(num_experts), W_LAYOUTS["nk"], _fi._DTYPES[torch.bfloat16],
+                              entry="fa_moe_gemm_mxfp4_glu_plan")
+
+
+def moe_gemm_mxfp4_glu(x, w_blocks, w_scales, expert_offsets, *, activation="swiglu_oai", gate_up="interleaved", alpha=1.702,
+                       limit=7.0, bias=None, sorted_slot=None, top_k=None, out=None):
+    """The gate-up grouped expert GEMM on MXFP4 weights with the gated activation in its epilogue (csrc/fa_moe_gemm_mxfp4.hip, the
+    GLU instantiations) - the gate-up layer of gpt-oss in one launch: out bf16 [M_max, I] from w_blocks uint8 [E, 2 I, K / 2] (or
+    [E, 2 I, K / 32, 16]), w_scales uint8 [E, 2 I, K / 32] and bias [E, 2 I] (bf16 or fp32).
+
+    gate_up "interleaved" (HF gpt-oss): weight row and bias column 2 j are the gate of output column j, 2 j + 1 its up.
+            "packed" (`moe_gemm_glu`'s order): rows / columns [0, I) are the gates, [I, 2 I) the ups.
+
+    With h EXACTLY the bits moe_gemm_mxfp4(x, w_blocks, w_scales, ..., bias=bias) writes - the same accumulator chains, the bias
+    added in fp32, one rounding to bf16 - and g, u the gate and up of output column j read from it as fp32:
+
+        "silu", "relu"   out = round_bf16(act(g) * u)              act_mul's one definition of act (csrc/fa_act.h)
+        "swiglu_oai"     gc = min(g, limit) (upper clamp only);  uc = clamp(u, -limit, limit);  a = gc * sigmoid(alpha * gc)
+                         out = round_bf16((uc + 1) * a)            fp32, one operation per operator, act_mul's sigmoid
+        rows from expert_offsets[E] on: +0
+
+    without the [M_max, 2 I] buffer, the strided copy that separates its columns and the activation's launch.  alpha must be
+    finite and limit > 0 (inf: no clamp); "silu" and "relu" ignore both.  With "silu" and "packed" the result is bit for bit
+    moe_gemm_glu's on the dequantised weights.  A tile is block_m rows by 64 output columns (`moe_gemm_mxfp4_glu_plan`).  Every
+    other argument, check, limit and guarantee is `moe_gemm_mxfp4`'s, with 2 I in the place of N (I a multiple of 8,
+    2 I <= 65536): one launch, no workspace, nothing read on the host, capturable, the same bits on every call, a row's bits a
+    function of its source row, its expert's weights and bias and K alone.  No autograd: an input that requires grad raises.
+    Not covered: MX or fp8 activations, fp16, the "kn" layout, a quantised output, the backward, the other act_mul activations."""
+    op = "moe_gemm_mxfp4_glu"
+    if activation not in GLU_MXFP4_ACTIVATIONS:
+        raise RuntimeError(f"{op}: activation must be one of {sorted(GLU_MXFP4_ACTIVATIONS)}, got {activation!r}")
+    if gate_up not in GATE_UP:
+        raise RuntimeError(f"{op}: gate_up must be one of {sorted(GATE_UP)}, got {gate_up!r}")
+    alpha, limit = float(alpha), float(limit)
+    if activation == "swiglu_oai" and (not math.isfinite(alpha) or not limit > 0):
+        raise RuntimeError(f"{op}: alpha must be finite and limit positive (inf: no clamp), got alpha {alpha} and limit {limit}")
+    s = _lib.FaMoeGemmMxfp4GluParams()
+    E, N, K = _mxfp4_weights(op, s, x, w_blocks, w_scales, bias, True)
+    s.activation, s.gate_up, s.alpha, s.limit = GLU_MXFP4_ACTIVATIONS[activation], GATE_UP[gate_up], alpha, limit
+    return _gemm_launch(op, s, _lib.call_moe_gemm_mxfp4_glu, x, [w_blocks, w_scales], E, N, N // 2, K, expert_offsets, bias,
+                        sorted_slot, top_k, out)
 
 
 def moe_gemm_glu_plan(M_max, I, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):
@@ -634,7 +699,8 @@ def moe_gemm_glu(x, w, expert_offsets, *, activation="silu", w_layout="nk", bias
     its round trip through memory and the second launch.  One launch, no workspace, capturable.  A tile is block_m rows by 64
     output columns over the 128-wide weight image of `moe_gemm` (`moe_gemm_glu_plan`).  Every other argument, limit and
     guarantee is `moe_gemm`'s, with 2 I in the place of N (I a multiple of 8, 2 I <= 65536).  No autograd (`moe_glu_linear`).
-    Not covered: interleaved gate / up columns, a clamped activation, a quantised output, fp8 operands."""
+    Not covered: a quantised output, fp8 operands (interleaved gate / up columns and the clamped SwiGLU of gpt-oss, on MXFP4
+    weights: `moe_gemm_mxfp4_glu`)."""
     return _gemm("moe_gemm_glu", x, w, expert_offsets, w_layout, bias, sorted_slot, top_k, out, activation)
 
 

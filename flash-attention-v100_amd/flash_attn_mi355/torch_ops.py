@@ -1251,6 +1251,24 @@ def _(x, w_blocks, w_scales, expert_offsets, bias, sorted_slot, top_k):
     return x.new_empty((M, w_blocks.shape[1]))
 
 
+# the gate-up layer on MXFP4 weights with the gated activation in the epilogue (moe.moe_gemm_mxfp4_glu; csrc/fa_moe_gemm_mxfp4.hip):
+# torch.ops.flash_attn_mi355.moe_gemm_mxfp4_glu
+@torch.library.custom_op(f"{_NS}::moe_gemm_mxfp4_glu", mutates_args=(), device_types="cuda")
+def moe_gemm_mxfp4_glu(x: Tensor, w_blocks: Tensor, w_scales: Tensor, expert_offsets: Tensor, activation: str, gate_up: str,
+                       alpha: float, limit: float, bias: Optional[Tensor], sorted_slot: Optional[Tensor],
+                       top_k: Optional[int]) -> Tensor:
+    """moe.moe_gemm_mxfp4_glu: out [M_max, I], a fresh contiguous bf16 tensor (the weights hold 2 I rows).  Functional and
+    capturable; no autograd is registered."""
+    return _moe.moe_gemm_mxfp4_glu(x, w_blocks, w_scales, expert_offsets, activation=activation, gate_up=gate_up, alpha=alpha,
+                                   limit=limit, bias=bias, sorted_slot=sorted_slot, top_k=top_k)
+
+
+@moe_gemm_mxfp4_glu.register_fake
+def _(x, w_blocks, w_scales, expert_offsets, activation, gate_up, alpha, limit, bias, sorted_slot, top_k):
+    M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
+    return x.new_empty((M, w_blocks.shape[1] // 2))
+
+
 # the weight / bias gradient of the grouped expert GEMM (moe.moe_gemm_wgrad; csrc/fa_moe_gemm_wgrad.hip) and the differentiable
 # expert layer built on moe_gemm, moe_combine and it (moe.moe_linear): torch.ops.flash_attn_mi355.moe_gemm_wgrad / .moe_linear
 @torch.library.custom_op(f"{_NS}::moe_gemm_wgrad", mutates_args=(), device_types="cuda")

@@ -1242,6 +1242,11 @@ typedef enum fa_act {
     FA_ACT_RELU = 3,
     FA_ACT_RELU2 = 4        /* squared ReLU */
 } fa_act;
+/* An activation code that continues fa_act but is no act(gate): the clamped SwiGLU of gpt-oss is a function of gate AND up.
+ * fa_moe_gemm_mxfp4_glu alone takes it; fa_act_mul, fa_act_mul_quant and fa_moe_gemm_glu reject it as an unknown activation. */
+typedef enum fa_act_gated {
+    FA_ACT_SWIGLU_OAI = 5
+} fa_act_gated;
 
 typedef struct fa_act_mul_params {
     size_t         struct_size;      /* sizeof(fa_act_mul_params) as the caller compiled it */
@@ -1798,6 +1803,70 @@ int    fa_moe_gemm_mxfp4(const fa_moe_gemm_mxfp4_params* s, void* stream);
 size_t fa_moe_gemm_mxfp4_params_size(void);
 int    fa_moe_gemm_mxfp4_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
                               int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
+
+/*
+ * fa_moe_gemm_mxfp4_glu: the gate-up grouped expert GEMM on MXFP4 weights with the gated activation in its epilogue
+ * (csrc/fa_moe_gemm_mxfp4.hip, the GLU instantiations of fa_moe_gemm_mxfp4's body) - the gate-up layer of gpt-oss in one launch.
+ * n is the number of OUTPUT columns (the intermediate size I); an expert's weight has 2 n rows: w_blocks uint8 [E, 2 n, k / 2],
+ * w_scales uint8 [E, 2 n, k / 32], bias [E, 2 n].  One launch, no workspace, no atomics, no host synchronisation.
+ *   gate_up        FA_MOE_GLU_INTERLEAVED (HF gpt-oss): weight row and bias column 2 j are the gate of output column j, 2 j + 1 its up.
+ *                  FA_MOE_GLU_PACKED (fa_moe_gemm_glu's order): rows / columns [0, n) are the gates, [n, 2 n) the ups.
+ *   values         h = EXACTLY the bits fa_moe_gemm_mxfp4(x, w_blocks, w_scales, n' = 2 n, bias, ...) writes: the v_mfma_f32_32x32x16
+ *                  chain over k ascending from +0, + bias in fp32, one rounding to bf16.  g, u = the gate and up elements of h for
+ *                  output column j, widened to fp32.  Then
+ *                    FA_ACT_SILU, FA_ACT_RELU   out = round_bf16(act(g) * u), act as in fa_act_mul (csrc/fa_act.h), one fp32 multiply
+ *                    FA_ACT_SWIGLU_OAI          gc = g > limit ? limit : g                (upper clamp only; a NaN stays a NaN)
+ *                                               uc = u > limit ? limit : (u < -limit ? -limit : u)
+ *                                               a  = gc * sig(alpha * gc)                 (sig: fa_act_mul's, hardware exp2 and reciprocal)
+ *                                               out = round_bf16((uc + 1) * a)            each operator one fp32 operation, in this order
+ *                  another activation: FA_ERR_INVALID_ARGUMENT.  Rows expert_offsets[E] <= r < rows: +0.
+ *   alpha, limit   FA_ACT_SWIGLU_OAI only (gpt-oss: 1.702 and 7), ignored otherwise: alpha finite, limit > 0 (+inf: no clamp), else
+ *                  FA_ERR_INVALID_ARGUMENT.
+ *   contract       the guarantees of fa_moe_gemm_mxfp4: two calls give the same bits, and a row's bits depend on its source row, its
+ *                  expert's weights and bias and k alone - in both plans, both orders, plain and gathered.  With FA_ACT_SILU and
+ *                  FA_MOE_GLU_PACKED the result is bit for bit fa_moe_gemm_glu's on the dequantised weights.
+ *   everything else (the code and scale formats and the scale bytes covered, x plain or through sorted_slot / top_k, expert_offsets,
+ *                  strides, alignment, bias_dtype, overlaps) is fa_moe_gemm_mxfp4's with 2 n weight rows and n columns of out.
+ *   limits         fa_moe_gemm_mxfp4's with n a multiple of 8 and 2 n <= 65536; w_blocks_expert_stride >= 2 n * k / 2 bytes,
+ *                  w_scales_expert_stride >= 2 n * k / 32.  Outside: FA_ERR_UNSUPPORTED, before any device work.
+ * fa_moe_gemm_mxfp4_glu_plan: block_m and block_k by fa_moe_gemm_mxfp4_plan's rule, block_n 64 (OUTPUT columns: a tile stages a
+ *   128-row weight image, 64 gates and their 64 ups), grid_m = floor(rows / block_m) + num_experts + 1, grid_n = ceil(n / 64).
+ */
+typedef enum fa_moe_glu_order {
+    FA_MOE_GLU_INTERLEAVED = 0,
+    FA_MOE_GLU_PACKED = 1
+} fa_moe_glu_order;
+
+typedef struct fa_moe_gemm_mxfp4_glu_params {
+    size_t         struct_size;      /* sizeof(fa_moe_gemm_mxfp4_glu_params) as the caller compiled it */
+    const void*    x;                /* [rows, k], or with sorted_slot [tokens, k], bf16 */
+    const void*    w_blocks;         /* uint8 [num_experts, 2 n, k / 2] */
+    const void*    w_scales;         /* uint8 [num_experts, 2 n, k / 32] */
+    const void*    bias;             /* [num_experts, 2 n] of `bias_dtype`, contiguous; NULL: none */
+    const void*    expert_offsets;   /* int32 [num_experts + 1], device */
+    const void*    sorted_slot;      /* int32 [rows]; NULL: the plain form */
+    void*          out;              /* [rows, n] bf16 */
+    int64_t        x_row_stride, out_row_stride;   /* elements, multiples of 8 */
+    int64_t        w_blocks_expert_stride;         /* bytes, >= 2 n * k / 2, a multiple of 16 */
+    int64_t        w_scales_expert_stride;         /* bytes, >= 2 n * k / 32 */
+    int64_t        rows;             /* M_max */
+    int64_t        tokens;           /* rows of x with sorted_slot; ignored without */
+    int32_t        num_experts, top_k;              /* top_k: with sorted_slot only */
+    int32_t        n, k;             /* n: output columns; the weight has 2 n rows */
+    int32_t        dtype;            /* FA_BF16 */
+    int32_t        bias_dtype;       /* FA_BF16 or FA_FP32; ignored without bias */
+    int32_t        layout;           /* FA_MOE_W_NK */
+    int32_t        activation;       /* FA_ACT_SILU, FA_ACT_RELU or FA_ACT_SWIGLU_OAI */
+    int32_t        gate_up;          /* fa_moe_glu_order */
+    float          alpha, limit;     /* FA_ACT_SWIGLU_OAI only */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_gemm_mxfp4_glu_params;
+
+int    fa_moe_gemm_mxfp4_glu(const fa_moe_gemm_mxfp4_glu_params* s, void* stream);
+size_t fa_moe_gemm_mxfp4_glu_params_size(void);
+int    fa_moe_gemm_mxfp4_glu_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                                  int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
 
 /*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
