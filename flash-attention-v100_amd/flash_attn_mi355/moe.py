@@ -256,9 +256,7 @@ def moe_sort(ids, num_experts, *, align=1):
         raise RuntimeError(f"{op}: ids must be an int32 tensor [tokens, k], got {ids.dtype} {tuple(ids.shape)}")
     T, K = ids.shape
     E, align = int(num_experts), int(align)
-    if not (2 <= E <= MAX_EXPERTS):
-        raise RuntimeError(f"{op}: num_experts must be in [2, {MAX_EXPERTS}], got {E}")
-    _topk(op, K)
+    _sizes(op, E, K)                                          # (k <= num_experts: the C entry refuses more, as the router's does)
     if not (1 <= align <= MAX_ALIGN):
         raise RuntimeError(f"{op}: align must be in [1, {MAX_ALIGN}], got {align}")
     M = sort_max_rows(T, K, E, align)

@@ -12,6 +12,8 @@ right one:
     "bias_late"      the bias is added after the rounding to 16 bits (two roundings)
     "kn_as_nk"       a "kn" weight's memory read as "nk"
     "pad_as_token0"  a padding slot (-1) reads token 0
+    "stale_last_step"  where the count of 64-element staging steps is even (the k loop ends in LDS stage 1), the last step's
+                     products are taken from the previous step's x and w; an odd count is computed right
 
 Witness data (`witness`): x, w and bias hold integers in [-3, 3] (bias: [-8, 8]), exact in fp16 and bf16.  Every product is an
 integer of magnitude <= 9, every partial sum of any subset in any order an integer of magnitude <= 9 K + 8 <= 25928 < 2^24 for
@@ -64,12 +66,16 @@ def gemm_ref(a, w, offsets, *, layout="nk", bias=None, variant=None, with_mag=Fa
             if off[e + 1] > off[e] and (off[e + 1] - off[e]) % 32 and nxt:
                 owner[off[nxt[0]]] = e                      # (a segment that ends inside a tile spills into what follows)
     kk = K // 64 * 64 if variant == "drop_k_tail" else K
+    k0 = (K - 1) // 64 * 64                                      # where the last staging step begins
+    stale = variant == "stale_last_step" and (k0 // 64) % 2 == 1
     for e in range(E):
         rows = np.nonzero(owner == e)[0]
         if len(rows) == 0:
             continue
         We = w_of(w, e, layout)
         out[rows] = a[rows, :kk] @ We[:kk]
+        if stale:
+            out[rows] += a[rows, k0 - 64:K - 64] @ We[k0 - 64:K - 64] - a[rows, k0:] @ We[k0:]
         if with_mag:
             mag[rows] = np.abs(a[rows, :kk]) @ np.abs(We[:kk])
         if bias is not None and variant != "bias_late":

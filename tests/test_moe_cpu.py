@@ -403,6 +403,8 @@ def test_python_argument_errors_on_cpu_tensors():
         moe.moe_sort(ids, 8, align=512)
     with pytest.raises(RuntimeError, match="num_experts must be in"):
         moe.moe_sort(ids, 1024)
+    with pytest.raises(RuntimeError, match=r"k must be in \[1, min\(num_experts"):       # (by name, not from the workspace query)
+        moe.moe_sort(torch.zeros(4, 3, dtype=torch.int32), 2)
     x = torch.zeros(4, 64, dtype=torch.bfloat16)
     ss = torch.zeros(8, dtype=torch.int32)
     with pytest.raises(RuntimeError, match="hidden size N"):
