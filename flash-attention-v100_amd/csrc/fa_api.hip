@@ -63,6 +63,8 @@ ActPlan act_plan(int64_t rows, int n);
 void launch_quant_fp8(const fa_quant_fp8_params& s, hipStream_t stream);                     // fa_quant.hip: dynamic fp8-e4m3 quantisation of [rows, n]
 void launch_add_norm_quant(const fa_add_norm_quant_params& s, hipStream_t stream);           // .. behind fa_add_norm's forward
 void launch_act_mul_quant(const fa_act_mul_quant_params& s, hipStream_t stream);             // .. behind fa_act_mul's forward
+void launch_mx_quant(const fa_mx_quant_params& s, hipStream_t stream);                       // fa_mx_quant.hip: 16-bit weights -> MXFP4 codes and scale bytes
+void launch_mx_dequant(const fa_mx_dequant_params& s, hipStream_t stream);                   // .. and back to bf16
 }  // namespace fa
 
 static thread_local std::string g_last_error;
@@ -256,6 +258,8 @@ size_t fa_moe_gemm_glu_params_size(void) { return sizeof(fa_moe_gemm_glu_params)
 size_t fa_moe_gemm_wgrad_params_size(void) { return sizeof(fa_moe_gemm_wgrad_params); }
 size_t fa_moe_gemm_mxfp4_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_params); }
 size_t fa_moe_gemm_mxfp4_glu_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_glu_params); }
+size_t fa_mx_quant_params_size(void) { return sizeof(fa_mx_quant_params); }
+size_t fa_mx_dequant_params_size(void) { return sizeof(fa_mx_dequant_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
 const char* fa_build_info(void) {
     return "libfa_mi355: gfx950 (CDNA4) hand-written HIP; mfma_f32_32x32x16_{bf16,f16}, mfma_scale_f32_32x32x64_f8f6f4 (fp8 q/k/v forward); "
@@ -1850,6 +1854,55 @@ static int moe_gemm_mxfp4_check(const fa_moe_gemm_mxfp4_params& s, const char* o
     return moe_gemm_check(op, g, out_n < 0 ? s.n : out_n, wq);
 }
 
+// ---- fa_mx_quant, fa_mx_dequant
+// what the two blocks share: the shape and its limits, the three tensors (`wname`: "w" or "out"), their strides and alignment
+static int mx_quant_common_check(const char* op, const char* wname, const void* w, const void* blocks, const void* scales, int64_t w_es,
+                                 int64_t blocks_es, int64_t scales_es, int num_experts, int n, int k, int layout, int elem_format) {
+    FA_CHECK(layout == FA_MOE_W_NK || layout == FA_MOE_W_KN, "%s: unknown layout %d", op, layout);
+    FA_CHECK(num_experts >= 0 && n >= 0 && k >= 0, "%s: num_experts, n and k must be non-negative", op);
+    FA_CHECK(w_es >= 0 && blocks_es >= 0 && scales_es >= 0, "%s: expert strides must be non-negative", op);
+    if (elem_format != FA_MX_ELEM_E2M1) return fail(FA_ERR_UNSUPPORTED, "%s: elem_format %d has no kernel in this build (FA_MX_ELEM_E2M1)", op, elem_format);
+    if (k % 32 != 0 || k > 32768) return fail(FA_ERR_UNSUPPORTED, "%s: k must be a multiple of 32 up to 32768, got %d", op, k);
+    if (n % 8 != 0 || n > 65536) return fail(FA_ERR_UNSUPPORTED, "%s: n must be a multiple of 8 up to 65536, got %d", op, n);
+    if (num_experts > 65535) return fail(FA_ERR_UNSUPPORTED, "%s: more than 65535 experts in one launch", op);
+    if (num_experts == 0 || n == 0 || k == 0) return FA_OK;
+    FA_CHECK(w && blocks && scales, "%s: %s, blocks and scales must not be NULL", op, wname);
+    const int64_t we = (int64_t)n * k;
+    if ((addr(w) & 15) != 0 || w_es % 8 != 0 || (num_experts > 1 && w_es < we))
+        return fail(FA_ERR_UNSUPPORTED, "%s: %s must be 16-byte aligned with an expert stride that is a multiple of 8 and at least n x k = %lld elements, got %lld",
+                    op, wname, (long long)we, (long long)w_es);
+    if ((addr(blocks) & 15) != 0 || blocks_es % 16 != 0 || (num_experts > 1 && blocks_es < we / 2))
+        return fail(FA_ERR_UNSUPPORTED, "%s: blocks must be 16-byte aligned with an expert stride that is a multiple of 16 and at least n x k / 2 = %lld bytes, got %lld",
+                    op, (long long)(we / 2), (long long)blocks_es);
+    if (num_experts > 1 && scales_es < we / 32)
+        return fail(FA_ERR_UNSUPPORTED, "%s: the scales' expert stride must be at least n x k / 32 = %lld bytes, got %lld", op,
+                    (long long)(we / 32), (long long)scales_es);
+    const View t[3] = {view_rows(wname, w, num_experts, w_es, we, 2), view_rows("blocks", blocks, num_experts, blocks_es, we / 2, 1),
+                       view_rows("scales", scales, num_experts, scales_es, we / 32, 1)};
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j) FA_CHECK(views_disjoint(t[i], t[j]), "%s: %s overlaps %s", op, t[i].name, t[j].name);
+    return FA_OK;
+}
+
+static int mx_quant_check(const fa_mx_quant_params& s) {
+    const char* op = "mx_quant";
+    FA_CHECK(s.reserved0 == 0 && s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_TRY(check_io_dtype(op, s.dtype, "dtype"));
+    FA_CHECK(s.scale_rule == FA_MX_SCALE_FLOOR || s.scale_rule == FA_MX_SCALE_RCEIL, "%s: unknown scale_rule %d", op, s.scale_rule);
+    return mx_quant_common_check(op, "w", s.w, s.blocks, s.scales, s.w_expert_stride, s.blocks_expert_stride, s.scales_expert_stride,
+                                 s.num_experts, s.n, s.k, s.layout, s.elem_format);
+}
+
+static int mx_dequant_check(const fa_mx_dequant_params& s) {
+    const char* op = "mx_dequant";
+    FA_CHECK(s.reserved[0] == 0 && s.reserved[1] == 0 && s.reserved[2] == 0 && s.reserved[3] == 0,
+             "%s: reserved fields must be 0 (zero-initialise the struct)", op);
+    FA_CHECK(s.dtype == FA_BF16, "%s: dtype (out's) must be bf16", op);
+    return mx_quant_common_check(op, "out", s.out, s.blocks, s.scales, s.out_expert_stride, s.blocks_expert_stride, s.scales_expert_stride,
+                                 s.num_experts, s.n, s.k, s.layout, s.elem_format);
+}
+
 // what fa_moe_gemm_mxfp4_glu and its plan ask of the output width
 static int moe_gemm_mxfp4_glu_n_check(const char* op, int n) {
     if (n < 8 || n > fa::MOE_GEMM_MAX_N / 2 || n % 8 != 0)
@@ -2381,6 +2434,24 @@ int fa_moe_gemm_mxfp4_glu(const fa_moe_gemm_mxfp4_glu_params* sp, void* stream) 
     if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
     fa::launch_moe_gemm_mxfp4_glu(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_gemm_mxfp4_glu launch");
+}
+
+int fa_mx_quant(const fa_mx_quant_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_mx_quant_params"));
+    const fa_mx_quant_params s = *sp;
+    FA_TRY(mx_quant_check(s));
+    if (s.num_experts == 0 || s.n == 0 || s.k == 0) return FA_OK;
+    fa::launch_mx_quant(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_mx_quant launch");
+}
+
+int fa_mx_dequant(const fa_mx_dequant_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_mx_dequant_params"));
+    const fa_mx_dequant_params s = *sp;
+    FA_TRY(mx_dequant_check(s));
+    if (s.num_experts == 0 || s.n == 0 || s.k == 0) return FA_OK;
+    fa::launch_mx_dequant(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_mx_dequant launch");
 }
 
 int fa_moe_gemm_wgrad_plan(int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,

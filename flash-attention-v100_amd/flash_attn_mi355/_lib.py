@@ -21,6 +21,8 @@ FA_MOE_GLU_INTERLEAVED, FA_MOE_GLU_PACKED = 0, 1                                
 FA_QUANT_ROW, FA_QUANT_GROUP, FA_QUANT_STATIC = 0, 1, 2                                  # enum fa_quant_mode
 FA_MOE_SOFTMAX, FA_MOE_SIGMOID = 0, 1                                                    # enum fa_moe_scoring
 FA_MOE_W_NK, FA_MOE_W_KN = 0, 1                                                          # enum fa_moe_w_layout
+FA_MX_SCALE_FLOOR, FA_MX_SCALE_RCEIL = 0, 1                                              # enum fa_mx_scale_rule
+FA_MX_ELEM_E2M1 = 0                                                                      # enum fa_mx_elem_format
 
 _i64, _i32, _f32, _u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_uint64
 _ptr = ctypes.c_void_p
@@ -625,6 +627,32 @@ class FaMoeGemmMxfp4GluParams(ctypes.Structure):
     ]
 
 
+class FaMxQuantParams(ctypes.Structure):
+    """Mirror of `struct fa_mx_quant_params` (include/fa_mi355.h): fa_mx_quant, 16-bit expert weights to MXFP4 codes and E8M0 scale
+    bytes.  struct_size must be set to sizeof(FaMxQuantParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("w", _ptr), ("blocks", _ptr), ("scales", _ptr),
+        ("w_expert_stride", _i64), ("blocks_expert_stride", _i64), ("scales_expert_stride", _i64),
+        ("num_experts", _i32), ("n", _i32), ("k", _i32),
+        ("dtype", _i32), ("layout", _i32), ("scale_rule", _i32), ("elem_format", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
+class FaMxDequantParams(ctypes.Structure):
+    """Mirror of `struct fa_mx_dequant_params` (include/fa_mi355.h): fa_mx_dequant, MXFP4 codes and scale bytes to bf16 weights.
+    struct_size must be set to sizeof(FaMxDequantParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("blocks", _ptr), ("scales", _ptr), ("out", _ptr),
+        ("blocks_expert_stride", _i64), ("scales_expert_stride", _i64), ("out_expert_stride", _i64),
+        ("num_experts", _i32), ("n", _i32), ("k", _i32),
+        ("dtype", _i32), ("layout", _i32), ("elem_format", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 EXT_OPS = ["fa_fwd_ext", "fa_varlen_fwd_ext", "fa_fwd_kvcache_ext", "fa_bwd_ext", "fa_varlen_bwd_ext"]
 
 EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
@@ -653,7 +681,8 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_moe_gemm_glu", "fa_moe_gemm_glu_params_size", "fa_moe_gemm_glu_plan",
            "fa_moe_gemm_wgrad", "fa_moe_gemm_wgrad_params_size", "fa_moe_gemm_wgrad_plan",
            "fa_moe_gemm_mxfp4", "fa_moe_gemm_mxfp4_params_size", "fa_moe_gemm_mxfp4_plan",
-           "fa_moe_gemm_mxfp4_glu", "fa_moe_gemm_mxfp4_glu_params_size", "fa_moe_gemm_mxfp4_glu_plan"] + EXT_OPS
+           "fa_moe_gemm_mxfp4_glu", "fa_moe_gemm_mxfp4_glu_params_size", "fa_moe_gemm_mxfp4_glu_plan",
+           "fa_mx_quant", "fa_mx_quant_params_size", "fa_mx_dequant", "fa_mx_dequant_params_size"] + EXT_OPS
 
 
 # The struct-taking row ops, each declared once: (entry point, struct class, workspace query or None).  The struct's size
@@ -689,6 +718,8 @@ ROW_OPS = [
     ("fa_moe_gemm_wgrad", FaMoeGemmWgradParams, None),
     ("fa_moe_gemm_mxfp4", FaMoeGemmMxfp4Params, None),
     ("fa_moe_gemm_mxfp4_glu", FaMoeGemmMxfp4GluParams, None),
+    ("fa_mx_quant", FaMxQuantParams, None),
+    ("fa_mx_dequant", FaMxDequantParams, None),
 ]
 
 
@@ -824,7 +855,7 @@ call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
 # call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
-# call_moe_gemm, call_moe_gemm_glu, call_moe_gemm_wgrad, call_moe_gemm_mxfp4, call_moe_gemm_mxfp4_glu,
+# call_moe_gemm, call_moe_gemm_glu, call_moe_gemm_wgrad, call_moe_gemm_mxfp4, call_moe_gemm_mxfp4_glu, call_mx_quant, call_mx_dequant,
 # call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes, sample_workspace_bytes, spec_accept_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:

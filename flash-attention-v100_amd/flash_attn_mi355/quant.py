@@ -42,7 +42,10 @@ Not differentiable: a tensor that requires grad raises.
 
 Out of scope: a backward or a straight-through estimator; device-resident static scales; per-tensor dynamic scales (a grid-wide
 reduction); E8M0 / MX power-of-two scales; e5m2 and the fnuz formats; column-major or transposed scales and codes; fp4; fusing
-into a GEMM; also writing the 16-bit output.  Nothing here is exported through the packages' `__all__` lists."""
+into a GEMM; also writing the 16-bit output.  Nothing here is exported through the packages' `__all__` lists.
+
+Weights are another matter: `quant_mxfp4` / `dequant_mxfp4` at the end of this module turn 16-bit expert weights into the MXFP4
+codes and E8M0 scale bytes `moe.moe_gemm_mxfp4` reads, and back (csrc/fa_mx_quant.hip); their rule is in their docstrings."""
 import ctypes
 import math
 
@@ -300,3 +303,151 @@ def act_and_mul_quant(x, *, activation="silu", mode="row", scale=None, scale_ub=
     gate, up = _act_mul._halves(x)
     _no_grad("act_and_mul_quant", x=x)
     return act_mul_quant(gate, up, activation=activation, mode=mode, scale=scale, scale_ub=scale_ub, out=out)
+
+
+# ------------------------------------------------------------------------------------------
+# MXFP4 weights: fa_mx_quant / fa_mx_dequant (csrc/fa_mx_quant.hip) - the tensors moe.moe_gemm_mxfp4 reads, made and unmade
+# ------------------------------------------------------------------------------------------
+MX_LAYOUTS = {"nk": _lib.FA_MOE_W_NK, "kn": _lib.FA_MOE_W_KN}
+MX_SCALE_RULES = {"floor": _lib.FA_MX_SCALE_FLOOR, "rceil": _lib.FA_MX_SCALE_RCEIL}
+MX_MAX_K, MX_MAX_N = 32768, 65536
+
+
+def _mx_layout(op, w_layout):
+    if w_layout not in MX_LAYOUTS:
+        raise RuntimeError(f"{op}: w_layout must be one of {sorted(MX_LAYOUTS)}, got {w_layout!r}")
+    return MX_LAYOUTS[w_layout]
+
+
+def _mx_dims(op, N, K):
+    if K % 32 != 0 or K > MX_MAX_K:
+        raise RuntimeError(f"{op}: K must be a multiple of 32 up to {MX_MAX_K}, got {K}")
+    if N % 8 != 0 or N > MX_MAX_N:
+        raise RuntimeError(f"{op}: N must be a multiple of 8 up to {MX_MAX_N}, got {N}")
+
+
+def _mx_experts(op, t, name, dtypes, shape=None):
+    """`t` as the [E, rows, cols] view the kernels address, each expert dense, the expert stride free: never a copy"""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+        raise RuntimeError(f"{op}: {name} must be a tensor of dtype {' or '.join(str(d) for d in dtypes)}, got "
+                           f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dim() not in (2, 3):
+        raise RuntimeError(f"{op}: {name} must have 2 or 3 dimensions, got {t.dim()}")
+    v = t.unsqueeze(0) if t.dim() == 2 else t
+    if shape is not None and tuple(v.shape) != tuple(shape):
+        raise RuntimeError(f"{op}: {name} must have shape {tuple(shape)[3 - t.dim():]}, got {tuple(t.shape)}")
+    if v.numel() and not (v.stride(2) == 1 and v.stride(1) == v.shape[2] and (v.shape[0] == 1 or v.stride(0) >= v.shape[1] * v.shape[2])):
+        raise RuntimeError(f"{op}: {name} needs a contiguous last dimension, dense experts and an expert stride that is at least an "
+                           f"expert (got strides {tuple(t.stride())})")
+    return v
+
+
+def _mx_es(v):
+    return v.stride(0) if v.shape[0] > 1 else v.shape[1] * v.shape[2]
+
+
+def _mx_placement(op, named):
+    """the C ABI's rules of place, by name and before any device work: `named` = (name, [E, rows, cols] view, alignment in bytes
+    of its address and expert stride or 0); no two of the tensors may share a byte (experts interleaved in one buffer do not)"""
+    spans = []
+    for name, v, align in named:
+        stride, row = _mx_es(v) * v.element_size(), v.shape[1] * v.shape[2] * v.element_size()
+        if align and (v.data_ptr() % align or stride % align):
+            raise RuntimeError(f"{op}: {name} must be {align}-byte aligned with an expert stride that is a multiple of {align} bytes "
+                               f"(got address % {align} = {v.data_ptr() % align}, stride {stride} bytes)")
+        spans.append((v.data_ptr(), name, stride, row, (v.shape[0] - 1) * stride + row))
+    spans.sort()
+    for i, (a0, na, sa, ra, ba) in enumerate(spans):
+        for b0, nb, sb, rb, _ in spans[i + 1:]:
+            delta = b0 - a0
+            if delta < ba and not (sa == sb and ra <= delta and delta + rb <= sa):
+                raise RuntimeError(f"{op}: {na} overlaps {nb}")
+
+
+def quant_mxfp4(w, *, w_layout="nk", scale_rule="floor", out=None):
+    """(blocks, scales) of the expert weights w, fp16 or bf16: w_layout "nk" [E, N, K] or "kn" [E, K, N] (2-D: one expert), the last
+    dimension contiguous, each expert dense and 16-byte aligned (an expert stride that is a multiple of 8 elements, of 16 bytes for
+    blocks; any for scales) - a view is taken as it is, never copied.  K is cut into blocks of 32.  blocks uint8
+    [E, N, K / 2] and scales uint8 [E, N, K / 32] in BOTH layouts: what `moe.moe_gemm_mxfp4` reads, element k in byte k // 2, the low
+    nibble for even k.  One launch (csrc/fa_mx_quant.hip).  Per block of 32 elements x_i of one weight row:
+        a NaN or +-inf among them    scale byte 255 (the whole block is NaN), every code byte 0
+        amax = max |x_i| = 0         scale byte 127, every code the signed zero
+        else amax = m 2^e, 1 <= m < 2   scale_rule "floor" (OCP): b = e - 2 + 127; "rceil" (the smallest power of two under which
+                                     nothing saturates): b = e - 2 + (m > 1.5) + 127; the byte is clamp(b, 2, 252)
+        code_i                       the sign of x_i and the nearest of 0, .5, 1, 1.5, 2, 3, 4, 6 to |x_i| / 2^(byte - 127), a tie to
+                                     the even code, above 6 to 6
+    A row's bits depend on its 32 elements alone, and "kn" gives the bits of "nk" on the transposed weights.  out=(blocks, scales):
+    the tensors to write, which may be expert-strided views.  K a multiple of 32 up to 32768, N a multiple of 8 up to 65536."""
+    op = "quant_mxfp4"
+    layout = _mx_layout(op, w_layout)
+    if scale_rule not in MX_SCALE_RULES:
+        raise RuntimeError(f"{op}: scale_rule must be one of {sorted(MX_SCALE_RULES)}, got {scale_rule!r}")
+    wv = _mx_experts(op, w, "w", tuple(_fi._DTYPES))
+    E = wv.shape[0]
+    N, K = (wv.shape[1], wv.shape[2]) if w_layout == "nk" else (wv.shape[2], wv.shape[1])
+    _mx_dims(op, N, K)
+    _no_grad(op, w=w)
+    lead = (E,) if w.dim() == 3 else ()
+    if out is None:
+        blocks = torch.empty(lead + (N, K // 2), dtype=torch.uint8, device=w.device)
+        scales = torch.empty(lead + (N, K // 32), dtype=torch.uint8, device=w.device)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise RuntimeError(f"{op}: out must be the pair (blocks, scales)")
+        blocks, scales = out
+    bv = _mx_experts(op, blocks, "out[0]" if out is not None else "blocks", (torch.uint8,), (E, N, K // 2))
+    sv = _mx_experts(op, scales, "out[1]" if out is not None else "scales", (torch.uint8,), (E, N, K // 32))
+    if blocks.dim() != w.dim() or scales.dim() != w.dim():
+        raise RuntimeError(f"{op}: out[0] and out[1] must have w's number of dimensions")
+    if wv.numel():
+        _mx_placement(op, [("w", wv, 16), ("out[0]", bv, 16), ("out[1]", sv, 0)])
+    _ra.same_device(op, [w, blocks, scales], w, "w's")
+    if wv.numel() == 0:
+        return blocks, scales
+    s = _lib.FaMxQuantParams()
+    s.struct_size = ctypes.sizeof(_lib.FaMxQuantParams)
+    s.w, s.blocks, s.scales = wv.data_ptr(), bv.data_ptr(), sv.data_ptr()
+    s.w_expert_stride, s.blocks_expert_stride, s.scales_expert_stride = _mx_es(wv), _mx_es(bv), _mx_es(sv)
+    s.num_experts, s.n, s.k = E, N, K
+    s.dtype, s.layout, s.scale_rule, s.elem_format = _fi._DTYPES[w.dtype], layout, MX_SCALE_RULES[scale_rule], _lib.FA_MX_ELEM_E2M1
+    with _fi._on_device(w.device):
+        _lib.call_mx_quant(s, _fi._stream(w.device))          # (queued: the views made here stay referenced until here)
+    del wv, bv, sv
+    return blocks, scales
+
+
+def dequant_mxfp4(blocks, scales, *, w_layout="nk", out=None):
+    """bf16 weights e2m1(code) * 2^(scale byte - 127) of blocks uint8 [E, N, K / 2] and scales uint8 [E, N, K / 32] (2-D: one
+    expert; expert-strided views are taken as they are): [E, N, K], or with w_layout "kn" [E, K, N].  One launch
+    (csrc/fa_mx_quant.hip).  Exact for the scale bytes 2 .. 252 - `moe.moe_gemm_mxfp4`'s definition of a weight; byte 255 makes the
+    block NaN; bytes 0, 1, 253, 254 give the formula's value rounded to bf16 (include/fa_mi355.h).  out: the tensor to write."""
+    op = "dequant_mxfp4"
+    layout = _mx_layout(op, w_layout)
+    bv = _mx_experts(op, blocks, "blocks", (torch.uint8,))
+    E, N, K = bv.shape[0], bv.shape[1], 2 * bv.shape[2]
+    _mx_dims(op, N, K)
+    sv = _mx_experts(op, scales, "scales", (torch.uint8,), (E, N, K // 32))
+    if scales.dim() != blocks.dim():
+        raise RuntimeError(f"{op}: scales must have blocks' number of dimensions")
+    shape = (N, K) if w_layout == "nk" else (K, N)
+    lead = (E,) if blocks.dim() == 3 else ()
+    if out is None:
+        out = torch.empty(lead + shape, dtype=torch.bfloat16, device=blocks.device)
+    elif isinstance(out, torch.Tensor) and out.dim() != blocks.dim():
+        raise RuntimeError(f"{op}: out must have blocks' number of dimensions")
+    ov = _mx_experts(op, out, "out", (torch.bfloat16,), (E,) + shape)
+    if ov.numel():
+        _mx_placement(op, [("blocks", bv, 16), ("scales", sv, 0), ("out", ov, 16)])
+    _ra.same_device(op, [blocks, scales, out], blocks, "blocks'")
+    if ov.numel() == 0:
+        return out
+    s = _lib.FaMxDequantParams()
+    s.struct_size = ctypes.sizeof(_lib.FaMxDequantParams)
+    s.blocks, s.scales, s.out = bv.data_ptr(), sv.data_ptr(), ov.data_ptr()
+    s.blocks_expert_stride, s.scales_expert_stride, s.out_expert_stride = _mx_es(bv), _mx_es(sv), _mx_es(ov)
+    s.num_experts, s.n, s.k = E, N, K
+    s.dtype, s.layout, s.elem_format = _lib.FA_BF16, layout, _lib.FA_MX_ELEM_E2M1
+    with _fi._on_device(blocks.device):
+        _lib.call_mx_dequant(s, _fi._stream(blocks.device))    # (queued: the views made here stay referenced until here)
+    del bv, sv, ov
+    return out

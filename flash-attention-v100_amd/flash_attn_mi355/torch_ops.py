@@ -1077,6 +1077,38 @@ for _op, _names in ((quant_fp8, ("x",)), (add_norm_quant, ("x", "residual", "wei
 del _op, _names, _bwd, _setup
 
 
+# MXFP4 expert weights made and unmade (quant.quant_mxfp4 / quant.dequant_mxfp4; csrc/fa_mx_quant.hip):
+# torch.ops.flash_attn_mi355.quant_mxfp4 / .dequant_mxfp4; not in __all__.  Functional, fresh contiguous outputs, capturable.
+@torch.library.custom_op(f"{_NS}::quant_mxfp4", mutates_args=(), device_types="cuda")
+def quant_mxfp4(w: Tensor, w_layout: str, scale_rule: str) -> Tuple[Tensor, Tensor]:
+    """quant.quant_mxfp4: (blocks uint8 [E, N, K / 2], scales uint8 [E, N, K / 32]) of w [E, N, K] ("nk") or [E, K, N] ("kn")"""
+    return _quant.quant_mxfp4(w, w_layout=w_layout, scale_rule=scale_rule)
+
+
+@quant_mxfp4.register_fake
+def _(w, w_layout, scale_rule):
+    N, K = (w.shape[-2], w.shape[-1]) if w_layout == "nk" else (w.shape[-1], w.shape[-2])
+    lead = tuple(w.shape[:-2])
+    return w.new_empty(lead + (N, K // 2), dtype=torch.uint8), w.new_empty(lead + (N, K // 32), dtype=torch.uint8)
+
+
+_bwd, _setup = _not_differentiable("quant_mxfp4", ("w",))
+quant_mxfp4.register_autograd(_bwd, setup_context=_setup)
+del _bwd, _setup
+
+
+@torch.library.custom_op(f"{_NS}::dequant_mxfp4", mutates_args=(), device_types="cuda")
+def dequant_mxfp4(blocks: Tensor, scales: Tensor, w_layout: str) -> Tensor:
+    """quant.dequant_mxfp4: bf16 [E, N, K] ("nk") or [E, K, N] ("kn") of blocks [E, N, K / 2] and scales [E, N, K / 32]"""
+    return _quant.dequant_mxfp4(blocks, scales, w_layout=w_layout)
+
+
+@dequant_mxfp4.register_fake
+def _(blocks, scales, w_layout):
+    N, K = blocks.shape[-2], 2 * blocks.shape[-1]
+    return blocks.new_empty(tuple(blocks.shape[:-2]) + ((N, K) if w_layout == "nk" else (K, N)), dtype=torch.bfloat16)
+
+
 # ------------------------------------------------------------------------------------------
 # what surrounds the expert GEMMs of a mixture-of-experts block (flash_attn_mi355.moe; csrc/fa_moe.hip).
 # Reached as torch.ops.flash_attn_mi355.moe_route / .moe_route_bwd / .moe_sort / .moe_permute / .moe_combine / .moe_combine_bwd;

@@ -1869,6 +1869,85 @@ int    fa_moe_gemm_mxfp4_glu_plan(int64_t rows, int32_t n, int32_t k, int32_t nu
                                   int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
 
 /*
+ * fa_mx_quant, fa_mx_dequant: 16-bit expert weights to the MXFP4 tensors fa_moe_gemm_mxfp4 reads, and back
+ * (csrc/fa_mx_quant.hip; additive: fa_params and FA_ABI_VERSION are unchanged).  Each is one launch with no workspace, no
+ * atomics and no host synchronisation; every output byte is written exactly once.
+ *   tensors        w (fa_mx_quant, fp16 / bf16) and out (fa_mx_dequant, bf16): FA_MOE_W_NK [E, n, k] or FA_MOE_W_KN [E, k, n],
+ *                  an expert dense (last dimension contiguous, row stride = row length), 16-byte aligned, the expert stride in
+ *                  ELEMENTS, a multiple of 8 and at least n * k.  blocks uint8 [E, n, k / 2] and scales uint8 [E, n, k / 32] in
+ *                  BOTH layouts - the memory fa_moe_gemm_mxfp4 reads: element k in byte k / 2, the low nibble for even k.
+ *                  blocks: 16-byte aligned, expert stride (BYTES) a multiple of 16 and at least n * k / 2; scales: any
+ *                  alignment, expert stride (BYTES) at least n * k / 32.  Inputs and outputs must not overlap.
+ *   the rule       per block of 32 k of one weight row (fp16 widened to fp32 first, so fp16 subnormals count):
+ *                  1. a NaN or +-inf among them: scale byte 255 (E8M0 NaN, OCP MX v1.0) and 16 code bytes 0.
+ *                  2. amax = max |x_i| = 0: scale byte 127, every code the signed zero (0x0, or 0x8 for -0).
+ *                  3. amax = m 2^e, 1 <= m < 2, from the bits.  FA_MX_SCALE_FLOOR (OCP): b = e - 2 + 127;
+ *                     FA_MX_SCALE_RCEIL (the smallest 2^s with amax / 2^s <= 6): b = e - 2 + (m > 1.5) + 127.
+ *                     The byte is clamp(b, 2, 252), the range fa_moe_gemm_mxfp4 covers.
+ *                  4. y_i = x_i / 2^(byte - 127), exact.  code = the sign bit of x_i and the nearest of 0, .5, 1, 1.5, 2, 3, 4, 6
+ *                     to |y_i|, a tie to the EVEN code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4),
+ *                     |y_i| > 6 to 6.  A negative value that rounds to zero is 0x8.
+ *                  A row's bits depend on its 32 elements alone: not on E, n, the layout, the strides or other rows, and
+ *                  FA_MOE_W_KN gives the bits of FA_MOE_W_NK on the transposed weights.
+ *   fa_mx_dequant  out = e2m1(code) * 2^(byte - 127), fa_moe_gemm_mxfp4's definition: exact in bf16 for bytes 2 ... 252.  Byte 255:
+ *                  the whole block is NaN (0x7FC0).  Bytes 0, 1, 253 and 254 are rejected by nothing and form no address: they
+ *                  give the formula's value rounded to bf16 - bytes 0 and 1 an exact bf16 subnormal or normal, bytes 253 and
+ *                  254 +-inf where the product reaches 2^128.
+ *   elem_format    FA_MX_ELEM_E2M1; another value: FA_ERR_UNSUPPORTED.
+ *   limits         k a multiple of 32 up to 32768, n a multiple of 8 up to 65536, num_experts up to 65535; outside, and for an
+ *                  alignment or stride rule above: FA_ERR_UNSUPPORTED, before any device work.  num_experts, n or k = 0: FA_OK
+ *                  without a launch.
+ * FA_ERR_INVALID_ARGUMENT before any launch: a short struct_size; a NULL tensor; a dtype other than FA_FP16 / FA_BF16 (out: FA_BF16);
+ * an unknown layout or scale_rule; a negative size or stride; an overlap; non-zero reserved fields.
+ */
+typedef enum fa_mx_scale_rule {
+    FA_MX_SCALE_FLOOR = 0,
+    FA_MX_SCALE_RCEIL = 1
+} fa_mx_scale_rule;
+
+typedef enum fa_mx_elem_format {
+    FA_MX_ELEM_E2M1 = 0
+} fa_mx_elem_format;
+
+typedef struct fa_mx_quant_params {
+    size_t         struct_size;      /* sizeof(fa_mx_quant_params) as the caller compiled it */
+    const void*    w;                /* [num_experts, n, k] or [num_experts, k, n] of `dtype` */
+    void*          blocks;           /* uint8 [num_experts, n, k / 2] */
+    void*          scales;           /* uint8 [num_experts, n, k / 32] */
+    int64_t        w_expert_stride;                /* elements, >= n * k, a multiple of 8 */
+    int64_t        blocks_expert_stride;           /* bytes, >= n * k / 2, a multiple of 16 */
+    int64_t        scales_expert_stride;           /* bytes, >= n * k / 32 */
+    int32_t        num_experts, n, k;
+    int32_t        dtype;            /* FA_FP16 or FA_BF16 */
+    int32_t        layout;           /* fa_moe_w_layout of w */
+    int32_t        scale_rule;       /* fa_mx_scale_rule */
+    int32_t        elem_format;      /* FA_MX_ELEM_E2M1 */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_mx_quant_params;
+
+int    fa_mx_quant(const fa_mx_quant_params* s, void* stream);
+size_t fa_mx_quant_params_size(void);
+
+typedef struct fa_mx_dequant_params {
+    size_t         struct_size;      /* sizeof(fa_mx_dequant_params) as the caller compiled it */
+    const void*    blocks;           /* uint8 [num_experts, n, k / 2] */
+    const void*    scales;           /* uint8 [num_experts, n, k / 32] */
+    void*          out;              /* [num_experts, n, k] or [num_experts, k, n] bf16 */
+    int64_t        blocks_expert_stride;           /* bytes, >= n * k / 2, a multiple of 16 */
+    int64_t        scales_expert_stride;           /* bytes, >= n * k / 32 */
+    int64_t        out_expert_stride;              /* elements, >= n * k, a multiple of 8 */
+    int32_t        num_experts, n, k;
+    int32_t        dtype;            /* FA_BF16 */
+    int32_t        layout;           /* fa_moe_w_layout of out */
+    int32_t        elem_format;      /* FA_MX_ELEM_E2M1 */
+    int64_t        reserved[4];      /* 0 */
+} fa_mx_dequant_params;
+
+int    fa_mx_dequant(const fa_mx_dequant_params* s, void* stream);
+size_t fa_mx_dequant_params_size(void);
+
+/*
  * Row gather / scatter for the padding helpers on both sides of the varlen path (HBM-bound byte movement).
  * Rows are `row_bytes` bytes (a multiple of 16, 16-byte aligned base pointers), indices are int64 on the device
  * (negative values count from the end, as in torch); no bounds checks beyond that (same contract as the reference's
