@@ -258,6 +258,7 @@ size_t fa_moe_gemm_glu_params_size(void) { return sizeof(fa_moe_gemm_glu_params)
 size_t fa_moe_gemm_wgrad_params_size(void) { return sizeof(fa_moe_gemm_wgrad_params); }
 size_t fa_moe_gemm_mxfp4_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_params); }
 size_t fa_moe_gemm_mxfp4_glu_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_glu_params); }
+size_t fa_moe_gemm_mxfp4_dgrad_params_size(void) { return sizeof(fa_moe_gemm_mxfp4_dgrad_params); }
 size_t fa_mx_quant_params_size(void) { return sizeof(fa_mx_quant_params); }
 size_t fa_mx_dequant_params_size(void) { return sizeof(fa_mx_dequant_params); }
 const char* fa_last_error(void) { return g_last_error.c_str(); }
@@ -1854,6 +1855,44 @@ static int moe_gemm_mxfp4_check(const fa_moe_gemm_mxfp4_params& s, const char* o
     return moe_gemm_check(op, g, out_n < 0 ? s.n : out_n, wq);
 }
 
+// what fa_moe_gemm_mxfp4_dgrad and its plan take: weights of n rows (contracted) and k columns (dx's) - fa_moe_gemm's "kn" limits
+// with the roles exchanged, k in whole scale groups
+static int moe_gemm_mxfp4_dgrad_shape_check(const char* op, int64_t rows, int n, int k, int num_experts, int layout, int dtype) {
+    if (dtype != FA_BF16) return fail(FA_ERR_UNSUPPORTED, "%s: dtype must be bf16", op);
+    if (layout != FA_MOE_W_NK) return fail(FA_ERR_UNSUPPORTED, "%s: layout (the weights') must be FA_MOE_W_NK", op);
+    if (n < 8 || n > fa::MOE_GEMM_MXFP4_DGRAD_MAX_N || n % 8 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: n must be a multiple of 8 in [8, %d], got %d", op, fa::MOE_GEMM_MXFP4_DGRAD_MAX_N, n);
+    if (k < 32 || k > fa::MOE_GEMM_MXFP4_DGRAD_MAX_K || k % 32 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: k must be a multiple of 32 in [32, %d], got %d", op, fa::MOE_GEMM_MXFP4_DGRAD_MAX_K, k);
+    return moe_gemm_shape_check(op, rows, k, n, num_experts, FA_MOE_W_KN, dtype);
+}
+
+// fa_moe_gemm_mxfp4_dgrad: the two weight tensors as fa_moe_gemm_mxfp4 checks them, then fa_moe_gemm's checks ("kn", x = dy,
+// out = dx, no bias, no gather) on everything else
+static int moe_gemm_mxfp4_dgrad_check(const fa_moe_gemm_mxfp4_dgrad_params& s) {
+    const char* op = "moe_gemm_mxfp4_dgrad";
+    FA_TRY(moe_gemm_mxfp4_dgrad_shape_check(op, s.rows, s.n, s.k, s.num_experts, s.layout, s.dtype));
+    const int64_t wb = (int64_t)s.n * s.k / 2, cb = (int64_t)s.n * s.k / 32;
+    if (s.w_blocks_expert_stride < wb || s.w_blocks_expert_stride % 16 != 0)
+        return fail(FA_ERR_UNSUPPORTED, "%s: w_blocks_expert_stride must be a multiple of 16 and at least n x k / 2 = %lld bytes, got %lld",
+                    op, (long long)wb, (long long)s.w_blocks_expert_stride);
+    if (s.w_scales_expert_stride < cb)
+        return fail(FA_ERR_UNSUPPORTED, "%s: w_scales_expert_stride must be at least n x k / 32 = %lld bytes, got %lld", op,
+                    (long long)cb, (long long)s.w_scales_expert_stride);
+    FA_CHECK(s.rows == 0 || s.w_scales, "%s: w_scales must not be NULL", op);
+    fa_moe_gemm_params g = {};
+    g.struct_size = sizeof(g);
+    g.x = s.dy, g.w = s.w_blocks, g.expert_offsets = s.expert_offsets, g.out = s.dx;
+    g.x_row_stride = s.dy_row_stride, g.out_row_stride = s.dx_row_stride;
+    g.rows = s.rows, g.tokens = s.rows, g.num_experts = s.num_experts, g.top_k = 1;
+    g.n = s.k, g.k = s.n, g.dtype = s.dtype, g.bias_dtype = s.dtype, g.layout = FA_MOE_W_KN;
+    g.reserved0 = s.reserved0;
+    for (int i = 0; i < 4; ++i) g.reserved[i] = s.reserved[i];
+    const View wq[2] = {view_rows("w_blocks", s.w_blocks, s.num_experts, s.w_blocks_expert_stride, wb, 1),
+                        view_rows("w_scales", s.w_scales, s.num_experts, s.w_scales_expert_stride, cb, 1)};
+    return moe_gemm_check(op, g, s.k, wq);
+}
+
 // ---- fa_mx_quant, fa_mx_dequant
 // what the two blocks share: the shape and its limits, the three tensors (`wname`: "w" or "out"), their strides and alignment
 static int mx_quant_common_check(const char* op, const char* wname, const void* w, const void* blocks, const void* scales, int64_t w_es,
@@ -2434,6 +2473,27 @@ int fa_moe_gemm_mxfp4_glu(const fa_moe_gemm_mxfp4_glu_params* sp, void* stream) 
     if (!s.sorted_slot) s.tokens = s.rows, s.top_k = 1;
     fa::launch_moe_gemm_mxfp4_glu(s, static_cast<hipStream_t>(stream));
     return check_hip("fa_moe_gemm_mxfp4_glu launch");
+}
+
+int fa_moe_gemm_mxfp4_dgrad_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                                 int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n) {
+    FA_TRY(moe_gemm_mxfp4_dgrad_shape_check("moe_gemm_mxfp4_dgrad_plan", rows, n, k, num_experts, layout, dtype));
+    const fa::MoeGemmPlan pl = fa::moe_gemm_mxfp4_dgrad_plan(rows, n, k, num_experts);
+    if (block_m) *block_m = pl.bm;
+    if (block_n) *block_n = pl.bn;
+    if (block_k) *block_k = pl.bk;
+    if (grid_m) *grid_m = pl.grid_m;
+    if (grid_n) *grid_n = pl.grid_n;
+    return FA_OK;
+}
+
+int fa_moe_gemm_mxfp4_dgrad(const fa_moe_gemm_mxfp4_dgrad_params* sp, void* stream) {
+    FA_TRY(check_header(sp, "fa_moe_gemm_mxfp4_dgrad_params"));
+    const fa_moe_gemm_mxfp4_dgrad_params s = *sp;
+    FA_TRY(moe_gemm_mxfp4_dgrad_check(s));
+    if (s.rows == 0) return FA_OK;
+    fa::launch_moe_gemm_mxfp4_dgrad(s, static_cast<hipStream_t>(stream));
+    return check_hip("fa_moe_gemm_mxfp4_dgrad launch");
 }
 
 int fa_mx_quant(const fa_mx_quant_params* sp, void* stream) {

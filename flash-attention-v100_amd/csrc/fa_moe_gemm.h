@@ -72,6 +72,17 @@ static inline MoeGemmPlan moe_gemm_mxfp4_glu_plan(int64_t m_max, int n, int k, i
 
 void launch_moe_gemm_mxfp4_glu(const fa_moe_gemm_mxfp4_glu_params& s, hipStream_t stream);
 
+// fa_moe_gemm_mxfp4_dgrad (fa_moe_gemm_mxfp4_dgrad.hip): the data gradient over weights of n rows and k columns is fa_moe_gemm's
+// "kn" form with the roles exchanged - k output columns, n contraction elements - and takes its plan: the bf16 weight image of
+// a step is built in LDS and has the 16-bit kernel's shape, [64 n][128 k].
+constexpr int MOE_GEMM_MXFP4_DGRAD_MAX_N = MOE_GEMM_MAX_K;   // the contraction
+constexpr int MOE_GEMM_MXFP4_DGRAD_MAX_K = 32768;            // dx's columns
+static inline MoeGemmPlan moe_gemm_mxfp4_dgrad_plan(int64_t m_max, int n, int k, int E) {
+    return moe_gemm_plan(m_max, k, n, E, FA_MOE_W_KN, FA_BF16);
+}
+
+void launch_moe_gemm_mxfp4_dgrad(const fa_moe_gemm_mxfp4_dgrad_params& s, hipStream_t stream);
+
 // fa_moe_gemm_wgrad (fa_moe_gemm_wgrad.hip): one workgroup per 128 x 128 tile of one expert's dW, the segment's rows staged 64 a
 // step.  dW is dense, so the grid is (ceil(n / 128), ceil(k / 128), E) whatever the segments hold.
 constexpr int MOE_WGRAD_BN = 128;                         // tile extent along n (the columns of dy)

@@ -55,31 +55,14 @@
 #include "fa_act.h"
 #include "fa_moe_gemm.h"
 #include "fa_moe_tile.h"
+#include "fa_mx_cvt.h"
 #include <type_traits>
 
 namespace fa {
 
 namespace {
 
-__device__ __forceinline__ uint32_t cvt_fp4x2(uint32_t w, float scale, std::integral_constant<int, 0>) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
-}
-__device__ __forceinline__ uint32_t cvt_fp4x2(uint32_t w, float scale, std::integral_constant<int, 1>) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
-}
-__device__ __forceinline__ uint32_t cvt_fp4x2(uint32_t w, float scale, std::integral_constant<int, 2>) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
-}
-__device__ __forceinline__ uint32_t cvt_fp4x2(uint32_t w, float scale, std::integral_constant<int, 3>) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
-}
-// 8 codes (one dword, element i in nibble i) times 2^(scale_byte - 127) -> the 8 bf16 of an MFMA operand
-__device__ __forceinline__ u32x4 dequant8(uint32_t w, uint32_t scale_byte) {
-    const float sc = __builtin_bit_cast(float, scale_byte << 23);
-    return u32x4{cvt_fp4x2(w, sc, std::integral_constant<int, 0>{}), cvt_fp4x2(w, sc, std::integral_constant<int, 1>{}),
-                 cvt_fp4x2(w, sc, std::integral_constant<int, 2>{}), cvt_fp4x2(w, sc, std::integral_constant<int, 3>{})};
-}
-
+// (cvt_fp4x2 and dequant8 - 8 codes times 2^(scale_byte - 127) -> the 8 bf16 of an MFMA operand: fa_mx_cvt.h)
 // The one body of fa_moe_gemm_mxfp4's kernels (GLU 0: P = fa_moe_gemm_mxfp4_params) and fa_moe_gemm_mxfp4_glu's (GLU 1: interleaved,
 // GLU 2: packed gate / up rows; P = fa_moe_gemm_mxfp4_glu_params, whose n counts OUTPUT columns).  With GLU 0 every
 // `if constexpr (GLU ...)` falls away and the four kernels are what they were.

@@ -1,4 +1,4 @@
-// fa_moe_tile.h - the device code that the grouped expert GEMMs (fa_moe_gemm.hip, fa_moe_gemm_mxfp4.hip) share: which tile of
+// fa_moe_tile.h - the device code that the grouped expert GEMMs (fa_moe_gemm.hip, fa_moe_gemm_mxfp4.hip, fa_moe_gemm_mxfp4_dgrad.hip) share: which tile of
 // out a workgroup owns, found from expert_offsets on the device, and the bounded buffer descriptor their loads go through.
 #pragma once
 #include "fa_common.h"

@@ -627,6 +627,20 @@ class FaMoeGemmMxfp4GluParams(ctypes.Structure):
     ]
 
 
+class FaMoeGemmMxfp4DgradParams(ctypes.Structure):
+    """Mirror of `struct fa_moe_gemm_mxfp4_dgrad_params` (include/fa_mi355.h): fa_moe_gemm_mxfp4_dgrad, the data gradient of the
+    grouped expert GEMM on MXFP4 weights (n: the weights' rows, contracted; k: dx's columns).  struct_size must be set to
+    sizeof(FaMoeGemmMxfp4DgradParams)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("dy", _ptr), ("w_blocks", _ptr), ("w_scales", _ptr), ("expert_offsets", _ptr), ("dx", _ptr),
+        ("dy_row_stride", _i64), ("dx_row_stride", _i64), ("w_blocks_expert_stride", _i64), ("w_scales_expert_stride", _i64),
+        ("rows", _i64),
+        ("num_experts", _i32), ("n", _i32), ("k", _i32), ("dtype", _i32), ("layout", _i32), ("reserved0", _i32),
+        ("reserved", _i64 * 4),
+    ]
+
+
 class FaMxQuantParams(ctypes.Structure):
     """Mirror of `struct fa_mx_quant_params` (include/fa_mi355.h): fa_mx_quant, 16-bit expert weights to MXFP4 codes and E8M0 scale
     bytes.  struct_size must be set to sizeof(FaMxQuantParams)."""
@@ -682,6 +696,7 @@ EXPORTS = ["fa_abi_version", "fa_params_size", "fa_last_error", "fa_build_info",
            "fa_moe_gemm_wgrad", "fa_moe_gemm_wgrad_params_size", "fa_moe_gemm_wgrad_plan",
            "fa_moe_gemm_mxfp4", "fa_moe_gemm_mxfp4_params_size", "fa_moe_gemm_mxfp4_plan",
            "fa_moe_gemm_mxfp4_glu", "fa_moe_gemm_mxfp4_glu_params_size", "fa_moe_gemm_mxfp4_glu_plan",
+           "fa_moe_gemm_mxfp4_dgrad", "fa_moe_gemm_mxfp4_dgrad_params_size", "fa_moe_gemm_mxfp4_dgrad_plan",
            "fa_mx_quant", "fa_mx_quant_params_size", "fa_mx_dequant", "fa_mx_dequant_params_size"] + EXT_OPS
 
 
@@ -718,6 +733,7 @@ ROW_OPS = [
     ("fa_moe_gemm_wgrad", FaMoeGemmWgradParams, None),
     ("fa_moe_gemm_mxfp4", FaMoeGemmMxfp4Params, None),
     ("fa_moe_gemm_mxfp4_glu", FaMoeGemmMxfp4GluParams, None),
+    ("fa_moe_gemm_mxfp4_dgrad", FaMoeGemmMxfp4DgradParams, None),
     ("fa_mx_quant", FaMxQuantParams, None),
     ("fa_mx_dequant", FaMxDequantParams, None),
 ]
@@ -769,7 +785,8 @@ def _load():
     lib.fa_act_mul_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
     lib.fa_moe_sort_plan.restype = ctypes.c_int
     lib.fa_moe_sort_plan.argtypes = [i64, ctypes.c_int32] + [ctypes.POINTER(i64)] * 3
-    for fn in (lib.fa_moe_gemm_plan, lib.fa_moe_gemm_glu_plan, lib.fa_moe_gemm_mxfp4_plan, lib.fa_moe_gemm_mxfp4_glu_plan):
+    for fn in (lib.fa_moe_gemm_plan, lib.fa_moe_gemm_glu_plan, lib.fa_moe_gemm_mxfp4_plan, lib.fa_moe_gemm_mxfp4_glu_plan,
+               lib.fa_moe_gemm_mxfp4_dgrad_plan):
         fn.restype = ctypes.c_int
         fn.argtypes = [i64] + [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_int32)] * 3 + [ctypes.POINTER(i64)] * 2
     lib.fa_moe_gemm_wgrad_plan.restype = ctypes.c_int
@@ -855,8 +872,8 @@ call_merge = _struct_call("fa_merge_states")
 # call_rotary, call_kv_store, call_kv_gather, call_rope_store, call_qk_norm_rope_store, call_qk_norm_rope_bwd, call_add_norm,
 # call_add_norm_bwd, call_cross_entropy, call_cross_entropy_bwd, call_act_mul, call_act_mul_bwd, call_quant_fp8, call_add_norm_quant,
 # call_act_mul_quant, call_moe_route, call_moe_route_bwd, call_moe_sort, call_moe_permute, call_moe_combine, call_moe_combine_bwd,
-# call_moe_gemm, call_moe_gemm_glu, call_moe_gemm_wgrad, call_moe_gemm_mxfp4, call_moe_gemm_mxfp4_glu, call_mx_quant, call_mx_dequant,
-# call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
+# call_moe_gemm, call_moe_gemm_glu, call_moe_gemm_wgrad, call_moe_gemm_mxfp4, call_moe_gemm_mxfp4_glu,
+# call_moe_gemm_mxfp4_dgrad, call_mx_quant, call_mx_dequant, call_sample, call_spec_accept, call_spec_walk; qk_norm_rope_bwd_workspace_bytes, add_norm_bwd_workspace_bytes,
 # cross_entropy_workspace_bytes, sample_workspace_bytes, spec_accept_workspace_bytes, moe_sort_workspace_bytes
 for _entry, _struct, _query in ROW_OPS:
     globals()["call_" + _entry[len("fa_"):]] = _struct_call(_entry)
@@ -894,7 +911,8 @@ def moe_sort_plan(slots, num_experts):
 def moe_gemm_plan(rows, n, k, num_experts, layout, dtype, entry="fa_moe_gemm_plan"):
     """fa_moe_gemm_plan: (block_m, block_n, block_k, grid_m, grid_n) of fa_moe_gemm, a function of its arguments alone; needs
     no device.  entry "fa_moe_gemm_glu_plan": the same of fa_moe_gemm_glu (n: its output columns); "fa_moe_gemm_mxfp4_plan": of
-    fa_moe_gemm_mxfp4; "fa_moe_gemm_mxfp4_glu_plan": of fa_moe_gemm_mxfp4_glu (n: its output columns)"""
+    fa_moe_gemm_mxfp4; "fa_moe_gemm_mxfp4_glu_plan": of fa_moe_gemm_mxfp4_glu (n: its output columns); "fa_moe_gemm_mxfp4_dgrad_plan": of
+    fa_moe_gemm_mxfp4_dgrad (n, k: the weights' rows and columns)"""
     blk = [ctypes.c_int32() for _ in range(3)]
     grid = [ctypes.c_int64() for _ in range(2)]
     rc = getattr(lib, entry)(rows, n, k, num_experts, layout, dtype, *(ctypes.byref(o) for o in blk + grid))

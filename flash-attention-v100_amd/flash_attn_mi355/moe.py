@@ -21,6 +21,8 @@ have their contracts).
   inference on MXFP4 expert weights (gpt-oss: interleaved gate / up rows, the clamped SwiGLU), weights never dequantised in memory:
     a = moe_gemm_mxfp4_glu(x, w1_blocks, w1_scales, expert_offsets, bias=b1, sorted_slot=sorted_slot, top_k=k)
     yp = moe_gemm_mxfp4(a, w2_blocks, w2_scales, expert_offsets, bias=b2)
+  training through FROZEN MXFP4 experts (gradients for x and bias; dx by moe_gemm_mxfp4_dgrad on csrc/fa_moe_gemm_mxfp4_dgrad.hip):
+    yp = moe_linear_mxfp4(a, w2_blocks, w2_scales, expert_offsets, bias=b2)
 
 No function synchronises with the host, every result is a pure function of its inputs (no ordering depends on an atomic, two calls
 give the same bits), all are capturable in a HIP graph.
@@ -580,7 +582,7 @@ def moe_gemm_mxfp4(x, w_blocks, w_scales, expert_offsets, *, bias=None, sorted_s
     the same accumulator chain of v_mfma_f32_32x32x16 over k ascending with the same operand slots, in both plans
     (`moe_gemm_mxfp4_plan`), plain and gathered.  x, bias, expert_offsets, sorted_slot / top_k, out, the +0 tail, the limits and
     the guarantees are `moe_gemm`'s, with K a multiple of 32.  One launch, no workspace, capturable.  No autograd: an input that
-    requires grad raises.  Not covered: fp16, the "kn" layout, MX or fp8 activations, a quantiser (the gated epilogue of a
+    requires grad raises (`moe_linear_mxfp4` is the differentiable name).  Not covered: fp16, the "kn" layout, MX or fp8 activations, a quantiser (the gated epilogue of a
     gate-up layer: `moe_gemm_mxfp4_glu`)."""
     op = "moe_gemm_mxfp4"
     s = _lib.FaMoeGemmMxfp4Params()
@@ -671,6 +673,112 @@ def moe_gemm_mxfp4_glu(x, w_blocks, w_scales, expert_offsets, *, activation="swi
     s.activation, s.gate_up, s.alpha, s.limit = GLU_MXFP4_ACTIVATIONS[activation], GATE_UP[gate_up], alpha, limit
     return _gemm_launch(op, s, _lib.call_moe_gemm_mxfp4_glu, x, [w_blocks, w_scales], E, N, N // 2, K, expert_offsets, bias,
                         sorted_slot, top_k, out)
+
+
+def moe_gemm_mxfp4_dgrad_plan(M_max, N, K, num_experts):
+    """(block_m, block_n, block_k, grid_m, grid_n) of `moe_gemm_mxfp4_dgrad` for weights of N rows and K columns: a function of
+    these arguments alone, no device.  It is `moe_gemm_plan(M_max, K, N, num_experts, w_layout="kn")`: block_n 128 columns of dx,
+    block_k 64 weight rows a step, grid_n = ceil(K / 128)"""
+    return _lib.moe_gemm_plan(int(M_max), int(N), int(K), int(num_experts), W_LAYOUTS["nk"], _fi._DTYPES[torch.bfloat16],
+                              entry="fa_moe_gemm_mxfp4_dgrad_plan")
+
+
+def moe_gemm_mxfp4_dgrad(dy, w_blocks, w_scales, expert_offsets, *, out=None):
+    """The data gradient of `moe_gemm_mxfp4` (csrc/fa_moe_gemm_mxfp4_dgrad.hip): dx bf16 [M_max, K] from dy bf16 [M_max, N] and the
+    very tensors the forward reads - w_blocks uint8 [E, N, K / 2] (or [E, N, K / 32, 16]), w_scales uint8 [E, N, K / 32]:
+
+        dx[r, k] = round_bf16(sum_n float(dy[r, n]) * W_e[n, k])      expert_offsets[e] <= r < expert_offsets[e + 1]
+        dx[r]    = +0                                                  expert_offsets[E] <= r < M_max
+
+    The contraction runs over the ROWS of the weight, so codes (two to a byte along k) and scale groups (32 k) lie along the
+    OUTPUT dimension: the kernel dequantises each 16-byte piece of codes with its one scale byte on the way into LDS and then
+    runs `moe_gemm`'s "kn" loop on that image.  dx has EXACTLY the bits of
+    moe_gemm(dy, dequant_mxfp4(w_blocks, w_scales), expert_offsets, w_layout="kn") in both plans (`moe_gemm_mxfp4_dgrad_plan`)
+    without the 2 E N K bytes of dequantised weights: 17 / 32 of a byte is read per weight instead of 2.  Every element of dx
+    is written exactly once.  One launch, no workspace, nothing read on the host, capturable.  The weight tensors, their strides
+    and alignment and the scale bytes covered (2 ... 252) are `moe_gemm_mxfp4`'s; dy and out: 16-byte aligned, contiguous last
+    dimension, row strides multiples of 8 (nothing is copied; another layout raises).
+
+    Limits: 2 <= E <= 512, N a multiple of 8 up to 32768, K a multiple of 32 up to 32768, bf16.  No autograd (`moe_linear_mxfp4`
+    is the differentiable name).  Not covered: a gathered or scatter-fused form (the backward of a gathered forward goes through
+    moe_combine_forward), any weight gradient, fp16, MX activations, the backward of `moe_gemm_mxfp4_glu`."""
+    op = "moe_gemm_mxfp4_dgrad"
+    if dy.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"{op}: dy requires grad, and {op} has no autograd (detach it, or run under no_grad)")
+    if dy.dtype != torch.bfloat16 or dy.dim() != 2:
+        raise RuntimeError(f"{op}: dy must be a bf16 tensor [rows, N], got {dy.dtype} {tuple(dy.shape)}")
+    M, N = dy.shape
+    if w_blocks.dtype != torch.uint8 or w_blocks.dim() not in (3, 4) or w_blocks.shape[1] != N:
+        raise RuntimeError(f"{op}: w_blocks must be a uint8 tensor [E, N, K / 2] or [E, N, K / 32, 16] with dy's N = {N} rows, got "
+                           f"{w_blocks.dtype} {tuple(w_blocks.shape)}")
+    if w_blocks.dim() == 4 and w_blocks.shape[3] != 16:
+        raise RuntimeError(f"{op}: a 4-d w_blocks must be [E, N, K / 32, 16], got {tuple(w_blocks.shape)}")
+    E = w_blocks.shape[0]
+    K = 2 * w_blocks.shape[2] if w_blocks.dim() == 3 else 32 * w_blocks.shape[2]
+    if K < 32 or K > GEMM_MAX_K or K % 32:
+        raise RuntimeError(f"{op}: K must be a multiple of 32 in [32, {GEMM_MAX_K}], got {K}")
+    _gemm_dim(op, N, "N", GEMM_MAX_K)
+    if w_scales.dtype != torch.uint8 or tuple(w_scales.shape) != (E, N, K // 32):
+        raise RuntimeError(f"{op}: w_scales must be uint8 of shape {(E, N, K // 32)}, got {w_scales.dtype} {tuple(w_scales.shape)}")
+    if not (2 <= E <= MAX_EXPERTS):
+        raise RuntimeError(f"{op}: num_experts (w_blocks.shape[0]) must be in [2, {MAX_EXPERTS}], got {E}")
+    if (not w_blocks[0].is_contiguous() or w_blocks.stride(0) < N * K // 2 or w_blocks.stride(0) % 16 or w_blocks.data_ptr() % 16):
+        raise RuntimeError(f"{op}: w_blocks must be 16-byte aligned with contiguous experts and an expert stride that is a multiple "
+                           f"of 16 and at least N K / 2, got strides {tuple(w_blocks.stride())}")
+    if not w_scales[0].is_contiguous() or w_scales.stride(0) < N * K // 32:
+        raise RuntimeError(f"{op}: w_scales must have contiguous experts and an expert stride of at least N K / 32, got strides "
+                           f"{tuple(w_scales.stride())}")
+    expert_offsets = _table(op, expert_offsets, (E + 1,), torch.int32, "expert_offsets")
+    if M >= 2 ** 31:
+        raise RuntimeError(f"{op}: M_max must stay below 2^31, got {M}")
+    if out is not None and (out.dtype != dy.dtype or tuple(out.shape) != (M, K)):
+        raise RuntimeError(f"{op}: out must be {dy.dtype} of shape {(M, K)}, got {out.dtype} {tuple(out.shape)}")
+    if M:
+        _gemm_rows(op, dy, "dy")
+        if out is not None:
+            _gemm_rows(op, out, "out")
+    _ra.same_device(op, [dy, w_blocks, w_scales, expert_offsets, out], dy, "dy's")
+    dev = dy.device
+    if out is None:
+        out = torch.empty((M, K), dtype=dy.dtype, device=dev)
+    if M == 0:
+        return out
+    s = _lib.FaMoeGemmMxfp4DgradParams()
+    s.struct_size = ctypes.sizeof(s)
+    s.dy, s.dy_row_stride = dy.data_ptr(), dy.stride(0)
+    s.w_blocks, s.w_blocks_expert_stride = w_blocks.data_ptr(), w_blocks.stride(0)
+    s.w_scales, s.w_scales_expert_stride = w_scales.data_ptr(), w_scales.stride(0)
+    s.expert_offsets = expert_offsets.data_ptr()
+    s.dx, s.dx_row_stride = out.data_ptr(), out.stride(0)
+    s.rows, s.num_experts, s.n, s.k = M, E, N, K
+    s.dtype, s.layout = _fi._DTYPES[dy.dtype], W_LAYOUTS["nk"]
+    with _fi._on_device(dev):
+        _lib.call_moe_gemm_mxfp4_dgrad(s, _fi._stream(dev))
+    del expert_offsets
+    return out
+
+
+def moe_linear_mxfp4(x, w_blocks, w_scales, expert_offsets, *, bias=None, sorted_slot=None, top_k=None, pos=None):
+    """The differentiable expert layer on frozen MXFP4 weights: the forward is `moe_gemm_mxfp4(x, w_blocks, w_scales,
+    expert_offsets, ...)`, bit for bit, with the same arguments and limits (and N <= 32768, the backward's contraction).  It is
+    differentiable in x and bias; the uint8 weights have no gradient.  The backward is `moe_linear`'s with the MXFP4 data
+    gradient in the place of the "kn" GEMM, from dy made conforming (a copy only where its layout cannot be read):
+
+        dx        moe_gemm_mxfp4_dgrad(dy, w_blocks, w_scales, expert_offsets); in the gather form followed by
+                  moe_combine_forward(.., None, pos) - pass `pos`, moe_sort's third result; without it the backward inverts
+                  sorted_slot on the device first
+        dbias     moe_gemm_wgrad(dy, x, expert_offsets, need_dw=False, need_dbias=True), in bias' dtype
+
+    The gradients have the bits of `moe_linear` on dequant_mxfp4(w_blocks, w_scales).  Only the gradients autograd asks for are
+    computed.  The tables have no gradient; no double backward."""
+    op = "moe_linear_mxfp4"
+    if (sorted_slot is None) != (top_k is None):
+        raise RuntimeError(f"{op}: sorted_slot and top_k go together")
+    if pos is not None and sorted_slot is None:
+        raise RuntimeError(f"{op}: pos goes with sorted_slot (the gather form)")
+    _fi._check_device(x, w_blocks, w_scales, expert_offsets, bias, sorted_slot, pos)
+    from . import torch_ops as _ops
+    return _ops.moe_linear_mxfp4(x, w_blocks, w_scales, expert_offsets, bias, sorted_slot, None if top_k is None else int(top_k), pos)
 
 
 def moe_gemm_glu_plan(M_max, I, K, num_experts, *, w_layout="nk", dtype=torch.bfloat16):

@@ -17,7 +17,8 @@ stable sort of the (token, k) slots by expert, the permutation into per-expert s
 mixture-of-experts block with autograd formulas, fa_moe_*, and `moe_gemm`, its forward grouped expert GEMM over `expert_offsets`,
 fa_moe_gemm, not differentiable, `moe_gemm_wgrad`, its weight and bias gradients, fa_moe_gemm_wgrad, and `moe_linear`, the
 differentiable expert layer built on them, `moe_gemm_glu`, the gate-up GEMM with the gated activation in its epilogue,
-fa_moe_gemm_glu, and `moe_glu_linear`, its differentiable form; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
+fa_moe_gemm_glu, and `moe_glu_linear`, its differentiable form, `moe_gemm_mxfp4_dgrad`, the data gradient of the expert GEMM on
+MXFP4 weights, fa_moe_gemm_mxfp4_dgrad, and `moe_linear_mxfp4`, the differentiable layer on frozen MXFP4 weights; `sample` / `sample_filter`: temperature / top-k / min-p / top-p token
 sampling from logits and the filtered logits alone, fa_sample, not differentiable; `spec_accept` / `spec_walk` / `spec_verify`:
 speculative-decoding verification, fa_spec_accept / fa_spec_walk, not differentiable - registered, but not listed in `__all__`).
 
@@ -1348,13 +1349,16 @@ def _moe_linear_setup(ctx, inputs, output):
 
 def _moe_linear_grads(dy, x, w, expert_offsets, sorted_slot, pos, w_layout, top_k, bias_dtype, need_dx, need_dw, need_db):
     """(dx, dw, dbias) of out = moe_gemm(x, w, ...) from dy, None where not needed: moe_linear's backward, and moe_glu_linear's
-    once dy has become dh"""
+    once dy has become dh.  w a (w_blocks, w_scales) pair: moe_linear_mxfp4's, the data gradient through moe_gemm_mxfp4_dgrad"""
     if not (dy.stride(1) == 1 and dy.stride(0) % 8 == 0 and dy.stride(0) >= dy.shape[1] and dy.stride(0) <= _moe.GEMM_MAX_ROW_STRIDE
             and dy.storage_offset() % 8 == 0):
         dy = dy.contiguous()
     dx = dw = db = None
     if need_dx:
-        dx = moe_gemm(dy, w, expert_offsets, "kn" if w_layout == "nk" else "nk", None, None, None)
+        if isinstance(w, tuple):
+            dx = moe_gemm_mxfp4_dgrad(dy, w[0], w[1], expert_offsets)
+        else:
+            dx = moe_gemm(dy, w, expert_offsets, "kn" if w_layout == "nk" else "nk", None, None, None)
         if sorted_slot is not None:
             T = x.shape[0]
             if pos is None:
@@ -1379,6 +1383,57 @@ def _moe_linear_backward(ctx, dy):
 
 
 moe_linear.register_autograd(_moe_linear_backward, setup_context=_moe_linear_setup)
+
+
+# the data gradient of the expert GEMM on MXFP4 weights (moe.moe_gemm_mxfp4_dgrad; csrc/fa_moe_gemm_mxfp4_dgrad.hip) and the
+# differentiable layer on frozen MXFP4 weights (moe.moe_linear_mxfp4): torch.ops.flash_attn_mi355.moe_gemm_mxfp4_dgrad /
+# .moe_linear_mxfp4
+@torch.library.custom_op(f"{_NS}::moe_gemm_mxfp4_dgrad", mutates_args=(), device_types="cuda")
+def moe_gemm_mxfp4_dgrad(dy: Tensor, w_blocks: Tensor, w_scales: Tensor, expert_offsets: Tensor) -> Tensor:
+    """moe.moe_gemm_mxfp4_dgrad: dx [M_max, K], a fresh contiguous bf16 tensor.  Functional and capturable; no autograd is
+    registered."""
+    return _moe.moe_gemm_mxfp4_dgrad(dy, w_blocks, w_scales, expert_offsets)
+
+
+@moe_gemm_mxfp4_dgrad.register_fake
+def _(dy, w_blocks, w_scales, expert_offsets):
+    return dy.new_empty((dy.shape[0], 32 * w_scales.shape[2]))
+
+
+@torch.library.custom_op(f"{_NS}::moe_linear_mxfp4", mutates_args=(), device_types="cuda")
+def moe_linear_mxfp4(x: Tensor, w_blocks: Tensor, w_scales: Tensor, expert_offsets: Tensor, bias: Optional[Tensor],
+                     sorted_slot: Optional[Tensor], top_k: Optional[int], pos: Optional[Tensor]) -> Tensor:
+    """moe.moe_linear_mxfp4: moe_gemm_mxfp4's out, differentiable in x and bias (moe_gemm_mxfp4_dgrad, moe_combine over pos,
+    moe_gemm_wgrad's dbias); pos is only read by the backward."""
+    return _moe.moe_gemm_mxfp4(x.detach(), w_blocks, w_scales, expert_offsets, bias=None if bias is None else bias.detach(),
+                               sorted_slot=sorted_slot, top_k=top_k)
+
+
+@moe_linear_mxfp4.register_fake
+def _(x, w_blocks, w_scales, expert_offsets, bias, sorted_slot, top_k, pos):
+    M = x.shape[0] if sorted_slot is None else sorted_slot.shape[0]
+    return x.new_empty((M, w_blocks.shape[1]))
+
+
+def _moe_linear_mxfp4_setup(ctx, inputs, output):
+    x, w_blocks, w_scales, expert_offsets, bias, sorted_slot, top_k, pos = inputs
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(x, w_blocks, w_scales, expert_offsets, sorted_slot, pos)
+    ctx.args = (top_k, None if bias is None else bias.dtype)
+
+
+def _moe_linear_mxfp4_backward(ctx, dy):
+    need_dx, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[4]
+    if dy is None or not (need_dx or need_db):
+        return (None,) * 8
+    x, w_blocks, w_scales, expert_offsets, sorted_slot, pos = ctx.saved_tensors
+    top_k, bias_dtype = ctx.args
+    dx, _, db = _moe_linear_grads(dy, x, (w_blocks, w_scales), expert_offsets, sorted_slot, pos, "nk", top_k, bias_dtype,
+                                  need_dx, False, need_db)
+    return dx, None, None, None, db, None, None, None
+
+
+moe_linear_mxfp4.register_autograd(_moe_linear_mxfp4_backward, setup_context=_moe_linear_mxfp4_setup)
 
 
 # the gate-up grouped expert GEMM with the gated activation in its epilogue (moe.moe_gemm_glu; csrc/fa_moe_gemm.hip) and the

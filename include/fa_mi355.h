@@ -1869,6 +1869,51 @@ int    fa_moe_gemm_mxfp4_glu_plan(int64_t rows, int32_t n, int32_t k, int32_t nu
                                   int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
 
 /*
+ * fa_moe_gemm_mxfp4_dgrad: the data gradient of fa_moe_gemm_mxfp4 (csrc/fa_moe_gemm_mxfp4_dgrad.hip; additive: fa_params and
+ * FA_ABI_VERSION are unchanged) - what training through frozen MXFP4 experts needs.  n counts the weights' rows (the columns of
+ * dy, contracted), k their columns (the columns of dx).  One launch, no workspace, no atomics, no host synchronisation.
+ *   values         dx[r, k] = round_bf16(sum_n float(dy[r, n]) * W_e[n, k]) for expert_offsets[e] <= r < expert_offsets[e + 1], W_e
+ *                  as fa_moe_gemm_mxfp4 defines it; rows expert_offsets[E] <= r < rows: +0.  Every element of dx is written
+ *                  exactly once (rows below a positive expert_offsets[0] are in no segment and are not written, as in fa_moe_gemm).
+ *   contract       dx has EXACTLY the bits of fa_moe_gemm(x = dy, w = the bf16 weights fa_mx_dequant writes in FA_MOE_W_NK, read as
+ *                  FA_MOE_W_KN with n and k exchanged): the same transposed product, one v_mfma_f32_32x32x16 chain per element over n
+ *                  ascending in steps of 16 from +0 with the same operand slots, one rounding - in both plans.  The kernel
+ *                  dequantises 16 bytes of codes with their one scale byte on the way into LDS; no bf16 weight exists in memory.
+ *   tensors        w_blocks, w_scales: the memory fa_moe_gemm_mxfp4 reads, with its strides, alignment rules and scale bytes
+ *                  2 ... 252 (layout FA_MOE_W_NK).  dy [rows, n], dx [rows, k] bf16: 16-byte aligned, row strides (elements)
+ *                  multiples of 8 up to 2^22, dx_row_stride >= k.  dx must not overlap an input.  The checks are fa_moe_gemm's
+ *                  and their messages name dy as x and dx as out.
+ *   limits         2 <= num_experts <= 512, n a multiple of 8 in [8, 32768], k a multiple of 32 in [32, 32768], dtype FA_BF16, rows
+ *                  < 2^31.  Outside: FA_ERR_UNSUPPORTED, before any device work.  rows = 0: FA_OK without a launch.
+ * fa_moe_gemm_mxfp4_dgrad_plan: fa_moe_gemm_plan(rows, k, n, num_experts, FA_MOE_W_KN, FA_BF16) - block_m 128 or 32 (rows <=
+ *   32 * num_experts), block_n 128 (columns of dx), block_k 64 (weight rows a step), grid_n = ceil(k / 128).  layout is the
+ *   weights' (FA_MOE_W_NK).  Needs no device.
+ */
+typedef struct fa_moe_gemm_mxfp4_dgrad_params {
+    size_t         struct_size;      /* sizeof(fa_moe_gemm_mxfp4_dgrad_params) as the caller compiled it */
+    const void*    dy;               /* [rows, n] bf16 */
+    const void*    w_blocks;         /* uint8 [num_experts, n, k / 2] */
+    const void*    w_scales;         /* uint8 [num_experts, n, k / 32] */
+    const void*    expert_offsets;   /* int32 [num_experts + 1], device */
+    void*          dx;               /* [rows, k] bf16 */
+    int64_t        dy_row_stride, dx_row_stride;   /* elements, multiples of 8 */
+    int64_t        w_blocks_expert_stride;         /* bytes, >= n * k / 2, a multiple of 16 */
+    int64_t        w_scales_expert_stride;         /* bytes, >= n * k / 32 */
+    int64_t        rows;             /* M_max */
+    int32_t        num_experts;
+    int32_t        n, k;             /* the weights' rows (contracted) and columns (dx's) */
+    int32_t        dtype;            /* FA_BF16 */
+    int32_t        layout;           /* FA_MOE_W_NK, the weights' */
+    int32_t        reserved0;        /* 0 */
+    int64_t        reserved[4];      /* 0 */
+} fa_moe_gemm_mxfp4_dgrad_params;
+
+int    fa_moe_gemm_mxfp4_dgrad(const fa_moe_gemm_mxfp4_dgrad_params* s, void* stream);
+size_t fa_moe_gemm_mxfp4_dgrad_params_size(void);
+int    fa_moe_gemm_mxfp4_dgrad_plan(int64_t rows, int32_t n, int32_t k, int32_t num_experts, int32_t layout, int32_t dtype,
+                                    int32_t* block_m, int32_t* block_n, int32_t* block_k, int64_t* grid_m, int64_t* grid_n);
+
+/*
  * fa_mx_quant, fa_mx_dequant: 16-bit expert weights to the MXFP4 tensors fa_moe_gemm_mxfp4 reads, and back
  * (csrc/fa_mx_quant.hip; additive: fa_params and FA_ABI_VERSION are unchanged).  Each is one launch with no workspace, no
  * atomics and no host synchronisation; every output byte is written exactly once.
